@@ -22,6 +22,10 @@ one JSON line (strong scaling: the total work is fixed, N = 1 is the single-GPU 
 
 `python bench.py --gpus N` with WORLD_SIZE unset starts its N ranks itself (child processes, before anything touches a GPU).
 Rank 0 prints ONE JSON line.  `value` = image pairs matched per second over all ranks.
+
+A plain run does only what `value` needs: set-up, warm-up, the timed steps, the line.  Everything described above beyond the
+headline -- the BA half, the side legs, configs 1-5, the oracle checks and the CPU baselines -- runs with `--full`.
+`--dump-outputs DIR` writes the last timed step's match lists as DIR/*.npy (seeded inputs: two builds compare file for file).
 """
 from __future__ import annotations
 
@@ -274,6 +278,19 @@ def e2e_leg(tag: str, feature: str, param: int, with_cpu: bool):
         shutil.rmtree(tmp, ignore_errors=True)
 
 
+def dump_outputs(out_dir: str, pairs, host, suffix: str = "") -> None:
+    """What a caller of PairMatcher.match receives, in float64 / float32: the step's pair list, every pair's match count, and the
+    match lists concatenated over the pairs in order (query / train indices, distances)."""
+    os.makedirs(out_dir, exist_ok=True)
+
+    def cat(k, dt):
+        return np.concatenate([h[k] for h in host]).astype(dt) if host else np.zeros(0, dt)
+    arrays = {"pairs": np.asarray(pairs, np.float64), "match_counts": np.array([len(h[0]) for h in host], np.float64),
+              "match_query_idx": cat(0, np.float64), "match_train_idx": cat(1, np.float64), "match_distance": cat(2, np.float32)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), a)
+
+
 def dry_run(args) -> int:
     """The launcher path without a GPU: every rank reads RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* exactly as the real run does,
     the ranks meet on MASTER_ADDR:MASTER_PORT (rank 0 listens, the others report in), and rank 0 prints the one JSON line."""
@@ -333,6 +350,11 @@ def main() -> int:
     ap.add_argument("--no-e2e", action="store_true", help="skip the config-1 / config-3 end-to-end legs (bin/sfm_native on the fountain images)")
     ap.add_argument("--config4-steps", type=int, default=2)
     ap.add_argument("--ba512-iters", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the BA half, the side legs, configs 1-5, the oracle checks and the CPU baselines "
+                         "(the --no-* options and the leg sizes above apply to this part)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's match lists as DIR/<name>.npy (rank r of N > 1: <name>_rank<r>.npy)")
     ap.add_argument("--dry-run", action="store_true",
                     help="exercise the launcher and the rank environment only: no torch / HIP import, no GPU; ranks meet over a "
                          "TCP socket on MASTER_ADDR:MASTER_PORT and rank 0 prints one JSON line with n_gpus")
@@ -410,7 +432,7 @@ def main() -> int:
     ctx.kernel_time(_lib.K_L2_KNN); ctx.kernel_time(_lib.K_L2_RESCAN); ctx.kernel_time(_lib.K_L2_SECOND)   # drain
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        pm.match(ratio)
+        last = pm.match(ratio)
     ctx.synchronize()
     torch.cuda.synchronize(dev)
     if world > 1:
@@ -421,14 +443,18 @@ def main() -> int:
     ctx.set_kernel_timing(False)
     n_q, n_rescan = pm.stats()
     n_second = pm.second_pass()
-    # the per-bank cost that sits OUTSIDE the step: the operand images / norms the matcher derives once per resident descriptor bank
-    # (PairMatcher.prepare -> esfm_match_prepare_dev: l2_split_bf16_kernel + l2_blockmax_kernel)
-    ctx.synchronize()
-    t0p = time.perf_counter()
-    for _ in range(20):
-        pm.prepare()
-    ctx.synchronize()
-    prepare_ms = (time.perf_counter() - t0p) / 20 * 1e3
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, pairs, last.to_host(), f"_rank{rank}" if world > 1 else "")
+    prepare_ms = None
+    if args.full:
+        # the per-bank cost that sits OUTSIDE the step: the operand images / norms the matcher derives once per resident descriptor bank
+        # (PairMatcher.prepare -> esfm_match_prepare_dev: l2_split_bf16_kernel + l2_blockmax_kernel)
+        ctx.synchronize()
+        t0p = time.perf_counter()
+        for _ in range(20):
+            pm.prepare()
+        ctx.synchronize()
+        prepare_ms = (time.perf_counter() - t0p) / 20 * 1e3
 
     tt = torch.tensor([elapsed], dtype=torch.float64, device=dev)
     npairs = torch.tensor([float(len(pairs))], dtype=torch.float64, device=dev)
@@ -439,11 +465,11 @@ def main() -> int:
     total_pairs = float(npairs.item())
     value = total_pairs * args.steps / elapsed
 
-    # correctness check (outside the timed region).  With the CPU baseline leg on (rank 0, N = 1) the oracle runs the step's WHOLE
-    # pair list there and every pair's match list is compared bit for bit (`verified_scope` says how much was checked); otherwise
-    # a spot check: 512 queries of this rank's first pair.
+    # correctness check (outside the timed region; --full only, a plain run leaves verified_vs_oracle null).  With the CPU baseline
+    # leg on (rank 0, N = 1) the oracle runs the step's WHOLE pair list there and every pair's match list is compared bit for bit
+    # (`verified_scope` says how much was checked); otherwise a spot check: 512 queries of this rank's first pair.
     verified, verified_scope, res_host = None, None, None
-    if rank == 0:
+    if rank == 0 and args.full:
         try:
             import oracle
             res_host = pm.match(ratio).to_host()
@@ -488,10 +514,11 @@ def main() -> int:
                 "finish_kernel": "l2_finish_kernel (threshold-filter second pass + brute force of overflowed chunks + ratio test + compaction)",
                 "finish_kernel_avg_ms": (s_ms / max(s_n, 1)), "second_pass_queries_per_step": n_second,
                 "launches_per_step": 2, "step_minus_kernels_ms": elapsed / args.steps * 1e3 - (k_ms / max(k_n, 1)) - (s_ms / max(s_n, 1)),
-                "rescanned_queries_per_step": n_rescan, "queries_per_step": n_q,
-                "prepare_ms": prepare_ms,
-                "prepare_note": "once per resident descriptor bank (bf16 operand images, norms), outside the timed step; value_including_prepare charges it to EVERY step",
-                "value_including_prepare": total_pairs / (elapsed / args.steps + prepare_ms * 1e-3)}
+                "rescanned_queries_per_step": n_rescan, "queries_per_step": n_q}
+    if prepare_ms is not None:
+        roofline.update({"prepare_ms": prepare_ms,
+                         "prepare_note": "once per resident descriptor bank (bf16 operand images, norms), outside the timed step; value_including_prepare charges it to EVERY step",
+                         "value_including_prepare": total_pairs / (elapsed / args.steps + prepare_ms * 1e-3)})
 
     out = {
         "metric": METRIC, "value": value, "unit": "image-pairs/s", "n_gpus": world, "steps": args.steps,
@@ -516,7 +543,7 @@ def main() -> int:
 
     roofline["parity"] = {"verified_vs_oracle": verified, "verified_scope": verified_scope}
     roofline["legs"] = {}
-    if world > 1:
+    if world > 1 and args.full:
         # round 4's headline as a side leg: per-GPU work fixed at 300 pairs per step (F images, F (F - 1) / 2 >= 300 N pairs over the ranks)
         try:
             n_fw = frames_for(world)
@@ -592,6 +619,13 @@ def main() -> int:
             except Exception as e:      # (the line must come out whatever the ordering step meets)
                 line = dict(out, finalize_error=repr(e))
             print(json.dumps(line), flush=True)
+
+    if not args.full:
+        emit()
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return 0
 
     # the library's own RCCL communicator for the sharded BA legs (esfm_comm_*: no callback into Python per all-reduce);
     # the 128-byte id travels through torch.distributed's store

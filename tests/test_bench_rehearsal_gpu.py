@@ -20,7 +20,7 @@ BENCH = os.path.join(ROOT, "bench.py")
 def _run(n, *flags, **env_extra):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env.update(ESFM_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0", **env_extra)
-    r = subprocess.run([sys.executable, BENCH, "--gpus", str(n), "--steps", "3", "--warmup", "1", "--no-e2e", *flags], env=env, stdout=subprocess.PIPE,
+    r = subprocess.run([sys.executable, BENCH, "--gpus", str(n), "--steps", "3", "--warmup", "1", "--full", "--no-e2e", *flags], env=env, stdout=subprocess.PIPE,
                        stderr=subprocess.PIPE, text=True, timeout=1500, cwd=ROOT)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
     lines = [json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")]
