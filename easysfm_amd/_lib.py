@@ -19,7 +19,7 @@ ESFM_L2_F32 = 0
 ESFM_HAMMING = 1
 ESFM_REDUCE_SUM = 0
 ESFM_REDUCE_MAX = 1
-K_L2_KNN, K_HAMMING_KNN, K_BA_LINEARIZE, K_BA_SCHUR, K_BA_SOLVE, K_L2_RESCAN, K_SOR_KNN, K_TRIANGULATE, K_RANSAC, K_SURF_DET, K_SURF_DESC, K_UNDISTORT, K_ORB_FAST, K_L2_SECOND = range(14)
+K_L2_KNN, K_HAMMING_KNN, K_BA_LINEARIZE, K_BA_SCHUR, K_BA_SOLVE, K_L2_RESCAN, K_SOR_KNN, K_TRIANGULATE, K_RANSAC, K_SURF_DET, K_SURF_DESC, K_UNDISTORT, K_ORB_FAST, K_L2_SECOND, K_CROSS_CHECK = range(15)
 BA_MAX_LOG = 256
 
 STATUS_NAMES = {
@@ -33,6 +33,7 @@ EXPORTED_SYMBOLS = [
     "esfm_ctx_synchronize", "esfm_ctx_stream", "esfm_ctx_set_kernel_timing", "esfm_ctx_kernel_time",
     "esfm_knn2_l2_f32", "esfm_knn2_hamming", "esfm_match_l2_f32", "esfm_match_hamming",
     "esfm_match_pairs_dev", "esfm_match_pairs", "esfm_knn2_pairs_dev", "esfm_knn2_pairs_screened_dev", "esfm_match_prepare_dev", "esfm_match_debug_counters", "esfm_match_release_prepared", "esfm_match_release_prepared_buffer", "esfm_match_prepared_buffer", "esfm_ctx_set_prepared_check", "esfm_match_last_stats", "esfm_match_last_second_pass", "esfm_ctx_set_l2_audit", "esfm_match_last_flagged",
+    "esfm_match_cross_l2_f32", "esfm_match_cross_hamming", "esfm_match_cross_pairs_dev", "esfm_match_cross_pairs",
     "esfm_shard_pair_list",
     "esfm_comm_get_unique_id", "esfm_comm_create", "esfm_comm_destroy", "esfm_comm_rank", "esfm_comm_world", "esfm_comm_rccl_ranks", "esfm_comm_allreduce",
     "esfm_ba_options_default", "esfm_ba_solve", "esfm_ba_problem_create", "esfm_ba_problem_set_params",
@@ -127,6 +128,10 @@ def lib() -> C.CDLL:
     L.esfm_knn2_pairs_screened_dev.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_double, vp, vp, vp]
     L.esfm_match_debug_counters.argtypes = [vp, vp]
     L.esfm_match_pairs.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_double, vp, vp, vp, vp, vp]
+    L.esfm_match_cross_l2_f32.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_double, vp, vp, vp, i32p]
+    L.esfm_match_cross_hamming.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_double, vp, vp, vp, i32p]
+    L.esfm_match_cross_pairs_dev.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_double, vp, vp, vp, vp, vp]
+    L.esfm_match_cross_pairs.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_double, vp, vp, vp, vp, vp]
     L.esfm_match_prepare_dev.argtypes = [vp, C.c_int, vp, C.c_int64, C.c_int]
     L.esfm_match_release_prepared.argtypes = [vp]
     L.esfm_match_release_prepared_buffer.argtypes = [vp, vp]

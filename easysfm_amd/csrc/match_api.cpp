@@ -377,6 +377,95 @@ int single_pair(esfm_ctx *ctx, esfm_metric metric, const void *q, int nq, const 
     return ESFM_OK;
 }
 
+// Cross-check over a pair list (esfm_match_cross_*): the plan is built over the MIRRORED list -- the caller's P pairs, then (t, q) for
+// each of them -- so one knn2_core pass writes both directions' 2-NN tables (with their markers: mo == NULL).  ratio+cross passes
+// `ratio` so the screen drops rows in both directions (a dropped row cannot match); cross alone passes +inf (every row's exact 2-NN).
+// cross_check_compact_kernel then joins pair p with pair P + p.  The caller's out_offset is the first P + 1 entries of the mirrored
+// plan's prefix sum (the forward pairs come first).
+int cross_pairs_dev(esfm_ctx *ctx, esfm_metric metric, const void *desc_dev, const int32_t *set_row_offset, int n_sets, int width,
+                    const int32_t *pairs, int n_pairs, int use_ratio, double ratio, int32_t *query_idx_dev, int32_t *train_idx_dev,
+                    float *distance_dev, int32_t *n_out_dev, int64_t *out_offset)
+{
+    if (int rc = check_common(ctx, metric, width)) return rc;
+    ESFM_REQUIRE(out_offset != nullptr, "out_offset is NULL");
+    ESFM_REQUIRE(use_ratio == 0 || use_ratio == 1, "use_ratio must be 0 (cross) or 1 (ratio+cross)");
+    ESFM_REQUIRE(use_ratio == 0 || ratio == ratio, "ratio is NaN");
+    ESFM_REQUIRE(n_pairs >= 0 && (n_pairs == 0 || pairs != nullptr), "pairs/n_pairs");
+    std::vector<int32_t> mirrored(4 * (size_t)n_pairs);
+    for (int p = 0; p < n_pairs; ++p) {
+        mirrored[2 * (size_t)p] = pairs[2 * p]; mirrored[2 * (size_t)p + 1] = pairs[2 * p + 1];
+        mirrored[2 * ((size_t)n_pairs + p)] = pairs[2 * p + 1]; mirrored[2 * ((size_t)n_pairs + p) + 1] = pairs[2 * p];
+    }
+    std::vector<int64_t> off(2 * (size_t)n_pairs + 1);
+    PairPlan plan;
+    if (int rc = make_plan(set_row_offset, n_sets, mirrored.data(), 2 * n_pairs,
+                           metric == ESFM_L2_F32 ? esfm::l2_query_block(width) : esfm::hamming_query_block(width), off.data(), &plan))
+        return rc;
+    for (int p = 0; p <= n_pairs; ++p) out_offset[p] = off[(size_t)p];
+    if (n_pairs == 0) return ESFM_OK;
+    ESFM_REQUIRE(n_out_dev != nullptr, "n_out_dev is NULL");
+    ESFM_REQUIRE(off[(size_t)n_pairs] == 0 || (query_idx_dev && train_idx_dev && distance_dev), "device pointer is NULL");
+    ESFM_REQUIRE(plan.total_queries == 0 || desc_dev, "desc_dev is NULL");
+    if (plan.total_queries == 0) {
+        ESFM_HIP_TRY(hipMemsetAsync(n_out_dev, 0, sizeof(int32_t) * (size_t)n_pairs, ctx->stream));
+        return ESFM_OK;
+    }
+    const PairDesc *dev_tab = nullptr;
+    if (int rc = upload_pairs(ctx, plan, &dev_tab)) return rc;
+    if (int rc = ctx->knn_idx.reserve(sizeof(int32_t) * 2 * (size_t)plan.total_queries)) return rc;
+    if (int rc = ctx->knn_dist.reserve(sizeof(float) * 2 * (size_t)plan.total_queries)) return rc;
+    if (int rc = knn2_core(ctx, metric, desc_dev, width, plan, dev_tab, ctx->knn_idx.as<int32_t>(), ctx->knn_dist.as<float>(),
+                           use_ratio ? ratio : (double)INFINITY, nullptr, nullptr))
+        return rc;
+    esfm::KernelTimer tm(ctx, ESFM_K_CROSS_CHECK);
+    return esfm::launch_cross_check_compact(ctx->stream, dev_tab, n_pairs, ctx->knn_idx.as<int32_t>(), ctx->knn_dist.as<float>(), use_ratio, ratio,
+                                            query_idx_dev, train_idx_dev, distance_dev, n_out_dev);
+}
+
+// Host-pointer single pair, cross-check: [train rows | query rows] staged into one device buffer, the pair (1, 0) (its mirror (0, 1)
+// comes with it), the list read back.
+int cross_single_pair(esfm_ctx *ctx, esfm_metric metric, const void *q, int nq, const void *t, int nt, int width, int use_ratio, double ratio,
+                      int32_t *query_idx, int32_t *train_idx, float *distance, int32_t *n_out)
+{
+    if (!n_out || (nq > 0 && (!query_idx || !train_idx || !distance))) { esfm::set_error("output pointer is NULL"); return ESFM_ERR_INVALID_ARG; }
+    if (int rc = check_common(ctx, metric, width)) return rc;
+    ESFM_REQUIRE(nq >= 0 && nt >= 0, "negative row count");
+    ESFM_REQUIRE(nq == 0 || q != nullptr, "q is NULL");
+    ESFM_REQUIRE(nt == 0 || t != nullptr, "t is NULL");
+    ESFM_REQUIRE(use_ratio == 0 || use_ratio == 1, "use_ratio must be 0 (cross) or 1 (ratio+cross)");
+    ESFM_REQUIRE(use_ratio == 0 || ratio == ratio, "ratio is NaN");
+    *n_out = 0;
+    if (nq == 0) return ESFM_OK;
+    const size_t row_bytes = metric == ESFM_L2_F32 ? sizeof(float) * (size_t)width : (size_t)width;
+    const size_t tb = row_bytes * (size_t)nt, qb = row_bytes * (size_t)nq;
+    if (int rc = ctx->stage_a.reserve(tb + qb + 16)) return rc;
+    if (int rc = ctx->stage_b.reserve(sizeof(int32_t) * (size_t)nq)) return rc;
+    if (int rc = ctx->stage_c.reserve(sizeof(int32_t) * (size_t)nq)) return rc;
+    if (int rc = ctx->stage_d.reserve(sizeof(float) * (size_t)nq)) return rc;
+    if (int rc = ctx->stage_e.reserve(sizeof(int32_t))) return rc;
+    hipStream_t st = ctx->stream;
+    char *d = ctx->stage_a.as<char>();
+    if (tb) ESFM_HIP_TRY(esfm::copy_h2d(d, t, tb, st));
+    ESFM_HIP_TRY(esfm::copy_h2d(d + tb, q, qb, st));
+    const int32_t offs[3] = {0, nt, nt + nq};
+    const int32_t pr[2] = {1, 0};
+    int64_t out_off[2];
+    if (int rc = cross_pairs_dev(ctx, metric, d, offs, 2, width, pr, 1, use_ratio, ratio, ctx->stage_b.as<int32_t>(), ctx->stage_c.as<int32_t>(),
+                                 ctx->stage_d.as<float>(), ctx->stage_e.as<int32_t>(), out_off))
+        return rc;
+    int32_t n = 0;
+    ESFM_HIP_TRY(esfm::copy_d2h(&n, ctx->stage_e.ptr, sizeof(int32_t), st));
+    ESFM_HIP_TRY(hipStreamSynchronize(st));
+    if (n > 0) {
+        ESFM_HIP_TRY(esfm::copy_d2h(query_idx, ctx->stage_b.ptr, sizeof(int32_t) * (size_t)n, st));
+        ESFM_HIP_TRY(esfm::copy_d2h(train_idx, ctx->stage_c.ptr, sizeof(int32_t) * (size_t)n, st));
+        ESFM_HIP_TRY(esfm::copy_d2h(distance, ctx->stage_d.ptr, sizeof(float) * (size_t)n, st));
+        ESFM_HIP_TRY(hipStreamSynchronize(st));
+    }
+    *n_out = n;
+    return ESFM_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -472,12 +561,17 @@ int esfm_match_pairs_dev(esfm_ctx *ctx, esfm_metric metric, const void *desc_dev
 // the whole pair list, one read-back.  The uploaded rows stay in the context (ctx->bank) and stay prepared, so a second call on
 // the same host buffer contents would still re-upload (the library cannot know the rows are unchanged) -- callers that match
 // the same sets repeatedly keep them on the device and use esfm_match_pairs_dev.
-int esfm_match_pairs(esfm_ctx *ctx, esfm_metric metric, const void *desc_host, const int32_t *set_row_offset, int n_sets, int width,
-                     const int32_t *pairs, int n_pairs, double ratio, int32_t *query_idx, int32_t *train_idx, float *distance,
-                     int32_t *n_out, int64_t *out_offset)
+// (cross: the cross-check filter of esfm_match_cross_pairs_dev with use_ratio; else esfm_match_pairs_dev's ratio test)
+static int match_pairs_host(esfm_ctx *ctx, esfm_metric metric, const void *desc_host, const int32_t *set_row_offset, int n_sets, int width,
+                            const int32_t *pairs, int n_pairs, bool cross, int use_ratio, double ratio, int32_t *query_idx, int32_t *train_idx,
+                            float *distance, int32_t *n_out, int64_t *out_offset)
 {
     if (int rc = check_common(ctx, metric, width)) return rc;
     ESFM_REQUIRE(out_offset != nullptr, "out_offset is NULL");
+    if (cross) {
+        ESFM_REQUIRE(use_ratio == 0 || use_ratio == 1, "use_ratio must be 0 (cross) or 1 (ratio+cross)");
+        ESFM_REQUIRE(use_ratio == 0 || ratio == ratio, "ratio is NaN");
+    }
     PairPlan plan;
     if (int rc = make_plan(set_row_offset, n_sets, pairs, n_pairs, metric == ESFM_L2_F32 ? esfm::l2_query_block(width) : esfm::hamming_query_block(width),
                            out_offset, &plan))
@@ -500,8 +594,10 @@ int esfm_match_pairs(esfm_ctx *ctx, esfm_metric metric, const void *desc_host, c
     if (int rc = ctx->stage_d.reserve(sizeof(float) * nq)) return rc;
     if (int rc = ctx->stage_e.reserve(sizeof(int32_t) * (size_t)n_pairs)) return rc;
     std::vector<int64_t> off2((size_t)n_pairs + 1);
-    if (int rc = esfm_match_pairs_dev(ctx, metric, ctx->bank.ptr, set_row_offset, n_sets, width, pairs, n_pairs, ratio, ctx->stage_b.as<int32_t>(),
-                                      ctx->stage_c.as<int32_t>(), ctx->stage_d.as<float>(), ctx->stage_e.as<int32_t>(), off2.data()))
+    if (int rc = cross ? cross_pairs_dev(ctx, metric, ctx->bank.ptr, set_row_offset, n_sets, width, pairs, n_pairs, use_ratio, ratio,
+                                         ctx->stage_b.as<int32_t>(), ctx->stage_c.as<int32_t>(), ctx->stage_d.as<float>(), ctx->stage_e.as<int32_t>(), off2.data())
+                       : esfm_match_pairs_dev(ctx, metric, ctx->bank.ptr, set_row_offset, n_sets, width, pairs, n_pairs, ratio, ctx->stage_b.as<int32_t>(),
+                                              ctx->stage_c.as<int32_t>(), ctx->stage_d.as<float>(), ctx->stage_e.as<int32_t>(), off2.data()))
         return rc;
     ESFM_HIP_TRY(esfm::copy_d2h(n_out, ctx->stage_e.ptr, sizeof(int32_t) * (size_t)n_pairs, st));
     ESFM_HIP_TRY(hipStreamSynchronize(st));
@@ -545,6 +641,43 @@ int esfm_match_pairs(esfm_ctx *ctx, esfm_metric metric, const void *desc_host, c
         memcpy(distance + so, hd.data() + dof, sizeof(float) * n);
     }
     return ESFM_OK;
+}
+
+int esfm_match_pairs(esfm_ctx *ctx, esfm_metric metric, const void *desc_host, const int32_t *set_row_offset, int n_sets, int width,
+                     const int32_t *pairs, int n_pairs, double ratio, int32_t *query_idx, int32_t *train_idx, float *distance,
+                     int32_t *n_out, int64_t *out_offset)
+{
+    return match_pairs_host(ctx, metric, desc_host, set_row_offset, n_sets, width, pairs, n_pairs, false, 0, ratio, query_idx, train_idx, distance,
+                            n_out, out_offset);
+}
+
+// ---- cross-check (include/esfm.h "Cross-check matching")
+int esfm_match_cross_l2_f32(esfm_ctx *ctx, const float *q, int nq, const float *t, int nt, int dim, int use_ratio, double ratio,
+                            int32_t *query_idx, int32_t *train_idx, float *distance, int32_t *n_out)
+{
+    return cross_single_pair(ctx, ESFM_L2_F32, q, nq, t, nt, dim, use_ratio, ratio, query_idx, train_idx, distance, n_out);
+}
+
+int esfm_match_cross_hamming(esfm_ctx *ctx, const uint8_t *q, int nq, const uint8_t *t, int nt, int nbytes, int use_ratio,
+                             double ratio, int32_t *query_idx, int32_t *train_idx, float *distance, int32_t *n_out)
+{
+    return cross_single_pair(ctx, ESFM_HAMMING, q, nq, t, nt, nbytes, use_ratio, ratio, query_idx, train_idx, distance, n_out);
+}
+
+int esfm_match_cross_pairs_dev(esfm_ctx *ctx, esfm_metric metric, const void *desc_dev, const int32_t *set_row_offset, int n_sets,
+                               int width, const int32_t *pairs, int n_pairs, int use_ratio, double ratio, int32_t *query_idx_dev,
+                               int32_t *train_idx_dev, float *distance_dev, int32_t *n_out_dev, int64_t *out_offset)
+{
+    return cross_pairs_dev(ctx, metric, desc_dev, set_row_offset, n_sets, width, pairs, n_pairs, use_ratio, ratio, query_idx_dev, train_idx_dev,
+                           distance_dev, n_out_dev, out_offset);
+}
+
+int esfm_match_cross_pairs(esfm_ctx *ctx, esfm_metric metric, const void *desc_host, const int32_t *set_row_offset, int n_sets, int width,
+                           const int32_t *pairs, int n_pairs, int use_ratio, double ratio, int32_t *query_idx, int32_t *train_idx,
+                           float *distance, int32_t *n_out, int64_t *out_offset)
+{
+    return match_pairs_host(ctx, metric, desc_host, set_row_offset, n_sets, width, pairs, n_pairs, true, use_ratio, ratio, query_idx, train_idx,
+                            distance, n_out, out_offset);
 }
 
 int esfm_match_prepare_dev(esfm_ctx *ctx, esfm_metric metric, const void *desc_dev, int64_t total_rows, int width)

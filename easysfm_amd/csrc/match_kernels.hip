@@ -19,6 +19,7 @@
 //   hamming_knn_kernel       other widths: XOR + popcount, (distance,index) packed into one u32 key
 // Both:
 //   ratio_compact_kernel     ratio test in double + ordered compaction per pair
+//   cross_check_compact_kernel  mutual-nearest-neighbour join of a pair's two directions (+ the ratio test on both) + compaction
 //
 // DESIGN.md "Matching" explains the data layout and the certificate.
 #include "match_kernels.hpp"
@@ -1328,6 +1329,13 @@ __device__ __forceinline__ void ld_coh_block(const void *p, uint32_t *out /* 4 N
 // threads' counts places them.  A train index < 0 (no neighbour; -2: dropped by the one-product pass's ratio screen) never passes; a
 // SECOND index of -3 says that pass has proved d0 < ratio d1 without looking for the second neighbour.
 // (Round 1: 256 threads, one query each, 16 sweeps of three barriers for a 4096-row set: 14 us per launch.)
+// The reference's test on one 2-NN record (i0, i1, d0, d1): every filter of this file that applies it calls this one predicate
+// (ratio_compact_pair, ratio_compact_pair_sparse, cross_check_compact_kernel), so ratio+cross can only keep what ratio keeps.
+__device__ __forceinline__ bool ratio_ok(int i0, int i1, float d0, float d1, double ratio)
+{
+    return i0 >= 0 && (i1 == -3 || (i1 >= 0 && (double)d0 < ratio * (double)d1));     // -3: the one-product pass proved the test
+}
+
 template <int THREADS, int kRatioPer, bool COHERENT = false>
 __device__ __forceinline__ void ratio_compact_pair(const PairDesc &pd, const int32_t *__restrict__ knn_idx, const float *__restrict__ knn_dist,
                                                    double ratio, int32_t *__restrict__ query_idx, int32_t *__restrict__ train_idx,
@@ -1362,7 +1370,7 @@ __device__ __forceinline__ void ratio_compact_pair(const PairDesc &pd, const int
             const int i0 = iv[2 * u], i1 = iv[2 * u + 1];
             const float d1 = dv[2 * u + 1];
             d0[u] = dv[2 * u]; ti[u] = i0;
-            pass[u] = q < pd.nq && (i0 >= 0) && (i1 == -3 || (i1 >= 0 && (double)d0[u] < ratio * (double)d1));     // -3: the one-product pass proved the test
+            pass[u] = q < pd.nq && ratio_ok(i0, i1, d0[u], d1, ratio);
             cnt += pass[u] ? 1 : 0;
         }
         // exclusive scan of cnt over the workgroup: inside the wave by shuffles, across waves through LDS
@@ -1423,7 +1431,7 @@ __device__ __forceinline__ void ratio_compact_pair_sparse(const PairDesc &pd, co
                          : "=&v"(*reinterpret_cast<uint2 *>(iv)), "=&v"(*reinterpret_cast<uint2 *>(iv + 2)) : "v"(knn_idx + o), "v"(knn_dist + o) : "memory");
             const int i0 = (int)iv[0], i1 = (int)iv[1];
             const float dd0 = __uint_as_float(iv[2]), dd1 = __uint_as_float(iv[3]);
-            const bool pass = qa + u < pd.nq && (i0 >= 0) && (i1 == -3 || (i1 >= 0 && (double)dd0 < ratio * (double)dd1));
+            const bool pass = qa + u < pd.nq && ratio_ok(i0, i1, dd0, dd1, ratio);
             // (static indexing keeps ti / d0 in registers)
 #pragma unroll
             for (int e = 0; e < PER; ++e) if (e == u) { ti[e] = i0; d0[e] = dd0; }
@@ -3064,6 +3072,71 @@ __global__ __launch_bounds__(kRatioThreads) void ratio_compact_kernel(const Pair
 }
 
 // ---------------------------------------------------------------------------------------------
+// Cross-check (strict mutual nearest neighbour) + ordered compaction: one workgroup per FORWARD pair p of a mirrored plan whose pair
+// n_pairs + p is p with query and train swapped, both 2-NN tables written by one knn pass with their markers (-2 screened, -3 proved).
+// Query q of pair p, F = its forward slot 0, is kept iff F >= 0 and the mirror's slot 0 at row F is q -- plus, use_ratio, ratio_ok on
+// both records.  The forward records are read as ratio_compact_pair reads them (kCrossPer consecutive queries per thread); the mirror
+// record of F is a gather from the mirror pair's slice (nt x 16 B: a few tens of KB that stay in L2).  Output as ratio_compact_pair's:
+// pair p's survivors query-ascending at out_off[p], the count in n_out[p], the distance the forward d0.
+constexpr int kCrossThreads = 1024, kCrossPer = 4;
+__global__ __launch_bounds__(kCrossThreads) void cross_check_compact_kernel(const PairDesc *__restrict__ pairs, int n_pairs,
+                                                                            const int32_t *__restrict__ knn_idx, const float *__restrict__ knn_dist,
+                                                                            int use_ratio, double ratio, int32_t *__restrict__ query_idx,
+                                                                            int32_t *__restrict__ train_idx, float *__restrict__ distance,
+                                                                            int32_t *__restrict__ n_out)
+{
+    __shared__ int s_wave[kCrossThreads / 64];
+    __shared__ int s_base;
+    const PairDesc pd = pairs[blockIdx.x], pm = pairs[n_pairs + blockIdx.x];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int2 *fi = reinterpret_cast<const int2 *>(knn_idx) + pd.out_off, *mi = reinterpret_cast<const int2 *>(knn_idx) + pm.out_off;
+    const float2 *fd = reinterpret_cast<const float2 *>(knn_dist) + pd.out_off, *md = reinterpret_cast<const float2 *>(knn_dist) + pm.out_off;
+    if (tid == 0) s_base = 0;
+    __syncthreads();
+    for (int q0 = 0; q0 < pd.nq; q0 += kCrossThreads * kCrossPer) {
+        const int qa = q0 + tid * kCrossPer;
+        int2 iv[kCrossPer]; float2 dv[kCrossPer];
+#pragma unroll
+        for (int u = 0; u < kCrossPer; ++u) { const int q = min(qa + u, pd.nq - 1); iv[u] = fi[q]; dv[u] = fd[q]; }
+        bool pass[kCrossPer];
+        int cnt = 0;
+#pragma unroll
+        for (int u = 0; u < kCrossPer; ++u) {
+            const int f = iv[u].x;
+            // (unsigned) f < pm.nq: a forward index is a row of the train set, the mirror's query set -- checked, not assumed
+            bool keep = qa + u < pd.nq && (unsigned)f < (unsigned)pm.nq && (!use_ratio || ratio_ok(f, iv[u].y, dv[u].x, dv[u].y, ratio));
+            if (keep) {
+                const int2 r = mi[f];
+                keep = r.x == qa + u;
+                if (keep && use_ratio) { const float2 rd = md[f]; keep = ratio_ok(r.x, r.y, rd.x, rd.y, ratio); }
+            }
+            pass[u] = keep;
+            cnt += keep ? 1 : 0;
+        }
+        // exclusive scan of cnt over the workgroup (as ratio_compact_pair)
+        int incl = cnt;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const int v = __shfl_up(incl, o);
+            if (lane >= o) incl += v;
+        }
+        if (lane == 63) s_wave[wave] = incl;
+        __syncthreads();
+        int off = s_base;
+        for (int w = 0; w < wave; ++w) off += s_wave[w];
+        size_t o = (size_t)pd.out_off + off + (incl - cnt);
+#pragma unroll
+        for (int u = 0; u < kCrossPer; ++u) {
+            if (pass[u]) { query_idx[o] = qa + u; train_idx[o] = iv[u].x; distance[o] = dv[u].x; ++o; }
+        }
+        __syncthreads();
+        if (tid == 0) { int t = 0; for (int w = 0; w < kCrossThreads / 64; ++w) t += s_wave[w]; s_base += t; }
+        __syncthreads();
+    }
+    if (tid == 0) n_out[blockIdx.x] = s_base;
+}
+
+// ---------------------------------------------------------------------------------------------
 // launchers
 
 static inline int div_up(long long a, long long b) { return (int)((a + b - 1) / b); }
@@ -3400,6 +3473,16 @@ int launch_ratio_compact(hipStream_t st, const PairDesc *pairs, int n_pairs, con
     if (n_pairs <= 0) return ESFM_OK;
     hipLaunchKernelGGL(ratio_compact_kernel, dim3(n_pairs), dim3(kRatioThreads), 0, st, pairs, knn_idx, knn_dist, ratio, query_idx,
                        train_idx, distance, n_out);
+    ESFM_HIP_TRY(hipGetLastError());
+    return ESFM_OK;
+}
+
+int launch_cross_check_compact(hipStream_t st, const PairDesc *pairs, int n_pairs, const int32_t *knn_idx, const float *knn_dist, int use_ratio,
+                               double ratio, int32_t *query_idx, int32_t *train_idx, float *distance, int32_t *n_out)
+{
+    if (n_pairs <= 0) return ESFM_OK;
+    hipLaunchKernelGGL(cross_check_compact_kernel, dim3(n_pairs), dim3(kCrossThreads), 0, st, pairs, n_pairs, knn_idx, knn_dist, use_ratio, ratio,
+                       query_idx, train_idx, distance, n_out);
     ESFM_HIP_TRY(hipGetLastError());
     return ESFM_OK;
 }

@@ -86,6 +86,11 @@ int launch_hamming_knn(hipStream_t st, int nbytes, const void *desc, long long t
 int launch_buffer_checksum(hipStream_t st, const void *buf, size_t bytes, unsigned long long *out);
 int launch_pack_match_lists(hipStream_t st, const long long *tab, const int32_t *n_out, int n_pairs, const int32_t *sq, const int32_t *stn, const float *sd,
                             int32_t *dq, int32_t *dtn, float *dd);
+// pairs: a mirrored table of 2 n_pairs entries (pair n_pairs + p is pair p with query and train swapped), knn_idx / knn_dist the
+// 2-NN tables of all of them with their markers.  Pair p keeps query q iff F = knn_idx[2 (out_off[p] + q)] >= 0 and the mirror's
+// nearest of row F is q (use_ratio: and ratio_ok on both records); output as launch_ratio_compact's, for the first n_pairs pairs.
+int launch_cross_check_compact(hipStream_t st, const PairDesc *pairs, int n_pairs, const int32_t *knn_idx, const float *knn_dist, int use_ratio,
+                               double ratio, int32_t *query_idx, int32_t *train_idx, float *distance, int32_t *n_out);
 int launch_ratio_compact(hipStream_t st, const PairDesc *pairs, int n_pairs, const int32_t *knn_idx, const float *knn_dist,
                          double ratio, int32_t *query_idx, int32_t *train_idx, float *distance, int32_t *n_out);
 

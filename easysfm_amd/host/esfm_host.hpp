@@ -178,16 +178,24 @@ public:
         return true;
     }
 
+    // cross_check: keep mutual nearest neighbours (esfm_match_cross_*, the mutual_nn branch of feature_match.py:24-27) that also pass
+    // the ratio test in both directions; ratio_thre == 0 in that mode: mutual nearest neighbours alone
     bool matchFeaturesORB(frame_t &cur_frame_1, frame_t &cur_frame_2, std::vector<DMatch> &matches, double ratio_thre = 0.8,
-                          bool show = false)
+                          bool show = false, bool cross_check = false)
     {
-        return run(cur_frame_1, cur_frame_2, matches, ratio_thre, true, "ORB");
+        return run(cur_frame_1, cur_frame_2, matches, ratio_thre, true, "ORB", cross_check);
     }
 
     bool matchFeaturesSURF(frame_t &cur_frame_1, frame_t &cur_frame_2, std::vector<DMatch> &matches, double ratio_thre = 0.5,
-                           bool show = false)
+                           bool show = false, bool cross_check = false)
     {
-        return run(cur_frame_1, cur_frame_2, matches, ratio_thre, false, "SURF");
+        return run(cur_frame_1, cur_frame_2, matches, ratio_thre, false, "SURF", cross_check);
+    }
+
+    // what the "# Correspondence" line names as the filter
+    static const char *filter_name(bool cross_check, double ratio_thre)
+    {
+        return !cross_check ? "Lowe ratio test" : (ratio_thre == 0.0 ? "cross-check" : "Lowe ratio test + cross-check");
     }
 
     // Which two frames start the reconstruction (the contract of feature_matching.cpp:160-229, defaults feature_matching.h:26): every
@@ -253,9 +261,10 @@ public:
     // The pair loop of test/sfm.cpp:140-161 in ONE call: matchFeatures{SURF,ORB}(frames[pairs[p].first], frames[pairs[p].second],
     // matches[p]) for every listed pair -- every frame's descriptors uploaded once, one launch sequence for the whole list
     // (esfm_match_pairs), the per-pair lines of feature_matching.cpp:96-97 / :141-142 printed with the call's time shared out
-    // evenly.  matches[p] is appended to, like the single-pair members.
+    // evenly.  matches[p] is appended to, like the single-pair members.  cross_check: as for the single-pair members
+    // (esfm_match_cross_pairs).
     bool matchFeaturesAllPairs(std::vector<frame_t> &frames, const std::vector<std::pair<int, int>> &pairs, bool hamming,
-                               std::vector<std::vector<DMatch>> &matches, double ratio_thre = -1.0)
+                               std::vector<std::vector<DMatch>> &matches, double ratio_thre = -1.0, bool cross_check = false)
     {
         if (ratio_thre < 0) ratio_thre = hamming ? 0.8 : 0.5;               // the members' defaults (feature_matching.h:17-21)
         matches.resize(pairs.size());
@@ -280,8 +289,12 @@ public:
         std::vector<float> d(std::max<size_t>(total, 1));
         std::vector<int64_t> out_off(pairs.size() + 1);
         auto tic = std::chrono::steady_clock::now();
-        const int rc = esfm_match_pairs(default_ctx(), hamming ? ESFM_HAMMING : ESFM_L2_F32, bank.data(), off.data(), int(frames.size()), width, pl.data(),
-                                        int(pairs.size()), ratio_thre, qi.data(), ti.data(), d.data(), n_out.data(), out_off.data());
+        const int rc = cross_check
+                           ? esfm_match_cross_pairs(default_ctx(), hamming ? ESFM_HAMMING : ESFM_L2_F32, bank.data(), off.data(), int(frames.size()), width,
+                                                    pl.data(), int(pairs.size()), ratio_thre != 0.0, ratio_thre, qi.data(), ti.data(), d.data(), n_out.data(),
+                                                    out_off.data())
+                           : esfm_match_pairs(default_ctx(), hamming ? ESFM_HAMMING : ESFM_L2_F32, bank.data(), off.data(), int(frames.size()), width, pl.data(),
+                                              int(pairs.size()), ratio_thre, qi.data(), ti.data(), d.data(), n_out.data(), out_off.data());
         if (rc != ESFM_OK) { std::cerr << esfm_last_error() << std::endl; return false; }
         const std::chrono::duration<double> dt = std::chrono::steady_clock::now() - tic;
         for (size_t p = 0; p < pairs.size(); ++p) {
@@ -289,7 +302,8 @@ public:
             for (int k = 0; k < n_out[p]; ++k) matches[p].push_back(DMatch(qi[o + size_t(k)], ti[o + size_t(k)], 0, d[o + size_t(k)]));
             if (!quiet) {
                 std::cout << "match " << (hamming ? "ORB" : "SURF") << " cost = " << dt.count() / double(pairs.size()) << " seconds. " << std::endl;
-                std::cout << "# Correspondence: Initial [ " << frames[size_t(pairs[p].first)].descriptors.rows << " ]  Filtered by Lowe ratio test [ " << n_out[p]
+                std::cout << "# Correspondence: Initial [ " << frames[size_t(pairs[p].first)].descriptors.rows << " ]  Filtered by "
+                          << filter_name(cross_check, ratio_thre) << " [ " << n_out[p]
                           << " ]" << std::endl;
             }
         }
@@ -306,7 +320,7 @@ private:
         return buf.get();
     }
 
-    bool run(frame_t &f1, frame_t &f2, std::vector<DMatch> &matches, double ratio, bool hamming, const char *tag)
+    bool run(frame_t &f1, frame_t &f2, std::vector<DMatch> &matches, double ratio, bool hamming, const char *tag, bool cross_check)
     {
         const DescMat &q = f1.descriptors, &t = f2.descriptors;
         if (q.rows > 0 && t.rows > 0 && (q.cols != t.cols || q.type != t.type)) { std::cerr << "descriptor shapes differ\n"; return false; }
@@ -315,7 +329,14 @@ private:
         std::vector<int32_t> qi(size_t(std::max(q.rows, 1))), ti(size_t(std::max(q.rows, 1)));
         std::vector<float> d(size_t(std::max(q.rows, 1)));
         int32_t n = 0;
-        int rc = hamming ? esfm_match_hamming(default_ctx(), q.ptr<uint8_t>(), q.rows, t.ptr<uint8_t>(), t.rows, q.cols, ratio, qi.data(),
+        int rc;
+        if (cross_check)
+            rc = hamming ? esfm_match_cross_hamming(default_ctx(), q.ptr<uint8_t>(), q.rows, t.ptr<uint8_t>(), t.rows, q.cols, ratio != 0.0, ratio,
+                                                    qi.data(), ti.data(), d.data(), &n)
+                         : esfm_match_cross_l2_f32(default_ctx(), q.ptr<float>(), q.rows, t.ptr<float>(), t.rows, q.cols, ratio != 0.0, ratio, qi.data(),
+                                                   ti.data(), d.data(), &n);
+        else
+            rc = hamming ? esfm_match_hamming(default_ctx(), q.ptr<uint8_t>(), q.rows, t.ptr<uint8_t>(), t.rows, q.cols, ratio, qi.data(),
                                               ti.data(), d.data(), &n)
                          : esfm_match_l2_f32(default_ctx(), q.ptr<float>(), q.rows, t.ptr<float>(), t.rows, q.cols, ratio, qi.data(),
                                              ti.data(), d.data(), &n);
@@ -325,7 +346,7 @@ private:
         if (!quiet) {
             std::chrono::duration<double> dt = std::chrono::steady_clock::now() - tic;
             std::cout << "match " << tag << " cost = " << dt.count() << " seconds. " << std::endl;
-            std::cout << "# Correspondence: Initial [ " << q.rows << " ]  Filtered by Lowe ratio test [ " << matches.size() - before
+            std::cout << "# Correspondence: Initial [ " << q.rows << " ]  Filtered by " << filter_name(cross_check, ratio) << " [ " << matches.size() - before
                       << " ]" << std::endl;
         }
         return true;

@@ -1,6 +1,7 @@
 // ./bin/sfm_native -- the reference executable's command line (cpp_code/test/sfm.cpp:32-50, cpp_code/script/run_fountain_small.sh:22-24)
 // as a native C++ program over the C ABI of libesfm_hip.so, through the host mirror of the reference's classes
-// (esfm_host.hpp).  Same thirteen positional arguments in the same order, same ASCII .ply of PointXYZRGB at argv[5], exit
+// (esfm_host.hpp).  Same thirteen positional arguments in the same order (an optional fourteenth picks the match filter: ratio,
+// the reference's and the default; cross; ratio+cross), same ASCII .ply of PointXYZRGB at argv[5], exit
 // status 1 on success like the reference (sfm.cpp:339).  The control flow is the one of
 // easysfm_amd/pipeline.py (the Python twin of this file); the (i, j < i) pair loop of sfm.cpp:140-170 is ONE batched call per stage
 // (every frame's descriptors uploaded once, one match launch sequence, one RANSAC / pose / depth batch -- INTEGRATION.md section 2;
@@ -78,11 +79,15 @@ int dump_image(const char *in, const char *out)
 int main(int argc, char **argv)
 {
     if (argc == 4 && std::string(argv[1]) == "--dump-image") return dump_image(argv[2], argv[3]);
-    if (argc != 14) {
+    // optional 14th argument: the match filter -- ratio (the reference's, default), cross (mutual nearest neighbours) or ratio+cross
+    const std::string match_filter = argc == 15 ? argv[14] : "ratio";
+    if ((argc != 14 && argc != 15) || (match_filter != "ratio" && match_filter != "cross" && match_filter != "ratio+cross")) {
         std::cerr << "usage: sfm_native image_folder image_list calib_K_file calib_distort_file output.ply feature_type(S) feature_parameter "
-                     "repro_dis_ransac find_init_frames ba_calib_change_tolerance ba_frequency launch_viewer view_sphere" << std::endl;
+                     "repro_dis_ransac find_init_frames ba_calib_change_tolerance ba_frequency launch_viewer view_sphere [match_filter: ratio | cross | ratio+cross]"
+                  << std::endl;
         return 2;
     }
+    const bool cross_check = match_filter != "ratio";
     const std::string image_data_path = argv[1], image_list_path = argv[2], calib_file_path = argv[3], distort_file_path = argv[4],
                       output_file_path = argv[5];
     char using_feature = argv[6][0];
@@ -185,8 +190,8 @@ int main(int argc, char **argv)
                     frame_pair_t &g = graph[size_t(i)][size_t(j)];
                     std::vector<DMatch> temp_matches, inlier_matches;
                     StageClock pc;
-                    if (using_feature == 'O') fm.matchFeaturesORB(frames[size_t(i)], frames[size_t(j)], temp_matches);   // sfm.cpp:153-160
-                    else fm.matchFeaturesSURF(frames[size_t(i)], frames[size_t(j)], temp_matches);
+                    if (using_feature == 'O') fm.matchFeaturesORB(frames[size_t(i)], frames[size_t(j)], temp_matches, match_filter == "cross" ? 0.0 : 0.8, false, cross_check);   // sfm.cpp:153-160
+                    else fm.matchFeaturesSURF(frames[size_t(i)], frames[size_t(j)], temp_matches, match_filter == "cross" ? 0.0 : 0.5, false, cross_check);
                     t_match += pc.lap();
                     if (int(temp_matches.size()) > num_min_pair) {
                         Matrix4f T = Matrix4f::Identity();
@@ -207,7 +212,7 @@ int main(int argc, char **argv)
             std::vector<std::pair<int, int>> pairs;
             for (int i = 0; i < frame_number; ++i) for (int j = 0; j < i; ++j) pairs.emplace_back(i, j);
             std::vector<std::vector<DMatch>> temp_matches;
-            if (!fm.matchFeaturesAllPairs(frames, pairs, using_feature == 'O', temp_matches)) return 3;
+            if (!fm.matchFeaturesAllPairs(frames, pairs, using_feature == 'O', temp_matches, match_filter == "cross" ? 0.0 : -1.0, cross_check)) return 3;
             t_match += pc.lap();
             std::vector<std::pair<int, int>> jobs;
             std::vector<std::vector<DMatch>> job_matches;

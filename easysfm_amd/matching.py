@@ -92,6 +92,56 @@ def match_pairs_host(sets: Sequence[np.ndarray], pairs, ratio: float, metric: in
     return [(qi[o:o + k].copy(), ti[o:o + k].copy(), d[o:o + k].copy()) for o, k in zip(out_off[:-1], n_out[:len(pairs)])]
 
 
+# ---- cross-check (mutual nearest neighbour), include/esfm.h "Cross-check matching": ratio=None is cross alone, a number is
+# ratio+cross (the ratio test in both directions as well)
+def _cross_args(ratio):
+    return (0, 0.0) if ratio is None else (1, float(ratio))
+
+
+def _match_cross(fn, q, t, ratio, ctx):
+    if q.shape[1] != t.shape[1]:
+        raise ValueError("descriptor widths differ")
+    use_ratio, r = _cross_args(ratio)
+    nq = q.shape[0]
+    qi = np.empty(max(nq, 1), np.int32); ti = np.empty(max(nq, 1), np.int32); d = np.empty(max(nq, 1), np.float32)
+    n = C.c_int32(0)
+    check(fn(ctx.handle, _ptr(q), nq, _ptr(t), t.shape[0], q.shape[1], use_ratio, r, _ptr(qi), _ptr(ti), _ptr(d), C.byref(n)))
+    return qi[:n.value].copy(), ti[:n.value].copy(), d[:n.value].copy()
+
+
+def match_cross_l2(q, t, ratio: Optional[float] = None, ctx: Optional[Context] = None):
+    """Mutual nearest neighbours of float descriptors (cv2.BFMatcher(NORM_L2, crossCheck=True) as feature_match.py:24-27 uses it, under
+    the strict rule of esfm.h); with `ratio`, also Lowe's test in both directions.  Returns (queryIdx, trainIdx, distance) arrays."""
+    ctx = ctx or default_context()
+    return _match_cross(lib().esfm_match_cross_l2_f32, _as_desc(q, np.float32), _as_desc(t, np.float32), ratio, ctx)
+
+
+def match_cross_hamming(q, t, ratio: Optional[float] = None, ctx: Optional[Context] = None):
+    """match_cross_l2 for binary descriptors (Hamming distance)."""
+    ctx = ctx or default_context()
+    return _match_cross(lib().esfm_match_cross_hamming, _as_desc(q, np.uint8), _as_desc(t, np.uint8), ratio, ctx)
+
+
+def match_cross_pairs_host(sets: Sequence[np.ndarray], pairs, ratio: Optional[float] = None, metric: int = ESFM_L2_F32,
+                           ctx: Optional[Context] = None):
+    """esfm_match_cross_pairs: match_pairs_host with the cross-check filter.  Returns [(queryIdx, trainIdx, distance)] per pair."""
+    ctx = ctx or default_context()
+    dt = np.float32 if metric == ESFM_L2_F32 else np.uint8
+    sets = [_as_desc(s_, dt) for s_ in sets]
+    width = sets[0].shape[1]
+    off = np.zeros(len(sets) + 1, np.int32)
+    np.cumsum([s_.shape[0] for s_ in sets], out=off[1:])
+    bank = np.ascontiguousarray(np.concatenate(sets, axis=0)) if off[-1] else np.zeros((1, width), dt)
+    pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+    total = int(sum(sets[i].shape[0] for i, _ in pairs))
+    use_ratio, r = _cross_args(ratio)
+    qi = np.zeros(max(total, 1), np.int32); ti = np.zeros(max(total, 1), np.int32); d = np.zeros(max(total, 1), np.float32)
+    n_out = np.zeros(max(len(pairs), 1), np.int32); out_off = np.zeros(len(pairs) + 1, np.int64)
+    check(lib().esfm_match_cross_pairs(ctx.handle, metric, _ptr(bank), _ptr(off), len(sets), width, _ptr(pairs), len(pairs), use_ratio, r,
+                                       _ptr(qi), _ptr(ti), _ptr(d), _ptr(n_out), _ptr(out_off)))
+    return [(qi[o:o + k].copy(), ti[o:o + k].copy(), d[o:o + k].copy()) for o, k in zip(out_off[:-1], n_out[:len(pairs)])]
+
+
 class FeatureMatching:
     """Mirror of p3dv::FeatureMatching's matching members (feature_matching.h:17-21)."""
 
@@ -103,18 +153,26 @@ class FeatureMatching:
         return self._ctx or default_context()
 
     def matchFeaturesORB(self, cur_frame_1: Frame, cur_frame_2: Frame, matches: List[DMatch],
-                         ratio_thre: float = 0.8, show: bool = False) -> bool:
+                         ratio_thre: float = 0.8, show: bool = False, cross_check: bool = False) -> bool:
         """feature_matching.cpp:71-97.  Query = cur_frame_1, train = cur_frame_2; survivors are
-        APPENDED to `matches` (the reference never clears it, :90)."""
-        qi, ti, d = match_hamming(cur_frame_1.descriptors, cur_frame_2.descriptors, ratio_thre, self.ctx)
+        APPENDED to `matches` (the reference never clears it, :90).  cross_check: keep mutual nearest neighbours
+        that also pass the ratio test in both directions (match_cross_hamming)."""
+        if cross_check:
+            qi, ti, d = match_cross_hamming(cur_frame_1.descriptors, cur_frame_2.descriptors, ratio_thre, self.ctx)
+        else:
+            qi, ti, d = match_hamming(cur_frame_1.descriptors, cur_frame_2.descriptors, ratio_thre, self.ctx)
         matches.extend(DMatch(int(a), int(b), float(c)) for a, b, c in zip(qi, ti, d))
         return True
 
     def matchFeaturesSURF(self, cur_frame_1: Frame, cur_frame_2: Frame, matches: List[DMatch],
-                          ratio_thre: float = 0.5, show: bool = False) -> bool:
+                          ratio_thre: float = 0.5, show: bool = False, cross_check: bool = False) -> bool:
         """feature_matching.cpp:115-142 with the exact brute-force matcher the Python prototype
-        uses (feature_match.py:33-34) instead of the approximate FlannBasedMatcher (:120)."""
-        qi, ti, d = match_l2(cur_frame_1.descriptors, cur_frame_2.descriptors, ratio_thre, self.ctx)
+        uses (feature_match.py:33-34) instead of the approximate FlannBasedMatcher (:120).  cross_check: keep mutual
+        nearest neighbours that also pass the ratio test in both directions (match_cross_l2)."""
+        if cross_check:
+            qi, ti, d = match_cross_l2(cur_frame_1.descriptors, cur_frame_2.descriptors, ratio_thre, self.ctx)
+        else:
+            qi, ti, d = match_l2(cur_frame_1.descriptors, cur_frame_2.descriptors, ratio_thre, self.ctx)
         matches.extend(DMatch(int(a), int(b), float(c)) for a, b, c in zip(qi, ti, d))
         return True
 
@@ -330,6 +388,18 @@ class PairMatcher:
         check(lib().esfm_match_pairs_dev(
             self.ctx.handle, b.metric, C.c_void_p(b.data.data_ptr()), _ptr(b.row_offset), b.n_sets, b.width,
             _ptr(self.pairs), len(self.pairs), float(ratio),
+            C.c_void_p(self.query_idx.data_ptr()), C.c_void_p(self.train_idx.data_ptr()),
+            C.c_void_p(self.distance.data_ptr()), C.c_void_p(self.n_out.data_ptr()), _ptr(self.offset)))
+        return PairMatches(self.pairs, self.offset, self.n_out, self.query_idx, self.train_idx, self.distance, self.ctx)
+
+    def match_cross(self, ratio: Optional[float] = None) -> PairMatches:
+        """esfm_match_cross_pairs_dev: mutual nearest neighbours of every pair (ratio=None), or ratio+cross (Lowe's test in both
+        directions as well).  Enqueues; does not synchronise."""
+        b = self.bank
+        use_ratio, r = _cross_args(ratio)
+        check(lib().esfm_match_cross_pairs_dev(
+            self.ctx.handle, b.metric, C.c_void_p(b.data.data_ptr()), _ptr(b.row_offset), b.n_sets, b.width,
+            _ptr(self.pairs), len(self.pairs), use_ratio, r,
             C.c_void_p(self.query_idx.data_ptr()), C.c_void_p(self.train_idx.data_ptr()),
             C.c_void_p(self.distance.data_ptr()), C.c_void_p(self.n_out.data_ptr()), _ptr(self.offset)))
         return PairMatches(self.pairs, self.offset, self.n_out, self.query_idx, self.train_idx, self.distance, self.ctx)

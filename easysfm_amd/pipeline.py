@@ -31,11 +31,18 @@ class FramePair:
     appro_depth: float = 1.0
 
 
+MATCH_FILTERS = ("ratio", "cross", "ratio+cross")
+
+
 def match_and_verify_all_pairs(frames: Sequence[Frame], use_feature: str = "S", ransac_reproj_distance: float = 1.0,
-                               num_min_pair: int = 20, ctx: Optional[Context] = None) -> List[List[FramePair]]:
+                               num_min_pair: int = 20, ctx: Optional[Context] = None, match_filter: str = "ratio") -> List[List[FramePair]]:
     """sfm.cpp:140-167 for every (i, j < i): matchFeatures{SURF,ORB}(frames[i], frames[j]); if more than num_min_pair
     matches survive, estimate2D2D_E5P_RANSAC (threshold = ransac_reproj_distance, prob 0.99) and getDepthFast on the inliers;
-    otherwise no inliers, identity transform, depth 1 (:147-148).  Returns img_match_graph[i][j]."""
+    otherwise no inliers, identity transform, depth 1 (:147-148).  Returns img_match_graph[i][j].
+    match_filter: "ratio" (the reference's one-way Lowe test), "cross" (mutual nearest neighbours) or "ratio+cross" (both, the
+    ratio test in both directions: esfm.h "Cross-check matching")."""
+    if match_filter not in MATCH_FILTERS:
+        raise ValueError(f"match_filter must be one of {MATCH_FILTERS}, not {match_filter!r}")
     ctx = ctx or default_context()
     n = len(frames)
     metric = ESFM_HAMMING if use_feature == "O" else ESFM_L2_F32
@@ -45,7 +52,11 @@ def match_and_verify_all_pairs(frames: Sequence[Frame], use_feature: str = "S", 
     if len(pairs) == 0:
         return graph
     bank = DescriptorBank([f.descriptors for f in frames], metric, device=f"cuda:{ctx.device}")
-    res = PairMatcher(bank, pairs, ctx).match(ratio).to_host()      # PairMatcher drains torch's upload stream before its first launch
+    pm = PairMatcher(bank, pairs, ctx)                                  # drains torch's upload stream before its first launch
+    if match_filter == "ratio":
+        res = pm.match(ratio).to_host()
+    else:
+        res = pm.match_cross(ratio if match_filter == "ratio+cross" else None).to_host()
     # RANSAC + pose for every pair with enough matches, in shared launches
     sel = [k for k in range(len(pairs)) if len(res[k][0]) > num_min_pair]
     if sel:
@@ -122,13 +133,13 @@ def propagate_track_ids(frames: Sequence[Frame], graph: List[List[FramePair]]):
 
 def run_sfm(frames: List[Frame], output_file: Optional[str] = None, use_feature: str = "S", ransac_reproj_distance: float = 1.0,
             use_track_frames_as_init: bool = True, fix_calib_tolerance_BA: float = 0.0, frequency_BA: int = 4,
-            ctx: Optional[Context] = None, verbose: bool = False):
+            ctx: Optional[Context] = None, verbose: bool = False, match_filter: str = "ratio"):
     """sfm.cpp:128-339.  Returns (sparse cloud before the final filter, filtered cloud, img_match_graph)."""
     ctx = ctx or default_context()
     fm, ee = FeatureMatching(ctx), MotionEstimator(ctx)
     for f in frames:
         f.init_pixel_ids()
-    graph = match_and_verify_all_pairs(frames, use_feature, ransac_reproj_distance, 20, ctx)
+    graph = match_and_verify_all_pairs(frames, use_feature, ransac_reproj_distance, 20, ctx, match_filter)
     track, n_unique = propagate_track_ids(frames, graph)
     if verbose:
         for i in range(len(frames)):

@@ -97,7 +97,8 @@ typedef enum esfm_kernel_id {
     ESFM_K_UNDISTORT = 11,    /* undistort_remap_kernel                                         */
     ESFM_K_ORB_FAST = 12,     /* orb_fast_kernel: FAST-9/16 score of every pyramid pixel          */
     ESFM_K_L2_SECOND = 13,    /* l2_finish_kernel: everything behind the one-product pass (re-rank of the ratio screen's survivors, threshold filter, ratio test, compaction) */
-    ESFM_K_COUNT = 14
+    ESFM_K_CROSS_CHECK = 14,  /* cross_check_compact_kernel: the mutual-nearest-neighbour join of esfm_match_cross_*       */
+    ESFM_K_COUNT = 15
 } esfm_kernel_id;
 int esfm_ctx_set_kernel_timing(esfm_ctx *ctx, int enable);
 int esfm_ctx_kernel_time(esfm_ctx *ctx, int kernel_id, double *total_ms, int64_t *launches);
@@ -213,6 +214,37 @@ int esfm_knn2_pairs_screened_dev(esfm_ctx *ctx, esfm_metric metric, const void *
                                  const int32_t *set_row_offset, int n_sets, int width,
                                  const int32_t *pairs, int n_pairs, double ratio,
                                  int32_t *knn_idx_dev, float *knn_dist_dev, int64_t *out_offset);
+
+/*
+ * Cross-check matching: the mutual-nearest-neighbour filter of the reference's Python prototype (python_code/feature_match.py:24-27,
+ * its `mutual_nn` branch: cv2.BFMatcher(cv2.NORM_L2, crossCheck=True).match), which the C++ matcher lacks (SURVEY.md:196: one direction
+ * only, no cross-check).  Distances, the (distance, index) ordering with ties to the lower index, and NaN handling are esfm_knn2_*'s.
+ * For one pair (query set Q, train set T): F(q) = the nearest train row of query row q, R(t) = the nearest query row of train row t
+ * (the same rule with the roles swapped: ties go to the lower QUERY index).
+ *   use_ratio = 0 (cross; `ratio` ignored): q emits (q, F(q), d(q, F(q))) iff F(q) >= 0 and R(F(q)) == q -- strict mutual nearest
+ *                 neighbour, also with nq == 1 or nt == 1.
+ *   use_ratio = 1 (ratio+cross): the same, and the ratio test of esfm_match_pairs_dev ((double)d0 < ratio * (double)d1) holds for
+ *                 row q of the forward table AND for row F(q) of the reverse one (both directions, as COLMAP does).  The result of
+ *                 pair (i, j) is then exactly the transpose of that of pair (j, i), and a subset of esfm_match_pairs_dev's list.
+ * This is the strict rule; OpenCV's crossCheck is not claimed: it may keep, for a query, the closest of the train rows whose nearest
+ * query it is, which is not always a mutual pair.  Output layout as esfm_match_pairs_dev (pair p owns [out_offset[p], out_offset[p] + nq_p),
+ * the first n_out[p] entries valid, query-ascending; the distance is the forward d0, bit-identical to the reverse one).
+ * use_ratio outside {0, 1}, or a NaN ratio with use_ratio = 1: ESFM_ERR_INVALID_ARG.
+ * Both directions run in one knn pass over a mirrored pair list (the pairs, then each with query and train swapped), so every query
+ * set is also a train set: sets are limited to 2^21 - 1 rows, and a 64-float L2 query set of more than 65 536 rows takes the
+ * three-product fallback instead of the one-product pass (correct, slower).  The prepared state (esfm_match_prepare_dev) serves both.
+ */
+int esfm_match_cross_l2_f32(esfm_ctx *ctx, const float *q, int nq, const float *t, int nt, int dim, int use_ratio, double ratio,
+                            int32_t *query_idx, int32_t *train_idx, float *distance, int32_t *n_out);
+int esfm_match_cross_hamming(esfm_ctx *ctx, const uint8_t *q, int nq, const uint8_t *t, int nt, int nbytes, int use_ratio,
+                             double ratio, int32_t *query_idx, int32_t *train_idx, float *distance, int32_t *n_out);
+int esfm_match_cross_pairs_dev(esfm_ctx *ctx, esfm_metric metric, const void *desc_dev, const int32_t *set_row_offset, int n_sets,
+                               int width, const int32_t *pairs, int n_pairs, int use_ratio, double ratio, int32_t *query_idx_dev,
+                               int32_t *train_idx_dev, float *distance_dev, int32_t *n_out_dev, int64_t *out_offset /*host, n_pairs+1*/);
+/* Host-pointer form, as esfm_match_pairs: upload once, prepare once, packed read-back.  Synchronises. */
+int esfm_match_cross_pairs(esfm_ctx *ctx, esfm_metric metric, const void *desc_host, const int32_t *set_row_offset, int n_sets,
+                           int width, const int32_t *pairs, int n_pairs, int use_ratio, double ratio, int32_t *query_idx,
+                           int32_t *train_idx, float *distance, int32_t *n_out /*n_pairs*/, int64_t *out_offset /*n_pairs+1*/);
 
 /* Counters of the last L2 batched call on this context (after a synchronise):
  * queries whose MFMA candidate list could not be certified and were re-scanned
