@@ -79,6 +79,41 @@ struct DevBuf {
     template <class T> T *as() const { return reinterpret_cast<T *>(ptr); }
 };
 
+// The matcher's context state (match_api.cpp alone touches it).
+struct MatchState {
+    DevBuf bank;   // esfm_match_pairs (host-pointer batched form): the uploaded descriptor rows of all sets
+    DevBuf norms, pair_tab, knn_idx, flagged, counters;
+    DevBuf pair_cnt, pair_list;   // three-product pass: its uncertified queries binned per pair (one counter per pair; the pair's slice of the query numbering)
+    // one-product pass, per-pair counters in two phases (a call fills phase l2_phase, its first kernel zeroes the other for the next
+    // call): the queries the re-rank left uncertified, listed in pair_list2, and the ratio screen's survivors, 48-byte entries in surv_list
+    DevBuf unc_cnt[2], surv_cnt[2], pair_list2, surv_list;
+    int l2_phase = 0;                  // phase the NEXT one-product call fills
+    int l2_phase_pairs[2] = {0, 0};    // entries of each phase that may be non-zero
+    int32_t *counters_cur = nullptr;   // the 16 counters of the last L2 call (esfm_match_last_stats / _second_pass / _flagged)
+    DevBuf fin_done;   // l2_finish_kernel / hamming_fp4_kernel: per-pair arrival counters
+    DevBuf knn_d2;     // exact second-best d^2 of the queries the one-product pass left uncertified (the refine pass's thresholds)
+    DevBuf l2_hi;      // one-product pass: bf16(t) and bf16(-2 q) images (128 B per row each) and the two residual norms per row
+    DevBuf hm_exp;     // Hamming: the FP4 form's nibble images or the i8 form's 0/1 bytes + start values (260 B per row); three-product pass: its split images
+    // esfm_match_prepare_dev: the derived per-row operands (bf16 images, norms, residual norms; the Hamming images) in l2_hi / norms /
+    // hm_exp belong to this descriptor buffer and are not recomputed by the match calls
+    const void *prep_desc = nullptr;
+    int prep_metric = 0, prep_width = 0;
+    bool prep_hm_fp4 = false;   // Hamming: hm_exp holds the FP4 form's nibble images (hamming_fp4_kernel), not the byte image of the i8 form
+    int64_t prep_rows = 0;
+    // esfm_ctx_set_prepared_check: the prepared buffer's fingerprint ([0] at prepare, [1] re-derived by every match call that relies on it)
+    int prep_check = 0;
+    bool prep_has_sum = false;
+    DevBuf prep_sum;
+    int64_t last_n_queries = 0;
+    size_t last_pair_bytes = 0;   // the pair table last uploaded (its copy is in esfm_ctx::pinned)
+    int l2_audit = 0;   // esfm_ctx_set_l2_audit: 0 product path, 1 no re-scan, 2 exact scan of every query, 3 one-product pass alone, 4 one-product pass alone with the ratio screen's rejections listed
+    void release()   // (every DevBuf above)
+    {
+        for (DevBuf *b : {&bank, &norms, &pair_tab, &knn_idx, &flagged, &counters, &pair_cnt, &pair_list, &unc_cnt[0], &unc_cnt[1], &surv_cnt[0],
+                          &surv_cnt[1], &pair_list2, &surv_list, &fin_done, &knn_d2, &l2_hi, &hm_exp, &prep_sum}) b->release();
+    }
+};
+
 }  // namespace esfm
 
 struct esfm_ctx {
@@ -86,36 +121,13 @@ struct esfm_ctx {
     hipStream_t stream = nullptr;
     bool owns_stream = false;
     int num_cu = 256;
-    // matching scratch
-    esfm::DevBuf bank;   // esfm_match_pairs (host-pointer batched form): the uploaded descriptor rows of all sets
-    esfm::DevBuf norms, pair_tab, knn_idx, knn_dist, flagged, counters, stage_a, stage_b, stage_c, stage_d, stage_e;
-    esfm::DevBuf pair_cnt, pair_list;   // uncertified queries of the L2 pass binned per pair (one counter per pair; the pair's slice of the query numbering)
-    esfm::DevBuf pair_cnt2, pair_list2;   // the same for the second (three-product) pass over what the one-product pass left uncertified
-    esfm::DevBuf pair_cnt2b;           // second phase of pair_cnt2: a call fills one phase, its one-product kernel zeroes the other for the next call
-    int l2_phase = 0;                  // phase the NEXT one-product call fills
-    int l2_phase_pairs[2] = {0, 0};    // entries of each phase that may be non-zero
-    int32_t *counters_cur = nullptr;   // the 16 counters of the last L2 call (esfm_match_last_stats / _second_pass / _flagged)
-    esfm::DevBuf fin_done;             // l2_finish_kernel: per-pair arrival counters
-    esfm::DevBuf surv_cnt, surv_cntb, surv_list;   // the ratio screen's survivors: per-pair counts (two phases), 48-byte entries in the pair's slice of the query numbering
-    // esfm_match_prepare_dev: the derived per-row operands (bf16 images, norms, residual norms; 0/1 byte image for Hamming) in l2_hi /
-    // norms / hm_exp belong to this descriptor buffer and are not recomputed by the match calls
-    const void *prep_desc = nullptr;
-    int prep_metric = 0, prep_width = 0;
-    bool prep_hm_fp4 = false;          // Hamming: hm_exp holds the FP4 form's nibble images (hamming_fp4_kernel), not the byte image of the i8 form
-    int64_t prep_rows = 0;
-    // esfm_ctx_set_prepared_check: the prepared buffer's fingerprint ([0] at prepare, [1] re-derived by every match call that relies on it)
-    int prep_check = 0;
-    bool prep_has_sum = false;
-    esfm::DevBuf prep_sum;
-    esfm::DevBuf knn_d2;   // exact second-best d^2 of the queries the one-product pass left uncertified (the refine pass's thresholds)
-    esfm::DevBuf l2_hi;    // one-product pass: bf16(t) and bf16(-2 q) images (128 B per row each) and the two residual norms per row
-    esfm::DevBuf hm_exp;   // expanded descriptor image: 0/1 bytes + start values (Hamming MFMA) or bf16 hi/lo halves (L2), 256 B per row
+    // shared scratch of the API modules; knn_dist is also ORB detection's keypoint scratch (orb_api.cpp), the rest of the matcher's
+    // state is in `match`
+    esfm::DevBuf knn_dist, stage_a, stage_b, stage_c, stage_d, stage_e;
+    esfm::MatchState match;
     // pinned host staging for small tables / counters
     void *pinned = nullptr;
     size_t pinned_cap = 0;
-    int64_t last_n_queries = 0;
-    size_t last_pair_bytes = 0;
-    int l2_audit = 0;   // esfm_ctx_set_l2_audit: 0 product path, 1 no re-scan, 2 exact scan of every query, 3 one-product pass alone, 4 one-product pass alone with the ratio screen's rejections listed
     int pin(size_t bytes);
     // a second pinned area for the per-round tables of the RANSAC loops (samples up, model counts and inlier counts down)
     void *pinned_rounds = nullptr;

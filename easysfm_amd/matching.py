@@ -30,52 +30,53 @@ def _as_desc(a, dtype) -> np.ndarray:
     return a
 
 
-def knn_match_l2(q, t, ctx: Optional[Context] = None) -> Tuple[np.ndarray, np.ndarray]:
-    """knnMatch(q, t, out, 2) under NORM_L2 (exact brute force).  Returns (idx[nq,2], dist[nq,2])."""
+def _one_pair(q, t, dtype, ctx, same_width=True):
     ctx = ctx or default_context()
-    q = _as_desc(q, np.float32); t = _as_desc(t, np.float32)
-    if q.shape[1] != t.shape[1]:
+    q = _as_desc(q, dtype); t = _as_desc(t, dtype)
+    if same_width and q.shape[1] != t.shape[1]:
         raise ValueError("descriptor widths differ")
+    return q, t, ctx
+
+
+def _knn2(fn, q, t, dtype, ctx):
+    q, t, ctx = _one_pair(q, t, dtype, ctx)
     nq = q.shape[0]
     idx = np.full((nq, 2), -1, np.int32); dist = np.zeros((nq, 2), np.float32)
-    check(lib().esfm_knn2_l2_f32(ctx.handle, _ptr(q), nq, _ptr(t), t.shape[0], q.shape[1], _ptr(idx), _ptr(dist)))
+    check(fn(ctx.handle, _ptr(q), nq, _ptr(t), t.shape[0], q.shape[1], _ptr(idx), _ptr(dist)))
     return idx, dist
+
+
+def knn_match_l2(q, t, ctx: Optional[Context] = None) -> Tuple[np.ndarray, np.ndarray]:
+    """knnMatch(q, t, out, 2) under NORM_L2 (exact brute force).  Returns (idx[nq,2], dist[nq,2])."""
+    return _knn2(lib().esfm_knn2_l2_f32, q, t, np.float32, ctx)
 
 
 def knn_match_hamming(q, t, ctx: Optional[Context] = None) -> Tuple[np.ndarray, np.ndarray]:
     """knnMatch(q, t, out, 2) for "BruteForce-Hamming".  Returns (idx[nq,2], dist[nq,2])."""
-    ctx = ctx or default_context()
-    q = _as_desc(q, np.uint8); t = _as_desc(t, np.uint8)
-    if q.shape[1] != t.shape[1]:
-        raise ValueError("descriptor widths differ")
-    nq = q.shape[0]
-    idx = np.full((nq, 2), -1, np.int32); dist = np.zeros((nq, 2), np.float32)
-    check(lib().esfm_knn2_hamming(ctx.handle, _ptr(q), nq, _ptr(t), t.shape[0], q.shape[1], _ptr(idx), _ptr(dist)))
-    return idx, dist
+    return _knn2(lib().esfm_knn2_hamming, q, t, np.uint8, ctx)
 
 
-def _match(fn, q, t, ratio, ctx):
+def _match(fn, q, t, dtype, ctx, filt, same_width=False):
+    """One pair through a single-pair entry point fn(ctx, q, nq, t, nt, width, *filt, queryIdx, trainIdx, distance, &n)."""
+    q, t, ctx = _one_pair(q, t, dtype, ctx, same_width)
     nq = q.shape[0]
     qi = np.empty(max(nq, 1), np.int32); ti = np.empty(max(nq, 1), np.int32); d = np.empty(max(nq, 1), np.float32)
     n = C.c_int32(0)
-    check(fn(ctx.handle, _ptr(q), nq, _ptr(t), t.shape[0], q.shape[1], float(ratio), _ptr(qi), _ptr(ti), _ptr(d), C.byref(n)))
+    check(fn(ctx.handle, _ptr(q), nq, _ptr(t), t.shape[0], q.shape[1], *filt, _ptr(qi), _ptr(ti), _ptr(d), C.byref(n)))
     return qi[:n.value].copy(), ti[:n.value].copy(), d[:n.value].copy()
 
 
 def match_l2(q, t, ratio: float = 0.5, ctx: Optional[Context] = None):
     """2-NN + Lowe ratio for float descriptors; returns (queryIdx, trainIdx, distance) arrays."""
-    ctx = ctx or default_context()
-    return _match(lib().esfm_match_l2_f32, _as_desc(q, np.float32), _as_desc(t, np.float32), ratio, ctx)
+    return _match(lib().esfm_match_l2_f32, q, t, np.float32, ctx, (float(ratio),))
 
 
 def match_hamming(q, t, ratio: float = 0.8, ctx: Optional[Context] = None):
-    ctx = ctx or default_context()
-    return _match(lib().esfm_match_hamming, _as_desc(q, np.uint8), _as_desc(t, np.uint8), ratio, ctx)
+    return _match(lib().esfm_match_hamming, q, t, np.uint8, ctx, (float(ratio),))
 
 
-def match_pairs_host(sets: Sequence[np.ndarray], pairs, ratio: float, metric: int = ESFM_L2_F32, ctx: Optional[Context] = None):
-    """esfm_match_pairs: the batched pair loop through HOST pointers (upload once, one launch sequence, one read-back) -- what the
-    C++ driver calls.  Returns [(queryIdx, trainIdx, distance)] per pair."""
+def _match_pairs_host(fn, sets, pairs, metric, ctx, *filt):
+    """The batched pair loop through HOST pointers, fn(ctx, metric, bank, ..., pairs, n_pairs, *filt, outputs...)."""
     ctx = ctx or default_context()
     dt = np.float32 if metric == ESFM_L2_F32 else np.uint8
     sets = [_as_desc(s_, dt) for s_ in sets]
@@ -87,9 +88,15 @@ def match_pairs_host(sets: Sequence[np.ndarray], pairs, ratio: float, metric: in
     total = int(sum(sets[i].shape[0] for i, _ in pairs))
     qi = np.zeros(max(total, 1), np.int32); ti = np.zeros(max(total, 1), np.int32); d = np.zeros(max(total, 1), np.float32)
     n_out = np.zeros(max(len(pairs), 1), np.int32); out_off = np.zeros(len(pairs) + 1, np.int64)
-    check(lib().esfm_match_pairs(ctx.handle, metric, _ptr(bank), _ptr(off), len(sets), width, _ptr(pairs), len(pairs), float(ratio),
-                                 _ptr(qi), _ptr(ti), _ptr(d), _ptr(n_out), _ptr(out_off)))
+    check(fn(ctx.handle, metric, _ptr(bank), _ptr(off), len(sets), width, _ptr(pairs), len(pairs), *filt,
+             _ptr(qi), _ptr(ti), _ptr(d), _ptr(n_out), _ptr(out_off)))
     return [(qi[o:o + k].copy(), ti[o:o + k].copy(), d[o:o + k].copy()) for o, k in zip(out_off[:-1], n_out[:len(pairs)])]
+
+
+def match_pairs_host(sets: Sequence[np.ndarray], pairs, ratio: float, metric: int = ESFM_L2_F32, ctx: Optional[Context] = None):
+    """esfm_match_pairs: the batched pair loop through HOST pointers (upload once, one launch sequence, one read-back) -- what the
+    C++ driver calls.  Returns [(queryIdx, trainIdx, distance)] per pair."""
+    return _match_pairs_host(lib().esfm_match_pairs, sets, pairs, metric, ctx, float(ratio))
 
 
 # ---- cross-check (mutual nearest neighbour), include/esfm.h "Cross-check matching": ratio=None is cross alone, a number is
@@ -98,48 +105,21 @@ def _cross_args(ratio):
     return (0, 0.0) if ratio is None else (1, float(ratio))
 
 
-def _match_cross(fn, q, t, ratio, ctx):
-    if q.shape[1] != t.shape[1]:
-        raise ValueError("descriptor widths differ")
-    use_ratio, r = _cross_args(ratio)
-    nq = q.shape[0]
-    qi = np.empty(max(nq, 1), np.int32); ti = np.empty(max(nq, 1), np.int32); d = np.empty(max(nq, 1), np.float32)
-    n = C.c_int32(0)
-    check(fn(ctx.handle, _ptr(q), nq, _ptr(t), t.shape[0], q.shape[1], use_ratio, r, _ptr(qi), _ptr(ti), _ptr(d), C.byref(n)))
-    return qi[:n.value].copy(), ti[:n.value].copy(), d[:n.value].copy()
-
-
 def match_cross_l2(q, t, ratio: Optional[float] = None, ctx: Optional[Context] = None):
     """Mutual nearest neighbours of float descriptors (cv2.BFMatcher(NORM_L2, crossCheck=True) as feature_match.py:24-27 uses it, under
     the strict rule of esfm.h); with `ratio`, also Lowe's test in both directions.  Returns (queryIdx, trainIdx, distance) arrays."""
-    ctx = ctx or default_context()
-    return _match_cross(lib().esfm_match_cross_l2_f32, _as_desc(q, np.float32), _as_desc(t, np.float32), ratio, ctx)
+    return _match(lib().esfm_match_cross_l2_f32, q, t, np.float32, ctx, _cross_args(ratio), same_width=True)
 
 
 def match_cross_hamming(q, t, ratio: Optional[float] = None, ctx: Optional[Context] = None):
     """match_cross_l2 for binary descriptors (Hamming distance)."""
-    ctx = ctx or default_context()
-    return _match_cross(lib().esfm_match_cross_hamming, _as_desc(q, np.uint8), _as_desc(t, np.uint8), ratio, ctx)
+    return _match(lib().esfm_match_cross_hamming, q, t, np.uint8, ctx, _cross_args(ratio), same_width=True)
 
 
 def match_cross_pairs_host(sets: Sequence[np.ndarray], pairs, ratio: Optional[float] = None, metric: int = ESFM_L2_F32,
                            ctx: Optional[Context] = None):
     """esfm_match_cross_pairs: match_pairs_host with the cross-check filter.  Returns [(queryIdx, trainIdx, distance)] per pair."""
-    ctx = ctx or default_context()
-    dt = np.float32 if metric == ESFM_L2_F32 else np.uint8
-    sets = [_as_desc(s_, dt) for s_ in sets]
-    width = sets[0].shape[1]
-    off = np.zeros(len(sets) + 1, np.int32)
-    np.cumsum([s_.shape[0] for s_ in sets], out=off[1:])
-    bank = np.ascontiguousarray(np.concatenate(sets, axis=0)) if off[-1] else np.zeros((1, width), dt)
-    pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
-    total = int(sum(sets[i].shape[0] for i, _ in pairs))
-    use_ratio, r = _cross_args(ratio)
-    qi = np.zeros(max(total, 1), np.int32); ti = np.zeros(max(total, 1), np.int32); d = np.zeros(max(total, 1), np.float32)
-    n_out = np.zeros(max(len(pairs), 1), np.int32); out_off = np.zeros(len(pairs) + 1, np.int64)
-    check(lib().esfm_match_cross_pairs(ctx.handle, metric, _ptr(bank), _ptr(off), len(sets), width, _ptr(pairs), len(pairs), use_ratio, r,
-                                       _ptr(qi), _ptr(ti), _ptr(d), _ptr(n_out), _ptr(out_off)))
-    return [(qi[o:o + k].copy(), ti[o:o + k].copy(), d[o:o + k].copy()) for o, k in zip(out_off[:-1], n_out[:len(pairs)])]
+    return _match_pairs_host(lib().esfm_match_cross_pairs, sets, pairs, metric, ctx, *_cross_args(ratio))
 
 
 class FeatureMatching:
@@ -382,51 +362,43 @@ class PairMatcher:
         """esfm_ctx_set_prepared_check: fingerprint the prepared buffer and verify it on every call (a debugging aid)."""
         check(lib().esfm_ctx_set_prepared_check(self.ctx.handle, 1 if enable else 0))
 
+    def _call(self, fn, *args) -> None:
+        """fn(ctx, metric, bank, row_offset, n_sets, width, pairs, n_pairs, *args, offset): one pair-list entry point."""
+        b = self.bank
+        check(fn(self.ctx.handle, b.metric, C.c_void_p(b.data.data_ptr()), _ptr(b.row_offset), b.n_sets, b.width,
+                 _ptr(self.pairs), len(self.pairs), *args, _ptr(self.offset)))
+
+    def _lists(self, fn, *filt) -> PairMatches:
+        self._call(fn, *filt, C.c_void_p(self.query_idx.data_ptr()), C.c_void_p(self.train_idx.data_ptr()),
+                   C.c_void_p(self.distance.data_ptr()), C.c_void_p(self.n_out.data_ptr()))
+        return PairMatches(self.pairs, self.offset, self.n_out, self.query_idx, self.train_idx, self.distance, self.ctx)
+
     def match(self, ratio: float) -> PairMatches:
         """Enqueue the whole pair list; does not synchronise."""
-        b = self.bank
-        check(lib().esfm_match_pairs_dev(
-            self.ctx.handle, b.metric, C.c_void_p(b.data.data_ptr()), _ptr(b.row_offset), b.n_sets, b.width,
-            _ptr(self.pairs), len(self.pairs), float(ratio),
-            C.c_void_p(self.query_idx.data_ptr()), C.c_void_p(self.train_idx.data_ptr()),
-            C.c_void_p(self.distance.data_ptr()), C.c_void_p(self.n_out.data_ptr()), _ptr(self.offset)))
-        return PairMatches(self.pairs, self.offset, self.n_out, self.query_idx, self.train_idx, self.distance, self.ctx)
+        return self._lists(lib().esfm_match_pairs_dev, float(ratio))
 
     def match_cross(self, ratio: Optional[float] = None) -> PairMatches:
         """esfm_match_cross_pairs_dev: mutual nearest neighbours of every pair (ratio=None), or ratio+cross (Lowe's test in both
         directions as well).  Enqueues; does not synchronise."""
-        b = self.bank
-        use_ratio, r = _cross_args(ratio)
-        check(lib().esfm_match_cross_pairs_dev(
-            self.ctx.handle, b.metric, C.c_void_p(b.data.data_ptr()), _ptr(b.row_offset), b.n_sets, b.width,
-            _ptr(self.pairs), len(self.pairs), use_ratio, r,
-            C.c_void_p(self.query_idx.data_ptr()), C.c_void_p(self.train_idx.data_ptr()),
-            C.c_void_p(self.distance.data_ptr()), C.c_void_p(self.n_out.data_ptr()), _ptr(self.offset)))
-        return PairMatches(self.pairs, self.offset, self.n_out, self.query_idx, self.train_idx, self.distance, self.ctx)
+        return self._lists(lib().esfm_match_cross_pairs_dev, *_cross_args(ratio))
+
+    def _tables(self):
+        torch = self.torch
+        shape = (max(self.total_queries, 1), 2)
+        return (torch.empty(shape, dtype=torch.int32, device=self.bank.device), torch.empty(shape, dtype=torch.float32, device=self.bank.device))
 
     def knn2(self):
         """Raw 2-NN table of every pair: (idx[sum nq, 2], dist[sum nq, 2]) device tensors."""
-        torch = self.torch
-        b = self.bank
         if self.knn_idx is None:
-            self.knn_idx = torch.empty((max(self.total_queries, 1), 2), dtype=torch.int32, device=b.device)
-            self.knn_dist = torch.empty((max(self.total_queries, 1), 2), dtype=torch.float32, device=b.device)
-        check(lib().esfm_knn2_pairs_dev(
-            self.ctx.handle, b.metric, C.c_void_p(b.data.data_ptr()), _ptr(b.row_offset), b.n_sets, b.width,
-            _ptr(self.pairs), len(self.pairs), C.c_void_p(self.knn_idx.data_ptr()), C.c_void_p(self.knn_dist.data_ptr()),
-            _ptr(self.offset)))
+            self.knn_idx, self.knn_dist = self._tables()
+        self._call(lib().esfm_knn2_pairs_dev, C.c_void_p(self.knn_idx.data_ptr()), C.c_void_p(self.knn_dist.data_ptr()))
         return self.knn_idx, self.knn_dist
 
     def knn2_screened(self, ratio: float):
         """Hamming only (esfm_knn2_pairs_screened_dev): the raw table of a pass that screens with `ratio` -- train index -2 marks
         the queries it dropped as unable to pass d0 < ratio d1."""
-        torch = self.torch
-        b = self.bank
-        idx = torch.empty((max(self.total_queries, 1), 2), dtype=torch.int32, device=b.device)
-        dist = torch.empty((max(self.total_queries, 1), 2), dtype=torch.float32, device=b.device)
-        check(lib().esfm_knn2_pairs_screened_dev(
-            self.ctx.handle, b.metric, C.c_void_p(b.data.data_ptr()), _ptr(b.row_offset), b.n_sets, b.width,
-            _ptr(self.pairs), len(self.pairs), float(ratio), C.c_void_p(idx.data_ptr()), C.c_void_p(dist.data_ptr()), _ptr(self.offset)))
+        idx, dist = self._tables()
+        self._call(lib().esfm_knn2_pairs_screened_dev, float(ratio), C.c_void_p(idx.data_ptr()), C.c_void_p(dist.data_ptr()))
         return idx, dist
 
     def set_l2_audit(self, mode: int) -> None:
