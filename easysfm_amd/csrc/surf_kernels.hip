@@ -14,6 +14,7 @@
 //   surf_rowsum_kernel        horizontal pass of the area shrink to 21 x 21, one thread per (window row, output column)
 //   surf_vector_kernel        one workgroup per keypoint: vertical pass, weighted gradients, 4 x 4 x 4 sums, normalisation
 #include "surf_kernels.hpp"
+#include "feature_math.hpp"
 
 #include <float.h>
 #include <math.h>
@@ -27,20 +28,6 @@ __device__ __forceinline__ float calc_haar(const int32_t *__restrict__ origin, c
     double d = 0.0;
     for (int k = 0; k < n; ++k) d += (origin[f[k].p0] + origin[f[k].p3] - origin[f[k].p1] - origin[f[k].p2]) * f[k].w;
     return (float)d;
-}
-
-// cv::fastAtan2 [upstream core/mathfuncs_core]: 7th-order odd polynomial, degrees, 0.3 degree accuracy
-__device__ __forceinline__ float fast_atan2(float y, float x)
-{
-    const float p1 = 0.9997878412794807f * (float)(180 / 3.14159265358979323846), p3 = -0.3258083974640975f * (float)(180 / 3.14159265358979323846),
-                p5 = 0.1555786518463281f * (float)(180 / 3.14159265358979323846), p7 = -0.04432655554792128f * (float)(180 / 3.14159265358979323846);
-    const float ax = fabsf(x), ay = fabsf(y);
-    float a, c, c2;
-    if (ax >= ay) { c = ay / (ax + (float)DBL_EPSILON); c2 = c * c; a = (((p7 * c2 + p5) * c2 + p3) * c2 + p1) * c; }
-    else { c = ax / (ay + (float)DBL_EPSILON); c2 = c * c; a = 90.f - (((p7 * c2 + p5) * c2 + p3) * c2 + p1) * c; }
-    if (x < 0) a = 180.f - a;
-    if (y < 0) a = 360.f - a;
-    return a;
 }
 
 __global__ __launch_bounds__(256) void surf_gray_kernel(const uint8_t *__restrict__ bgr, int n, uint8_t *__restrict__ gray)

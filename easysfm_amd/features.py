@@ -1,5 +1,6 @@
 """Host-side mirror of the reference's feature extraction over the C ABI:
-``FeatureMatching::detectFeaturesSURF`` (cpp_code/src/feature_matching.cpp:43-69) and ``detectFeaturesORB`` (:14-41).  The
+``FeatureMatching::detectFeaturesSURF`` (cpp_code/src/feature_matching.cpp:43-69) and ``detectFeaturesORB`` (:14-41), and
+the Python prototype's SIFT branch (``detectFeaturesSIFT``, feature type 'I').  The
 Hessian pyramid / FAST + Harris pyramid, the orientations and the descriptors are computed in libesfm_hip.so on the GPU.
 ORB's 256 intensity tests use this library's own seeded point pairs: cv::ORB's learned table ships only inside OpenCV, so the
 descriptors are ORB descriptors in kind, not bit-compatible with OpenCV's (esfm.h, oracle/orb_ref.c).  Also here: the image
@@ -78,6 +79,40 @@ def detectFeaturesORB(cur_frame: Frame, max_num: int = 5000, show: bool = False,
     cur_frame.keypoints_full = kp
     cur_frame.descriptors = desc
     print(f"Found {len(kp)} features")
+    return True
+
+
+def sift_detect_and_compute(image, nfeatures: int = 0, max_keypoints: Optional[int] = None,
+                            ctx: Optional[Context] = None) -> Tuple[np.ndarray, np.ndarray]:
+    """esfm_sift_detect_and_compute.  image: [rows, cols] gray or [rows, cols, 3] BGR uint8; nfeatures as SIFT_create's first
+    argument (0 = all).  Returns (keypoints [n, 7] float32: x, y, size, angle, response, octave, class_id; descriptors [n, 128]
+    float32 with integer values 0..255)."""
+    ctx = ctx or default_context()
+    img = np.ascontiguousarray(image, np.uint8)
+    if img.ndim == 2:
+        rows, cols, ch = img.shape[0], img.shape[1], 1
+    elif img.ndim == 3 and img.shape[2] == 3:
+        rows, cols, ch = img.shape[0], img.shape[1], 3
+    else:
+        raise ValueError("image must be [rows, cols] or [rows, cols, 3] uint8")
+    cap = int(max_keypoints) if max_keypoints is not None else rows * cols // 4 + 4096      # DoG extrema are far sparser
+    kp = np.zeros((max(cap, 1), 7), np.float32); desc = np.zeros((max(cap, 1), 128), np.float32)
+    n = C.c_int32(0)
+    check(lib().esfm_sift_detect_and_compute(ctx.handle, C.c_void_p(img.ctypes.data), rows, cols, ch, int(nfeatures), cap,
+                                             C.c_void_p(kp.ctypes.data), C.c_void_p(desc.ctypes.data), C.byref(n)))
+    return kp[:n.value].copy(), desc[:n.value].copy()
+
+
+def detectFeaturesSIFT(cur_frame: Frame, nfeatures: int = 0, show: bool = False, ctx: Optional[Context] = None) -> bool:
+    """The prototype's SIFT branch (SIFT_create(nfeatures) + detectAndCompute) in the style of detectFeaturesSURF: fills
+    cur_frame.keypoints (pt), keypoints_full and descriptors (N x 128 float32) from cur_frame.rgb_image (BGR)."""
+    if cur_frame.rgb_image is None:
+        raise ValueError("frame has no image")
+    kp, desc = sift_detect_and_compute(cur_frame.rgb_image, int(nfeatures), None, ctx)
+    cur_frame.keypoints = np.ascontiguousarray(kp[:, :2], np.float32)
+    cur_frame.keypoints_full = kp
+    cur_frame.descriptors = desc
+    print(f"Found {len(kp)} features.")
     return True
 
 

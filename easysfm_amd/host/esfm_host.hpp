@@ -178,6 +178,31 @@ public:
         return true;
     }
 
+    // the Python prototype's SIFT branch (feature_match.py:12-16, SIFT_create(nfeatures) + detectAndCompute); nfeatures 0 = all
+    bool detectFeaturesSIFT(frame_t &cur_frame, int nfeatures = 0, bool show = false)
+    {
+        (void)show;
+        const ImageMat &img = cur_frame.rgb_image;
+        if (img.empty()) { std::cerr << "frame has no image" << std::endl; return false; }
+        const int cap = img.rows * img.cols / 4 + 4096;    // DoG extrema are far sparser (kept between frames: see detectFeaturesSURF)
+        float *kp = scratch_f32(kp_buf_, kp_cap_, size_t(7) * size_t(cap)), *desc = scratch_f32(desc_buf_, desc_cap_, size_t(128) * size_t(cap));
+        int32_t n = 0;
+        if (esfm_sift_detect_and_compute(default_ctx(), img.data.data(), img.rows, img.cols, img.channels, nfeatures, cap, kp, desc, &n) != ESFM_OK) {
+            std::cerr << esfm_last_error() << std::endl;
+            return false;
+        }
+        cur_frame.keypoints.resize(size_t(n));
+        for (int k = 0; k < n; ++k) {
+            KeyPoint &q = cur_frame.keypoints[size_t(k)];
+            const float *v = &kp[size_t(7) * size_t(k)];
+            q.pt.x = v[0]; q.pt.y = v[1]; q.size = v[2]; q.angle = v[3]; q.response = v[4]; q.octave = int(v[5]); q.class_id = int(v[6]);
+        }
+        cur_frame.descriptors.create(n, 128, DescMat::F32);
+        if (n) std::memcpy(cur_frame.descriptors.ptr<float>(), desc, sizeof(float) * size_t(128) * size_t(n));
+        if (!quiet) std::cout << "Found " << n << " features." << std::endl;
+        return true;
+    }
+
     // cross_check: keep mutual nearest neighbours (esfm_match_cross_*, the mutual_nn branch of feature_match.py:24-27) that also pass
     // the ratio test in both directions; ratio_thre == 0 in that mode: mutual nearest neighbours alone
     bool matchFeaturesORB(frame_t &cur_frame_1, frame_t &cur_frame_2, std::vector<DMatch> &matches, double ratio_thre = 0.8,
@@ -190,6 +215,13 @@ public:
                            bool show = false, bool cross_check = false)
     {
         return run(cur_frame_1, cur_frame_2, matches, ratio_thre, false, "SURF", cross_check);
+    }
+
+    // SIFT rows are 128 floats on the same L2 path; 0.7 is the prototype's nn_ratio (feature_match.py:5)
+    bool matchFeaturesSIFT(frame_t &cur_frame_1, frame_t &cur_frame_2, std::vector<DMatch> &matches, double ratio_thre = 0.7,
+                           bool show = false, bool cross_check = false)
+    {
+        return run(cur_frame_1, cur_frame_2, matches, ratio_thre, false, "SIFT", cross_check);
     }
 
     // what the "# Correspondence" line names as the filter

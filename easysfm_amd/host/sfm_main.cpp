@@ -82,7 +82,7 @@ int main(int argc, char **argv)
     // optional 14th argument: the match filter -- ratio (the reference's, default), cross (mutual nearest neighbours) or ratio+cross
     const std::string match_filter = argc == 15 ? argv[14] : "ratio";
     if ((argc != 14 && argc != 15) || (match_filter != "ratio" && match_filter != "cross" && match_filter != "ratio+cross")) {
-        std::cerr << "usage: sfm_native image_folder image_list calib_K_file calib_distort_file output.ply feature_type(S) feature_parameter "
+        std::cerr << "usage: sfm_native image_folder image_list calib_K_file calib_distort_file output.ply feature_type(S | O | I) feature_parameter "
                      "repro_dis_ransac find_init_frames ba_calib_change_tolerance ba_frequency launch_viewer view_sphere [match_filter: ratio | cross | ratio+cross]"
                   << std::endl;
         return 2;
@@ -96,7 +96,7 @@ int main(int argc, char **argv)
     const bool use_track_frames_as_init = std::atoi(argv[9]) != 0;
     const double fix_calib_tolerance_BA = std::atof(argv[10]);
     const int frequency_BA = std::max(1, std::atoi(argv[11]));
-    if (using_feature != 'S' && using_feature != 'O') { std::cout << "Wrong feature input. Use SURF as default feature." << std::endl; using_feature = 'S'; }
+    if (using_feature != 'S' && using_feature != 'O' && using_feature != 'I') { std::cout << "Wrong feature input. Use SURF as default feature." << std::endl; using_feature = 'S'; }
 
     try {
         DataIO io;
@@ -170,6 +170,7 @@ int main(int argc, char **argv)
             t_import += t_wait + t_und;
             std::cout << "Feature extraction of Frame [ " << i << " ]" << std::endl;
             if (using_feature == 'O' ? !fm.detectFeaturesORB(frames[size_t(i)], feature_extract_parameter)          // sfm.cpp:112-117
+                : using_feature == 'I' ? !fm.detectFeaturesSIFT(frames[size_t(i)], feature_extract_parameter)    // SIFT: the parameter is nfeatures
                                      : !fm.detectFeaturesSURF(frames[size_t(i)], feature_extract_parameter)) return 3;
             frames[size_t(i)].init_pixel_ids();
             const double t_det = clk.lap();
@@ -191,6 +192,7 @@ int main(int argc, char **argv)
                     std::vector<DMatch> temp_matches, inlier_matches;
                     StageClock pc;
                     if (using_feature == 'O') fm.matchFeaturesORB(frames[size_t(i)], frames[size_t(j)], temp_matches, match_filter == "cross" ? 0.0 : 0.8, false, cross_check);   // sfm.cpp:153-160
+                    else if (using_feature == 'I') fm.matchFeaturesSIFT(frames[size_t(i)], frames[size_t(j)], temp_matches, match_filter == "cross" ? 0.0 : 0.7, false, cross_check);
                     else fm.matchFeaturesSURF(frames[size_t(i)], frames[size_t(j)], temp_matches, match_filter == "cross" ? 0.0 : 0.5, false, cross_check);
                     t_match += pc.lap();
                     if (int(temp_matches.size()) > num_min_pair) {
@@ -212,7 +214,8 @@ int main(int argc, char **argv)
             std::vector<std::pair<int, int>> pairs;
             for (int i = 0; i < frame_number; ++i) for (int j = 0; j < i; ++j) pairs.emplace_back(i, j);
             std::vector<std::vector<DMatch>> temp_matches;
-            if (!fm.matchFeaturesAllPairs(frames, pairs, using_feature == 'O', temp_matches, match_filter == "cross" ? 0.0 : -1.0, cross_check)) return 3;
+            const double ratio_thre = match_filter == "cross" ? 0.0 : using_feature == 'I' ? 0.7 : -1.0;        // -1: the S / O members' defaults
+            if (!fm.matchFeaturesAllPairs(frames, pairs, using_feature == 'O', temp_matches, ratio_thre, cross_check)) return 3;
             t_match += pc.lap();
             std::vector<std::pair<int, int>> jobs;
             std::vector<std::vector<DMatch>> job_matches;

@@ -166,6 +166,16 @@ class FeatureMatching:
         from .features import detectFeaturesORB
         return detectFeaturesORB(cur_frame, max_num, show, self._ctx)
 
+    def matchFeaturesSIFT(self, cur_frame_1: Frame, cur_frame_2: Frame, matches: List[DMatch],
+                          ratio_thre: float = 0.7, show: bool = False, cross_check: bool = False) -> bool:
+        """The prototype's SIFT matching (feature_match.py, nn_ratio 0.7): matchFeaturesSURF's L2 path on 128-float rows."""
+        return self.matchFeaturesSURF(cur_frame_1, cur_frame_2, matches, ratio_thre, show, cross_check)
+
+    def detectFeaturesSIFT(self, cur_frame: Frame, nfeatures: int = 0, show: bool = False) -> bool:
+        """The prototype's SIFT branch (features.detectFeaturesSIFT)."""
+        from .features import detectFeaturesSIFT
+        return detectFeaturesSIFT(cur_frame, nfeatures, show, self._ctx)
+
     # ---- frame selection (feature_matching.cpp:160-268): integer logic on the track matrix, host side ----
     def findInitializeFramePair(self, feature_track_matrix, frames, img_match_graph, min_track_num_init: int = 100,
                                 max_depth_baseline_ratio_init: float = 50.0):

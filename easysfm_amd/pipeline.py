@@ -36,7 +36,7 @@ MATCH_FILTERS = ("ratio", "cross", "ratio+cross")
 
 def match_and_verify_all_pairs(frames: Sequence[Frame], use_feature: str = "S", ransac_reproj_distance: float = 1.0,
                                num_min_pair: int = 20, ctx: Optional[Context] = None, match_filter: str = "ratio") -> List[List[FramePair]]:
-    """sfm.cpp:140-167 for every (i, j < i): matchFeatures{SURF,ORB}(frames[i], frames[j]); if more than num_min_pair
+    """sfm.cpp:140-167 for every (i, j < i): matchFeatures{SURF,ORB,SIFT}(frames[i], frames[j]) (use_feature S, O or I); if more than num_min_pair
     matches survive, estimate2D2D_E5P_RANSAC (threshold = ransac_reproj_distance, prob 0.99) and getDepthFast on the inliers;
     otherwise no inliers, identity transform, depth 1 (:147-148).  Returns img_match_graph[i][j].
     match_filter: "ratio" (the reference's one-way Lowe test), "cross" (mutual nearest neighbours) or "ratio+cross" (both, the
@@ -46,7 +46,7 @@ def match_and_verify_all_pairs(frames: Sequence[Frame], use_feature: str = "S", 
     ctx = ctx or default_context()
     n = len(frames)
     metric = ESFM_HAMMING if use_feature == "O" else ESFM_L2_F32
-    ratio = 0.8 if use_feature == "O" else 0.5
+    ratio = {"O": 0.8, "I": 0.7}.get(use_feature, 0.5)                   # I (SIFT): the prototype's nn_ratio
     pairs = np.array([(i, j) for i in range(n) for j in range(i)], np.int32).reshape(-1, 2)
     graph: List[List[FramePair]] = [[FramePair(i, j) for j in range(i)] for i in range(n)]
     if len(pairs) == 0:

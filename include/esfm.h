@@ -98,7 +98,9 @@ typedef enum esfm_kernel_id {
     ESFM_K_ORB_FAST = 12,     /* orb_fast_kernel: FAST-9/16 score of every pyramid pixel          */
     ESFM_K_L2_SECOND = 13,    /* l2_finish_kernel: everything behind the one-product pass (re-rank of the ratio screen's survivors, threshold filter, ratio test, compaction) */
     ESFM_K_CROSS_CHECK = 14,  /* cross_check_compact_kernel: the mutual-nearest-neighbour join of esfm_match_cross_*       */
-    ESFM_K_COUNT = 15
+    ESFM_K_SIFT_PYR = 15,     /* esfm_sift_detect_and_compute: Gaussian pyramid, DoG and extrema (all octaves, one bracket) */
+    ESFM_K_SIFT_DESC = 16,    /* esfm_sift_detect_and_compute: sift_orient_kernel and sift_describe_kernel                   */
+    ESFM_K_COUNT = 17
 } esfm_kernel_id;
 int esfm_ctx_set_kernel_timing(esfm_ctx *ctx, int enable);
 int esfm_ctx_kernel_time(esfm_ctx *ctx, int kernel_id, double *total_ms, int64_t *launches);
@@ -601,6 +603,37 @@ int esfm_surf_detect_and_compute(esfm_ctx *ctx, const uint8_t *image, int rows, 
 int esfm_orb_detect_and_compute(esfm_ctx *ctx, const uint8_t *image, int rows, int cols, int channels, int nfeatures,
                                 int max_keypoints, float *keypoints /*7 each*/, uint8_t *descriptors /*32 each*/,
                                 int32_t *n_keypoints);
+
+/*
+ * SIFT detection + description (feature type 'I'; the Python prototype's SIFT branch, SIFT_create(nfeatures) +
+ * detectAndCompute): OpenCV 3.4 xfeatures2d SIFT with its defaults -- 3 layers per octave, contrastThreshold 0.04,
+ * edgeThreshold 10, sigma 1.6, an image upsampled x2 first (firstOctave -1), float pyramid.  image: rows x cols x channels
+ * (1 = gray, 3 = BGR, converted with cvtColor's fixed-point weights) bytes, host, sides up to 16384.  keypoints: 7 floats each
+ * -- x, y (input pixels), size, angle (degrees), response (|contrast|), OpenCV's packed octave (an integer below 2^24, exact in
+ * float), class_id (-1); descriptors: 128 floats each with integer values 0..255, as OpenCV 3.x stores them (what
+ * esfm_match_l2_f32 takes).  At most max_keypoints are written.
+ *
+ * Operation by operation (tests/sift_ref/sift_ref.c writes every step down and is bit-identical to this entry point):
+ *   base = gray upsampled x2 (INTER_LINEAR, exact) blurred with sqrtf(1.6^2 - 4 * 0.5^2); nOctaves = cvRound(log2(min side of
+ *   the base) - 2) + 1; 6 Gaussian layers per octave (GaussianBlur on CV_32F: getGaussianKernel taps from the host's exp(),
+ *   BORDER_REFLECT_101 iterated for kernels wider than the image, the row pass summed over the taps in order, the column pass
+ *   as w[r] c + sum_k w[r+k] (up_k + down_k)); the next octave starts from every second pixel of layer 3; DoG = layer
+ *   differences; candidates |v| > 1 and >= / <= all 26 neighbours, 5 px inside; adjustLocalExtrema (3 x 3 float solve by
+ *   partial pivoting, at most 5 steps, contrast and edge tests); a 36-bin orientation histogram per candidate, smoothed
+ *   [1 4 6 4 1] / 16, one keypoint per peak >= 0.8 max; the 4 x 4 x 8 descriptor with trilinear splits, the 0.2 clamp and the
+ *   512 scale, saturated to bytes.  exp / exp2 / sin / cos are this library's own written-out polynomial routines (double
+ *   range reduction and Horner, within 1 ulp of the true value), atan2 is cv::fastAtan2's polynomial.  Keypoints come out in
+ *   scan order (octave, layer, row, column, then orientation peak), duplicates (same x, y, size, angle) removed keeping the
+ *   first.  Documented deviations from OpenCV: nfeatures > 0 keeps every keypoint whose response is >= the nfeatures-th largest
+ *   (ties included) in scan order, where OpenCV's retainBest uses nth_element (its set on ties and its order are
+ *   implementation-defined); removeDuplicated keeps the scan order instead of re-sorting; the exp / sin / cos routines are not
+ *   OpenCV's, so bit parity with OpenCV binaries is not claimed.  A candidate or keypoint list beyond the internal lists'
+ *   capacity (a sixteenth of the interior samples plus 4096; twice that for keypoints) is ESFM_ERR_NUMERIC, never a silent
+ *   truncation.
+ */
+int esfm_sift_detect_and_compute(esfm_ctx *ctx, const uint8_t *image, int rows, int cols, int channels, int nfeatures,
+                                 int max_keypoints, float *keypoints /*7 each*/, float *descriptors /*128 each*/,
+                                 int32_t *n_keypoints);
 
 /* ---- Image undistortion (undistort part) -------------------------------
  * MotionEstimator::doUnDistort (cpp_code/src/estimate_motion.cpp:431-441): cv::undistort(rgb_image, out, K, distort_coeff), run
