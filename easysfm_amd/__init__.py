@@ -19,6 +19,8 @@ from .motion import (MotionEstimator, find_essential_mat, find_essential_pairs, 
 
 from .features import (detectFeaturesORB, detectFeaturesSIFT, detectFeaturesSURF, import_distort, orb_detect_and_compute,  # noqa: F401
                        sift_detect_and_compute, surf_detect_and_compute, undistort)
+from .mvs import (MVSOptions, default_mvs_options, dense_reconstruct, dense_reconstruction, mvs_depth_maps, mvs_fuse,  # noqa: F401
+                  mvs_plan)
 from .pipeline import FramePair, match_and_verify_all_pairs, propagate_track_ids, run_sfm  # noqa: F401
 
 __version__ = "0.1.0"

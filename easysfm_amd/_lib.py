@@ -19,7 +19,7 @@ ESFM_L2_F32 = 0
 ESFM_HAMMING = 1
 ESFM_REDUCE_SUM = 0
 ESFM_REDUCE_MAX = 1
-K_L2_KNN, K_HAMMING_KNN, K_BA_LINEARIZE, K_BA_SCHUR, K_BA_SOLVE, K_L2_RESCAN, K_SOR_KNN, K_TRIANGULATE, K_RANSAC, K_SURF_DET, K_SURF_DESC, K_UNDISTORT, K_ORB_FAST, K_L2_SECOND, K_CROSS_CHECK, K_SIFT_PYR, K_SIFT_DESC = range(17)
+K_L2_KNN, K_HAMMING_KNN, K_BA_LINEARIZE, K_BA_SCHUR, K_BA_SOLVE, K_L2_RESCAN, K_SOR_KNN, K_TRIANGULATE, K_RANSAC, K_SURF_DET, K_SURF_DESC, K_UNDISTORT, K_ORB_FAST, K_L2_SECOND, K_CROSS_CHECK, K_SIFT_PYR, K_SIFT_DESC, K_MVS_SWEEP, K_MVS_FUSE = range(19)
 BA_MAX_LOG = 256
 
 STATUS_NAMES = {
@@ -43,6 +43,7 @@ EXPORTED_SYMBOLS = [
     "esfm_sor_filter", "esfm_sor_mean_distances_dev", "esfm_triangulate_points", "esfm_triangulate_pairs",
     "esfm_find_essential_mat", "esfm_find_essential_pairs", "esfm_recover_pose", "esfm_recover_pose_pairs", "esfm_ransac_sample_stream", "esfm_five_point_models", "esfm_five_point_models_host",
     "esfm_solve_pnp_ransac", "esfm_surf_detect_and_compute", "esfm_orb_detect_and_compute", "esfm_sift_detect_and_compute", "esfm_undistort",
+    "esfm_mvs_options_default", "esfm_mvs_plan", "esfm_mvs_depth_maps", "esfm_mvs_fuse",
 ]
 
 
@@ -82,6 +83,15 @@ class BASummary(C.Structure):
 
     def log(self):
         return [self.iterations[i] for i in range(min(self.num_iterations + 1, BA_MAX_LOG))]
+
+
+class MVSOptions(C.Structure):
+    """esfm_mvs_options (include/esfm.h, "Dense reconstruction")."""
+    _fields_ = [
+        ("num_planes", C.c_int32), ("window_radius", C.c_int32), ("max_neighbours", C.c_int32), ("min_shared_points", C.c_int32),
+        ("best_k", C.c_int32), ("depth_margin", C.c_float), ("max_cost", C.c_float), ("min_var", C.c_float),
+        ("fuse_min_views", C.c_int32), ("fuse_reproj_px", C.c_float), ("fuse_rel_depth", C.c_float),
+    ]
 
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p)
@@ -177,6 +187,11 @@ def lib() -> C.CDLL:
     L.esfm_orb_detect_and_compute.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, i32p]
     L.esfm_sift_detect_and_compute.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, i32p]
     L.esfm_undistort.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]
+    L.esfm_mvs_options_default.argtypes = [C.POINTER(MVSOptions)]
+    L.esfm_mvs_options_default.restype = None
+    L.esfm_mvs_plan.argtypes = [C.c_int, vp, vp, C.c_int, vp, vp, vp, C.POINTER(MVSOptions), vp, vp]
+    L.esfm_mvs_depth_maps.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.POINTER(MVSOptions), vp, vp]
+    L.esfm_mvs_fuse.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.POINTER(MVSOptions), vp, vp, i32p]
     L.esfm_solve_pnp_ransac.argtypes = [vp, vp, vp, C.c_int, vp, C.c_int, C.c_double, C.c_double, vp, vp, vp, vp, i32p, i32p]
     L.esfm_ba_problem_set_params.argtypes = [vp, vp, vp]
     L.esfm_ba_problem_solve.argtypes = [vp, C.POINTER(BAOptions), ALLREDUCE_FN, vp, C.POINTER(BASummary)]

@@ -941,4 +941,78 @@ public:
     int ref_process_camera_id_ = -1;
 };
 
+// ---- dense reconstruction (esfm.h "Dense reconstruction"; the reference README's TODO "add multi-view stereo dense
+// reconstruction"): the same CSR of observed cloud points as easysfm_amd/mvs.py, then esfm_mvs_plan, esfm_mvs_depth_maps and
+// esfm_mvs_fuse.  process_frame_id as in doSFMBA: false = registered.
+class DenseReconstruction {
+public:
+    // returns false (message on stderr) on a library error; n_depth_maps = views with a depth range
+    bool reconstruct(const std::vector<frame_t> &frames, const std::vector<bool> &process_frame_id, const pointcloud_sparse_t &cloud,
+                     std::vector<PointXYZRGB> &dense, int &n_depth_maps)
+    {
+        dense.clear();
+        n_depth_maps = 0;
+        const int n = int(frames.size());
+        esfm_mvs_options opt;
+        esfm_mvs_options_default(&opt);
+        int rows = -1, cols = -1, ch = -1;
+        for (int v = 0; v < n; ++v) {
+            if (process_frame_id[size_t(v)]) continue;
+            const ImageMat &im = frames[size_t(v)].rgb_image;
+            if (im.empty()) { std::cerr << "dense reconstruction: registered frame " << v << " has no image" << std::endl; return false; }
+            if (rows < 0) { rows = im.rows; cols = im.cols; ch = im.channels; }
+            if (im.rows != rows || im.cols != cols || im.channels != ch) { std::cerr << "dense reconstruction: frames differ in size" << std::endl; return false; }
+        }
+        if (rows < 0) return true;
+        const size_t plane = size_t(rows) * size_t(cols) * size_t(ch);
+        std::vector<uint8_t> images(plane * size_t(n), 0), registered(size_t(n), 0);
+        std::vector<float> K4(size_t(4) * n), poses(size_t(12) * n), xyz(size_t(3) * cloud.points.size());
+        std::unordered_map<int, int> point_of;
+        for (size_t k = 0; k < cloud.points.size(); ++k) {
+            xyz[3 * k] = cloud.points[k].x; xyz[3 * k + 1] = cloud.points[k].y; xyz[3 * k + 2] = cloud.points[k].z;
+            point_of.emplace(cloud.unique_point_ids[k], int(k));
+        }
+        std::vector<int32_t> obs_off(size_t(n) + 1, 0), obs_pts;
+        for (int v = 0; v < n; ++v) {
+            const frame_t &f = frames[size_t(v)];
+            registered[size_t(v)] = process_frame_id[size_t(v)] ? 0 : 1;
+            if (registered[size_t(v)]) std::copy(f.rgb_image.data.begin(), f.rgb_image.data.end(), images.begin() + plane * size_t(v));
+            const float k4[4] = {f.K_cam(0, 0), f.K_cam(0, 2), f.K_cam(1, 1), f.K_cam(1, 2)};
+            std::copy(k4, k4 + 4, &K4[size_t(4) * v]);
+            for (int i = 0; i < 3; ++i) for (int j = 0; j < 4; ++j) poses[size_t(12) * v + 4 * i + j] = f.pose_cam(i, j);
+            // the cloud points whose track id is among the frame's ids, in cloud order
+            std::vector<char> seen(cloud.points.size(), 0);
+            for (int id : f.unique_pixel_ids) {
+                auto it = point_of.find(id);
+                if (it != point_of.end()) seen[size_t(it->second)] = 1;
+            }
+            for (size_t k = 0; k < seen.size(); ++k) if (seen[k]) obs_pts.push_back(int32_t(k));
+            obs_off[size_t(v) + 1] = int32_t(obs_pts.size());
+        }
+        std::vector<int32_t> nb(size_t(n) * opt.max_neighbours);
+        std::vector<float> range(size_t(2) * n);
+        int rc = esfm_mvs_plan(n, registered.data(), poses.data(), int(cloud.points.size()), xyz.data(), obs_off.data(), obs_pts.data(), &opt,
+                               nb.data(), range.data());
+        if (rc != ESFM_OK) { std::cerr << esfm_last_error() << std::endl; return false; }
+        for (int v = 0; v < n; ++v) n_depth_maps += range[size_t(2) * v] > 0.f;
+        const size_t n_px = size_t(n) * rows * cols;
+        std::vector<float> depth(n_px), cost(n_px), out_xyz(3 * n_px);
+        std::vector<uint8_t> out_rgb(3 * n_px);
+        rc = esfm_mvs_depth_maps(default_ctx(), n, rows, cols, ch, images.data(), K4.data(), poses.data(), nb.data(), range.data(), &opt,
+                                 depth.data(), cost.data());
+        if (rc != ESFM_OK) { std::cerr << esfm_last_error() << std::endl; return false; }
+        int32_t n_points = 0;
+        rc = esfm_mvs_fuse(default_ctx(), n, rows, cols, ch, images.data(), K4.data(), poses.data(), nb.data(), depth.data(), &opt,
+                           out_xyz.data(), out_rgb.data(), &n_points);
+        if (rc != ESFM_OK) { std::cerr << esfm_last_error() << std::endl; return false; }
+        dense.resize(size_t(n_points));
+        for (size_t k = 0; k < dense.size(); ++k) {
+            PointXYZRGB &p = dense[k];
+            p.x = out_xyz[3 * k]; p.y = out_xyz[3 * k + 1]; p.z = out_xyz[3 * k + 2];
+            p.r = out_rgb[3 * k]; p.g = out_rgb[3 * k + 1]; p.b = out_rgb[3 * k + 2];
+        }
+        return true;
+    }
+};
+
 }  // namespace p3dv

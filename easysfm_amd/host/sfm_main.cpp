@@ -79,11 +79,14 @@ int dump_image(const char *in, const char *out)
 int main(int argc, char **argv)
 {
     if (argc == 4 && std::string(argv[1]) == "--dump-image") return dump_image(argv[2], argv[3]);
-    // optional 14th argument: the match filter -- ratio (the reference's, default), cross (mutual nearest neighbours) or ratio+cross
-    const std::string match_filter = argc == 15 ? argv[14] : "ratio";
-    if ((argc != 14 && argc != 15) || (match_filter != "ratio" && match_filter != "cross" && match_filter != "ratio+cross")) {
+    // optional 14th argument: the match filter -- ratio (the reference's, default), cross (mutual nearest neighbours) or ratio+cross;
+    // optional 15th (needs the 14th): a dense .ply path, or none
+    const std::string match_filter = argc >= 15 ? argv[14] : "ratio";
+    const std::string dense_file = argc == 16 && std::string(argv[15]) != "none" ? argv[15] : "";
+    if ((argc != 14 && argc != 15 && argc != 16) || (match_filter != "ratio" && match_filter != "cross" && match_filter != "ratio+cross")) {
         std::cerr << "usage: sfm_native image_folder image_list calib_K_file calib_distort_file output.ply feature_type(S | O | I) feature_parameter "
-                     "repro_dis_ransac find_init_frames ba_calib_change_tolerance ba_frequency launch_viewer view_sphere [match_filter: ratio | cross | ratio+cross]"
+                     "repro_dis_ransac find_init_frames ba_calib_change_tolerance ba_frequency launch_viewer view_sphere [match_filter: ratio | cross | ratio+cross "
+                     "[dense.ply | none]]"
                   << std::endl;
         return 2;
     }
@@ -353,6 +356,20 @@ int main(int argc, char **argv)
         std::cout << "stage seconds: import+undistort " << t_import << " detect " << t_detect << " match " << t_match << " verify " << t_verify << " tracks " << t_tracks
                   << " register " << t_register << " register_next_frame " << t_next << " register_pnp " << t_pnp << " ba " << t_ba << " ba_calls " << n_ba << " sor " << t_sor << " total " << total_clock.lap()
                   << " frames " << frame_number << " pairs " << frame_number * (frame_number - 1) / 2 << " batched " << (pair_by_pair ? 0 : 1) << std::endl;
+        if (!dense_file.empty()) {
+            // dense reconstruction after the final BA, on the cloud before the filter (it carries the track ids)
+            clk.lap();
+            std::vector<PointXYZRGB> dense;
+            int n_maps = 0;
+            DenseReconstruction dr;
+            if (!dr.reconstruct(frames, todo, cloud, dense, n_maps)) return 3;
+            const double t_dense = clk.lap();
+            std::cout << "Dense reconstruction: [" << n_maps << "] depth maps, [" << dense.size() << "] points." << std::endl;
+            const std::filesystem::path dense_dir = std::filesystem::path(dense_file).parent_path();
+            if (!dense_dir.empty()) std::filesystem::create_directories(dense_dir);
+            if (!io.writePlyFile(dense_file, dense)) return 3;
+            std::cout << "dense seconds: reconstruct " << t_dense << " write " << clk.lap() << std::endl;
+        }
     } catch (const std::exception &e) {       // 1 is the reference's SUCCESS status: a failure must not look like one
         std::cerr << "sfm_native: " << e.what() << std::endl;
         return 3;

@@ -18,6 +18,7 @@ from .ba import BundleAdjustment
 from .cloud import CProceesing, write_ply
 from .matching import DescriptorBank, FeatureMatching, PairMatcher
 from .motion import MotionEstimator, _dehomogenise, find_essential_pairs, pixel2cam, recover_pose_pairs, triangulate_pairs
+from .mvs import dense_reconstruction
 from .types import DMatch, Frame, SparsePointCloud
 
 
@@ -133,8 +134,10 @@ def propagate_track_ids(frames: Sequence[Frame], graph: List[List[FramePair]]):
 
 def run_sfm(frames: List[Frame], output_file: Optional[str] = None, use_feature: str = "S", ransac_reproj_distance: float = 1.0,
             use_track_frames_as_init: bool = True, fix_calib_tolerance_BA: float = 0.0, frequency_BA: int = 4,
-            ctx: Optional[Context] = None, verbose: bool = False, match_filter: str = "ratio"):
-    """sfm.cpp:128-339.  Returns (sparse cloud before the final filter, filtered cloud, img_match_graph)."""
+            ctx: Optional[Context] = None, verbose: bool = False, match_filter: str = "ratio", dense_output_file: Optional[str] = None):
+    """sfm.cpp:128-339.  Returns (sparse cloud before the final filter, filtered cloud, img_match_graph).
+    dense_output_file: after the final BA and the sparse .ply, run dense_reconstruct on the registered frames and the cloud
+    before the filter (it carries the track ids) and write the dense cloud there (esfm.h "Dense reconstruction")."""
     ctx = ctx or default_context()
     fm, ee = FeatureMatching(ctx), MotionEstimator(ctx)
     for f in frames:
@@ -191,4 +194,9 @@ def run_sfm(frames: List[Frame], output_file: Optional[str] = None, use_feature:
     out = CProceesing(ctx).SORFilter(cloud)
     if output_file:
         write_ply(output_file, out)
+    if dense_output_file:
+        dense, _, rng, _, _ = dense_reconstruction(frames, todo, cloud, ctx=ctx)
+        if verbose:
+            print(f"Dense reconstruction: [{int(np.count_nonzero(rng[:, 0] > 0))}] depth maps, [{len(dense.xyz)}] points.")
+        write_ply(dense_output_file, dense)
     return cloud, out, graph

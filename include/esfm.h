@@ -100,7 +100,9 @@ typedef enum esfm_kernel_id {
     ESFM_K_CROSS_CHECK = 14,  /* cross_check_compact_kernel: the mutual-nearest-neighbour join of esfm_match_cross_*       */
     ESFM_K_SIFT_PYR = 15,     /* esfm_sift_detect_and_compute: Gaussian pyramid, DoG and extrema (all octaves, one bracket) */
     ESFM_K_SIFT_DESC = 16,    /* esfm_sift_detect_and_compute: sift_orient_kernel and sift_describe_kernel                   */
-    ESFM_K_COUNT = 17
+    ESFM_K_MVS_SWEEP = 17,    /* esfm_mvs_depth_maps: mvs_sweep_kernel (plane sweep, all views x tiles in one launch)       */
+    ESFM_K_MVS_FUSE = 18,     /* esfm_mvs_fuse: mvs_fuse_kernel, the block-offset scan and the ordered write                */
+    ESFM_K_COUNT = 19
 } esfm_kernel_id;
 int esfm_ctx_set_kernel_timing(esfm_ctx *ctx, int enable);
 int esfm_ctx_kernel_time(esfm_ctx *ctx, int kernel_id, double *total_ms, int64_t *launches);
@@ -648,6 +650,82 @@ int esfm_sift_detect_and_compute(esfm_ctx *ctx, const uint8_t *image, int rows, 
  * the image (INTER_LINEAR, BORDER_CONSTANT). */
 int esfm_undistort(esfm_ctx *ctx, const uint8_t *image, int rows, int cols, int channels, const double *K4, const double *dist4,
                    uint8_t *out);
+
+/* ---- Dense reconstruction: plane-sweep depth maps and depth-map fusion ------------------------------
+ * The reference README's TODO list: "add multi-view stereo dense reconstruction".  Runs after the final bundle adjustment on the
+ * registered poses, the (undistorted) images and the sparse cloud with its track ids.  The classic fronto-parallel plane sweep with
+ * windowed NCC (Collins 1996; Gallup et al. 2007) and a geometric-consistency fusion of the depth maps.  Every f32 formula below is
+ * written with its operation order; tests/mvs_ref.py restates this text and the GPU reproduces it bit for bit (no contraction of
+ * mul + add, correctly rounded division and sqrt, window sums as row-major loops from the top-left tap).
+ *
+ * Conventions.  Poses: 12 floats per view, row-major [R | t] mapping world to camera (x_cam = R X + t), Frame.pose_cam[:3, :4].
+ * K4 = (fx, cx, fy, cy) per view.  Pixel (col x, row y) has its centre at (x, y).  images: n_views x rows x cols x channels u8
+ * (3 = BGR, 1 = grey), all views one size; grey values are cvtColor's fixed-point BGR2GRAY (as SURF), used as f32 0..255.
+ * Depth is z in the reference camera; 0 = no estimate.  neighbours: n_views x max_neighbours view indices, -1 = none (skipped).
+ *
+ * Options (esfm_mvs_options_default; every call rejects an out-of-range value with ESFM_ERR_INVALID_ARG and writes nothing):
+ *   num_planes D 128 (3..1024), window_radius r 3 (1..7), max_neighbours 4 (1..8), min_shared_points 20 (>= 1), best_k 2
+ *   (1..max_neighbours), depth_margin 0.25 (>= 0), max_cost 0.5 (not NaN), min_var 4.0 grey levels^2 (> 0, finite),
+ *   fuse_min_views 2 (1..max_neighbours), fuse_reproj_px 1.0 (> 0), fuse_rel_depth 0.01 (> 0).
+ *
+ * esfm_mvs_plan (host only, no GPU): view selection and depth range.  registered[v] != 0 marks a registered view; obs_offsets
+ * [n_views + 1] / obs_points: CSR of the cloud points (indices into xyz) view v observes -- the points whose track id is among
+ * the frame's unique_pixel_ids; duplicates count once.  Neighbours of registered view r: every other registered view v scored
+ * by |obs(r) n obs(v)|, kept if score >= min_shared_points, the best max_neighbours by score descending, ties to the lower
+ * index, padded with -1.  Depth range: z = ((R20 X0 + R21 X1) + R22 X2) + t2 (f32) of the points of obs(r) with z > 0,
+ * sorted ascending; fewer than 10 (or no neighbour, or view not registered): (0, 0); otherwise lo = z[floor(0.02 (n - 1))],
+ * hi = z[ceil(0.98 (n - 1))], d_min = lo / (1 + depth_margin), d_max = hi * (1 + depth_margin) (f32, 1 + depth_margin first).
+ * neighbours out: n_views x max_neighbours; depth_range out: n_views x 2 (d_min, d_max).
+ *
+ * esfm_mvs_depth_maps: depth and cost, n_views x rows x cols f32 each, for every view with d_min > 0 (others: depth 0,
+ * cost +inf).  Rejected: a neighbour index out of range or equal to the view; d_min >= d_max (when d_min > 0; a range must be
+ * finite); an image smaller than the window (rows or cols < 2 r + 1).  A source needs only its image and pose.
+ *   Planes: in double, step = (1/d_min - 1/d_max) / (D - 1), invd_k = 1/d_max + k step; k = 0 is the farthest.
+ *   Homographies, per source s of reference r, in double with explicit scalar loops (sums from 0 over l = 0, 1, 2):
+ *   R_sr[i][j] = sum_l Rs[i][l] Rr[j][l]; t_sr[i] = ts[i] - sum_l R_sr[i][l] tr[l]; M = R_sr with M[i][2] += t_sr[i] invd_k;
+ *   A[i][j] = sum_l M[i][l] Kr^-1[l][j] with Kr^-1 = [[1/fx, 0, -cx/fx], [0, 1/fy, -cy/fy], [0, 0, 1]];
+ *   H[i][j] = sum_l Ks[i][l] A[l][j]; each entry rounded to f32 once.
+ *   Warped value of reference pixel (x, y) (f32): w = (h6 x + h7 y) + h8, nu = (h0 x + h1 y) + h2, nv = (h3 x + h4 y) + h5,
+ *   u = nu / w, v = nv / w, x0 = floorf(u), fx = u - x0, y0 = floorf(v), fy = v - y0; valid only if w > 0, 0 <= x0,
+ *   x0 + 1 < cols, 0 <= y0, y0 + 1 < rows; value = (1 - fy) ((1 - fx) I00 + fx I01) + fy ((1 - fx) I10 + fx I11).
+ *   Every window tap of every reference pixel uses this same per-pixel value.
+ *   Cost of one source (n = (2r+1)^2 taps, row-major from the top-left tap, sums from 0): mr = (sum ref) / n, ms = (sum src) / n;
+ *   cov = sum (ref - mr)(src - ms), vr = sum (ref - mr)^2, vs = sum (src - ms)^2; c = 1 - cov / sqrtf(vr vs).  Invalid if
+ *   any tap is invalid, vr < n min_var or vs < n min_var (n min_var in f32).
+ *   Aggregation: the v valid source costs sorted ascending, m = min(best_k, v), C_k = (their sum in ascending order) / m;
+ *   v = 0: plane invalid.  Winner k* = first k with the smallest valid C_k.  depth = 0 if the reference window leaves the image,
+ *   no plane is valid, C_k* > max_cost or k* in {0, D - 1}; otherwise a = C_{k*-1}, b = C_k*, c = C_{k*+1}, den = (a - 2b) + c,
+ *   off = den > 0 ? 0.5f (a - c) / den : 0, clamped to [-0.5, 0.5], 0 if a or c is invalid; depth = 1 / ((float)invd_k* +
+ *   off (float)step).  cost = C_k*, +inf where no plane is valid.
+ *
+ * esfm_mvs_fuse: depth (n_views x rows x cols, e.g. from esfm_mvs_depth_maps) to a coloured cloud.  For every view r and pixel
+ * (x, y) with d > 0 (f32 throughout): xc = ((x - cx) / fx) d, yc = ((y - cy) / fy) d, zc = d; e = (xc, yc, zc) - t;
+ * X[j] = (R[0][j] e0 + R[1][j] e1) + R[2][j] e2.  For each neighbour s (list order, -1 skipped): p = Rs X + ts as
+ * ((Rs[i][0] X0 + Rs[i][1] X1) + Rs[i][2] X2) + ts[i]; if p2 > 0: u = fx_s (p0 / p2) + cx_s, v = fy_s (p1 / p2) + cy_s,
+ * px = floorf(u + 0.5f), py = floorf(v + 0.5f); if 0 <= px < cols, 0 <= py < rows and d_s = depth_s[py][px] > 0: Y = the
+ * back-projection of (px, py) with d_s in s (as X), q = Rr Y + tr (as p), du = (fx (q0 / q2) + cx) - x, dv likewise,
+ * consistent if du du + dv dv < fuse_reproj_px fuse_reproj_px and fabsf(q2 - d) < fuse_rel_depth d.  The pixel is kept if at
+ * least fuse_min_views neighbours are consistent; its point is (X + Y_1 + Y_2 ...) / (1 + count), summed X first, then the
+ * consistent Y in neighbour order, per coordinate; its colour the reference pixel as RGB (grey: a grey triple).  Points are
+ * ordered by (view, row, col); xyz / rgb hold n_views rows cols points (3 floats / 3 bytes each), *n_points the number written.
+ * Duplicate surface points seen from several views are not removed.
+ * Both compute entry points take host pointers; without a usable device they return ESFM_ERR_NO_DEVICE (no CPU fallback). */
+typedef struct esfm_mvs_options {
+    int32_t num_planes, window_radius, max_neighbours, min_shared_points, best_k;
+    float depth_margin, max_cost, min_var;
+    int32_t fuse_min_views;
+    float fuse_reproj_px, fuse_rel_depth;
+} esfm_mvs_options;
+void esfm_mvs_options_default(esfm_mvs_options *opt);
+int esfm_mvs_plan(int n_views, const uint8_t *registered, const float *poses /*12 each*/, int n_points, const float *xyz /*3 each*/,
+                  const int32_t *obs_offsets /*n_views + 1*/, const int32_t *obs_points, const esfm_mvs_options *opt,
+                  int32_t *neighbours /*n_views x max_neighbours*/, float *depth_range /*2 each*/);
+int esfm_mvs_depth_maps(esfm_ctx *ctx, int n_views, int rows, int cols, int channels, const uint8_t *images, const float *K4 /*4 each*/,
+                        const float *poses /*12 each*/, const int32_t *neighbours, const float *depth_range /*2 each*/,
+                        const esfm_mvs_options *opt, float *depth, float *cost);
+int esfm_mvs_fuse(esfm_ctx *ctx, int n_views, int rows, int cols, int channels, const uint8_t *images, const float *K4 /*4 each*/,
+                  const float *poses /*12 each*/, const int32_t *neighbours, const float *depth, const esfm_mvs_options *opt,
+                  float *xyz, uint8_t *rgb, int32_t *n_points);
 
 #ifdef __cplusplus
 }
