@@ -61,7 +61,7 @@ long readback_timeout_s()
 
 // A problem's ~45 device arrays are carved from a few chunks (256-byte aligned, 256 spare bytes behind each array) instead of one
 // hipMalloc each: the small problems of an incremental reconstruction -- a BA call every ba_frequency frames, a dozen cameras and a
-// few thousand observations -- are set up and torn down once per call (scratch/ba_small_time.py: set-up 0.3 - 0.9 ms, tear-down 0.4 -
+// few thousand observations -- are set up and torn down once per call (profiles/r05_driver_surf_undistort_pnp.txt: set-up 0.3 - 0.9 ms, tear-down 0.4 -
 // 0.9 ms with one or two chunks; 0.14 / 0.0 ms once the chunks come from and go back to the context, below; the call's 4 - 5 ms are
 // its up to 50 LM iterations of 0.075 - 0.087 ms, a launch-latency chain).  An
 // array that does not fit the current chunk's rest opens a chunk of its own size (at least kArenaChunk): the large arrays of BA-512

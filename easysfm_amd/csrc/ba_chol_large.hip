@@ -91,7 +91,6 @@ __global__ __launch_bounds__(256) void chol3_kernel(double *__restrict__ W, doub
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     if (tid == 0) fail = 0;
     const bool chain_wg = (i == j + 1 && i < nb);
-    if (chain_wg) CHOL_T(j, 0);
     __shared__ int seen;
     auto wait_flag = [&](const int *f, bool urgent, int at_least = 1) {  // thread 0 polls (relaxed) until *f >= at_least, then a workgroup-scope acquire
         if (tid == 0) {
@@ -105,8 +104,7 @@ __global__ __launch_bounds__(256) void chol3_kernel(double *__restrict__ W, doub
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
     };
     auto factor_and_publish = [&](double *T, double *O, int c) {      // T: the finished diagonal tile of column c (LDS); O: scratch tile
-        tile_potrf64_inv(T, O, Vi, &fail, Ldiag + (size_t)c * LSLOT + LINV_OFF, &rpart[c], c > 0 ? c - 1 : 63);
-        CHOL_T(c - 1, 7);
+        tile_potrf64_inv(T, O, Vi, &fail, Ldiag + (size_t)c * LSLOT + LINV_OFF, &rpart[c]);
         if (tid == 0 && fail) scal[SC_CHOL_FAIL] = 1.0;
         publish_flag(&ready[c]);
     };
@@ -191,7 +189,6 @@ __global__ __launch_bounds__(256) void chol3_kernel(double *__restrict__ W, doub
     for (int cb = 0; cb < 4; ++cb) store_d16(Xi + (16 * wave) * ULD + 16 * cb, ULD, acc[cb], lane);
     // the first tile below the diagonal also finishes the next diagonal tile: fetch its partial sum while waiting for L_jj^-1
     const bool next_diag = chain_wg;
-    if (next_diag) CHOL_T(j, 1);
     // The ten lower 16 x 16 blocks of the next diagonal tile over the four waves as 3 + 3 + 3 + 1 (a row strip per wave would be
     // 1 + 2 + 3 + 4: the slowest wave sets the pace, 48 matrix instructions instead of 64): wave w's q-th block is (dbi, dbj)[w][q].
     const int dbi[3] = {wave == 3 ? 3 : wave, wave == 2 ? 2 : (wave == 1 ? 1 : 3), wave == 2 ? 2 : 3};
@@ -209,7 +206,6 @@ __global__ __launch_bounds__(256) void chol3_kernel(double *__restrict__ W, doub
             }
     }
     // X_ij = C L_jj^-T once the inverse is there
-    if (next_diag) CHOL_T(j, 2);
     {
         // all 32 KB in flight at once (as a loop the compiler made it sixteen round trips, load -> wait -> LDS store: 4 us of the
         // 25 us a block column takes, on the critical chain) -- and the first 16 KB (rows 0..31: thread t's q-th load is in row
@@ -220,7 +216,6 @@ __global__ __launch_bounds__(256) void chol3_kernel(double *__restrict__ W, doub
 #pragma unroll
         for (int q = 0; q < 4; ++q) lv[q] = Lk[tid + 256 * q];
         wait_flag(&ready[j], true);
-        if (next_diag) CHOL_T(j, 3);
 #pragma unroll
         for (int q = 4; q < CB * CB / 512; ++q) lv[q] = Lk[tid + 256 * q];
 #pragma unroll
@@ -230,7 +225,6 @@ __global__ __launch_bounds__(256) void chol3_kernel(double *__restrict__ W, doub
         }
     }
     __syncthreads();
-    if (next_diag) CHOL_T(j, 4);
     doublex4 x[4] = {doublex4{0, 0, 0, 0}, doublex4{0, 0, 0, 0}, doublex4{0, 0, 0, 0}, doublex4{0, 0, 0, 0}};
     strip_pqt64<false, true>(x, Xi, Xj, wave, lane);
     if (!next_diag) {
@@ -279,11 +273,8 @@ __global__ __launch_bounds__(256) void chol3_kernel(double *__restrict__ W, doub
     for (int q = 0; q < 3; ++q)
         if (q < dnb) store_d16(Xj + (16 * dbi[q]) * ULD + 16 * dbj[q], ULD, dacc[q], lane);
     __syncthreads();
-    CHOL_T(j, 5);
     publish_flag(&xcount[i], j + 1);                    // (the X stores above have long been acknowledged)
-    CHOL_T(j, 6);
     factor_and_publish(Xj, Xi, i);
-    CHOL_T(j, 9);
 }
 
 // The whole backward substitution L' y = z.  z_b = row 0 of the factor's tile (nb, b) in W2; ybuf: nb * CB doubles, every one the
@@ -374,12 +365,6 @@ __global__ __launch_bounds__(kSmallThreads) void ba_chol_small_kernel(BADev d, d
     __shared__ int fail;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     if (tid == 0) fail = 0;
-#ifdef ESFM_CHOL_PROFILE
-    long long prof[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tm0 = wall_clock64();
-#define CHOL_MARK(q) do { const long long tm1 = wall_clock64(); prof[q] += tm1 - tm0; tm0 = tm1; } while (0)
-#else
-#define CHOL_MARK(q) do { } while (0)
-#endif
     const double *S = d.red, *rc = d.red + (size_t)n * n, *FtF = d.camacc, *Ftr = d.camacc + 36 * (size_t)d.n_cam;
     // assemble W = F'F + D_c^2 + S_schur (lower block triangle, full diagonal blocks), identity padding, z = F'r + rhs_corr.
     // Pass 1: S -> LDS, one block per wave and round, lane = (row, 4 consecutive columns), every round's loads in flight at
@@ -428,7 +413,6 @@ __global__ __launch_bounds__(kSmallThreads) void ba_chol_small_kernel(BADev d, d
     }
     if (tid < np) z[tid] = zr;
     __syncthreads();
-    CHOL_MARK(0);
 
     // Block column b: panel X_i = A_i Linv_b' (MFMA), then the trailing update A_ij -= X_i X_j' (MFMA) -- during which wave 0
     // updates block (b+1, b+1) FIRST and factors / inverts it (look-ahead: the serial pivot chain of the next block column runs
@@ -436,7 +420,6 @@ __global__ __launch_bounds__(kSmallThreads) void ba_chol_small_kernel(BADev d, d
     // last wave during the panel, z_j -= z_b X_j' by the last threads during the update.
     if (wave == 0) potrf16_fused_inv(A + blk_off(0, 0), &fail, lane);
     __syncthreads();
-    CHOL_MARK(1);
 #pragma unroll 1
     for (int b = 0; b < nb; ++b) {
         if (wave == kSmallThreads / 64 - 1) {
@@ -454,7 +437,6 @@ __global__ __launch_bounds__(kSmallThreads) void ba_chol_small_kernel(BADev d, d
             store_d16(A + blk_off(i, b), VLD, acc, lane);
         }
         __syncthreads();
-        CHOL_MARK(2);
         const int m = nb - 1 - b;
         if (wave == 0) {
             if (m > 0) {
@@ -484,9 +466,7 @@ __global__ __launch_bounds__(kSmallThreads) void ba_chol_small_kernel(BADev d, d
             }
         }
         __syncthreads();
-        CHOL_MARK(3);
     }
-    CHOL_MARK(4);
     // backward substitution L' y = z through the block inverses: y_b = Linv_bb' (z_b - sum_{i > b} L_ib' y_i)
     for (int b = nb - 1; b >= 0; --b) {
         if (tid < SB) {
@@ -506,16 +486,10 @@ __global__ __launch_bounds__(kSmallThreads) void ba_chol_small_kernel(BADev d, d
         }
         __syncthreads();
     }
-    CHOL_MARK(5);
     for (int i = tid; i < n; i += kSmallThreads) { const double y = fail ? 0.0 : rd[i]; rd[i] = y; d.y_c[i] = y; }
     if (tid == 0 && fail) d.scal[SC_CHOL_FAIL] = 1.0;
     __syncthreads();
     ba_camera_step_body(d, rd, z);       // candidate cameras from y (z: reduction scratch from here on)
-#ifdef ESFM_CHOL_PROFILE
-    CHOL_MARK(6);
-    if (tid == 0) printf("chol_small [10 ns]: assemble %lld potrf %lld panel %lld update %lld inverse %lld back %lld tail %lld\n", prof[0], prof[1], prof[2], prof[3], prof[4], prof[5], prof[6]);
-#endif
-#undef CHOL_MARK
 }
 
 bool ba_chol_small_fits(int n_cam) { return (6 * n_cam + SB - 1) / SB <= kSmallMaxNb; }

@@ -15,7 +15,6 @@
 // Skipped tiles are exact zeros of the dense factorisation in the same elimination order, so the result differs from the dense
 // path's only by the ORDER of the eliminations (a symmetric permutation), i.e. in rounding.  Every wait is for a workgroup
 // dispatched earlier; the schedule is fixed, the result bit-reproducible.
-#define ESFM_CHOL_NO_TRACE
 #include "ba_chol_tile.hpp"
 #include "ba_chol_sparse.hpp"
 
@@ -23,16 +22,6 @@
 #include <cstdlib>
 
 namespace esfm {
-
-#ifdef ESFM_SPARSE_TRACE
-// timing-only build (scratch/build_variant_sparse.sh NAME -DESFM_SPARSE_TRACE): every workgroup of chol_sparse_kernel leaves
-// s_memrealtime stamps (10 ns ticks) at its stages; scratch/sparse_trace.py reads them through esfm_debug_sparse_trace
-__device__ unsigned long long g_sparse_trace[4096 * 8];
-#define SP_T(q) do { if (threadIdx.x == 0 && blockIdx.x < 4096) g_sparse_trace[blockIdx.x * 8 + (q)] = wall_clock64(); } while (0)
-extern "C" int esfm_debug_sparse_trace(unsigned long long *out) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_sparse_trace), sizeof(g_sparse_trace)); }
-#else
-#define SP_T(q) do { } while (0)
-#endif
 
 // ---------------------------------------------------------------------------------------------
 // element (hi, lo) of the reduced system, hi >= lo original unknowns, from the fixed-point buffer; what is read is cleared
@@ -140,7 +129,7 @@ __global__ __launch_bounds__(256) void ba_sparse_pack_kernel(BADev d, SparseDev 
 //           chain of the elimination tree the next column's inverse is one workgroup away from this column's, as in chol3_kernel.
 //           (First build: the diagonal tile's updates in a loop of their own AFTER the own tile's, in column order -- a separator's
 //           workgroup then did a dozen long-available tiles behind the one it had really been waiting for: 217 us on BA-512, of
-//           which 110 us were such queues, scratch/sparse_trace.py.)
+//           which 110 us were such queues.)
 __global__ __launch_bounds__(256) void chol_sparse_kernel(SparseDev sp, double *__restrict__ scal)
 {
     __shared__ __attribute__((aligned(16))) double Xi[CB * ULD];
@@ -151,7 +140,6 @@ __global__ __launch_bounds__(256) void chol_sparse_kernel(SparseDev sp, double *
     const SparseWg w = sp.wgs[blockIdx.x];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     if (tid == 0) fail = 0;
-    SP_T(0);
     // thread 0 polls (relaxed) until every flag of the list reads >= at_least (block == false: looks once); then a workgroup-scope acquire
     auto wait2 = [&](const int *fa, const int *fb, int at_least, bool block) -> bool {
         if (tid == 0) {
@@ -249,16 +237,13 @@ __global__ __launch_bounds__(256) void chol_sparse_kernel(SparseDev sp, double *
             __syncthreads();               // every wave is past its reads of Xi / Xj
         }
     }
-    SP_T(1);                                           // updates done
     if (diag) {
 #pragma unroll
         for (int cb = 0; cb < 4; ++cb) store_d16(Xi + (16 * wave) * ULD + 16 * cb, ULD, acc[cb], lane);
         __syncthreads();
         factor_and_publish(Xi, Xj, w.J);
-        SP_T(7);
         return;
     }
-    SP_T(2);
 #pragma unroll
     for (int cb = 0; cb < 4; ++cb) store_d16(Xi + (16 * wave) * ULD + 16 * cb, ULD, acc[cb], lane);
     // X_IJ = C L_JJ^-T once the inverse is there: all 32 KB in flight at once, the first 16 KB (rows 0..31) as soon as the factoring
@@ -273,7 +258,6 @@ __global__ __launch_bounds__(256) void chol_sparse_kernel(SparseDev sp, double *
 #pragma unroll
         for (int q = 0; q < 4; ++q) lv[q] = Lk[tid + 256 * q];
         if (!there) wait2(&sp.ready[w.J], nullptr, 1, true);
-        SP_T(3);                                       // inverse of the column's diagonal tile seen
 #pragma unroll
         for (int q = 4; q < CB * CB / 512; ++q) lv[q] = Lk[tid + 256 * q];
 #pragma unroll
@@ -293,7 +277,7 @@ __global__ __launch_bounds__(256) void chol_sparse_kernel(SparseDev sp, double *
             const int r = 16 * wave + (lane >> 4) + 4 * g, c = 16 * cb + (lane & 15);
             st_coh(&Xout[r * CB + c], x[cb][g]);
         }
-    if (!chain) { publish_flag(&sp.xready[w.slot]); SP_T(5); return; }
+    if (!chain) { publish_flag(&sp.xready[w.slot]); return; }
     // chain: X also goes to LDS as the operand of diagonal tile (I, I)'s last update; its flag is raised once the factorisation
     // below has its operands (nobody on the critical chain waits for it)
     __syncthreads();                                    // every wave is past its reads of Xi (C) and Xj (L^-1)
@@ -315,11 +299,8 @@ __global__ __launch_bounds__(256) void chol_sparse_kernel(SparseDev sp, double *
     for (int q = 0; q < 3; ++q)
         if (q < dnb) store_d16(Xj + (16 * dbi[q]) * ULD + 16 * dbj[q], ULD, dacc[q], lane);
     __syncthreads();
-    SP_T(4);                                           // X in LDS, diagonal tile complete
     publish_flag(&sp.xready[w.slot]);                   // (the X stores above have long been acknowledged)
-    SP_T(5);
     factor_and_publish(Xj, Xi, w.I);
-    SP_T(7);
 }
 
 // Backward substitution L' y = z down the elimination tree.  Workgroup for column b (dispatched in descending b): z_b = row 0 of

@@ -115,19 +115,6 @@ __device__ __forceinline__ void publish_flag(int *f, int value = 1)
     if (threadIdx.x == 0) __hip_atomic_store(f, value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-#if defined(ESFM_CHOL_TRACE) && !defined(ESFM_CHOL_NO_TRACE)
-// timing-only build (scratch/build_variant_chol.sh NAME -DESFM_CHOL_TRACE): the chain workgroup (j+1, j) leaves s_memrealtime stamps
-// (10 ns ticks) at its stages; scratch/chol_trace.py reads them through esfm_debug_chol_trace
-__device__ unsigned long long g_chol_trace[64 * 12];
-#define CHOL_T(col, q) do { if (threadIdx.x == 0) g_chol_trace[(col) * 12 + (q)] = wall_clock64(); } while (0)
-// CHOL_ACC(var): var += ticks since the previous CHOL_ACC (wave 0 only)
-#define CHOL_ACC(var) do { const long long tm1 = wall_clock64(), cy1 = clock64(); var += tm1 - tm0; var##_cyc += cy1 - cy0; tm0 = tm1; cy0 = cy1; } while (0)
-extern "C" int esfm_debug_chol_trace(unsigned long long *out) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_chol_trace), sizeof(g_chol_trace)); }
-#else
-#define CHOL_T(col, q) do { } while (0)
-#define CHOL_ACC(var) do { } while (0)
-#endif
-
 // 256 threads: in-place Cholesky of the 64 x 64 tile T (LDS, row-major ULD; upper part must be zero) AND the inverse of the factor
 // in O (LDS, ULD).  Vi: 4 blocks of 16 x VLD (inverses of the diagonal sub-blocks).
 // Factorisation, sub-block column b: panel X_i = A_i Linv_bb' (waves b+1 .. 3), then the trailing update -- during which wave 0
@@ -144,13 +131,10 @@ extern "C" int esfm_debug_chol_trace(unsigned long long *out) { return (int)hipM
 // from here, every wave storing what it computed itself: rows 0..31 while wave 0 is still in the LAST pivot chain -- part_flag counts
 // the three waves that have done so, and a consumer that sees 3 starts fetching those 16 KB a microsecond before the tile is finished
 // -- and rows 32..63 at the end; the caller raises the tile's ready flag behind them (publish_flag).
-__device__ __forceinline__ void tile_potrf64_inv(double *T, double *O, double *Vi, int *fail, double *__restrict__ Ld, int *part_flag, int trace_col = 0)
+__device__ __forceinline__ void tile_potrf64_inv(double *T, double *O, double *Vi, int *fail, double *__restrict__ Ld, int *part_flag)
 {
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int jc = wave - 1;
-#if defined(ESFM_CHOL_TRACE) && !defined(ESFM_CHOL_NO_TRACE)
-    long long tm0 = wall_clock64(), cy0 = clock64(), t_potrf = 0, t_rest = 0, t_potrf_cyc = 0, t_rest_cyc = 0;
-#endif
     auto copy_vi = [&](int b) {                          // O_bb = Vi_b
         for (int e = lane; e < SB * SB; e += 64) O[(SB * b + e / SB) * ULD + SB * b + e % SB] = Vi[b * SB * VLD + (e / SB) * VLD + e % SB];
     };
@@ -163,7 +147,6 @@ __device__ __forceinline__ void tile_potrf64_inv(double *T, double *O, double *V
     };
     if (wave == 0) {
         potrf16_fused_to(T, ULD, Vi, fail, lane);
-        CHOL_ACC(t_potrf);
     } else {
         // zeros above the diagonal blocks: block column jc (rows < 16 jc), and wave 1 also takes block column 3
         for (int e = lane; e < SB * jc * SB; e += 64) O[(e / SB) * ULD + SB * jc + e % SB] = 0.0;
@@ -185,9 +168,7 @@ __device__ __forceinline__ void tile_potrf64_inv(double *T, double *O, double *V
             acc = pqt16(acc, T + (SB * i) * ULD + SB * b, ULD, T + (SB * i) * ULD + SB * b, ULD, -1.0, lane);
             store_d16(T + (SB * i) * ULD + SB * i, ULD, acc, lane);
             __builtin_amdgcn_wave_barrier();
-            CHOL_ACC(t_rest);
             potrf16_fused_to(T + (SB * i) * ULD + SB * i, ULD, Vi + i * SB * VLD, fail, lane);
-            CHOL_ACC(t_potrf);
         } else {
             int idx = 0;
             for (int i = b + 1; i < 4; ++i)
@@ -224,10 +205,6 @@ __device__ __forceinline__ void tile_potrf64_inv(double *T, double *O, double *V
         __builtin_amdgcn_wave_barrier();
         for (int e = lane; e < 2 * SB * SB; e += 64) st_coh(&Ld[(2 * SB + e / SB) * CB + SB * cb + e % SB], O[(2 * SB + e / SB) * ULD + SB * cb + e % SB]);
     }
-#if defined(ESFM_CHOL_TRACE) && !defined(ESFM_CHOL_NO_TRACE)
-    if (tid == 0) { CHOL_ACC(t_rest); g_chol_trace[trace_col * 12 + 10] = (unsigned long long)t_potrf; g_chol_trace[trace_col * 12 + 11] = (unsigned long long)t_rest;
-                    g_chol_trace[trace_col * 12 + 8] = (unsigned long long)t_potrf_cyc; (void)t_rest_cyc; }    // (slot 8, "inv64", is free since the inverse moved)
-#endif
 }
 
 // this wave's 16-row strip of  P (64 x 64, LDS ULD) * Q' (Q 64 x 64, LDS ULD): four 16 x 16 outputs, K = 64

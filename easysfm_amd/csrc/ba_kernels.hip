@@ -291,19 +291,6 @@ __device__ __forceinline__ int qexp_of(double diag)
     return (sd > 1e-120 && sd < 1e120) ? ilogb(sd) + 1 : -400;   // a zero column only ever contributes zeros
 }
 
-#ifdef ESFM_LIN_TRACE
-// timing-only build (scratch/build_variant_ba.sh NAME -DESFM_LIN_TRACE): s_memrealtime ticks (10 ns) summed over the waves of ba_linearize_kernel:
-// [0] prologue (LDS clear, exponents, first loads), [1] the loop, [2] everything behind it, [3] waves, [4] loop iterations
-__device__ unsigned long long g_lin_trace[8];
-__device__ unsigned long long g_lin_wave[512 * 8 * 5];
-extern "C" int esfm_debug_lin_waves(unsigned long long *out) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_lin_wave), sizeof(g_lin_wave)); }
-extern "C" int esfm_debug_lin_trace(unsigned long long *out, int reset)
-{
-    if (reset) { unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0}; return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_lin_trace), z, sizeof(z)); }
-    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_lin_trace), sizeof(g_lin_trace));
-}
-#endif
-
 // ---------------------------------------------------------------------------------------------
 // Jacobian sweep: 16 B in, 160 B out per observation (+ 32 B with free intrinsics), and the per-camera sums F'F / F'r.
 //
@@ -327,22 +314,19 @@ extern "C" int esfm_debug_lin_trace(unsigned long long *out, int reset)
 // Round 5, BA-512 (two waves per SIMD -- 250 registers; the LDS sums of 512 cameras leave room for one workgroup per CU anyway): the
 // loop's loads are issued one observation AHEAD of its stores (see the loop): 228 -> 187 us; ONE workgroup per CU instead of two in
 // sequence (each paid a 9-us prologue -- LDS clear, exponents -- and an 8-us epilogue): -> 161 - 167 us.  What the loop waits for is
-// neither memory nor issue slots but ITSELF (-DESFM_LIN_TRACE, scratch/lin_trace.py: 5.6 us per iteration and wave = 13 400 cycles
+// neither memory nor issue slots but ITSELF (stage stamps, profiles/r05_ba512_sweep_and_schur_decomposition.txt: 5.6 us per iteration and wave = 13 400 cycles
 // for 2 x 1 266 instructions): timing-only builds without the 20 stores AND the 35 LDS atomics take 177 us against 186; a build that
 // takes sin / cos / 1/theta from a per-camera table -- 1 080 instructions instead of 1 266, bit-identical results -- takes exactly as
 // long (5.58 against 5.60 us per iteration: measured, not kept); allowing fused multiply-adds removes 8 % of the instructions.  The
 // f64 dependency chains of one observation (division -> Jacobian -> scaling -> products -> fixed point) at two waves per SIMD are the
 // critical path; more waves would need the kernel in 128 registers.  A pure copy of the same 18 + 18 arrays runs at 5.9 TB/s in ANY
-// layout (SoA of doubles as here, double2, tiles of 64: scratch/ubench/soa_stream.hip), so the layout is not what holds the sweep back.
+// layout (SoA of doubles as here, double2, tiles of 64: profiles/r05_soa_stream_ubench.txt), so the layout is not what holds the sweep back.
 constexpr int kLinThreadsLarge = 512, kLinThreadsSmall = 256;
 constexpr int kLinSmallObs = 1 << 20;
 constexpr int kLinLdsPerCam = 27 * 8 + 7 * 8 + 4 + 7 * 4;   // acc, maxima, count, exponents
 
-#ifndef ESFM_LIN_OCC
-#define ESFM_LIN_OCC 1
-#endif
 template <bool PRIV, bool CALIB, int kLinThreads>
-__global__ __launch_bounds__(kLinThreads, kLinThreads == 256 ? ESFM_LIN_OCC : 1) void ba_linearize_kernel(BADev d, double cauchy_a, int use_scaling, ScalBase sbase, double *__restrict__ slabs,
+__global__ __launch_bounds__(kLinThreads, 1) void ba_linearize_kernel(BADev d, double cauchy_a, int use_scaling, ScalBase sbase, double *__restrict__ slabs,
                                                                    int prov_rexp)
 {
     // prov_rexp != INT_MIN (PRIV, several observations per thread: BA-512): PROVISIONAL fixed-point exponents -- the previous
@@ -352,10 +336,6 @@ __global__ __launch_bounds__(kLinThreads, kLinThreads == 256 ? ESFM_LIN_OCC : 1)
     // and column: if one fails (a first linearisation, a problem that changed under the solver) the workgroup clears its sums and
     // runs the two-pass form below.  Either way the integers are exact sums on the grid the slab is converted with.  (Round 3: the
     // re-read of pass 2 was 336 MB of BA-512's sweep.)
-#ifdef ESFM_LIN_TRACE
-    const unsigned long long lt0 = __builtin_amdgcn_s_memrealtime();
-    unsigned long long lt_iters = 0;
-#endif
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     double *red = reinterpret_cast<double *>(lds_raw);                                  // [8] reduction scratch, [10] intrinsics-block sums
     unsigned long long *acc = reinterpret_cast<unsigned long long *>(lds_raw) + 18;     // PRIV: [n_real_cam * 27]
@@ -449,13 +429,7 @@ __global__ __launch_bounds__(kLinThreads, kLinThreads == 256 ? ESFM_LIN_OCC : 1)
         // the way in it would wait for "all but two" memory operations in EVERY iteration -- the stores again)
         __builtin_amdgcn_s_waitcnt(0x0f70);
     }
-#ifdef ESFM_LIN_TRACE
-    const unsigned long long lt1 = __builtin_amdgcn_s_memrealtime();
-#endif
     for (int k = k_first; k < n_obs; k += kstride) {
-#ifdef ESFM_LIN_TRACE
-        ++lt_iters;
-#endif
         // the next observation's parameters and the indices of the one after: requested in front of this observation's arithmetic
         // (and so ahead of its stores in the queue)
         // (with free intrinsics the kernel has no registers left for that: there the requests go out after the arithmetic, in front
@@ -546,23 +520,6 @@ __global__ __launch_bounds__(kLinThreads, kLinThreads == 256 ? ESFM_LIN_OCC : 1)
         }
         ix_cur = ix_nxt; ix_nxt = ix_nn; par_cur = par_nxt;
     }
-#ifdef ESFM_LIN_TRACE
-    const unsigned long long lt2 = __builtin_amdgcn_s_memrealtime();
-    struct LinTraceEnd {
-        unsigned long long t0, t1, t2, it;
-        __device__ ~LinTraceEnd() {
-            if ((threadIdx.x & 63) == 0) {
-                const unsigned long long t3 = __builtin_amdgcn_s_memrealtime();
-                atomicAdd(&g_lin_trace[0], t1 - t0); atomicAdd(&g_lin_trace[1], t2 - t1); atomicAdd(&g_lin_trace[2], t3 - t2);
-                atomicAdd(&g_lin_trace[3], 1ull); atomicAdd(&g_lin_trace[4], it);
-                if (blockIdx.x < 512) {       // per wave of the last launch: start, loop start, loop end, end (10-ns ticks), XCC id (scratch/lin_trace.py)
-                    unsigned long long *w = &g_lin_wave[(blockIdx.x * 8 + (threadIdx.x >> 6)) * 5];
-                    w[0] = t0; w[1] = t1; w[2] = t2; w[3] = t3; w[4] = __builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (3 << 11)) & 15;   // HW_REG_XCC_ID
-                }
-            }
-        }
-    } lin_trace_end{lt0, lt1, lt2, lt_iters};
-#endif
     {
         const int slots[2] = {SC_COST, SC_LIN_BAD};
         const double vals[2] = {cost, bad};
@@ -899,10 +856,7 @@ __global__ __launch_bounds__(64) void ba_point_prep_kernel(BADev d, double radiu
 // idle (22 workgroups for 25 cameras; a latency-bound walk over the tracks), so back to back they cost 8 + 12 us of a 180-us
 // LM iteration on BA-25 and together 12.  The first n_red workgroups are ba_camacc_reduce_kernel's, the others take 256 points
 // each (the singular-point count is an integer-valued sum and the gradient maximum a maximum: the wider workgroup changes no bit).
-#ifndef ESFM_PREP_OCC
-#define ESFM_PREP_OCC 1
-#endif
-__global__ __launch_bounds__(256, ESFM_PREP_OCC) void ba_point_prep_camacc_kernel(BADev d, double radius, double min_diag, double max_diag, ScalBase sbase,
+__global__ __launch_bounds__(256, 1) void ba_point_prep_camacc_kernel(BADev d, double radius, double min_diag, double max_diag, ScalBase sbase,
                                                                    const double *__restrict__ slabs, int n_slabs, int with_gradient, int n_red)
 {
     __shared__ double lds[256];
@@ -1271,24 +1225,6 @@ constexpr size_t kMfLdsBytes = sizeof(double) * (4 * kMfWaveDoubles + 6 * kSchur
 static_assert(4 * kMfWaveDoubles >= kMfRows * (kMfRows + 1), "the staging area is reused for the 80 x 81 result");
 static_assert(kSchurMfCams <= 16 && 6 * kSchurMfCams <= kMfRows, "slot masks are 16 bits; the window's rows fit the tile grid");
 
-#ifndef ESFM_SCHUR_OCC
-#define ESFM_SCHUR_OCC 2
-#endif
-#ifdef ESFM_SCHUR_TRACE
-// timing-only build (scratch/build_variant_ba.sh NAME -DESFM_SCHUR_TRACE): s_memrealtime ticks (10 ns) per stage, summed over the waves:
-// [0] waiting for a batch's rows, [1] W / Y into LDS, [2] matrix products, [3] batches, [4] the workgroup's sum + flush, [5] workgroups
-__device__ unsigned long long g_schur_trace[8];
-extern "C" int esfm_debug_schur_trace(unsigned long long *out, int reset)
-{
-    if (reset) { unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0}; return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_schur_trace), z, sizeof(z)); }
-    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_schur_trace), sizeof(g_schur_trace));
-}
-#define SCH_T0() unsigned long long sch_t = __builtin_amdgcn_s_memrealtime()
-#define SCH_T(q) do { const unsigned long long t_ = __builtin_amdgcn_s_memrealtime(); sch_acc[q] += t_ - sch_t; sch_t = t_; } while (0)
-#else
-#define SCH_T0() do { } while (0)
-#define SCH_T(q) do { } while (0)
-#endif
 // Both tables in ONE launch (round 5): workgroups [0, n_plain) take the plain numbering's chunks, the rest the seam's (camera indices
 // rotated by `rot_seam`).  The seam's table is 2 % of BA-512's observations in ~100 short chunks whose fixed costs -- zeroing 120
 // accumulator registers, the 80 x 81 sum through LDS, 3 240 fixed-point atomics -- made a launch of their own last 47 us; behind the
@@ -1297,7 +1233,7 @@ struct SchurMfTables {
     const int32_t *slot_obs[2]; const int2 *slot_pc[2]; const int32_t *batch_slot[2]; const int32_t *chunk_batch0[2]; const int32_t *chunk_cam0[2];
     int n_plain, rot_seam;
 };
-__global__ __launch_bounds__(256, ESFM_SCHUR_OCC) void ba_schur_mfma_kernel(BADev d, int rhs_exp, SchurMfTables tabs)
+__global__ __launch_bounds__(256, 2) void ba_schur_mfma_kernel(BADev d, int rhs_exp, SchurMfTables tabs)
 {
     const int tb = (int)blockIdx.x >= tabs.n_plain ? 1 : 0;
     const int32_t *__restrict__ slot_obs = tabs.slot_obs[tb];
@@ -1375,10 +1311,6 @@ __global__ __launch_bounds__(256, ESFM_SCHUR_OCC) void ba_schur_mfma_kernel(BADe
     };
     fetch_ids(b0 + wave);
     fetch_rows();
-#ifdef ESFM_SCHUR_TRACE
-    unsigned long long sch_acc[5] = {0, 0, 0, 0, 0};
-#endif
-    SCH_T0();
     for (int b = b0 + wave; b < b1; b += 4) {
         const int nob = nx_nob;
         const bool valid = lane < nob;
@@ -1399,10 +1331,6 @@ __global__ __launch_bounds__(256, ESFM_SCHUR_OCC) void ba_schur_mfma_kernel(BADe
         const double M[9] = {Mi[0], Mi[1], Mi[2], Mi[1], Mi[3], Mi[4], Mi[2], Mi[4], Mi[5]};
         const double ag0 = ag[0], ag1 = ag[1], ag2 = ag[2];
         if (lane < kMfMaxPts) pmask[lane] = 0u;
-#ifdef ESFM_SCHUR_TRACE
-        __builtin_amdgcn_s_waitcnt(0x0f70);
-        SCH_T(0);
-#endif
         if (valid) {
             atomicOr(&pmask[q], 1u << slot);
             if (first) pfirst[q] = lane;
@@ -1430,10 +1358,6 @@ __global__ __launch_bounds__(256, ESFM_SCHUR_OCC) void ba_schur_mfma_kernel(BADe
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         fetch_rows();                   // the next batch's (its ids were requested at the top; clamped to lane 0's slot past the end)
-#ifdef ESFM_SCHUR_TRACE
-        __builtin_amdgcn_s_waitcnt(0xc07f);
-        SCH_T(1);
-#endif
         // The K = 4 slices of one matrix instruction are four consecutive (point, column) pairs of the batch -- slice 4 t + k is column
         // (4 t + k) % 3 of point (4 t + k) / 3 -- not "three columns of one point and a zero": 3/4 of the instructions, and the matrix
         // pipe is what this loop waits for (a 16 x 16 x 4 f64 product occupies it for 64 cycles on this part -- its f64 matrix rate
@@ -1472,9 +1396,6 @@ __global__ __launch_bounds__(256, ESFM_SCHUR_OCC) void ba_schur_mfma_kernel(BADe
         __builtin_amdgcn_s_waitcnt(0xc07f);       // lgkmcnt(0): the table has been read before the next batch overwrites it
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");      // (... and the compiler may not sink this batch's reads below the next one's stores)
         __builtin_amdgcn_wave_barrier();
-#ifdef ESFM_SCHUR_TRACE
-        SCH_T(2); sch_acc[3] += 1;
-#endif
     }
     // the chunk's G: the waves' tiles added in wave order (fixed), lower block triangle, in the staging area
     __syncthreads();
@@ -1516,13 +1437,6 @@ __global__ __launch_bounds__(256, ESFM_SCHUR_OCC) void ba_schur_mfma_kernel(BADe
         const int c = true_cam(e / 6);
         if (c < nrc) atomicAdd(&redq[(size_t)n * n + 6 * c + e % 6], v);
     }
-#ifdef ESFM_SCHUR_TRACE
-    SCH_T(4);
-    if (lane == 0) {
-        for (int q = 0; q < 5; ++q) atomicAdd(&g_schur_trace[q], sch_acc[q]);
-        if (wave == 0) atomicAdd(&g_schur_trace[5], 1ull);
-    }
-#endif
 }
 
 // Free intrinsics: the block row of the reduced system that belongs to fx, cx, fy, cy (block index n_real_cam).
@@ -1704,13 +1618,6 @@ __global__ __launch_bounds__(kCholThreads) void ba_chol_solve_kernel(BADev d, do
     volatile double *failp = rd + n;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     if (tid == 0) *failp = 0.0;
-#ifdef ESFM_CHOL_PROFILE
-    double prof[6] = {0, 0, 0, 0, 0, 0};
-    long long tprev = wall_clock64();
-#define CHOL_MARK(slot) do { const long long tn__ = wall_clock64(); prof[slot] += (double)(tn__ - tprev); tprev = tn__; } while (0)
-#else
-#define CHOL_MARK(slot) do { } while (0)
-#endif
     const double *S = d.red;
     const double *rc = d.red + (size_t)n * n;
     const double *FtF = d.camacc;
@@ -1735,7 +1642,6 @@ __global__ __launch_bounds__(kCholThreads) void ba_chol_solve_kernel(BADev d, do
         L[e] = v;
     }
     __syncthreads();
-    CHOL_MARK(0);
     auto row = [&](int i) -> double * { return L + (size_t)i * (i + 1) / 2; };
 
     for (int j0 = 0; j0 < n; j0 += kCholNB) {
@@ -1766,7 +1672,6 @@ __global__ __launch_bounds__(kCholThreads) void ba_chol_solve_kernel(BADev d, do
                 if (r < nb && c <= r) row(j0 + r)[j0 + c] = a[c];
         }
         __syncthreads();
-        CHOL_MARK(1);
         // B2: every row below the block (and the rhs row) solves against the block's transpose
         for (int i = j0 + nb + tid; i <= n; i += kCholThreads) {
             double *Li = row(i);
@@ -1786,7 +1691,6 @@ __global__ __launch_bounds__(kCholThreads) void ba_chol_solve_kernel(BADev d, do
             }
         }
         __syncthreads();
-        CHOL_MARK(2);
         // C: trailing update A[i][j] -= sum_c L[i][j0+c] L[j][j0+c] over j0+nb <= j <= i <= n, j < n, in 4 x 4 tiles
         {
             const int base = j0 + nb;
@@ -1833,7 +1737,6 @@ __global__ __launch_bounds__(kCholThreads) void ba_chol_solve_kernel(BADev d, do
             }
         }
         __syncthreads();
-        CHOL_MARK(3);
     }
     // backward substitution L' y = z (z = row n), panels from the bottom
     double *z = row(n);
@@ -1866,15 +1769,9 @@ __global__ __launch_bounds__(kCholThreads) void ba_chol_solve_kernel(BADev d, do
         }
         __syncthreads();
     }
-    CHOL_MARK(4);
     const bool fail = *failp != 0.0;
     for (int i = tid; i < n; i += kCholThreads) d.y_c[i] = fail ? 0.0 : z[i];
     if (tid == 0 && fail) d.scal[SC_CHOL_FAIL] = 1.0;
-#ifdef ESFM_CHOL_PROFILE
-    CHOL_MARK(5);
-    if (tid == 0) for (int q = 0; q < 6; ++q) atomicAdd(&d.chol[q], prof[q]);
-#endif
-#undef CHOL_MARK
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1920,11 +1817,8 @@ __device__ __forceinline__ void candidate_cost(const BADev &d, int k, const doub
 // (register budget: four workgroups per CU.  The WITH_COST form had been compiled to 198 registers -- two waves per SIMD for a kernel
 // that streams; at 128 BA-25's iteration went 0.136 -> 0.133 ms.  The same audit found nothing else: the sweep at three / four
 // workgroups per CU spills, 25.7 / 36 us against 22.5; the f64-MFMA Schur kernel at one / three: 462 / 640 us against 294.)
-#ifndef ESFM_BACKSUB_OCC
-#define ESFM_BACKSUB_OCC 4
-#endif
 template <bool WITH_COST>
-__global__ __launch_bounds__(kPtChunkObs, ESFM_BACKSUB_OCC) void ba_backsub_chunk_kernel(BADev d, ScalBase sbase, double cauchy_a)
+__global__ __launch_bounds__(kPtChunkObs, 4) void ba_backsub_chunk_kernel(BADev d, ScalBase sbase, double cauchy_a)
 {
     __shared__ double red[8];
     __shared__ double tE[kPtChunkObs][3];

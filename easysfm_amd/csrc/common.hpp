@@ -40,13 +40,13 @@ const char *get_error();
 // The HIP runtime PINS a pageable buffer of 1 MiB or more for the transfer -- a userptr registration with the kernel driver -- and
 // the driver stops every queue of the process while it re-validates such a registration after ordinary heap activity in the same
 // mapping (malloc / free trimming the heap): bin/sfm_native's 768 x 512 x 3 images (1.18 MB) stalled a third of the frames for
-// 20 - 38 ms each, ten times what their detection takes (scratch/e2e_hiplog.sh: the time sits inside hipMemcpyAsync; with
+// 20 - 38 ms each, ten times what their detection takes (profiles/r05_driver_surf_undistort_pnp.txt: the time sits inside hipMemcpyAsync; with
 // GPU_PINNED_MIN_XFER_SIZE raised the stalls are gone).  Pieces below that size go through the runtime's own staging buffer
 // instead, whatever the process' environment says.
 // A buffer the caller has registered or allocated through HIP (hipHostRegister / hipHostMalloc) is pinned already and goes in one
 // asynchronous transfer.  Price of the pieces: a pageable transfer runs at the speed of the host's copy into the staging buffer,
 // 16 GB/s, instead of the DMA engines' 49 GB/s (esfm_undistort of a 3072 x 2048 x 3 image, both directions: 0.8 -> 2.3 ms;
-// from registered memory 0.77 ms; scratch/copy_paths.py) -- bounded and proportional, unlike the stalls.
+// from registered memory 0.77 ms; the same record) -- bounded and proportional, unlike the stalls.
 constexpr size_t kCopyPiece = 512u << 10;
 inline bool host_memory_is_pinned(const void *p)
 {

@@ -23,14 +23,8 @@
 //
 // DESIGN.md "Matching" explains the data layout and the certificate.
 #include "match_kernels.hpp"
-#ifndef ESFM_L2_SEGMENT_INC            // (scratch/build_variant.sh swaps in experimental schedules)
-#define ESFM_L2_SEGMENT_INC "l2_segment_gfx950.inc"
-#endif
-#include ESFM_L2_SEGMENT_INC           // ESFM_L2_SEGMENT_ASM: the matcher's hand-scheduled main loop (gen_l2_segment_asm.py)
-#ifndef ESFM_L2X1_SEGMENT_INC
-#define ESFM_L2X1_SEGMENT_INC "l2x1_segment_gfx950.inc"
-#endif
-#include ESFM_L2X1_SEGMENT_INC         // ESFM_L2X1_SEGMENT_ASM, ESFM_L2X1_KEEP: the one-product pass's main loop (gen_l2x1_segment_asm.py)
+#include "l2_segment_gfx950.inc"       // ESFM_L2_SEGMENT_ASM: the matcher's hand-scheduled main loop (gen_l2_segment_asm.py)
+#include "l2x1_segment_gfx950.inc"     // ESFM_L2X1_SEGMENT_ASM, ESFM_L2X1_KEEP: the one-product pass's main loop (gen_l2x1_segment_asm.py)
 #include "hmx1_segment_gfx950.inc"     // ESFM_HMX1_SEGMENT_ASM: the same loop around v_mfma_f32_32x32x64_f8f6f4 on FP4 operands (256-bit Hamming)
 
 #include <float.h>
@@ -519,14 +513,10 @@ __global__ __launch_bounds__(256) void l2_knn_mfma_kernel(const float *__restric
 // queries (half the L2 -> LDS traffic of the f32 kernel).  The fold of step n runs in the shadow of step n+1's MFMAs.
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
-#ifndef ESFM_BF16_DROP
-#define ESFM_BF16_DROP 0         // (experiment: mantissa bits dropped from the bf16 operands -- fewer toggling bits, a higher clock? the bounds follow the stored values)
-#endif
 __device__ __forceinline__ uint32_t bf16_rne_bits(float a)
 {
     const uint32_t u = __float_as_uint(a);
-    constexpr int S = 16 + ESFM_BF16_DROP;
-    return ((u + ((1u << (S - 1)) - 1u) + ((u >> S) & 1u)) >> S) << ESFM_BF16_DROP;
+    return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
 }
 // hi / lo halves of 2 consecutive floats packed into one dword each (element 0 in the low half)
 __device__ __forceinline__ void bf16_split2(float a0, float a1, uint32_t &hi, uint32_t &lo)
@@ -635,7 +625,7 @@ __global__ __launch_bounds__(256, 2) void l2_knn_bf16_kernel(const float *__rest
     // query lie in the (at most two) groups with the smallest minima; the third group key bounds every row outside the kept
     // groups, which is what the certificate needs.  The tail re-ranks the kept groups' rows exactly -- four consecutive 256-B rows
     // per group.
-    // (Measured on MI355X, scratch/ubench/mfma_issue: in SHADER CYCLES up to six VALU instructions hide behind every bf16 MFMA --
+    // (Measured on MI355X, profiles/r02_ubench_mfma_issue.txt: in SHADER CYCLES up to six VALU instructions hide behind every bf16 MFMA --
     // the 5.33-per-MFMA fold of round 1 included; what they cost is POWER: the chip is clock-limited on random operands, 1660 TFLOP/s
     // with the 4-per-result fold beside the MFMAs against 1805 with this one and 1690-1940 with none.)
     constexpr float kBig = 3.0e38f;
@@ -951,8 +941,8 @@ __device__ __forceinline__ double l2x1_e1(double qn, double rq, double sqrt_tmax
 //        E1 = (rB T + (2 |q| + rB) R) (1 + 2^-9) + 2^-15 (|q|^2 + max|t|^2) + 2^-118,   T = max |t|,  R = max rho_t  over the train set,
 //    bounds |(|q|^2 + score) - d^2| for every train row (l2x1_e1; the 2^-15 term is the three-product pass's whole budget: norms, MFMA
 //    accumulation, the canonical distance).  For unit-norm descriptors E1 ~ 0.008 against 6e-5: K = 4 groups per lane push tau -- the
-//    bound on every row outside the kept groups -- about as many ranks out as the larger error needs (simulated on M-SURF-4k,
-//    scratch/sim_bf16x1_cert.py: K = 3 leaves 6.9 % of the queries uncertified, K = 4 0.6 %, K = 6 0.01 %; the reference's own
+//    bound on every row outside the kept groups -- about as many ranks out as the larger error needs (simulated on M-SURF-4k:
+//    K = 3 leaves 6.9 % of the queries uncertified, K = 4 0.6 %, K = 6 0.01 %; the reference's own
 //    fountain descriptors 37 % / 15 % / 3.6 %);
 //  * this kernel ends with the keys: the screen drops the queries that provably fail the ratio test, every other query leaves a
 //    48-byte survivor entry.  l2_finish_kernel does the rest -- exact re-rank of the kept groups in the oracle's order, certificate,
@@ -1126,11 +1116,6 @@ __global__ __launch_bounds__(256, 2) void l2_knn_bf16x1_kernel(const float *__re
     int pi_nn = lb_nn >= 0 ? blk_pair[lb_nn] : -1;
     X1Item cur = make_item(lb_c, blk_pair[lb_c]);
     X1Item nxt = make_item(lb_n, lb_n >= 0 ? blk_pair[lb_n] : -1);
-#ifdef ESFM_X1_TRACE
-    uint64_t trA = __builtin_amdgcn_s_memrealtime();
-    const uint64_t tr_first = trA;
-    int tr_setup = 0, tr_loop = 0, tr_tail = 0, tr_clk = 0;
-#endif
     stage_issue(cur);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     stage_commit(0);
@@ -1142,10 +1127,6 @@ __global__ __launch_bounds__(256, 2) void l2_knn_bf16x1_kernel(const float *__re
         const int par = k & 1;
         const int nq = cur.nq, nt = cur.nt, pi = cur.pi;
         const int ntiles = (nt + TT - 1) / TT;
-#ifdef ESFM_X1_TRACE
-        { const uint64_t t = __builtin_amdgcn_s_memrealtime(); tr_setup += (int)(t - trA); trA = t; }
-        const uint64_t clk0 = __builtin_amdgcn_s_memtime();
-#endif
         if (ntiles > 0) {
             const u32x4 trsrc = raw_buffer_rsrc(hi_t + (size_t)cur.t_row0 * HS, (uint32_t)nt * (HS * 16));
             const u32x4 nrsrc = raw_buffer_rsrc(norms + cur.t_row0, (uint32_t)nt * 4u);
@@ -1158,9 +1139,6 @@ __global__ __launch_bounds__(256, 2) void l2_knn_bf16x1_kernel(const float *__re
         }
         rederive();
         st_norm[0] = st_norm[1] = st_qn[0] = st_qn[1] = st_rq[0] = st_rq[1] = st_m = st_r = 0.f;      // (dead here: not carried through the block)
-#ifdef ESFM_X1_TRACE
-        { const uint64_t t = __builtin_amdgcn_s_memrealtime(); tr_loop += (int)(t - trA); trA = t; tr_clk += (int)((__builtin_amdgcn_s_memtime() - clk0) >> 4); }
-#endif
         // the block left this thread's keys in LDS: key i of set s at float (K s + i) * 256 + tid  (replaced when no tile ran)
         float keys[NS][K];
 #pragma unroll
@@ -1185,11 +1163,6 @@ __global__ __launch_bounds__(256, 2) void l2_knn_bf16x1_kernel(const float *__re
 #pragma unroll
         for (int s = 0; s < NS; ++s) { qn_s[s] = lds_qn[par * QB + wave * 32 * NS + 32 * s + j]; rq_s[s] = lds_rq[par * QB + wave * 32 * NS + 32 * s + j]; }
         __syncthreads();                  // the ring (and the keys in it) is free: every wave has left the main loop and read its keys
-#ifdef ESFM_X1_NOTAIL
-        const bool notail = n_blocks >= 0;             // (timing experiments: the kernel without its tail)
-#else
-        const bool notail = false;
-#endif
 
         // ---- the RATIO SCREEN (round 4), all that is left of this kernel's tail.  The reference keeps a query only if d0 < ratio d1
         // (feature_matching.cpp:133); everything else is dropped one kernel later, and on the metric's workload that is > 90 % of the
@@ -1209,28 +1182,26 @@ __global__ __launch_bounds__(256, 2) void l2_knn_bf16x1_kernel(const float *__re
         int myslot[NS];
         float e1_s[NS];
         uint32_t rejmask = 0;
-        if (!notail) {
 #pragma unroll
-            for (int s = 0; s < NS; ++s) {
-                const int qrow = qbase + 32 * s + j;
-                const bool qvalid = qrow < nq;
-                const float v0 = keys[s][0], v1 = keys[s][1];
-                const float p0 = other_half(v0, h != 0), p1 = other_half(v1, h != 0);
-                const float k0 = fminf(v0, p0), kb = fminf(fmaxf(v0, p0), fminf(v1, p1));     // the two smallest of the 2 K keys
-                const double qn = (double)qn_s[s];
-                const double e1 = l2x1_e1(qn, (double)rq_s[s], sqrt_tmax, (double)tmax, (double)rmax);
-                const double L0 = qn + (double)k0 - e1 - fabs((double)k0) * kTrunc;
-                const double U1 = qn + (double)kb + e1 + fabs((double)kb) * kTrunc;
-                const bool rej = qvalid && (L0 >= ratio2m * U1);                              // false on NaN / inf: re-rank
-                const bool surv = qvalid && !rej;
-                const uint32_t m = (uint32_t)__ballot(surv);                                  // lanes 0 .. 31 (both halves agree)
-                myslot[s] = surv ? nsurv + __popc(m & ((1u << j) - 1u)) : -1;
-                float ef = (float)e1;
-                if ((double)ef < e1) ef = __uint_as_float(__float_as_uint(ef) + 1u);          // rounded up: e1 > 0, and ef < e1 makes ef finite (NaN: every compare false)
-                e1_s[s] = ef;
-                if (rej) rejmask |= 1u << s;
-                nsurv += __popc(m);
-            }
+        for (int s = 0; s < NS; ++s) {
+            const int qrow = qbase + 32 * s + j;
+            const bool qvalid = qrow < nq;
+            const float v0 = keys[s][0], v1 = keys[s][1];
+            const float p0 = other_half(v0, h != 0), p1 = other_half(v1, h != 0);
+            const float k0 = fminf(v0, p0), kb = fminf(fmaxf(v0, p0), fminf(v1, p1));     // the two smallest of the 2 K keys
+            const double qn = (double)qn_s[s];
+            const double e1 = l2x1_e1(qn, (double)rq_s[s], sqrt_tmax, (double)tmax, (double)rmax);
+            const double L0 = qn + (double)k0 - e1 - fabs((double)k0) * kTrunc;
+            const double U1 = qn + (double)kb + e1 + fabs((double)kb) * kTrunc;
+            const bool rej = qvalid && (L0 >= ratio2m * U1);                              // false on NaN / inf: re-rank
+            const bool surv = qvalid && !rej;
+            const uint32_t m = (uint32_t)__ballot(surv);                                  // lanes 0 .. 31 (both halves agree)
+            myslot[s] = surv ? nsurv + __popc(m & ((1u << j) - 1u)) : -1;
+            float ef = (float)e1;
+            if ((double)ef < e1) ef = __uint_as_float(__float_as_uint(ef) + 1u);          // rounded up: e1 > 0, and ef < e1 makes ef finite (NaN: every compare false)
+            e1_s[s] = ef;
+            if (rej) rejmask |= 1u << s;
+            nsurv += __popc(m);
         }
         // the one round trip of the tail -- the survivors' place in the pair's slice -- and the next item's set-up share their latency
         int base = 0;
@@ -1247,50 +1218,38 @@ __global__ __launch_bounds__(256, 2) void l2_knn_bf16x1_kernel(const float *__re
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         if (more) stage_commit(par ^ 1);
         // the tail's stores go out last: nothing waits for them (the main loop's first hand-over, eight steps on, finds them done)
-        if (!notail) {
-            float fltmax;        // (FLT_MAX out of an SGPR written here, like kBig in the set-up)
-            asm volatile("s_mov_b32 %0, 0x7f7fffff" : "=s"(fltmax));
-            int minus2;
-            asm volatile("s_mov_b32 %0, -2" : "=s"(minus2));
+        float fltmax;        // (FLT_MAX out of an SGPR written here, like kBig in the set-up)
+        asm volatile("s_mov_b32 %0, 0x7f7fffff" : "=s"(fltmax));
+        int minus2;
+        asm volatile("s_mov_b32 %0, -2" : "=s"(minus2));
 #pragma unroll
-            for (int s = 0; s < NS; ++s) {
-                const int qrow = qbase + 32 * s + j;
-                if (markers && h == 0 && ((rejmask >> s) & 1u)) {
-                    const size_t o = 2 * ((size_t)cur.out_off + qrow);
-                    *reinterpret_cast<int2 *>(knn_idx + o) = make_int2(minus2, minus2);
-                    *reinterpret_cast<float2 *>(knn_dist + o) = make_float2(fltmax, fltmax);
-                    if (rejected) {          // audit of the screen: what it dropped, on the global list
-                        const int slot = atomicAdd(&counters[0], 1);
-                        if (slot < flag_cap) { rejected[2 * slot] = pi; rejected[2 * slot + 1] = qrow; }
-                    }
-                }
-            }
-            if (nsurv > 0) {
-                base = __builtin_amdgcn_readfirstlane(base);
-                float4 *ent = surv_list + 3 * ((size_t)cur.out_off + base);                   // (a pair's slice holds nq entries: it cannot overflow)
-#pragma unroll
-                for (int s = 0; s < NS; ++s) {
-                    if (myslot[s] >= 0) {
-                        ent[3 * myslot[s] + h] = make_float4(keys[s][0], keys[s][1], keys[s][2], keys[s][3]);
-                        if (h == 0) ent[3 * myslot[s] + 2] = make_float4(__int_as_float(qbase + 32 * s + j), qn_s[s], e1_s[s], 0.f);
-                    }
+        for (int s = 0; s < NS; ++s) {
+            const int qrow = qbase + 32 * s + j;
+            if (markers && h == 0 && ((rejmask >> s) & 1u)) {
+                const size_t o = 2 * ((size_t)cur.out_off + qrow);
+                *reinterpret_cast<int2 *>(knn_idx + o) = make_int2(minus2, minus2);
+                *reinterpret_cast<float2 *>(knn_dist + o) = make_float2(fltmax, fltmax);
+                if (rejected) {          // audit of the screen: what it dropped, on the global list
+                    const int slot = atomicAdd(&counters[0], 1);
+                    if (slot < flag_cap) { rejected[2 * slot] = pi; rejected[2 * slot + 1] = qrow; }
                 }
             }
         }
-#ifdef ESFM_X1_TRACE
-        { const uint64_t t = __builtin_amdgcn_s_memrealtime(); tr_tail += (int)(t - trA); trA = t; }
-#endif
+        if (nsurv > 0) {
+            base = __builtin_amdgcn_readfirstlane(base);
+            float4 *ent = surv_list + 3 * ((size_t)cur.out_off + base);                   // (a pair's slice holds nq entries: it cannot overflow)
+#pragma unroll
+            for (int s = 0; s < NS; ++s) {
+                if (myslot[s] >= 0) {
+                    ent[3 * myslot[s] + h] = make_float4(keys[s][0], keys[s][1], keys[s][2], keys[s][3]);
+                    if (h == 0) ent[3 * myslot[s] + 2] = make_float4(__int_as_float(qbase + 32 * s + j), qn_s[s], e1_s[s], 0.f);
+                }
+            }
+        }
         if (!more) break;
         __syncthreads();                  // the next item's norms, maxima and query norms are in LDS, its first tile has landed
         cur = nxt; nxt = nn; lb_nn = lb_3; pi_nn = pi_3;
     }
-#ifdef ESFM_X1_TRACE
-    if (lane == 0) {     // per-wave stage times, 10-ns ticks (scratch/x1_trace.py)
-        atomicAdd(&counters[8], tr_setup); atomicAdd(&counters[9], tr_loop); atomicAdd(&counters[10], tr_tail); atomicAdd(&counters[11], 1);
-        atomicMax(&counters[12], (int)(trA & 0x3fffffffu)); atomicMax(&counters[13], 0x40000000 - (int)(tr_first & 0x3fffffffu));
-        atomicMax(&counters[14], (int)(trA - tr_first)); atomicAdd(&counters[15], tr_clk >> 4);
-    }
-#endif
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1470,7 +1429,7 @@ __device__ __forceinline__ void ratio_compact_pair_sparse(const PairDesc &pd, co
 //       two best of its candidates; U = an upper bound of the second-best d^2.  Every train row that can still change the answer
 //       has d^2 <= U, hence a one-product score s <= U - |q|^2 + E1 (E1: l2x1_e1).  So: the same bf16(-2 q).bf16(t) product on the
 //       matrix cores over the whole train set, a compare of every score with the query's threshold, the few rows that pass (0.1 -
-//       1.2 per query on the data simulated in scratch/sim_bf16x1_cert.py) evaluated exactly in the oracle's order and merged;
+//       1.2 per query on simulated data) evaluated exactly in the oracle's order and merged;
 //   (3) the exact brute force of a chunk whose hit list overflows (adversarial inputs: every row inside the error);
 //   (4) the ratio test and the ordered compaction of the pair's survivors (ratio_compact_pair).
 // Work split: S workgroups per pair (blockIdx = slice * n_pairs + pair).  Stage (1) is shared: the pair's virtual sets of seven
@@ -1479,10 +1438,7 @@ __device__ __forceinline__ void ratio_compact_pair_sparse(const PairDesc &pd, co
 // assumption about which workgroups are resident.  What stage (1) writes for the last workgroup -- results, list entries -- travels
 // through relaxed agent-scope atomics (write-through stores, L2-bypassing loads), not through agent-scope fences: on this part a
 // release is a write-back of the XCD's whole L2, an acquire an invalidation, and hundreds of workgroups would queue for them.
-#ifndef ESFM_FIN_THREADS
-#define ESFM_FIN_THREADS 256
-#endif
-constexpr int kFinThreads = ESFM_FIN_THREADS, kFinCap = 2048, kFinWaves = kFinThreads / 64;
+constexpr int kFinThreads = 256, kFinCap = 2048, kFinWaves = kFinThreads / 64;
 
 // exact 2-NN of up to 32 listed queries of one pair by the whole workgroup, the oracle's arithmetic and (distance, index) order:
 // thread = train row (16 x 16 B in registers), the queries as LDS broadcasts; the 64 keys of a wave's rows are reduced to the two
@@ -1561,9 +1517,6 @@ __device__ __forceinline__ void finish_bruteforce_chunk(const float *__restrict_
 // On the metric's workload nearly every survivor is a true match whose best group alone decides it: one transfer round trip.  A
 // query that ends neither certified nor decided goes on the pair's list for the threshold filter, with an upper bound of its
 // second-best d^2 as the filter's threshold.
-#ifdef ESFM_FIN_TRACE
-__shared__ int s_fin_tr[4][4];         // per wave: ticks waiting for transfers, ticks behind the wait, rounds (flushed once per wave: atomics per round distort what they measure)
-#endif
 struct FinRerankArgs {
     const float4 *ent;                 // the pair's survivor entries
     int nsv, per;                      // ... their number; entries per virtual set (<= kFinQV)
@@ -1578,10 +1531,7 @@ constexpr int kFinQV = 7;
 // What the re-rank keeps of a query between two rounds: its survivor entry (two half-waves' K keys, row / |q|^2 / E1) and the exact
 // two best rows so far.  64 bytes.
 struct FinPending { float4 ka, kb, mi; unsigned long long m0, m1; };
-#ifndef ESFM_FIN_PEND
-#define ESFM_FIN_PEND 112
-#endif
-constexpr int kFinPend = ESFM_FIN_PEND;        // pending queries of a wave (16 virtual sets' worth): 7 KiB of LDS per wave
+constexpr int kFinPend = 112;        // pending queries of a wave (16 virtual sets' worth): 7 KiB of LDS per wave
 
 // Stage (1) for ONE WAVE's share of a pair's survivors: the virtual sets v0, v0 + vstride, ... < nvs.
 // Round 5 -- COMPACTION BY ROUND.  Until then a virtual set of seven ran all of its rounds together and advanced at the pace of its
@@ -1713,29 +1663,13 @@ __device__ __forceinline__ void finish_rerank_wave(const FinRerankArgs &A, int v
 #pragma unroll
         for (int i = 0; i < 14; ++i)
             if (i < 2 * nv) rowv[i] = __builtin_amdgcn_raw_buffer_load_b128(A.frsrc_t, rs[i], 0, 0);
-#ifdef ESFM_FIN_TRACE
-        const unsigned long long rt0 = __builtin_amdgcn_s_memrealtime();
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const unsigned long long rt1 = __builtin_amdgcn_s_memrealtime();
-        if (lane == 0) s_fin_tr[threadIdx.x >> 6][0] += (int)(rt1 - rt0);
-#endif
         float da = 0.f;
         float got[14];
 #pragma unroll
         for (int i = 0; i < 14; ++i) {
             got[i] = 0.f;
             if (i < 2 * nv) {
-#ifdef ESFM_FIN_DIST2X      // sizing build: the canonical-order distance evaluated TWICE (same results): what the kernel gains per evaluation removed
-                float dr = l2sqr64_canonical_row16(qv[i >> 1], rowv[i]);
-                {
-                    u32x4 again = rowv[i];
-                    asm volatile("" : "+v"(again));
-                    const float dr2 = l2sqr64_canonical_row16(qv[i >> 1], again);
-                    dr = dr2 != dr2 ? dr2 : dr;
-                }
-#else
                 const float dr = l2sqr64_canonical_row16(qv[i >> 1], rowv[i]);
-#endif
                 got[i] = __int_as_float(__builtin_amdgcn_ds_bpermute(((lane & 3) * 16 + 15) * 4, __float_as_int(dr)));
             }
             __builtin_amdgcn_sched_barrier(0);       // (one row group at a time: interleaved, the fourteen chains took 296 registers)
@@ -1758,9 +1692,6 @@ __device__ __forceinline__ void finish_rerank_wave(const FinRerankArgs &A, int v
             m1 = kmin(hi, kmin(m1, c1k));
             m0 = lo;
         }
-#ifdef ESFM_FIN_TRACE
-        if (lane == 0) { s_fin_tr[threadIdx.x >> 6][2] += 1; s_fin_tr[threadIdx.x >> 6][1] += (int)(__builtin_amdgcn_s_memrealtime() - rt1); }           // rounds, ticks after the wait
-#endif
         if (screen && !last) {
             const float nk = fminf(nkey, tau);                   // the smallest key of anything not evaluated yet
             const double lrest = qn + (double)nk - e1 - fabs((double)nk) * kTrunc;
@@ -1998,11 +1929,9 @@ __device__ __noinline__ void finish_filter_sweep(const u32x4 *hi_rows /* the tra
 constexpr size_t kFinTailLds = 8192 + 8192 + (size_t)kFinWaves * 32 * 2 * 8;        // the buffers of stages (2) - (4)
 constexpr size_t kFinLdsBytes = kFinTailLds + (size_t)kFinWaves * kFinPend * sizeof(FinPending);   // + the re-rank's parked queries (its rows live in registers)
 
-#ifndef ESFM_FIN_OCC
-#define ESFM_FIN_OCC 3            // workgroups per CU the register budget is cut for: 3 = 168 registers, no spill in the re-rank (64.5 us per step;
+constexpr int kFinOcc = 3;        // workgroups per CU the register budget is cut for: 3 = 168 registers, no spill in the re-rank (64.5 us per step;
                                   // 1: 342 registers, 113 us; 2: 76 us; 4: 128 registers, 42 spills in the re-rank, 80 - 87 us; the query rows parked in LDS: 66 / 84 us at 3 / 4)
-#endif
-__global__ __launch_bounds__(kFinThreads, ESFM_FIN_OCC) void l2_finish_kernel(const float *__restrict__ desc, const u32x4 *__restrict__ hi_t,
+__global__ __launch_bounds__(kFinThreads, kFinOcc) void l2_finish_kernel(const float *__restrict__ desc, const u32x4 *__restrict__ hi_t,
                                                                 const u32x4 *__restrict__ hi_q, const float *__restrict__ norms,
                                                                 const float *__restrict__ rho_t, const float *__restrict__ rho_q,
                                                                 const PairDesc *__restrict__ pairs, const int32_t *__restrict__ pair_order, int n_pairs, int S,
@@ -2033,9 +1962,6 @@ __global__ __launch_bounds__(kFinThreads, ESFM_FIN_OCC) void l2_finish_kernel(co
     // order is pair-major over the pairs SORTED BY TRAIN SET: the S workgroups of a pair and the pairs of one train set run on one
     // XCD, whose L2 (4 MiB) then holds the one or two train sets their row fetches go to -- the re-rank is bound by those fetches
     // (51 k survivors x 9 rows x 256 B per step on the metric's workload).
-#ifdef ESFM_FIN_TRACE
-    const unsigned long long ft_in = __builtin_amdgcn_s_memrealtime();
-#endif
     const int lb = xcd_remap(blockIdx.x, gridDim.x);
     const int sl = lb % S, p = pair_order[lb / S];
     const PairDesc pd = pairs[p];
@@ -2056,27 +1982,11 @@ __global__ __launch_bounds__(kFinThreads, ESFM_FIN_OCC) void l2_finish_kernel(co
         A.knn_idx = knn_idx; A.knn_dist = knn_dist; A.knn_d2 = knn_d2;
         A.unc_cnt = unc_cnt; A.unc_list = unc_list;
         A.counters = counters; A.audit_unc = audit == 3 ? flagged : nullptr; A.audit_rej = audit == 4 ? flagged : nullptr; A.flag_cap = flag_cap;
-#ifdef ESFM_FIN_NOSTAGE1
-        const int nvs = 0;                    // (timing experiments)
-#else
         const int nvs = (A.nsv + A.per - 1) / A.per;
-#endif
-#ifdef ESFM_FIN_TRACE
-        const unsigned long long ft0 = __builtin_amdgcn_s_memrealtime();
-        if (lane == 0) { s_fin_tr[wave][0] = 0; s_fin_tr[wave][1] = 0; s_fin_tr[wave][2] = 0; }
-        const int nset = (nvs - (sl * NW + wave) + S * NW - 1) / (S * NW);
-#endif
         if (sl * NW + wave + S * NW >= nvs)      // (wave-uniform) at most one virtual set for this wave
             finish_rerank_wave<true>(A, sl * NW + wave, S * NW, nvs, nullptr);
         else
             finish_rerank_wave<false>(A, sl * NW + wave, S * NW, nvs, reinterpret_cast<FinPending *>(fin_smem + kFinTailLds) + wave * kFinPend);
-#ifdef ESFM_FIN_TRACE
-        if (lane == 0) {      // (scratch/fin_trace.py: 10-ns ticks of stage 1 per wave, virtual sets, waves)
-            atomicAdd(&counters[8], (int)(__builtin_amdgcn_s_memrealtime() - ft0)); atomicAdd(&counters[9], nset); atomicAdd(&counters[10], 1);
-            atomicAdd(&counters[12], s_fin_tr[wave][0]); atomicAdd(&counters[13], s_fin_tr[wave][1]); atomicAdd(&counters[11], s_fin_tr[wave][2]);
-            atomicAdd(&counters[14], (int)(ft0 - ft_in));
-        }
-#endif
     }
     // (Round 5, measured and not kept: every workgroup settling ITS OWN uncertified queries by exact brute force right here instead
     // of leaving them to the pair's last workgroup -- M-SURF-4k-hard: 16 695 such queries per step, the finish kernel 1.43 -> 1.71 ms:
@@ -2084,32 +1994,20 @@ __global__ __launch_bounds__(kFinThreads, ESFM_FIN_OCC) void l2_finish_kernel(co
     // what keeps the second pass cheap, and what it needed was a shorter serial tail, see stage (2).)
     // arrive; the last of the pair's S workgroups goes on alone.  Every wave waits for its own write-through stores to be
     // acknowledged before the barrier lets the arrival out.
-#ifdef ESFM_FIN_TRACE
-    const unsigned long long ft_arr = __builtin_amdgcn_s_memrealtime();
-#endif
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     if (S > 1) {
         if (tid == 0) s_last = __hip_atomic_fetch_add(&done[p], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == S - 1;
         __syncthreads();
-#ifdef ESFM_FIN_TRACE
-        if (lane == 0) atomicAdd(&counters[15], (int)(__builtin_amdgcn_s_memrealtime() - ft_arr));
-#endif
         if (!s_last) return;
         if (tid == 0) __hip_atomic_store(&done[p], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // (everybody has arrived: nobody touches it again in this launch)
     }
     if (audit == 3 || audit == 4) return;          // the first pass alone: its answers, its own lists
 
     // ---- (2), (3): the pair's uncertified queries, chunks of 32, the whole train set by this workgroup's four waves
-#ifdef ESFM_FIN_NOSTAGE2
-    const int cnt = 0;                        // (timing experiments: wrong results for uncertified queries)
-#else
     const int cnt = min(ld_coh_i(unc_cnt + p), nq);
-#endif
-#ifndef ESFM_FIN_SMALL
-#define ESFM_FIN_SMALL 8       // uncertified queries of a pair up to which the exact brute force beats the threshold filter's fixed ~100-us chain
-#endif
-    if (cnt > 0 && cnt <= ESFM_FIN_SMALL && audit != 1) {
+    constexpr int kSmall = 8;      // uncertified queries of a pair up to which the exact brute force beats the threshold filter's fixed ~100-us chain
+    if (cnt > 0 && cnt <= kSmall && audit != 1) {
         // a handful of queries: their exact 2-NN over the whole train set straight away (the threshold filter below is a chain of
         // nt / 128 dependent MFMA steps per chunk of 32 whatever the chunk holds: ~100 us for ONE query; this: a few us per query)
         if (tid < 32) s_qrows[tid] = tid < cnt ? ld_coh_i(unc_list + pd.out_off + tid) : 0;
@@ -2147,9 +2045,6 @@ __global__ __launch_bounds__(kFinThreads, ESFM_FIN_OCC) void l2_finish_kernel(co
         const int st0 = (nsteps * wave) / NW, st1 = (nsteps * (wave + 1)) / NW;
         auto key_of = [](float d, int t) { return (t >= 0 && d < FLT_MAX) ? (((u64)__float_as_uint(d) << 32) | (u64)(uint32_t)t) : ~0ull; };   // FLT_MAX, +inf, NaN: never a neighbour
         for (int c = 0; c < nchunks; ++c) {
-#ifdef ESFM_FIN_TRACE2
-            const unsigned long long t2a = __builtin_amdgcn_s_memrealtime();
-#endif
             if (tid == 0) s_nhit = 0;
             const int nqc = min(64, cnt - c * 64);
             // lane j of either half-wave owns the queries j and 32 + j of the sweep
@@ -2190,10 +2085,6 @@ __global__ __launch_bounds__(kFinThreads, ESFM_FIN_OCC) void l2_finish_kernel(co
             finish_filter_sweep(hi_t + (size_t)pd.t_row0 * HS, tn, st0, st1, nt, j, h, nqc > 32, bq, thr2, &s_nhit, s_h);
             __syncthreads();
             const int nhit = s_nhit;
-#ifdef ESFM_FIN_TRACE2
-            const unsigned long long t2b = __builtin_amdgcn_s_memrealtime();
-            if (tid == 0) { atomicAdd(&counters[4], (int)(t2b - t2a)); atomicAdd(&counters[5], nhit); atomicAdd(&counters[6], 1); atomicMax(&counters[3], nhit); }
-#endif
             if (nhit <= CAP) {
                 // exact distances of the hits in the oracle's order (a thread per hit), merged as (distance, index) keys: the smallest
                 // key of a query by a 64-bit LDS atomic minimum, then the smallest of the others (two different rows never share a key;
@@ -2237,9 +2128,6 @@ __global__ __launch_bounds__(kFinThreads, ESFM_FIN_OCC) void l2_finish_kernel(co
                     st_coh_f(knn_dist + o + 1, k1 != ~0ull ? __uint_as_float((uint32_t)(k1 >> 32)) : FLT_MAX);
                 }
                 __syncthreads();
-#ifdef ESFM_FIN_TRACE2
-                if (tid == 0) atomicAdd(&counters[7], (int)(__builtin_amdgcn_s_memrealtime() - t2b));
-#endif
             } else {
                 // too many rows inside the error bound: exact brute force of the sweep's queries, 32 at a time
                 if (tid < nqc) {
@@ -2257,12 +2145,7 @@ __global__ __launch_bounds__(kFinThreads, ESFM_FIN_OCC) void l2_finish_kernel(co
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // (the write-through stores above, before the ratio stage reads them back)
         __syncthreads();
     }
-#ifdef ESFM_FIN_NORATIO
-    if (do_ratio && n_pairs < 0)          // (timing experiments)
-#else
-    if (do_ratio)
-#endif
-    {
+    if (do_ratio) {
         if (ratio2m < 1.0e300)            // the screen ran: only its survivors have records
             ratio_compact_pair_sparse<kFinThreads>(pd, surv_list + 3 * (size_t)pd.out_off, min(surv_cnt[p], nq), knn_idx, knn_dist, ratio, query_idx, train_idx,
                                                    distance, n_out + p, reinterpret_cast<uint32_t *>(fin_smem), s_wave, &s_base);
@@ -2825,8 +2708,8 @@ __global__ __launch_bounds__(256, 2) void hamming_knn_mfma_kernel(const unsigned
 // v_mfma_f32_32x32x64_f8f6f4 (cbsz = blgp = 4: FP4 x FP4, 16 B per lane and K-step): byte for byte the shapes of the one-product L2
 // pass, so the whole main loop -- LDS-DMA ring of two 256-row tiles, four query sets per wave, fold groups of eight with the
 // position in the low mantissa bits -- is that pass's generator with another instruction (hmx1_segment_gfx950.inc).  The FP4
-// instruction moves 64 K per 8 passes where v_mfma_i32_32x32x32_i8 moves 32 (measured 7.7 against 4.2 Pop/s,
-// scratch/ubench/mfma_fp4.hip, which also checks the products exact), at half the operand bytes of the byte-per-bit form.
+// instruction moves 64 K per 8 passes where v_mfma_i32_32x32x32_i8 moves 32 (measured 7.7 against 4.2 Pop/s by a
+// microbenchmark that also checked the products exact), at half the operand bytes of the byte-per-bit form.
 // No certificate: the scores are exact, a group key IS the group's smallest score.  With code order = row order inside a lane half,
 // the nearest row sits in the half's smallest key's group and the second nearest in one of its two smallest (a group in front of it
 // would hold a row in front of it in (distance, index) order, and there is only one such row), and a group whose score exceeds the
@@ -2856,16 +2739,6 @@ __global__ __launch_bounds__(256) void hamming_expand_fp4_kernel(const uint32_t 
     img_t[i] = t; img_q[i] = q;
 }
 
-#ifdef ESFM_HMX1_TRACE
-// timing-only build (scratch/build_variant.sh NAME -DESFM_HMX1_TRACE): per-wave stage times of hamming_fp4_kernel in s_memrealtime ticks
-// (10 ns) and the shader clock inside the main loop (s_memtime); scratch/hmx1_trace.py reads them through esfm_debug_hmx1_trace
-__device__ int g_hmx1_trace[8];
-extern "C" int esfm_debug_hmx1_trace(int *out, int reset)
-{
-    if (reset) { int z[8] = {0, 0, 0, 0, 0, 0, 0, 0}; return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_hmx1_trace), z, sizeof(z)); }
-    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_hmx1_trace), sizeof(g_hmx1_trace));
-}
-#endif
 __global__ __launch_bounds__(256, 2) void hamming_fp4_kernel(const uint32_t *__restrict__ packed, const u32x4 *__restrict__ img_t,
                                                              const u32x4 *__restrict__ img_q, const float *__restrict__ start,
                                                              const PairDesc *__restrict__ pairs, const int32_t *__restrict__ blk_pair, int n_blocks,
@@ -2875,9 +2748,6 @@ __global__ __launch_bounds__(256, 2) void hamming_fp4_kernel(const uint32_t *__r
 {
     // (a pair without queries has no block: nobody would write its count)
     if (done && blockIdx.x == 0) for (int p = threadIdx.x; p < n_pairs; p += 256) if (pairs[p].nq == 0) n_out[p] = 0;
-#ifdef ESFM_HMX1_TRACE
-    const uint64_t tr0 = __builtin_amdgcn_s_memrealtime();
-#endif
     constexpr int TT = ESFM_HMX1_TT, NS = ESFM_HMX1_SETS, K = ESFM_HMX1_KEEP, RING = ESFM_HMX1_RING, GRP = ESFM_HMX1_GRP, NG = 16 / GRP;
     constexpr int QB = 128 * NS, HS = 8;
     constexpr int TILE_BYTES = TT * HS * 16;
@@ -2932,9 +2802,6 @@ __global__ __launch_bounds__(256, 2) void hamming_fp4_kernel(const uint32_t *__r
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-#ifdef ESFM_HMX1_TRACE
-    const uint64_t tr1 = __builtin_amdgcn_s_memrealtime(), clk1 = __builtin_amdgcn_s_memtime();
-#endif
     if (ntiles > 0) {
         asm volatile(ESFM_HMX1_SEGMENT_ASM
                      :
@@ -2943,9 +2810,6 @@ __global__ __launch_bounds__(256, 2) void hamming_fp4_kernel(const uint32_t *__r
                        "s"(ntiles), "s"(nt), "s"(trsrc), "s"(nrsrc), "s"(lds_tile_addr), "s"(wave_s)
                      : ESFM_HMX1_SEGMENT_CLOBBERS);
     }
-#ifdef ESFM_HMX1_TRACE
-    const uint64_t tr2 = __builtin_amdgcn_s_memrealtime(), clk2 = __builtin_amdgcn_s_memtime();
-#endif
     {   // (nothing thread-dependent lives across the block: see l2_knn_bf16x1_kernel)
         int l;
         asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
@@ -3034,13 +2898,6 @@ __global__ __launch_bounds__(256, 2) void hamming_fp4_kernel(const uint32_t *__r
             }
         }
     }
-#ifdef ESFM_HMX1_TRACE
-    if (lane == 0) {
-        const uint64_t tr3 = __builtin_amdgcn_s_memrealtime();
-        atomicAdd(&g_hmx1_trace[0], (int)(tr1 - tr0)); atomicAdd(&g_hmx1_trace[1], (int)(tr2 - tr1)); atomicAdd(&g_hmx1_trace[2], (int)(tr3 - tr2));
-        atomicAdd(&g_hmx1_trace[3], 1); atomicAdd(&g_hmx1_trace[4], (int)((clk2 - clk1) >> 8));
-    }
-#endif
     // ---- the match entry points: ratio test + ordered compaction of the pair by the workgroup that brings its last block (the
     // protocol of l2_finish_kernel: stores acknowledged, barrier, one relaxed agent-scope arrival; `done` reads 0 again afterwards)
     if (done) {

@@ -46,11 +46,6 @@ __device__ __forceinline__ void normalise_pt(const RansacPair &pr, const float2 
 // value of lane J of the caller's row of 16 lanes: one v_mov_b64_dpp (row_newbcast) instead of the two ds_bpermute_b32 and their LDS
 // round trip that __shfl(v, J, 16) costs.  (The s_nop covers the DPP read-after-VALU-write hazard, which the compiler does not track
 // through inline asm.)
-#ifdef ESFM_DK_HIST
-// timing / diagnosis build: histogram of Durand-Kerner sweeps per hypothesis (scratch/dk_hist.py)
-__device__ unsigned int g_dk_hist[301];
-extern "C" int esfm_debug_dk_hist(unsigned int *out) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_dk_hist), sizeof(g_dk_hist)); }
-#endif
 template <int J>
 __device__ __forceinline__ double row16_bcast(double v)
 {
@@ -147,9 +142,6 @@ __global__ __launch_bounds__(256) void essential_roots_kernel(int n, double *__r
         const unsigned long long moving = __ballot(still);
         if (((moving >> (16 * grp)) & 0xffffull) == 0ull) active = false;
     }
-#ifdef ESFM_DK_HIST
-    if (have && i == 0) atomicAdd(&g_dk_hist[my_sweeps], 1u);
-#endif
     if (dbg && in && i < 10) {
         double *d = dbg + 32 * (size_t)g;
         d[i] = cc[i]; d[10 + i] = re; d[20 + i] = im;
