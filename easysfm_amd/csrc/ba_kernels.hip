@@ -12,7 +12,7 @@
 //   ba_backsub_*_kernel    back-substitution (observation-parallel, 2 passes), candidate point, model cost change
 //   ba_cost_kernel         robustified cost of a parameter vector (candidate evaluation)
 //
-// The LM control flow (accept/reject, radius) lives in ba_api.cpp.  DESIGN.md "Bundle adjustment".
+// The LM control flow (accept/reject, radius) lives in ba_solve.cpp.  DESIGN.md "Bundle adjustment".
 #include <array>
 
 #include "ba_kernels.hpp"
@@ -322,7 +322,6 @@ __device__ __forceinline__ int qexp_of(double diag)
 // critical path; more waves would need the kernel in 128 registers.  A pure copy of the same 18 + 18 arrays runs at 5.9 TB/s in ANY
 // layout (SoA of doubles as here, double2, tiles of 64: profiles/r05_soa_stream_ubench.txt), so the layout is not what holds the sweep back.
 constexpr int kLinThreadsLarge = 512, kLinThreadsSmall = 256;
-constexpr int kLinSmallObs = 1 << 20;
 constexpr int kLinLdsPerCam = 27 * 8 + 7 * 8 + 4 + 7 * 4;   // acc, maxima, count, exponents
 
 template <bool PRIV, bool CALIB, int kLinThreads>
@@ -2160,8 +2159,33 @@ int ba_red_pack(hipStream_t st, const BADev &d, double *packed, bool unpack)
     return ESFM_OK;
 }
 
+// ---- the size-dependent kernel forms (BaForms, ba_kernels.hpp): the one place their thresholds are written ----
+constexpr int kLinSmallObs = 1 << 20;              // observations from which a problem is `large`
+constexpr size_t kLinLdsBudget = 160 * 1024;       // the sweep: one workgroup per CU may take all of a CU's LDS
+constexpr size_t kSchurLdsBudget = 156 * 1024;     // the LDS-slab Schur kernel
+constexpr size_t kCholLdsBudget = 150 * 1024;      // the one-workgroup reduced solve with its packed factor in LDS
+// dynamic LDS of the three kernels that have an in-LDS form
+static size_t lin_lds_bytes(int n_real_cam) { return 18 * sizeof(double) + (size_t)n_real_cam * kLinLdsPerCam; }
+static size_t schur_lds_bytes(int n_cam)     // [nblk * kSchurPitch] blocks, [6 n_cam] right-hand side, then [6 n_cam] ints: qexp
+{
+    return sizeof(double) * ((size_t)n_cam * (n_cam + 1) / 2 * kSchurPitch + 6 * (size_t)n_cam) + sizeof(int) * 6 * (size_t)n_cam;
+}
+static size_t chol_lds_bytes(int n_cam) { const size_t n = 6 * (size_t)n_cam; return sizeof(double) * ((n + 1) * (n + 2) / 2 + n + 2); }
+
+BaForms ba_forms(int n_real_cam, bool has_calib, int n_obs)
+{
+    const int n_cam = n_real_cam + (has_calib ? 1 : 0);
+    BaForms f;
+    f.schur = schur_lds_bytes(n_cam) <= kSchurLdsBudget ? BaForms::SCHUR_LDS_SLABS : BaForms::SCHUR_TABLES;
+    f.sweep_sums_in_lds = lin_lds_bytes(n_real_cam) <= kLinLdsBudget;
+    f.large = n_obs >= kLinSmallObs;
+    f.solve = ba_chol_small_fits(n_cam) ? BaForms::SOLVE_SMALL_ONE_WG : chol_lds_bytes(n_cam) <= kCholLdsBudget ? BaForms::SOLVE_LDS : BaForms::SOLVE_TILED;
+    return f;
+}
+
 int ba_linearize(hipStream_t st, const BADev &d, int num_cu, double cauchy_a, bool use_scaling, esfm_ctx *timing_ctx, int *deferred_slabs, double cost_bound)
 {
+    const BaForms &forms = d.parts->forms;
     // provisional exponent of the residual column (see the kernel): sqrt(sum r^2) <= sqrt(2 cost) < 2^prov_rexp
     int prov_rexp = INT_MIN;
     if (cost_bound > 0.0 && cost_bound < 1e300) prov_rexp = std::ilogb(std::sqrt(2.0 * cost_bound)) + 1;
@@ -2171,14 +2195,14 @@ int ba_linearize(hipStream_t st, const BADev &d, int num_cu, double cauchy_a, bo
         ESFM_HIP_TRY(hipMemsetAsync(d.qexp, 0, sizeof(int32_t) * 6 * (size_t)d.n_cam, st));
         return ESFM_OK;
     }
-    const size_t priv_bytes = 18 * sizeof(double) + (size_t)d.n_real_cam * kLinLdsPerCam;
-    const bool small = d.n_obs < kLinSmallObs;
+    const size_t priv_bytes = lin_lds_bytes(d.n_real_cam);
+    const bool small = !forms.large;
     const int kLinThreads = small ? kLinThreadsSmall : kLinThreadsLarge;
     // (the 512-thread form fills a CU's registers with ONE workgroup -- 250 registers x 8 waves -- so a second workgroup per CU only runs
     // after the first, paying the 9-us prologue (LDS clear, exponents) and the 8-us epilogue (guard, slab) again: one per CU)
-    static const int grid_mul = getenv("ESFM_LIN_GRID_MUL") ? atoi(getenv("ESFM_LIN_GRID_MUL")) : 0;       // developer switch (A/B)
-    const int grid = std::min(div_up(d.n_obs, kLinThreads), std::max(1, num_cu) * (grid_mul > 0 ? grid_mul : (small ? 2 : 1)));
-    const bool priv = priv_bytes <= 160 * 1024 && d.lin_slabs && (size_t)grid * d.n_cam * 27 <= d.lin_slab_cap;
+    const int grid = std::min(div_up(d.n_obs, kLinThreads), std::max(1, num_cu) * (small ? 2 : 1));
+    const bool priv = forms.sweep_sums_in_lds;
+    if (priv && (size_t)grid * ba_lin_slab_doubles(d.n_cam) > d.lin_slab_cap) { set_error("BA sweep: %d slabs do not fit lin_slabs", grid); return ESFM_ERR_INVALID_ARG; }
     ScalBase sbase;
     { const int slots[2] = {SC_COST, SC_LIN_BAD}; if (int rc = scal_reserve<2>(st, d, slots, grid, sbase)) return rc; }
     if (priv) {
@@ -2192,7 +2216,7 @@ int ba_linearize(hipStream_t st, const BADev &d, int num_cu, double cauchy_a, bo
         LAUNCH_CHECK();
         d.parts->grad_done = d.parts->single_rank;
         // one rank, per-point blocks by the walking kernel next: the slab reduction rides in that launch (ba_point_prep_camacc)
-        if (deferred_slabs && d.parts->single_rank && !(d.n_pchunks > 0 && d.n_obs >= (1 << 20)) && d.n_pt > 0) { *deferred_slabs = grid; return ESFM_OK; }
+        if (deferred_slabs && d.parts->single_rank && !(d.n_pchunks > 0 && forms.large) && d.n_pt > 0) { *deferred_slabs = grid; return ESFM_OK; }
         hipLaunchKernelGGL(ba_camacc_reduce_kernel, dim3(div_up(d.n_cam * 27, kRedEnt)), dim3(256), 0, st, d, d.lin_slabs, grid, d.parts->single_rank ? 1 : 0);
         LAUNCH_CHECK();
         return ESFM_OK;
@@ -2224,7 +2248,7 @@ int ba_point_prep(hipStream_t st, const BADev &d, double radius, double min_diag
         return ESFM_OK;
     }
     if (d.n_pt <= 0) return ESFM_OK;
-    if (fresh && d.n_pchunks > 0 && d.n_obs >= (1 << 20)) {        // (see ba_point_prep_chunk_kernel for the crossover)
+    if (fresh && d.n_pchunks > 0 && d.parts->forms.large) {        // (see ba_point_prep_chunk_kernel for the crossover)
         if (int rc = scal_reserve<1>(st, d, slots, d.n_pchunks, sbase)) return rc;
         hipLaunchKernelGGL(ba_point_prep_chunk_kernel, dim3(d.n_pchunks), dim3(kPtChunkObs), 0, st, d, radius, min_diag, max_diag, sbase);
         LAUNCH_CHECK();
@@ -2270,24 +2294,25 @@ static int schur_to_double(hipStream_t st, const BADev &d, int rhs_exp)
     return ESFM_OK;
 }
 
-int ba_schur(hipStream_t st, const BADev &d, int num_cu, double *slabs, size_t slab_capacity_doubles, double rhs_bound)
+int ba_schur(hipStream_t st, const BADev &d, int num_cu, double rhs_bound)
 {
+    const BaForms &forms = d.parts->forms;
     // (the slab path writes every entry of red anything reads -- lower blocks and right-hand side -- in its reduce kernel; the other
     // paths and the free-intrinsics kernel accumulate into it)
-    const bool slab_path = d.n_obs > 0 && !d.has_calib && slabs &&
-                           sizeof(double) * ((size_t)(d.n_cam * (d.n_cam + 1) / 2) * kSchurPitch + 6 * (size_t)d.n_cam) + sizeof(int) * 6 * (size_t)d.n_cam <= 156 * 1024;
+    const bool slab_path = forms.schur == BaForms::SCHUR_LDS_SLABS && d.n_obs > 0 && !d.has_calib;
     d.parts->red_fixed = false;
     if (!slab_path && !d.parts->red_clean) ESFM_HIP_TRY(hipMemsetAsync(d.red, 0, sizeof(double) * ba_red_doubles(d.n_cam), st));
     if (d.n_obs <= 0) return ESFM_OK;
     d.parts->red_clean = false;
     const int rhs_exp = bound_exponent(rhs_bound);
     const bool finish = !d.has_calib;    // with free intrinsics ba_schur_calib adds its block row first, then converts
-    const int nblk = d.n_cam * (d.n_cam + 1) / 2;
-    const int slab_doubles = nblk * 36 + 6 * d.n_cam;
-    const size_t lds_bytes = sizeof(double) * ((size_t)nblk * kSchurPitch + 6 * (size_t)d.n_cam) + sizeof(int) * 6 * (size_t)d.n_cam;
-    constexpr int schur_threads = 1024;     // (512: 39 us, 256: 52 us against 35 us on BA-25 -- every workgroup zeroes and writes out a 96 KB slab)
-    const int n_slabs = std::max(1, std::min(num_cu, div_up(d.n_obs, schur_threads)));
-    if (lds_bytes <= 156 * 1024 && slabs && (size_t)n_slabs * slab_doubles <= slab_capacity_doubles) {
+    if (forms.schur == BaForms::SCHUR_LDS_SLABS) {
+        const int slab_doubles = (int)ba_schur_slab_doubles(d.n_cam);
+        const size_t lds_bytes = schur_lds_bytes(d.n_cam);
+        constexpr int schur_threads = 1024;     // (512: 39 us, 256: 52 us against 35 us on BA-25 -- every workgroup zeroes and writes out a 96 KB slab)
+        const int n_slabs = std::max(1, std::min(num_cu, div_up(d.n_obs, schur_threads)));
+        double *slabs = d.slabs;
+        if ((size_t)n_slabs * slab_doubles > d.slab_cap) { set_error("BA Schur: %d slabs do not fit the slab buffer", n_slabs); return ESFM_ERR_INVALID_ARG; }
         ESFM_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&ba_schur_lds_kernel),
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
         hipLaunchKernelGGL(ba_schur_lds_kernel, dim3(n_slabs), dim3(schur_threads), lds_bytes, st, d, slabs, slab_doubles, rhs_exp);
@@ -2297,44 +2322,39 @@ int ba_schur(hipStream_t st, const BADev &d, int num_cu, double *slabs, size_t s
         LAUNCH_CHECK();
         return ESFM_OK;
     }
-    const bool tables = d.n_mchunks[0] + d.n_mchunks[1] + d.n_chunks + d.n_chunks_b + d.n_wide_obs > 0;
-    if (tables) {
-        // narrow tracks (nearly all of them in a sequence capture): the matrix-core kernel, plain and rotated camera numbering
-        if (d.n_mchunks[0] + d.n_mchunks[1] > 0) {
-            SchurMfTables tabs;
-            for (int tb = 0; tb < 2; ++tb) {
-                tabs.slot_obs[tb] = d.mslot_obs[tb]; tabs.slot_pc[tb] = reinterpret_cast<const int2 *>(d.mslot_pc[tb]); tabs.batch_slot[tb] = d.mbatch_slot[tb];
-                tabs.chunk_batch0[tb] = d.mchunk_batch0[tb]; tabs.chunk_cam0[tb] = d.mchunk_cam0[tb];
-            }
-            tabs.n_plain = d.n_mchunks[0]; tabs.rot_seam = d.n_real_cam / 2;
-            ESFM_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&ba_schur_mfma_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMfLdsBytes));
-            hipLaunchKernelGGL(ba_schur_mfma_kernel, dim3(d.n_mchunks[0] + d.n_mchunks[1]), dim3(256), kMfLdsBytes, st, d, rhs_exp, tabs);
-            LAUNCH_CHECK();
+    // SCHUR_TABLES: every observation is in exactly one of the tables (make_ba_layout)
+    // narrow tracks (nearly all of them in a sequence capture): the matrix-core kernel, plain and rotated camera numbering
+    if (d.n_mchunks[0] + d.n_mchunks[1] > 0) {
+        SchurMfTables tabs;
+        for (int tb = 0; tb < 2; ++tb) {
+            tabs.slot_obs[tb] = d.mslot_obs[tb]; tabs.slot_pc[tb] = reinterpret_cast<const int2 *>(d.mslot_pc[tb]); tabs.batch_slot[tb] = d.mbatch_slot[tb];
+            tabs.chunk_batch0[tb] = d.mchunk_batch0[tb]; tabs.chunk_cam0[tb] = d.mchunk_cam0[tb];
         }
-        constexpr size_t win_bytes = sizeof(double) * (kWinBlocks * kSchurPitch + 6 * kWinCams);
-        if (d.n_chunks > 0 || d.n_chunks_b > 0)
-            ESFM_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&ba_schur_window_kernel),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)win_bytes));
-        if (d.n_chunks > 0) {
-            hipLaunchKernelGGL(ba_schur_window_kernel, dim3(d.n_chunks), dim3(1024), win_bytes, st, d, rhs_exp, d.slot_obs, d.chunk_slot, d.chunk_cam0, 0);
-            LAUNCH_CHECK();
-        }
-        if (d.n_chunks_b > 0) {        // the tracks that are narrow once the camera indices are rotated by half the loop
-            hipLaunchKernelGGL(ba_schur_window_kernel, dim3(d.n_chunks_b), dim3(1024), win_bytes, st, d, rhs_exp, d.slot_obs_b, d.chunk_slot_b, d.chunk_cam0_b,
-                               d.n_real_cam / 2);
-            LAUNCH_CHECK();
-        }
-        // tracks wider than the window in both index spaces go through the plain kernel, spread over the chip (inside the window
-        // kernel they would all land in the chunks of the lowest cameras and the whole launch would wait for those workgroups)
-        if (d.n_wide_obs > 0) {
-            hipLaunchKernelGGL(ba_schur_kernel, dim3(div_up(d.n_wide_obs, 256)), dim3(256), 0, st, d, rhs_exp, d.wide_obs, d.n_wide_obs);
-            LAUNCH_CHECK();
-        }
-    } else {
-        hipLaunchKernelGGL(ba_schur_kernel, dim3(div_up(d.n_obs, 256)), dim3(256), 0, st, d, rhs_exp, (const int32_t *)nullptr, 0);
+        tabs.n_plain = d.n_mchunks[0]; tabs.rot_seam = d.n_real_cam / 2;
+        ESFM_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&ba_schur_mfma_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMfLdsBytes));
+        hipLaunchKernelGGL(ba_schur_mfma_kernel, dim3(d.n_mchunks[0] + d.n_mchunks[1]), dim3(256), kMfLdsBytes, st, d, rhs_exp, tabs);
         LAUNCH_CHECK();
     }
-    if (finish && ba_solve_is_tiled(d.n_cam) && (d.parts->single_rank || d.sparse)) {
+    constexpr size_t win_bytes = sizeof(double) * (kWinBlocks * kSchurPitch + 6 * kWinCams);
+    if (d.n_chunks > 0 || d.n_chunks_b > 0)
+        ESFM_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&ba_schur_window_kernel),
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)win_bytes));
+    if (d.n_chunks > 0) {
+        hipLaunchKernelGGL(ba_schur_window_kernel, dim3(d.n_chunks), dim3(1024), win_bytes, st, d, rhs_exp, d.slot_obs, d.chunk_slot, d.chunk_cam0, 0);
+        LAUNCH_CHECK();
+    }
+    if (d.n_chunks_b > 0) {        // the tracks that are narrow once the camera indices are rotated by half the loop
+        hipLaunchKernelGGL(ba_schur_window_kernel, dim3(d.n_chunks_b), dim3(1024), win_bytes, st, d, rhs_exp, d.slot_obs_b, d.chunk_slot_b, d.chunk_cam0_b,
+                           d.n_real_cam / 2);
+        LAUNCH_CHECK();
+    }
+    // tracks wider than the window in both index spaces go through the plain kernel, spread over the chip (inside the window
+    // kernel they would all land in the chunks of the lowest cameras and the whole launch would wait for those workgroups)
+    if (d.n_wide_obs > 0) {
+        hipLaunchKernelGGL(ba_schur_kernel, dim3(div_up(d.n_wide_obs, 256)), dim3(256), 0, st, d, rhs_exp, d.wide_obs, d.n_wide_obs);
+        LAUNCH_CHECK();
+    }
+    if (finish && forms.solve == BaForms::SOLVE_TILED && (d.parts->single_rank || d.sparse)) {
         // the tiled solve's assembly kernel reads red next: it converts on the way and clears what it has read (the structure-aware
         // solve of several ranks: its pack kernel does)
         d.parts->red_fixed = true; d.parts->red_rhs_exp = rhs_exp;
@@ -2343,26 +2363,20 @@ int ba_schur(hipStream_t st, const BADev &d, int num_cu, double *slabs, size_t s
     return finish ? schur_to_double(st, d, rhs_exp) : ESFM_OK;
 }
 
-bool ba_solve_is_tiled(int n_cam)
-{
-    const int n = 6 * n_cam;
-    return n_cam > 0 && !ba_chol_small_fits(n_cam) && sizeof(double) * ((size_t)(n + 1) * (n + 2) / 2 + n + 2) > 150 * 1024;
-}
-
 int ba_solve_reduced(hipStream_t st, const BADev &d, double radius, double min_diag, double max_diag)
 {
     if (d.n_cam <= 0) return ESFM_OK;
-    const int n = 6 * d.n_cam;
-    const size_t bytes = sizeof(double) * ((size_t)(n + 1) * (n + 2) / 2 + n + 2);
-    if (ba_chol_small_fits(d.n_cam)) return ba_solve_reduced_small(st, d, radius, min_diag, max_diag);
-    if (d.sparse) return ba_solve_reduced_sparse(st, d, d.sparse, radius, min_diag, max_diag);
-    if (bytes <= 150 * 1024) {
-        ESFM_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&ba_chol_solve_kernel<true>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-        hipLaunchKernelGGL(ba_chol_solve_kernel<true>, dim3(1), dim3(kCholThreads), bytes, st, d, radius, min_diag, max_diag);
-    } else {
+    switch (d.parts->forms.solve) {
+    case BaForms::SOLVE_SMALL_ONE_WG: return ba_solve_reduced_small(st, d, radius, min_diag, max_diag);
+    case BaForms::SOLVE_TILED:
+        if (d.sparse) return ba_solve_reduced_sparse(st, d, d.sparse, radius, min_diag, max_diag);
         return ba_solve_reduced_large(st, d, radius, min_diag, max_diag);
+    case BaForms::SOLVE_LDS: break;
     }
+    const size_t bytes = chol_lds_bytes(d.n_cam);
+    ESFM_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&ba_chol_solve_kernel<true>),
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    hipLaunchKernelGGL(ba_chol_solve_kernel<true>, dim3(1), dim3(kCholThreads), bytes, st, d, radius, min_diag, max_diag);
     LAUNCH_CHECK();
     return ESFM_OK;
 }
@@ -2420,7 +2434,7 @@ void ba_scal_discard(const BADev &d, int first_slot, int end_slot)
 
 int ba_camera_step(hipStream_t st, const BADev &d)
 {
-    if (ba_chol_small_fits(d.n_cam)) return ESFM_OK;     // the one-workgroup reduced solve has done it
+    if (d.parts->forms.solve == BaForms::SOLVE_SMALL_ONE_WG) return ESFM_OK;     // the one-workgroup reduced solve has done it
     hipLaunchKernelGGL(ba_camera_step_kernel, dim3(1), dim3(256), 0, st, d);
     LAUNCH_CHECK();
     return ESFM_OK;

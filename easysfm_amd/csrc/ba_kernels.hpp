@@ -1,7 +1,8 @@
-// Launch interface between ba_api.cpp (LM control loop on the host) and ba_kernels.hip.
+// Launch interface between ba_solve.cpp (LM control loop on the host), ba_api.cpp (problem set-up) and ba_kernels.hip.
 #pragma once
 
 #include "common.hpp"
+#include "ba_layout.hpp"
 
 namespace esfm {
 
@@ -21,6 +22,23 @@ enum BAScalar {
     SC_MAX_COUNT = 2, SC_COUNT = 24
 };
 
+// Which form of the size-dependent kernels a problem takes.  A function of the problem's sizes alone (ba_forms, next to the
+// launchers): evaluated once at creation, sizes the buffers each form needs and is what every launcher reads (BADev::parts->forms);
+// conditions of the running solve (one rank or several, bounds, the structure-aware plan) combine with it at the launch sites.
+// DESIGN.md section 5 has the table.
+struct BaForms {
+    enum Schur { SCHUR_LDS_SLABS,   // all camera blocks of S in every workgroup's LDS, summed over per-workgroup slabs (ba_schur_lds_kernel)
+                 SCHUR_TABLES };    // matrix-core / windowed / wide tables of BaLayout
+    enum Solve { SOLVE_SMALL_ONE_WG,   // one-workgroup MFMA solve, the camera step included (ba_chol_small_kernel)
+                 SOLVE_LDS,            // one workgroup, packed factor in LDS (ba_chol_solve_kernel)
+                 SOLVE_TILED };        // multi-workgroup tiled solve, dense or structure-aware (ba_chol_large.hip, ba_chol_sparse.hip)
+    Schur schur = SCHUR_LDS_SLABS;
+    Solve solve = SOLVE_SMALL_ONE_WG;
+    bool sweep_sums_in_lds = false;    // the Jacobian sweep keeps the per-camera sums in LDS (else: camera chunks, BaLayout::cchunk_*)
+    bool large = false;                // >= 2^20 observations: 512-thread sweep, chunked per-point blocks, candidate cost in a pass of its own
+};
+BaForms ba_forms(int n_real_cam, bool has_calib, int n_obs);
+
 // Device-resident bundle-adjustment problem.  Observations are sorted by point (CSR), so a
 // point's observations are contiguous: obs k in [pt_start[p], pt_start[p+1]) belongs to point p.
 //
@@ -29,6 +47,7 @@ enum BAScalar {
 // n_cam = n_real_cam + has_calib is the number of 6-wide blocks of the reduced system and every per-block array
 // (x_c, scale_c, camacc, red, y_c ...) simply has one more block; observations only ever name real cameras.
 struct ScalParts {                             // host-side bookkeeping of one problem
+    BaForms forms;                             // set at creation
     int n[SC_SUM_COUNT];                       // per-workgroup scalar partials pending on the device, per slot
     bool single_rank = true;                   // no all-reduce callback in the running solve
     bool grad_done = false;                    // the camera part of max|gradient| came with the last linearisation
@@ -40,8 +59,6 @@ struct ScalParts {                             // host-side bookkeeping of one p
     int red_rhs_exp = 0;
 };
 struct SparseSolve;                            // the structure-aware reduced solve of one problem (ba_chol_sparse.hpp); host object
-// does ba_solve_reduced take the tiled path (ba_solve_reduced_large) for this camera count?
-bool ba_solve_is_tiled(int n_cam);
 struct ScalCounts { int n[SC_SUM_COUNT]; };   // kernel argument: how many partials each slot has pending
 struct ScalBase { int b[6]; };                // kernel argument: first partial index of this launch, per slot it commits
 
@@ -131,10 +148,6 @@ struct BADev {
     int4 *pchunk_info = nullptr;        // [n_pchunks] {first point, end point, first observation, end observation}: what a chunk's workgroup needs before it can request anything else, in ONE load
     int n_pchunks = 0;
 };
-constexpr int kCamChunk = 256, kCamPart = 37;
-constexpr int kPtChunkObs = 256;               // observations per point chunk (back-substitution, per-point normal blocks)
-constexpr int kSchurWinCams = 28;              // cameras in the windowed Schur kernel's LDS window
-constexpr int kSchurMfCams = 13;               // cameras in the matrix-core Schur kernel's window (80 rows = 5 MFMA block rows)
 
 inline size_t ba_camacc_doubles(int n_cam) { return (size_t)42 * (size_t)n_cam; }
 inline size_t ba_red_doubles(int n_cam) { const size_t n = 6 * (size_t)n_cam; return n * n + n; }
@@ -151,19 +164,17 @@ int ba_linearize(hipStream_t st, const BADev &d, int num_cu, double cauchy_a, bo
 int ba_point_prep(hipStream_t st, const BADev &d, double radius, double min_diag, double max_diag, bool fresh_jacobian, int deferred_slabs = 0);
 int ba_jacobi_scaling(hipStream_t st, const BADev &d);
 int ba_camera_gradient(hipStream_t st, const BADev &d);
-// slabs: scratch for the LDS-privatised variant (n_cam small), >= ba_schur_slab_doubles(n_cam, num_cu) doubles, or NULL
-int ba_schur(hipStream_t st, const BADev &d, int num_cu, double *slabs, size_t slab_capacity_doubles, double rhs_bound);
-inline size_t ba_schur_slab_doubles(int n_cam, int num_cu)
-{
-    const size_t per = (size_t)n_cam * (n_cam + 1) / 2 * 36 + 6 * (size_t)n_cam;
-    return per * sizeof(double) <= 156 * 1024 ? per * (size_t)num_cu : 0;
-}
+// BaForms::SCHUR_LDS_SLABS: d.slabs holds one slab of ba_schur_slab_doubles(n_cam) per compute unit
+int ba_schur(hipStream_t st, const BADev &d, int num_cu, double rhs_bound);
+inline size_t ba_schur_slab_doubles(int n_cam) { return (size_t)n_cam * (n_cam + 1) / 2 * 36 + 6 * (size_t)n_cam; }
+// BaForms::sweep_sums_in_lds: d.lin_slabs holds ba_lin_slab_doubles(n_cam) per workgroup of the sweep, at most two per compute unit
+inline size_t ba_lin_slab_doubles(int n_cam) { return (size_t)27 * (size_t)n_cam; }
 int ba_solve_reduced(hipStream_t st, const BADev &d, double radius, double min_diag, double max_diag);
 // multi-workgroup blocked Cholesky for systems beyond one workgroup's LDS (ba_chol_large.hip); d.chol must hold
 // ba_chol_large_doubles(n_cam) doubles
 int ba_solve_reduced_large(hipStream_t st, const BADev &d, double radius, double min_diag, double max_diag);
 size_t ba_chol_large_doubles(int n_cam);
-// one-workgroup MFMA solve for n = 6 n_cam <= 176 (ba_chol_large.hip)
+// one-workgroup MFMA solve for n = 6 n_cam <= 176 (ba_chol_large.hip); ba_forms is the one caller of the predicate
 bool ba_chol_small_fits(int n_cam);
 int ba_solve_reduced_small(hipStream_t st, const BADev &d, double radius, double min_diag, double max_diag);
 // intrinsics row/column block of the reduced system (has_calib): runs after ba_schur, adds into d.red

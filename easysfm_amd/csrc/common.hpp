@@ -134,7 +134,7 @@ struct esfm_ctx {
     size_t pinned_rounds_cap = 0;
     int pin_rounds(size_t bytes);
     // device chunks and pinned scalar mailboxes of destroyed BA problems, kept for the next problem of this context (an incremental
-    // reconstruction sets one up and tears it down every ba_frequency frames: ba_api.cpp dev_alloc / esfm_ba_problem_destroy)
+    // reconstruction sets one up and tears it down every ba_frequency frames: ba_api.cpp ba_dev_alloc_bytes / esfm_ba_problem_destroy)
     struct BaChunk { void *ptr; size_t bytes; };
     std::vector<BaChunk> ba_chunks;
     std::vector<void *> ba_mailboxes;

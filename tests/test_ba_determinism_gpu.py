@@ -3,8 +3,9 @@
 No reduction of the solver depends on the order in which workgroups or waves arrive:
   * per-camera sums F'F / F'r: gathered per camera in observation order (ba_camacc_chunk_kernel), chunk sums added in order;
   * scalar sums (cost, model cost change, norms): per-workgroup partials added in block order by the last workgroup;
-  * the Schur complement: addends rounded to a common power-of-two grid whose partial sums fit 53 bits, so the f64 atomics and
-    the slab / all-reduce sums are exact (BADev::quant in easysfm_amd/csrc/ba_kernels.hpp);
+  * the Schur complement: accumulated as 64-bit fixed-point integers, entry (r, c) scaled by 2^(60 - qexp[r] - qexp[c]), so the
+    LDS / global integer atomics and the slab sums are exact whatever their order; converted to f64 once, before the solve
+    (BADev::qexp in easysfm_amd/csrc/ba_kernels.hpp);
   * max-reductions are order-independent; the Cholesky kernels have a fixed schedule.
 Two solves of the same problem must therefore agree in every bit of the parameters and of the iteration log.
 """
