@@ -8,8 +8,8 @@ no CPU fallback.
 from ._lib import BAOptions, BASummary, Context, EsfmError, ESFM_HAMMING, ESFM_L2_F32, LIB_PATH, lib  # noqa: F401
 from .types import DMatch, Frame, SparsePointCloud  # noqa: F401
 from .matching import (DescriptorBank, FeatureMatching, PairMatcher, knn_match_hamming, knn_match_l2,  # noqa: F401
-                       match_cross_hamming, match_cross_l2, match_cross_pairs_host, match_hamming, match_l2, match_pairs_host,
-                       shard_pair_list)
+                       match_cross_hamming, match_cross_l2, match_cross_pairs_host, match_guided_hamming, match_guided_l2,
+                       match_guided_pairs_host, match_hamming, match_l2, match_pairs_host, shard_pair_list)
 from .ba import (BAProblem, BundleAdjustment, Comm, ba_solve, ba_solve_ex, ba_sweep_bytes_per_obs, default_options, line_search_next_step, reduced_plan, shard_points,  # noqa: F401
                  torch_allreduce_callback)
 
@@ -21,6 +21,6 @@ from .features import (detectFeaturesORB, detectFeaturesSIFT, detectFeaturesSURF
                        sift_detect_and_compute, surf_detect_and_compute, undistort)
 from .mvs import (MVSOptions, default_mvs_options, dense_reconstruct, dense_reconstruction, mvs_depth_maps, mvs_fuse,  # noqa: F401
                   mvs_plan)
-from .pipeline import FramePair, match_and_verify_all_pairs, propagate_track_ids, run_sfm  # noqa: F401
+from .pipeline import MATCH_FILTERS, FramePair, match_and_verify_all_pairs, propagate_track_ids, run_sfm  # noqa: F401
 
 __version__ = "0.1.0"

@@ -34,6 +34,7 @@ EXPORTED_SYMBOLS = [
     "esfm_knn2_l2_f32", "esfm_knn2_hamming", "esfm_match_l2_f32", "esfm_match_hamming",
     "esfm_match_pairs_dev", "esfm_match_pairs", "esfm_knn2_pairs_dev", "esfm_knn2_pairs_screened_dev", "esfm_match_prepare_dev", "esfm_match_debug_counters", "esfm_match_release_prepared", "esfm_match_release_prepared_buffer", "esfm_match_prepared_buffer", "esfm_ctx_set_prepared_check", "esfm_match_last_stats", "esfm_match_last_second_pass", "esfm_ctx_set_l2_audit", "esfm_match_last_flagged",
     "esfm_match_cross_l2_f32", "esfm_match_cross_hamming", "esfm_match_cross_pairs_dev", "esfm_match_cross_pairs",
+    "esfm_match_guided_pairs_dev", "esfm_match_guided_pairs", "esfm_knn2_guided_pairs_dev", "esfm_match_guided_l2_f32", "esfm_match_guided_hamming",
     "esfm_shard_pair_list",
     "esfm_comm_get_unique_id", "esfm_comm_create", "esfm_comm_destroy", "esfm_comm_rank", "esfm_comm_world", "esfm_comm_rccl_ranks", "esfm_comm_allreduce",
     "esfm_ba_options_default", "esfm_ba_solve", "esfm_ba_problem_create", "esfm_ba_problem_set_params",
@@ -142,6 +143,12 @@ def lib() -> C.CDLL:
     L.esfm_match_cross_hamming.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_double, vp, vp, vp, i32p]
     L.esfm_match_cross_pairs_dev.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_double, vp, vp, vp, vp, vp]
     L.esfm_match_cross_pairs.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_double, vp, vp, vp, vp, vp]
+    guided = [vp, C.c_int, vp, vp, vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, C.c_double]     # ctx .. K4_per_pair, max_epipolar_px
+    L.esfm_match_guided_pairs_dev.argtypes = guided + [C.c_int, C.c_double, C.c_int, vp, vp, vp, vp, vp]
+    L.esfm_match_guided_pairs.argtypes = guided + [C.c_int, C.c_double, C.c_int, vp, vp, vp, vp, vp]
+    L.esfm_knn2_guided_pairs_dev.argtypes = guided + [vp, vp, vp, vp]
+    L.esfm_match_guided_l2_f32.argtypes = [vp, vp, vp, C.c_int, vp, vp, C.c_int, C.c_int, vp, vp, C.c_double, C.c_int, C.c_double, C.c_int, vp, vp, vp, i32p]
+    L.esfm_match_guided_hamming.argtypes = L.esfm_match_guided_l2_f32.argtypes
     L.esfm_match_prepare_dev.argtypes = [vp, C.c_int, vp, C.c_int64, C.c_int]
     L.esfm_match_release_prepared.argtypes = [vp]
     L.esfm_match_release_prepared_buffer.argtypes = [vp, vp]

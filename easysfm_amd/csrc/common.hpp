@@ -125,6 +125,9 @@ struct esfm_ctx {
     // state is in `match`
     esfm::DevBuf knn_dist, stage_a, stage_b, stage_c, stage_d, stage_e;
     esfm::MatchState match;
+    // the guided matcher's own scratch (guided_api.cpp alone touches it; nothing of `match` is shared with it): pair + geometry tables,
+    // both directions' 2-NN tables, and the host-pointer forms' uploaded descriptor rows and keypoints
+    esfm::DevBuf guided_tab, guided_idx, guided_dist, guided_bank, guided_kp;
     // pinned host staging for small tables / counters
     void *pinned = nullptr;
     size_t pinned_cap = 0;

@@ -342,6 +342,96 @@ public:
         return true;
     }
 
+    // Epipolar-guided second pass (esfm.h "Epipolar-guided matching", esfm_match_guided_pairs) for pairs that have an essential
+    // matrix: E holds 9 doubles per listed pair (what estimate2D2D_E5P_RANSAC[_pairs] returned), K is frame pairs[p].first's for both
+    // images as there, max_epipolar_px the RANSAC's threshold, ratio_thre / cross_check the first pass's filter (ratio_thre == 0:
+    // cross alone).  matches[p] is REPLACED by the pair's guided list.
+    bool matchFeaturesGuidedAllPairs(std::vector<frame_t> &frames, const std::vector<std::pair<int, int>> &pairs, bool hamming,
+                                     const std::vector<double> &E, double max_epipolar_px, std::vector<std::vector<DMatch>> &matches,
+                                     double ratio_thre = -1.0, bool cross_check = false)
+    {
+        if (ratio_thre < 0) ratio_thre = hamming ? 0.8 : 0.5;
+        matches.assign(pairs.size(), {});
+        if (pairs.empty()) return true;
+        int width = 0;
+        for (const frame_t &f : frames) if (f.descriptors.rows > 0) { width = f.descriptors.cols; break; }
+        if (width == 0) return true;
+        const size_t row_bytes = hamming ? size_t(width) : size_t(width) * 4;
+        std::vector<int32_t> off(frames.size() + 1, 0);
+        for (size_t i = 0; i < frames.size(); ++i) {
+            const DescMat &d = frames[i].descriptors;
+            if (d.rows > 0 && (d.cols != width || d.type != (hamming ? DescMat::U8 : DescMat::F32))) { std::cerr << "descriptor shapes differ\n"; return false; }
+            if (size_t(d.rows) != frames[i].keypoints.size()) { std::cerr << "one keypoint per descriptor row\n"; return false; }
+            off[i + 1] = off[i] + d.rows;
+        }
+        std::vector<uint8_t> bank(size_t(off.back()) * row_bytes + 16);
+        std::vector<float> kps(size_t(off.back()) * 2 + 2);
+        for (size_t i = 0; i < frames.size(); ++i) {
+            if (frames[i].descriptors.rows > 0) std::memcpy(bank.data() + size_t(off[i]) * row_bytes, frames[i].descriptors.bytes.data(), size_t(frames[i].descriptors.rows) * row_bytes);
+            for (size_t k = 0; k < frames[i].keypoints.size(); ++k) { kps[2 * (size_t(off[i]) + k)] = frames[i].keypoints[k].pt.x; kps[2 * (size_t(off[i]) + k) + 1] = frames[i].keypoints[k].pt.y; }
+        }
+        std::vector<int32_t> pl(2 * pairs.size());
+        std::vector<float> K4(4 * pairs.size());
+        size_t total = 0;
+        for (size_t p = 0; p < pairs.size(); ++p) {
+            pl[2 * p] = pairs[p].first; pl[2 * p + 1] = pairs[p].second; total += size_t(frames[size_t(pairs[p].first)].descriptors.rows);
+            const Matrix3f &K = frames[size_t(pairs[p].first)].K_cam;
+            K4[4 * p] = K(0, 0); K4[4 * p + 1] = K(0, 2); K4[4 * p + 2] = K(1, 1); K4[4 * p + 3] = K(1, 2);
+        }
+        std::vector<int32_t> qi(std::max<size_t>(total, 1)), ti(std::max<size_t>(total, 1)), n_out(pairs.size());
+        std::vector<float> d(std::max<size_t>(total, 1));
+        std::vector<int64_t> out_off(pairs.size() + 1);
+        const int rc = esfm_match_guided_pairs(default_ctx(), hamming ? ESFM_HAMMING : ESFM_L2_F32, bank.data(), kps.data(), off.data(), int(frames.size()),
+                                               width, pl.data(), int(pairs.size()), E.data(), K4.data(), max_epipolar_px, ratio_thre != 0.0, ratio_thre,
+                                               cross_check, qi.data(), ti.data(), d.data(), n_out.data(), out_off.data());
+        if (rc != ESFM_OK) { std::cerr << esfm_last_error() << std::endl; return false; }
+        for (size_t p = 0; p < pairs.size(); ++p) {
+            const size_t o = size_t(out_off[p]);
+            for (int k = 0; k < n_out[p]; ++k) matches[p].push_back(DMatch(qi[o + size_t(k)], ti[o + size_t(k)], 0, d[o + size_t(k)]));
+            if (!quiet) std::cout << "# Guided correspondence: pair ( " << pairs[p].first << " , " << pairs[p].second << " ) [ " << n_out[p] << " ]" << std::endl;
+        }
+        return true;
+    }
+
+    // The same for one pair (esfm_match_guided_l2_f32 / _hamming); `matches` is replaced.
+    bool matchFeaturesGuided(frame_t &f1, frame_t &f2, bool hamming, const double E[9], double max_epipolar_px, std::vector<DMatch> &matches,
+                             double ratio_thre = -1.0, bool cross_check = false)
+    {
+        if (ratio_thre < 0) ratio_thre = hamming ? 0.8 : 0.5;
+        matches.clear();
+        const DescMat &q = f1.descriptors, &t = f2.descriptors;
+        if (q.rows > 0 && t.rows > 0 && (q.cols != t.cols || q.type != t.type)) { std::cerr << "descriptor shapes differ\n"; return false; }
+        if ((hamming && q.type != DescMat::U8) || (!hamming && q.type != DescMat::F32)) { std::cerr << "wrong descriptor type\n"; return false; }
+        if (size_t(q.rows) != f1.keypoints.size() || size_t(t.rows) != f2.keypoints.size()) { std::cerr << "one keypoint per descriptor row\n"; return false; }
+        std::vector<float> kq(2 * f1.keypoints.size() + 2), kt(2 * f2.keypoints.size() + 2);
+        for (size_t k = 0; k < f1.keypoints.size(); ++k) { kq[2 * k] = f1.keypoints[k].pt.x; kq[2 * k + 1] = f1.keypoints[k].pt.y; }
+        for (size_t k = 0; k < f2.keypoints.size(); ++k) { kt[2 * k] = f2.keypoints[k].pt.x; kt[2 * k + 1] = f2.keypoints[k].pt.y; }
+        const float K4[4] = {f1.K_cam(0, 0), f1.K_cam(0, 2), f1.K_cam(1, 1), f1.K_cam(1, 2)};
+        std::vector<int32_t> qi(size_t(std::max(q.rows, 1))), ti(size_t(std::max(q.rows, 1)));
+        std::vector<float> d(size_t(std::max(q.rows, 1)));
+        int32_t n = 0;
+        const int rc = hamming ? esfm_match_guided_hamming(default_ctx(), q.ptr<uint8_t>(), kq.data(), q.rows, t.ptr<uint8_t>(), kt.data(), t.rows, q.cols, E, K4,
+                                                           max_epipolar_px, ratio_thre != 0.0, ratio_thre, cross_check, qi.data(), ti.data(), d.data(), &n)
+                               : esfm_match_guided_l2_f32(default_ctx(), q.ptr<float>(), kq.data(), q.rows, t.ptr<float>(), kt.data(), t.rows, q.cols, E, K4,
+                                                          max_epipolar_px, ratio_thre != 0.0, ratio_thre, cross_check, qi.data(), ti.data(), d.data(), &n);
+        if (rc != ESFM_OK) { std::cerr << esfm_last_error() << std::endl; return false; }
+        for (int k = 0; k < n; ++k) matches.push_back(DMatch(qi[size_t(k)], ti[size_t(k)], 0, d[size_t(k)]));
+        if (!quiet) std::cout << "# Guided correspondence: [ " << n << " ]" << std::endl;
+        return true;
+    }
+
+    // The union of a pair's RANSAC inliers and its guided list, in ascending query order: a query both lists hold carries the same
+    // train row in both (esfm.h, property (b)), so the guided entries of the queries `inliers` lacks are added.
+    static void mergeGuided(std::vector<DMatch> &inliers, const std::vector<DMatch> &guided)
+    {
+        std::vector<int> held;
+        for (const DMatch &m : inliers) held.push_back(m.queryIdx);
+        std::sort(held.begin(), held.end());
+        for (const DMatch &m : guided)
+            if (!std::binary_search(held.begin(), held.end(), m.queryIdx)) inliers.push_back(m);
+        std::stable_sort(inliers.begin(), inliers.end(), [](const DMatch &a, const DMatch &b) { return a.queryIdx < b.queryIdx; });
+    }
+
 private:
     // detection outputs' landing buffers, uninitialised, grown on demand, kept for the object's life
     std::unique_ptr<float[]> kp_buf_, desc_buf_;
@@ -500,7 +590,7 @@ public:
     // estimate_motion.cpp:27-97: cv::findEssentialMat(RANSAC) on the matched pixels with frame 1's K, inliers appended,
     // cv::recoverPose with the RANSAC mask -> T = [R | t; 0 0 0 1]
     bool estimate2D2D_E5P_RANSAC(frame_t &cur_frame_1, frame_t &cur_frame_2, std::vector<DMatch> &matches, std::vector<DMatch> &inlier_matches,
-                                 Matrix4f &T, double ransac_thre = 1.0, double ransac_prob = 0.99, bool show = false)
+                                 Matrix4f &T, double ransac_thre = 1.0, double ransac_prob = 0.99, bool show = false, double *E_out = nullptr /* 9: the essential matrix */)
     {
         std::vector<float> p1, p2;
         gather(cur_frame_1, cur_frame_2, matches, 1, p1, p2);
@@ -510,6 +600,7 @@ public:
         double E[9], R[9], t[3];
         int rc = esfm_find_essential_mat(default_ctx(), p1.data(), p2.data(), n, K4, ransac_prob, ransac_thre, E, mask.data(), nullptr);
         if (rc != ESFM_OK) { std::cerr << esfm_last_error() << std::endl; return false; }
+        if (E_out) std::copy(E, E + 9, E_out);
         for (int i = 0; i < n; ++i) if (mask[size_t(i)]) inlier_matches.push_back(matches[size_t(i)]);   // :55-61
         rc = esfm_recover_pose(default_ctx(), E, p1.data(), p2.data(), n, K4, R, t, mask.data(), nullptr);   // :67
         if (rc != ESFM_OK) { std::cerr << esfm_last_error() << std::endl; return false; }
@@ -524,7 +615,8 @@ public:
     // return for that job (appro_depth stays untouched where the per-pair getDepthFast is not reached or fails).
     bool estimate2D2D_E5P_RANSAC_pairs(std::vector<frame_t> &frames, const std::vector<std::pair<int, int>> &jobs, const std::vector<std::vector<DMatch>> &matches,
                                        std::vector<std::vector<DMatch>> &inlier_matches, std::vector<Matrix4f> &T, std::vector<double> &appro_depth,
-                                       std::vector<char> &ok, double ransac_thre = 1.0, double ransac_prob = 0.99, int random_rate = 20)
+                                       std::vector<char> &ok, double ransac_thre = 1.0, double ransac_prob = 0.99, int random_rate = 20,
+                                       std::vector<double> *E_out = nullptr /* 9 per job: the essential matrices */)
     {
         const size_t nj = jobs.size();
         inlier_matches.assign(nj, {}); T.assign(nj, Matrix4f::Identity()); ok.assign(nj, 0);
@@ -545,6 +637,7 @@ public:
         int rc = esfm_find_essential_pairs(default_ctx(), int(nj), off.data(), p1.data(), p2.data(), K4.data(), ransac_prob, ransac_thre, E.data(), mask.data(),
                                            status.data(), nullptr);
         if (rc != ESFM_OK) { std::cerr << esfm_last_error() << std::endl; return false; }
+        if (E_out) *E_out = E;
         for (size_t p = 0; p < nj; ++p) {
             if (!status[p]) { for (int k = off[p]; k < off[p + 1]; ++k) mask[size_t(k)] = 0; continue; }
             for (int k = off[p]; k < off[p + 1]; ++k) if (mask[size_t(k)]) inlier_matches[p].push_back(matches[p][size_t(k - off[p])]);   // :55-61

@@ -79,14 +79,18 @@ int dump_image(const char *in, const char *out)
 int main(int argc, char **argv)
 {
     if (argc == 4 && std::string(argv[1]) == "--dump-image") return dump_image(argv[2], argv[3]);
-    // optional 14th argument: the match filter -- ratio (the reference's, default), cross (mutual nearest neighbours) or ratio+cross;
+    // optional 14th argument: the match filter -- ratio (the reference's, default), cross (mutual nearest neighbours) or ratio+cross,
+    // or one of these with +guided appended (a second, epipolar-guided pass over the verified pairs; the union is kept);
     // optional 15th (needs the 14th): a dense .ply path, or none
-    const std::string match_filter = argc >= 15 ? argv[14] : "ratio";
+    const std::string filter_arg = argc >= 15 ? argv[14] : "ratio";
+    const std::string guided_suffix = "+guided";
+    const bool guided = filter_arg.size() > guided_suffix.size() && filter_arg.compare(filter_arg.size() - guided_suffix.size(), guided_suffix.size(), guided_suffix) == 0;
+    const std::string match_filter = guided ? filter_arg.substr(0, filter_arg.size() - guided_suffix.size()) : filter_arg;      // the first pass's filter
     const std::string dense_file = argc == 16 && std::string(argv[15]) != "none" ? argv[15] : "";
     if ((argc != 14 && argc != 15 && argc != 16) || (match_filter != "ratio" && match_filter != "cross" && match_filter != "ratio+cross")) {
         std::cerr << "usage: sfm_native image_folder image_list calib_K_file calib_distort_file output.ply feature_type(S | O | I) feature_parameter "
-                     "repro_dis_ransac find_init_frames ba_calib_change_tolerance ba_frequency launch_viewer view_sphere [match_filter: ratio | cross | ratio+cross "
-                     "[dense.ply | none]]"
+                     "repro_dis_ransac find_init_frames ba_calib_change_tolerance ba_frequency launch_viewer view_sphere [match_filter: ratio | cross | ratio+cross | "
+                     "ratio+guided | cross+guided | ratio+cross+guided [dense.ply | none]]"
                   << std::endl;
         return 2;
     }
@@ -187,6 +191,7 @@ int main(int argc, char **argv)
         const int num_min_pair = 20;
         const size_t nf = size_t(frame_number);
         std::vector<std::vector<frame_pair_t>> graph(nf, std::vector<frame_pair_t>(nf));
+        const double guided_ratio = match_filter == "cross" ? 0.0 : using_feature == 'O' ? 0.8 : using_feature == 'I' ? 0.7 : 0.5;
         const bool pair_by_pair = std::getenv("ESFM_PAIR_BY_PAIR") != nullptr && std::atoi(std::getenv("ESFM_PAIR_BY_PAIR")) != 0;
         if (pair_by_pair) {
             for (int i = 0; i < frame_number; ++i)
@@ -200,10 +205,17 @@ int main(int argc, char **argv)
                     t_match += pc.lap();
                     if (int(temp_matches.size()) > num_min_pair) {
                         Matrix4f T = Matrix4f::Identity();
-                        if (ee.estimate2D2D_E5P_RANSAC(frames[size_t(i)], frames[size_t(j)], temp_matches, inlier_matches, T, ransac_reproj_distance)) {
+                        double E[9];
+                        if (ee.estimate2D2D_E5P_RANSAC(frames[size_t(i)], frames[size_t(j)], temp_matches, inlier_matches, T, ransac_reproj_distance, 0.99, false, E)) {
                             g.T_21 = T;
                             double depth = 1.0;
                             if (ee.getDepthFast(frames[size_t(i)], frames[size_t(j)], T, inlier_matches, depth)) g.appro_depth = depth;
+                            if (guided) {        // second pass along the epipolar lines, same filter; T_21 and the depth stay the first pass's
+                                std::vector<DMatch> guided_matches;
+                                if (!fm.matchFeaturesGuided(frames[size_t(i)], frames[size_t(j)], using_feature == 'O', E, ransac_reproj_distance, guided_matches,
+                                                            guided_ratio, cross_check)) return 3;
+                                FeatureMatching::mergeGuided(inlier_matches, guided_matches);
+                            }
                             g.matches.swap(inlier_matches);
                             if (!g.matches.empty()) std::cout << "Pair ( " << i << " , " << j << " ): [" << g.matches.size() << "] verified matches." << std::endl;
                         }
@@ -228,21 +240,33 @@ int main(int argc, char **argv)
             std::vector<Matrix4f> Ts;
             std::vector<double> depths;
             std::vector<char> ok;
-            if (!ee.estimate2D2D_E5P_RANSAC_pairs(frames, jobs, job_matches, inliers, Ts, depths, ok, ransac_reproj_distance)) {
+            std::vector<double> Es;
+            if (!ee.estimate2D2D_E5P_RANSAC_pairs(frames, jobs, job_matches, inliers, Ts, depths, ok, ransac_reproj_distance, 0.99, 20, &Es)) {
                 // A batch entry point fails as a whole when ONE pair is unusable (a non-finite essential matrix, say); the reference's
                 // loop -- and ESFM_PAIR_BY_PAIR=1 above -- only loses that pair (estimate_motion.cpp:27-97 returns false, sfm.cpp:165
                 // carries on).  Same here: the batch's pairs are verified one by one, a failing pair is skipped.
                 std::cout << "batched verification failed (" << esfm_last_error() << "): verifying pair by pair" << std::endl;
                 inliers.assign(jobs.size(), {}); Ts.assign(jobs.size(), Matrix4f::Identity()); depths.assign(jobs.size(), 1.0); ok.assign(jobs.size(), 0);
+                Es.assign(9 * jobs.size(), 0.0);
                 for (size_t p = 0; p < jobs.size(); ++p) {
                     frame_t &fi = frames[size_t(jobs[p].first)], &fj = frames[size_t(jobs[p].second)];
                     Matrix4f T = Matrix4f::Identity();
-                    if (!ee.estimate2D2D_E5P_RANSAC(fi, fj, job_matches[p], inliers[p], T, ransac_reproj_distance)) continue;
+                    if (!ee.estimate2D2D_E5P_RANSAC(fi, fj, job_matches[p], inliers[p], T, ransac_reproj_distance, 0.99, false, &Es[9 * p])) continue;
                     double depth = 1.0;
                     Ts[p] = T;
                     if (ee.getDepthFast(fi, fj, T, inliers[p], depth)) depths[p] = depth;
                     ok[p] = 1;
                 }
+            }
+            if (guided) {       // ONE guided call for every pair with a model, the first pass's filter; each keeps the union
+                std::vector<std::pair<int, int>> gjobs;
+                std::vector<double> gE;
+                std::vector<size_t> gidx;
+                for (size_t p = 0; p < jobs.size(); ++p)
+                    if (ok[p]) { gjobs.push_back(jobs[p]); gE.insert(gE.end(), Es.begin() + 9 * long(p), Es.begin() + 9 * long(p) + 9); gidx.push_back(p); }
+                std::vector<std::vector<DMatch>> guided_matches;
+                if (!fm.matchFeaturesGuidedAllPairs(frames, gjobs, using_feature == 'O', gE, ransac_reproj_distance, guided_matches, guided_ratio, cross_check)) return 3;
+                for (size_t s = 0; s < gidx.size(); ++s) FeatureMatching::mergeGuided(inliers[gidx[s]], guided_matches[s]);
             }
             for (size_t p = 0; p < jobs.size(); ++p) {
                 if (!ok[p]) continue;

@@ -122,6 +122,64 @@ def match_cross_pairs_host(sets: Sequence[np.ndarray], pairs, ratio: Optional[fl
     return _match_pairs_host(lib().esfm_match_cross_pairs, sets, pairs, metric, ctx, *_cross_args(ratio))
 
 
+# ---- epipolar-guided matching, include/esfm.h "Epipolar-guided matching": the search of a query row restricted to the train rows the
+# pair's essential matrix admits.  ratio=None switches the ratio test off (then cross_check must be on)
+def _guided_args(ratio, cross_check):
+    return (0, 0.0, int(bool(cross_check))) if ratio is None else (1, float(ratio), int(bool(cross_check)))
+
+
+def _as_kp(kp, rows) -> np.ndarray:
+    kp = np.ascontiguousarray(kp, np.float32).reshape(-1, 2)
+    if kp.shape[0] != rows:
+        raise ValueError("one keypoint (u, v) per descriptor row")
+    return kp
+
+
+def _geometry(E, K4, n_pairs):
+    E = np.ascontiguousarray(E, np.float64).reshape(-1, 9); K4 = np.ascontiguousarray(K4, np.float32).reshape(-1, 4)
+    if E.shape[0] != n_pairs or K4.shape[0] != n_pairs:
+        raise ValueError("one essential matrix and one K4 (fx, cx, fy, cy) per pair")
+    return E, K4
+
+
+def _match_guided(fn, q, kp_q, t, kp_t, dtype, E, K4, max_epipolar_px, ratio, cross_check, ctx):
+    q, t, ctx = _one_pair(q, t, dtype, ctx)
+    kp_q = _as_kp(kp_q, q.shape[0]); kp_t = _as_kp(kp_t, t.shape[0])
+    E, K4 = _geometry(E, K4, 1)
+    nq = q.shape[0]
+    qi = np.empty(max(nq, 1), np.int32); ti = np.empty(max(nq, 1), np.int32); d = np.empty(max(nq, 1), np.float32)
+    n = C.c_int32(0)
+    check(fn(ctx.handle, _ptr(q), _ptr(kp_q), nq, _ptr(t), _ptr(kp_t), t.shape[0], q.shape[1], _ptr(E), _ptr(K4), float(max_epipolar_px),
+             *_guided_args(ratio, cross_check), _ptr(qi), _ptr(ti), _ptr(d), C.byref(n)))
+    return qi[:n.value].copy(), ti[:n.value].copy(), d[:n.value].copy()
+
+
+def match_guided_l2(q, kp_q, t, kp_t, E, K4, max_epipolar_px: float = 1.0, ratio: Optional[float] = 0.5, cross_check: bool = False,
+                    ctx: Optional[Context] = None):
+    """esfm_match_guided_l2_f32: one pair's guided match list.  kp_q / kp_t: [rows, 2] pixels, E [3,3], K4 = fx, cx, fy, cy (the query
+    frame's).  Returns (queryIdx, trainIdx, distance) arrays."""
+    return _match_guided(lib().esfm_match_guided_l2_f32, q, kp_q, t, kp_t, np.float32, E, K4, max_epipolar_px, ratio, cross_check, ctx)
+
+
+def match_guided_hamming(q, kp_q, t, kp_t, E, K4, max_epipolar_px: float = 1.0, ratio: Optional[float] = 0.8, cross_check: bool = False,
+                         ctx: Optional[Context] = None):
+    """match_guided_l2 for binary descriptors (Hamming distance)."""
+    return _match_guided(lib().esfm_match_guided_hamming, q, kp_q, t, kp_t, np.uint8, E, K4, max_epipolar_px, ratio, cross_check, ctx)
+
+
+def match_guided_pairs_host(sets: Sequence[np.ndarray], keypoints: Sequence[np.ndarray], pairs, E, K4, max_epipolar_px: float,
+                            ratio: Optional[float], cross_check: bool = False, metric: int = ESFM_L2_F32, ctx: Optional[Context] = None):
+    """esfm_match_guided_pairs: the guided pass of a pair list through HOST pointers.  Returns [(queryIdx, trainIdx, distance)] per pair."""
+    pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+    E, K4 = _geometry(E, K4, len(pairs))
+    rows = sum(np.asarray(s_).shape[0] for s_ in sets)
+    kp = np.concatenate([_as_kp(k, np.asarray(s_).shape[0]) for k, s_ in zip(keypoints, sets)], axis=0) if rows else np.zeros((1, 2), np.float32)
+
+    def fn(h, metric_, bank, *rest):
+        return lib().esfm_match_guided_pairs(h, metric_, bank, _ptr(kp), *rest)
+    return _match_pairs_host(fn, sets, pairs, metric, ctx, _ptr(E), _ptr(K4), float(max_epipolar_px), *_guided_args(ratio, cross_check))
+
+
 class FeatureMatching:
     """Mirror of p3dv::FeatureMatching's matching members (feature_matching.h:17-21)."""
 
@@ -251,7 +309,8 @@ class DescriptorBank:
     """All descriptor sets of a reconstruction, concatenated in one HBM buffer (torch owns the
     memory; the kernels see a raw device pointer)."""
 
-    def __init__(self, sets: Sequence[np.ndarray], metric: int, device: str = "cuda:0"):
+    def __init__(self, sets: Sequence[np.ndarray], metric: int, device: str = "cuda:0", keypoints: Optional[Sequence[np.ndarray]] = None):
+        """keypoints (optional): one [rows, 2] array of pixel positions per set, kept beside the rows for PairMatcher.match_guided."""
         import torch
         if not torch.cuda.is_available():
             raise RuntimeError("no MI355X visible: DescriptorBank needs a GPU (easysfm_amd has no CPU fallback)")
@@ -268,6 +327,12 @@ class DescriptorBank:
         host = np.concatenate(sets, axis=0) if sets else np.zeros((0, self.width), dt)
         self.device = torch.device(device)
         self.data = torch.from_numpy(host).to(self.device)
+        self.keypoints = None
+        if keypoints is not None:
+            if len(keypoints) != len(sets):
+                raise ValueError("one keypoint array per descriptor set")
+            kp = [_as_kp(k, s.shape[0]) for k, s in zip(keypoints, sets)]
+            self.keypoints = torch.from_numpy(np.concatenate(kp, axis=0) if kp else np.zeros((0, 2), np.float32)).to(self.device)
         self._matchers = []          # live PairMatchers (weak): update() re-prepares them
 
     @property
@@ -391,6 +456,42 @@ class PairMatcher:
         """esfm_match_cross_pairs_dev: mutual nearest neighbours of every pair (ratio=None), or ratio+cross (Lowe's test in both
         directions as well).  Enqueues; does not synchronise."""
         return self._lists(lib().esfm_match_cross_pairs_dev, *_cross_args(ratio))
+
+    def _guided_call(self, fn, pair_indices, E, K4, max_epipolar_px, filt, alloc):
+        """fn(ctx, metric, bank, keypoints, row_offset, n_sets, width, sub-list, n, E, K4, max_epipolar_px, *filt, *outputs, offset) on
+        self.pairs[pair_indices]; alloc(total queries, pairs) makes the output tensors.  Returns (sub-list, offset, outputs)."""
+        b = self.bank
+        if b.keypoints is None:
+            raise ValueError("guided matching needs a DescriptorBank built with keypoints")
+        sub = np.ascontiguousarray(self.pairs[np.asarray(pair_indices, np.int64)], np.int32).reshape(-1, 2)
+        E, K4 = _geometry(E, K4, len(sub))
+        offset = np.zeros(len(sub) + 1, np.int64)
+        outs = alloc(max(int(b.rows[sub[:, 0]].sum()) if len(sub) else 0, 1), max(len(sub), 1))
+        check(fn(self.ctx.handle, b.metric, C.c_void_p(b.data.data_ptr()), C.c_void_p(b.keypoints.data_ptr()), _ptr(b.row_offset), b.n_sets, b.width,
+                 _ptr(sub), len(sub), _ptr(E), _ptr(K4), float(max_epipolar_px), *filt, *(C.c_void_p(o.data_ptr()) for o in outs), _ptr(offset)))
+        return sub, offset, outs
+
+    def match_guided(self, pair_indices, E, K4, max_epipolar_px: float, ratio: Optional[float], cross_check: bool = False) -> PairMatches:
+        """esfm_match_guided_pairs_dev on self.pairs[pair_indices]: E [n, 3, 3] and K4 [n, 4] (fx, cx, fy, cy) per listed pair.  The
+        result has buffers of its own (this matcher's match() outputs stay as they are).  Enqueues; does not synchronise."""
+        torch, dev = self.torch, self.bank.device
+
+        def alloc(total, n_pairs):
+            return (torch.empty(total, dtype=torch.int32, device=dev), torch.empty(total, dtype=torch.int32, device=dev),
+                    torch.empty(total, dtype=torch.float32, device=dev), torch.empty(n_pairs, dtype=torch.int32, device=dev))
+        sub, offset, (qi, ti, d, n_out) = self._guided_call(lib().esfm_match_guided_pairs_dev, pair_indices, E, K4, max_epipolar_px,
+                                                            _guided_args(ratio, cross_check), alloc)
+        return PairMatches(sub, offset, n_out, qi, ti, d, self.ctx)
+
+    def knn2_guided(self, pair_indices, E, K4, max_epipolar_px: float):
+        """esfm_knn2_guided_pairs_dev: (idx [sum nq, 2], dist [sum nq, 2], n_adm [sum nq]) device tensors and the host offsets."""
+        torch, dev = self.torch, self.bank.device
+
+        def alloc(total, n_pairs):
+            return (torch.empty((total, 2), dtype=torch.int32, device=dev), torch.empty((total, 2), dtype=torch.float32, device=dev),
+                    torch.empty(total, dtype=torch.int32, device=dev))
+        _, offset, (idx, dist, n_adm) = self._guided_call(lib().esfm_knn2_guided_pairs_dev, pair_indices, E, K4, max_epipolar_px, (), alloc)
+        return idx, dist, n_adm, offset
 
     def _tables(self):
         torch = self.torch

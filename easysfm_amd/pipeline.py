@@ -32,7 +32,19 @@ class FramePair:
     appro_depth: float = 1.0
 
 
-MATCH_FILTERS = ("ratio", "cross", "ratio+cross")
+MATCH_FILTERS = ("ratio", "cross", "ratio+cross", "ratio+guided", "cross+guided", "ratio+cross+guided")
+
+
+def merge_guided(plain, guided):
+    """The union of a pair's plain RANSAC inliers and its guided list, (queryIdx, trainIdx, distance) arrays each, in ascending
+    query order: a query both lists hold carries the same train row in both (esfm.h "Epipolar-guided matching", property (b)), so
+    the guided entries of the queries the plain list lacks are added."""
+    pq, pt, pd = plain
+    gq, gt, gd = guided
+    new = ~np.isin(gq, pq)
+    q = np.concatenate([pq, gq[new]]); t = np.concatenate([pt, gt[new]]); d = np.concatenate([pd, gd[new]])
+    order = np.argsort(q, kind="stable")
+    return q[order], t[order], d[order]
 
 
 def match_and_verify_all_pairs(frames: Sequence[Frame], use_feature: str = "S", ransac_reproj_distance: float = 1.0,
@@ -41,7 +53,10 @@ def match_and_verify_all_pairs(frames: Sequence[Frame], use_feature: str = "S", 
     matches survive, estimate2D2D_E5P_RANSAC (threshold = ransac_reproj_distance, prob 0.99) and getDepthFast on the inliers;
     otherwise no inliers, identity transform, depth 1 (:147-148).  Returns img_match_graph[i][j].
     match_filter: "ratio" (the reference's one-way Lowe test), "cross" (mutual nearest neighbours) or "ratio+cross" (both, the
-    ratio test in both directions: esfm.h "Cross-check matching")."""
+    ratio test in both directions: esfm.h "Cross-check matching").  With "+guided" appended, every pair that got an essential
+    matrix is matched a second time with the search restricted to the rows that matrix admits within ransac_reproj_distance (one
+    esfm_match_guided_pairs_dev call, the same filter), and its matches become the union of the RANSAC inliers and that list;
+    T_21 and appro_depth stay those of the first pass."""
     if match_filter not in MATCH_FILTERS:
         raise ValueError(f"match_filter must be one of {MATCH_FILTERS}, not {match_filter!r}")
     ctx = ctx or default_context()
@@ -52,12 +67,15 @@ def match_and_verify_all_pairs(frames: Sequence[Frame], use_feature: str = "S", 
     graph: List[List[FramePair]] = [[FramePair(i, j) for j in range(i)] for i in range(n)]
     if len(pairs) == 0:
         return graph
-    bank = DescriptorBank([f.descriptors for f in frames], metric, device=f"cuda:{ctx.device}")
+    guided = match_filter.endswith("+guided")
+    first_filter = match_filter[:-len("+guided")] if guided else match_filter
+    kps = [np.asarray(f.keypoints, np.float32).reshape(-1, 2) for f in frames] if guided else None
+    bank = DescriptorBank([f.descriptors for f in frames], metric, device=f"cuda:{ctx.device}", keypoints=kps)
     pm = PairMatcher(bank, pairs, ctx)                                  # drains torch's upload stream before its first launch
-    if match_filter == "ratio":
+    if first_filter == "ratio":
         res = pm.match(ratio).to_host()
     else:
-        res = pm.match_cross(ratio if match_filter == "ratio+cross" else None).to_host()
+        res = pm.match_cross(ratio if first_filter == "ratio+cross" else None).to_host()
     # RANSAC + pose for every pair with enough matches, in shared launches
     sel = [k for k in range(len(pairs)) if len(res[k][0]) > num_min_pair]
     if sel:
@@ -68,6 +86,12 @@ def match_and_verify_all_pairs(frames: Sequence[Frame], use_feature: str = "S", 
                         frames[pairs[k][0]].K_cam[1, 2]] for k in sel], np.float32)
         Es, mask, status, _ = find_essential_pairs(off, p1, p2, K4, 0.99, ransac_reproj_distance, ctx)
         good, Rs, ts, _ = recover_pose_pairs(off, p1, p2, K4, Es, mask, ctx)
+        verified = [s for s in range(len(sel)) if status[s]]
+        extra = {}
+        if guided and verified:
+            lists = pm.match_guided([sel[s] for s in verified], Es[verified], K4[verified], ransac_reproj_distance,
+                                    None if first_filter == "cross" else ratio, first_filter != "ratio").to_host()
+            extra = dict(zip(verified, lists))
         # getDepthFast: every 20th inlier match, identity vs T_21, frame i's K for both images
         jobs_P2, jobs_a, jobs_b, jobs_off, jobs_k = [], [], [], [0], []
         for s, k in enumerate(sel):
@@ -77,7 +101,8 @@ def match_and_verify_all_pairs(frames: Sequence[Frame], use_feature: str = "S", 
                 continue
             m = mask[off[s]:off[s + 1]]
             q, t, d = res[k]
-            g.matches = [DMatch(int(a), int(b), float(c)) for a, b, c in zip(q[m], t[m], d[m])]
+            kept = (q[m], t[m], d[m]) if s not in extra else merge_guided((q[m], t[m], d[m]), extra[s])
+            g.matches = [DMatch(int(a), int(b), float(c)) for a, b, c in zip(*kept)]
             T = np.eye(4, dtype=np.float32)
             T[:3, :3] = Rs[s].astype(np.float32); T[:3, 3] = ts[s].astype(np.float32)
             g.T_21 = T

@@ -250,6 +250,65 @@ int esfm_match_cross_pairs(esfm_ctx *ctx, esfm_metric metric, const void *desc_h
                            int width, const int32_t *pairs, int n_pairs, int use_ratio, double ratio, int32_t *query_idx,
                            int32_t *train_idx, float *distance, int32_t *n_out /*n_pairs*/, int64_t *out_offset /*n_pairs+1*/);
 
+/*
+ * Epipolar-guided matching: a second matching pass for image pairs that already have an essential matrix (COLMAP's guided_matching;
+ * the reference has none -- its README lists "try more robust outlier filter" as a to-do).  The descriptor search of a query row is
+ * restricted to the train rows that lie on the query's epipolar line, so that a repeated structure's twin elsewhere in the image no
+ * longer makes the ratio test reject the match.
+ * For one pair: query set Q (nq descriptor rows and keypoints), train set T (nt), E[9] row-major double, K4 = fx, cx, fy, cy (float; the
+ * query frame's, used for both images as estimate2D2D_E5P_RANSAC does), max_epipolar_px (double).
+ * 1. Admissibility.  adm(q, t) is exactly the inlier test of esfm_find_essential_mat's RANSAC (sampson_inlier in ransac_kernels.hip,
+ *    find_inliers in oracle/ransac_ref.c):
+ *      x1 = ((double)uq - cx) / fx, y1 = ((double)vq - cy) / fy for the query keypoint, x2, y2 the same for the train keypoint;
+ *      thr = max_epipolar_px / ((fx + fy) / 2.0), tsq = (float)(thr * thr);
+ *      Ex0 = E0*x1 + E1*y1 + E2, Ex1 = E3*x1 + E4*y1 + E5, Ex2 = E6*x1 + E7*y1 + E8;
+ *      Et0 = E0*x2 + E3*y2 + E6, Et1 = E1*x2 + E4*y2 + E7;
+ *      v = x2*Ex0 + y2*Ex1 + Ex2;  err = (float)(v*v / (Ex0*Ex0 + Ex1*Ex1 + Et0*Et0 + Et1*Et1));  adm = err <= tsq.
+ *    All arithmetic in double, left to right, no fused multiply-add; a NaN anywhere makes the row inadmissible.  There is ONE predicate
+ *    per (query row, train row): the reverse direction of the cross-check evaluates this same expression with the same operand roles.
+ * 2. Guided 2-NN.  For each query the two best ADMISSIBLE train rows under esfm_knn2_*'s ordering (ascending (distance, train index),
+ *    ties to the lower index, a NaN distance never inserted), distances as esfm_knn2_* (L2: sqrtf of the canonical sum; Hamming: the
+ *    bit count as float).  A missing neighbour is index -1, distance FLT_MAX.  n_adm[q]: the number of admissible train rows.
+ * 3. Filters, on that table and on the reverse one (for each train row its two best admissible query rows, ties to the lower query index).
+ *      use_ratio:   row q passes iff it has TWO admissible neighbours and (double)d0 < ratio * (double)d1; a query with fewer than two
+ *                   admissible rows emits nothing (the convention of nt < 2 in esfm_match_*).
+ *      cross_check: q emits iff R(F(q)) == q on the guided tables; with use_ratio the ratio test must hold on the forward row q and on
+ *                   the reverse row F(q) (the strict rule of esfm_match_cross_*).
+ *    At least one of the two must be on.  use_ratio or cross_check outside {0, 1}, neither on, a NaN ratio with use_ratio = 1,
+ *    max_epipolar_px NaN or <= 0: ESFM_ERR_INVALID_ARG.  max_epipolar_px = +inf is allowed: every row with a finite error is admissible.
+ * 4. Output as esfm_match_pairs_dev: pair p owns [out_offset[p], out_offset[p] + nq_p), the first n_out[p] entries valid, query-ascending,
+ *    the distance the forward d0.
+ * Two properties follow.  (a) With max_epipolar_px = +inf and finite keypoints the lists equal esfm_match_pairs' (ratio) and
+ * esfm_match_cross_pairs' (cross, ratio+cross) on the same data, entry for entry.  (b) A plain match (q, t) that passes filter f and is
+ * admissible: if q emits anything under guided-f, it emits the same t (and with a cross filter no other query can claim t), so the union
+ * of the plain RANSAC inliers and the guided list has one train row per query -- and one query per train row with a cross filter.
+ * kp_dev: float2 (u, v) per row, concatenated like the descriptors.  E (9 doubles per pair) and K4_per_pair (4 floats per pair) are HOST
+ * arrays.  L2 of any dim >= 1, Hamming of 16, 32 or 64 bytes, empty sets, sets of at most 2^21 - 1 rows.  The call reads the raw
+ * descriptor rows only: it neither needs nor disturbs esfm_match_prepare_dev's state.  Enqueues on the context's stream; does not
+ * synchronise.  The results are bit-reproducible from run to run.
+ */
+int esfm_match_guided_pairs_dev(esfm_ctx *ctx, esfm_metric metric, const void *desc_dev, const float *kp_dev, const int32_t *set_row_offset,
+                                int n_sets, int width /*dim or nbytes*/, const int32_t *pairs, int n_pairs, const double *E /*host, 9 per pair*/,
+                                const float *K4_per_pair /*host, 4 per pair*/, double max_epipolar_px, int use_ratio, double ratio,
+                                int cross_check, int32_t *query_idx_dev, int32_t *train_idx_dev, float *distance_dev,
+                                int32_t *n_out_dev /*n_pairs*/, int64_t *out_offset /*host, n_pairs+1*/);
+/* Host-pointer form, as esfm_match_pairs: descriptors and keypoints are uploaded once, the lists come back packed.  Synchronises. */
+int esfm_match_guided_pairs(esfm_ctx *ctx, esfm_metric metric, const void *desc_host, const float *kp_host, const int32_t *set_row_offset,
+                            int n_sets, int width, const int32_t *pairs, int n_pairs, const double *E, const float *K4_per_pair,
+                            double max_epipolar_px, int use_ratio, double ratio, int cross_check, int32_t *query_idx, int32_t *train_idx,
+                            float *distance, int32_t *n_out /*n_pairs*/, int64_t *out_offset /*n_pairs+1*/);
+/* The raw forward table of step 2 (layout as esfm_knn2_pairs_dev) and n_adm per query (n_adm_dev: sum(nq_p) entries, may be NULL). */
+int esfm_knn2_guided_pairs_dev(esfm_ctx *ctx, esfm_metric metric, const void *desc_dev, const float *kp_dev, const int32_t *set_row_offset,
+                               int n_sets, int width, const int32_t *pairs, int n_pairs, const double *E, const float *K4_per_pair,
+                               double max_epipolar_px, int32_t *knn_idx_dev, float *knn_dist_dev, int32_t *n_adm_dev, int64_t *out_offset);
+/* One pair, host pointers (kp_q / kp_t: 2 floats per row).  Synchronise. */
+int esfm_match_guided_l2_f32(esfm_ctx *ctx, const float *q, const float *kp_q, int nq, const float *t, const float *kp_t, int nt, int dim,
+                             const double *E, const float *K4, double max_epipolar_px, int use_ratio, double ratio, int cross_check,
+                             int32_t *query_idx, int32_t *train_idx, float *distance, int32_t *n_out);
+int esfm_match_guided_hamming(esfm_ctx *ctx, const uint8_t *q, const float *kp_q, int nq, const uint8_t *t, const float *kp_t, int nt, int nbytes,
+                              const double *E, const float *K4, double max_epipolar_px, int use_ratio, double ratio, int cross_check,
+                              int32_t *query_idx, int32_t *train_idx, float *distance, int32_t *n_out);
+
 /* Counters of the last L2 batched call on this context (after a synchronise):
  * queries whose MFMA candidate list could not be certified and were re-scanned
  * exactly (see DESIGN.md "certified re-rank").  For tests and profiling. */
