@@ -11,12 +11,9 @@
 #include <vector>
 
 #include "../../include/esfm.h"
+#include "error.hpp"   // set_error, get_error, ESFM_REQUIRE
 
 namespace esfm {
-
-// Thread-local last-error text behind esfm_last_error().
-void set_error(const char *fmt, ...);
-const char *get_error();
 
 #define ESFM_HIP_TRY(expr)                                                                      \
     do {                                                                                        \
@@ -26,14 +23,6 @@ const char *get_error();
                               __LINE__);                                                        \
             return e__ == hipErrorOutOfMemory ? ESFM_ERR_OOM : ESFM_ERR_HIP;                    \
         }                                                                                       \
-    } while (0)
-
-#define ESFM_REQUIRE(cond, msg)                     \
-    do {                                            \
-        if (!(cond)) {                              \
-            ::esfm::set_error("%s: %s", __func__, msg); \
-            return ESFM_ERR_INVALID_ARG;            \
-        }                                           \
     } while (0)
 
 // Host <-> device copies of caller-owned memory (ordered on `st` like hipMemcpyAsync; pageable memory makes them synchronous).
@@ -121,7 +110,8 @@ struct esfm_ctx {
     hipStream_t stream = nullptr;
     bool owns_stream = false;
     int num_cu = 256;
-    // shared scratch of the API modules; knn_dist is also ORB detection's keypoint scratch (orb_api.cpp), the rest of the matcher's
+    // shared scratch of the API modules (stage_b .. stage_e: the host-pointer matchers' device-side lists, stage_a their packed
+    // read-back, match_readback.cpp); knn_dist is also ORB detection's keypoint scratch (orb_api.cpp), the rest of the matcher's
     // state is in `match`
     esfm::DevBuf knn_dist, stage_a, stage_b, stage_c, stage_d, stage_e;
     esfm::MatchState match;

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Generates l2_segment_gfx950.inc: the hand-scheduled main loop of l2_knn_bf16_kernel (match_kernels.hip) as ONE inline-asm
+"""Generates l2_segment_gfx950.inc: the hand-scheduled main loop of l2_knn_bf16_kernel (match_l2_bf16x3.hip) as ONE inline-asm
 block with fixed registers -- the distance GEMM of one SEGMENT (<= 16 tiles of 128 train rows = 64 steps of 32) for a wave's two
 sets of 32 queries, with the fused two-level top-3 fold.
 

@@ -6,17 +6,16 @@
 #include <vector>
 
 #include "guided_kernels.hpp"
+#include "match_plan.hpp"
 
 using esfm::GuidedGeom;
 using esfm::PairDesc;
 
 namespace {
 
-struct GuidedPlan {
-    std::vector<PairDesc> tab;      // the forward pairs; with `mirror`, followed by each of them with query and train swapped
+// What is guided in a guided call's plan: every forward pair's geometry.
+struct GuidedPlan : esfm::PairPlan {
     std::vector<GuidedGeom> geom;   // one per forward pair
-    int n_fwd = 0, n_blocks = 0;
-    int64_t fwd_queries = 0, total_queries = 0;
 };
 
 int check_filters(int use_ratio, double ratio, int cross_check)
@@ -30,14 +29,9 @@ int check_filters(int use_ratio, double ratio, int cross_check)
 
 int check_guided(esfm_ctx *ctx, esfm_metric metric, int width, double max_epipolar_px)
 {
-    if (!ctx) { esfm::set_error("ctx is NULL"); return ESFM_ERR_INVALID_ARG; }
-    if (metric != ESFM_L2_F32 && metric != ESFM_HAMMING) { esfm::set_error("unknown metric %d", (int)metric); return ESFM_ERR_INVALID_ARG; }
-    ESFM_REQUIRE(width > 0, "descriptor width must be positive");
+    if (int rc = esfm::check_metric_width(ctx, metric, width, "check_guided: descriptor width must be positive")) return rc;
     ESFM_REQUIRE(max_epipolar_px > 0.0, "max_epipolar_px must be positive (+inf allowed) and not NaN");
-    if (metric == ESFM_HAMMING && !esfm::hamming_supported(width)) {
-        esfm::set_error("hamming descriptors must be 16, 32 or 64 bytes (got %d)", width);
-        return ESFM_ERR_UNSUPPORTED;
-    }
+    if (int rc = esfm::check_hamming_width(metric, width)) return rc;
     return esfm::set_device(ctx);
 }
 
@@ -46,33 +40,10 @@ int make_plan(const int32_t *set_row_offset, int n_sets, const int32_t *pairs, i
               double max_epipolar_px, bool mirror, int64_t *out_offset, GuidedPlan *plan)
 {
     ESFM_REQUIRE(out_offset != nullptr, "out_offset is NULL");
-    ESFM_REQUIRE(set_row_offset != nullptr && n_sets >= 1, "set_row_offset/n_sets");
+    ESFM_REQUIRE(set_row_offset != nullptr && n_sets >= 1, "set_row_offset/n_sets");      // (first, as ever; make_plan looks again)
     ESFM_REQUIRE(n_pairs >= 0 && (n_pairs == 0 || (pairs != nullptr && E != nullptr && K4 != nullptr)), "pairs/E/K4_per_pair/n_pairs");
-    ESFM_REQUIRE(set_row_offset[0] == 0, "set_row_offset[0] must be 0");
-    for (int s = 0; s < n_sets; ++s) ESFM_REQUIRE(set_row_offset[s + 1] >= set_row_offset[s], "set_row_offset must be non-decreasing");
-    plan->n_fwd = n_pairs;
-    plan->tab.resize((size_t)n_pairs * (mirror ? 2 : 1));
+    if (int rc = esfm::make_plan(set_row_offset, n_sets, pairs, n_pairs, esfm::kGuidedQueryBlock, 0, mirror, esfm::kGuidedPlanRules, out_offset, plan)) return rc;
     plan->geom.resize((size_t)n_pairs);
-    int64_t off = 0, blk = 0;
-    for (size_t g = 0; g < plan->tab.size(); ++g) {
-        const int p = (int)(g % (size_t)std::max(n_pairs, 1));
-        const bool rev = g >= (size_t)n_pairs;
-        const int qs = pairs[2 * p + (rev ? 1 : 0)], ts = pairs[2 * p + (rev ? 0 : 1)];
-        ESFM_REQUIRE(qs >= 0 && qs < n_sets && ts >= 0 && ts < n_sets, "pair refers to a set out of range");
-        PairDesc &d = plan->tab[g];
-        d.q_row0 = set_row_offset[qs]; d.nq = set_row_offset[qs + 1] - set_row_offset[qs];
-        d.t_row0 = set_row_offset[ts]; d.nt = set_row_offset[ts + 1] - set_row_offset[ts];
-        ESFM_REQUIRE(d.nt < (1 << 21) && d.nq < (1 << 21), "sets are limited to 2^21-1 rows");   // row field of the queue entries and keys
-        d.out_off = off; d.blk_off = (int32_t)blk; d.blk_off2 = 0;
-        if (!rev) out_offset[p] = off;
-        off += d.nq;
-        blk += (d.nq + esfm::kGuidedQueryBlock - 1) / esfm::kGuidedQueryBlock;
-        ESFM_REQUIRE(blk < (int64_t)1 << 31, "too many workgroups for one launch; split the pair list");
-        if (g + 1 == (size_t)n_pairs) { out_offset[n_pairs] = off; plan->fwd_queries = off; }
-    }
-    if (n_pairs == 0) out_offset[0] = 0;
-    plan->total_queries = off;
-    plan->n_blocks = (int)blk;
     for (int p = 0; p < n_pairs; ++p) {
         GuidedGeom &gm = plan->geom[(size_t)p];
         for (int k = 0; k < 9; ++k) gm.E[k] = E[9 * (size_t)p + k];
@@ -132,8 +103,6 @@ int match_lists_dev(esfm_ctx *ctx, esfm_metric metric, const void *desc_dev, con
     return esfm::launch_ratio_compact(ctx->stream, dev_tab, n_pairs, knn_idx, knn_dist, ratio, query_idx_dev, train_idx_dev, distance_dev, n_out_dev);
 }
 
-size_t row_bytes_of(esfm_metric metric, int width) { return metric == ESFM_L2_F32 ? sizeof(float) * (size_t)width : (size_t)width; }
-
 // Host pointers in and out: upload once, one launch sequence, the lists packed on the device before the read-back.
 int match_pairs_host(esfm_ctx *ctx, esfm_metric metric, const void *desc_host, const float *kp_host, const int32_t *set_row_offset, int n_sets,
                      int width, const int32_t *pairs, int n_pairs, const double *E, const float *K4, double max_epipolar_px, int use_ratio,
@@ -153,52 +122,18 @@ int match_pairs_host(esfm_ctx *ctx, esfm_metric metric, const void *desc_host, c
     ESFM_REQUIRE(desc_host && kp_host && query_idx && train_idx && distance, "host pointer is NULL");
     hipStream_t st = ctx->stream;
     const size_t rows = (size_t)set_row_offset[n_sets];
-    if (int rc = ctx->guided_bank.reserve(row_bytes_of(metric, width) * rows + 16)) return rc;
+    if (int rc = ctx->guided_bank.reserve(esfm::match_row_bytes(metric, width) * rows + 16)) return rc;
     if (int rc = ctx->guided_kp.reserve(sizeof(float) * 2 * rows + 16)) return rc;
-    ESFM_HIP_TRY(esfm::copy_h2d(ctx->guided_bank.ptr, desc_host, row_bytes_of(metric, width) * rows, st));
+    ESFM_HIP_TRY(esfm::copy_h2d(ctx->guided_bank.ptr, desc_host, esfm::match_row_bytes(metric, width) * rows, st));
     ESFM_HIP_TRY(esfm::copy_h2d(ctx->guided_kp.ptr, kp_host, sizeof(float) * 2 * rows, st));
-    if (int rc = ctx->stage_b.reserve(sizeof(int32_t) * nq)) return rc;
-    if (int rc = ctx->stage_c.reserve(sizeof(int32_t) * nq)) return rc;
-    if (int rc = ctx->stage_d.reserve(sizeof(float) * nq)) return rc;
-    if (int rc = ctx->stage_e.reserve(sizeof(int32_t) * (size_t)n_pairs)) return rc;
+    if (int rc = esfm::reserve_match_list_stage(ctx, nq, n_pairs)) return rc;
     std::vector<int64_t> off2((size_t)n_pairs + 1);
     if (int rc = match_lists_dev(ctx, metric, ctx->guided_bank.ptr, ctx->guided_kp.as<float>(), set_row_offset, n_sets, width, pairs, n_pairs, E, K4,
                                  max_epipolar_px, use_ratio, ratio, cross_check, ctx->stage_b.as<int32_t>(), ctx->stage_c.as<int32_t>(),
                                  ctx->stage_d.as<float>(), ctx->stage_e.as<int32_t>(), off2.data()))
         return rc;
-    ESFM_HIP_TRY(esfm::copy_d2h(n_out, ctx->stage_e.ptr, sizeof(int32_t) * (size_t)n_pairs, st));
-    ESFM_HIP_TRY(hipStreamSynchronize(st));
-    size_t total = 0;
-    for (int p = 0; p < n_pairs; ++p) total += (size_t)n_out[p];
-    if (total == 0) return ESFM_OK;
-    // packed read-back (as esfm_match_pairs): the transfer is proportional to the matches, not to the queries
-    std::vector<long long> tab(2 * (size_t)n_pairs);
-    {
-        long long run = 0;
-        for (int p = 0; p < n_pairs; ++p) { tab[2 * (size_t)p] = off2[(size_t)p]; tab[2 * (size_t)p + 1] = run; run += n_out[p]; }
-    }
-    const size_t tab_bytes = (sizeof(long long) * tab.size() + 255) & ~(size_t)255;
-    if (int rc = ctx->stage_a.reserve(tab_bytes + 12 * total + 64)) return rc;
-    char *base = ctx->stage_a.as<char>();
-    int32_t *dq = reinterpret_cast<int32_t *>(base + tab_bytes), *dtn = dq + total;
-    float *dd = reinterpret_cast<float *>(dtn + total);
-    ESFM_HIP_TRY(esfm::copy_h2d(base, tab.data(), sizeof(long long) * tab.size(), st));
-    if (int rc = esfm::launch_pack_match_lists(st, reinterpret_cast<const long long *>(base), ctx->stage_e.as<int32_t>(), n_pairs, ctx->stage_b.as<int32_t>(),
-                                               ctx->stage_c.as<int32_t>(), ctx->stage_d.as<float>(), dq, dtn, dd))
-        return rc;
-    std::vector<int32_t> hq(2 * total);
-    std::vector<float> hd(total);
-    ESFM_HIP_TRY(esfm::copy_d2h(hq.data(), dq, sizeof(int32_t) * 2 * total, st));
-    ESFM_HIP_TRY(esfm::copy_d2h(hd.data(), dd, sizeof(float) * total, st));
-    ESFM_HIP_TRY(hipStreamSynchronize(st));
-    for (int p = 0; p < n_pairs; ++p) {
-        const size_t n = (size_t)n_out[p], so = (size_t)tab[2 * (size_t)p], dof = (size_t)tab[2 * (size_t)p + 1];
-        if (!n) continue;
-        memcpy(query_idx + so, hq.data() + dof, sizeof(int32_t) * n);
-        memcpy(train_idx + so, hq.data() + total + dof, sizeof(int32_t) * n);
-        memcpy(distance + so, hd.data() + dof, sizeof(float) * n);
-    }
-    return ESFM_OK;
+    // packed read-back (as esfm_match_pairs, always packed): the transfer is proportional to the matches, not to the queries
+    return esfm::read_back_match_lists(ctx, n_pairs, off2.data(), nq, false, query_idx, train_idx, distance, n_out);
 }
 
 // One pair through the host-pointer form: sets [train rows | query rows], the pair (1, 0).
@@ -213,7 +148,7 @@ int single_pair(esfm_ctx *ctx, esfm_metric metric, const void *q, const float *k
     ESFM_REQUIRE(nt == 0 || (t && kp_t), "t / kp_t is NULL");
     ESFM_REQUIRE(nq == 0 || (query_idx && train_idx && distance), "output pointer is NULL");
     *n_out = 0;
-    const size_t rb = row_bytes_of(metric, width);
+    const size_t rb = esfm::match_row_bytes(metric, width);
     std::vector<char> bank(rb * ((size_t)nt + (size_t)nq) + 1);
     std::vector<float> kps(2 * ((size_t)nt + (size_t)nq) + 1);
     if (nt) { memcpy(bank.data(), t, rb * (size_t)nt); memcpy(kps.data(), kp_t, sizeof(float) * 2 * (size_t)nt); }

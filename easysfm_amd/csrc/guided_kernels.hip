@@ -6,6 +6,7 @@
 #include <cstdlib>
 
 #include "guided_kernels.hpp"
+#include "match_device.hpp"   // find_pair_by_block, l2sqr_canonical: the plain matcher's own
 
 namespace esfm {
 
@@ -19,16 +20,6 @@ constexpr int kChunk = 16;          // rows between two looks at the queue's fil
 constexpr int kQueueCap = 8192;     // admissible (lane, row) entries waiting for their descriptor distance
 static_assert(kQueueCap >= 2 * kThreads * kChunk, "a chunk's pushes must fit behind the drain threshold");
 constexpr u64 kEmpty = ~0ull;
-
-__device__ __forceinline__ int pair_of_block(const PairDesc *pairs, int n, int lb)
-{
-    int lo = 0, hi = n - 1;   // last p with blk_off[p] <= lb
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (pairs[mid].blk_off <= lb) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
 
 // A row in the role it plays in the predicate, once per (pair, row): the query role's (Ex0, Ex1, Ex2, Ex0^2 + Ex1^2), the train
 // role's (x2, y2, Et0^2, Et1^2).  The normalisation is ransac_kernels.hip's normalise_pt.
@@ -66,44 +57,6 @@ __device__ __forceinline__ bool guided_admissible(const double4 q, const double4
     return guided_admissible_divide(p, den, g.tsq);
 }
 
-// l2sqr_canonical of match_kernels.hip (oracle/match_ref.c esfm_ref_l2sqr): 8 partial sums over blocks of 8, separate multiply
-// and add, (acc[c] + acc[c + 4]) summed left to right, then the scalar tail.
-template <bool VEC>
-__device__ __forceinline__ float guided_l2sqr(const float *__restrict__ a, const float *__restrict__ b, int n)
-{
-    float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    int j = 0;
-    for (; j <= n - 8; j += 8) {
-        float av[8], bv[8];
-        if (VEC) {
-            const float4 a0 = *reinterpret_cast<const float4 *>(a + j), a1 = *reinterpret_cast<const float4 *>(a + j + 4);
-            const float4 b0 = *reinterpret_cast<const float4 *>(b + j), b1 = *reinterpret_cast<const float4 *>(b + j + 4);
-            av[0] = a0.x; av[1] = a0.y; av[2] = a0.z; av[3] = a0.w; av[4] = a1.x; av[5] = a1.y; av[6] = a1.z; av[7] = a1.w;
-            bv[0] = b0.x; bv[1] = b0.y; bv[2] = b0.z; bv[3] = b0.w; bv[4] = b1.x; bv[5] = b1.y; bv[6] = b1.z; bv[7] = b1.w;
-        } else {
-#pragma unroll
-            for (int c = 0; c < 8; ++c) { av[c] = a[j + c]; bv[c] = b[j + c]; }
-        }
-#pragma unroll
-        for (int c = 0; c < 8; ++c) {
-            const float t = __fsub_rn(av[c], bv[c]);
-            acc[c] = __fadd_rn(acc[c], __fmul_rn(t, t));
-        }
-    }
-    const float s0 = __fadd_rn(acc[0], acc[4]);
-    const float s1 = __fadd_rn(acc[1], acc[5]);
-    const float s2 = __fadd_rn(acc[2], acc[6]);
-    const float s3 = __fadd_rn(acc[3], acc[7]);
-    float d = __fadd_rn(s0, s1);
-    d = __fadd_rn(d, s2);
-    d = __fadd_rn(d, s3);
-    for (; j < n; ++j) {
-        const float t = __fsub_rn(a[j], b[j]);
-        d = __fadd_rn(d, __fmul_rn(t, t));
-    }
-    return d;
-}
-
 enum { kL2Vec = 0, kL2Scalar = 1, kHamming = 2 };
 
 // the plain matcher's distance of two rows of the descriptor buffer (width: floats or bytes)
@@ -117,7 +70,7 @@ __device__ __forceinline__ float guided_distance(const void *__restrict__ desc, 
         return (float)d;
     }
     const float *a = static_cast<const float *>(desc) + qrow * (size_t)width, *b = static_cast<const float *>(desc) + trow * (size_t)width;
-    return sqrtf(guided_l2sqr<MODE == kL2Vec>(a, b, width));
+    return sqrtf(l2sqr_canonical<MODE == kL2Vec>(a, b, width));
 }
 
 // One workgroup per (pair, block of 256 own rows), a lane per own row.  The other set streams through LDS as records, 256 rows
@@ -138,7 +91,7 @@ __global__ __launch_bounds__(kThreads) void guided_knn2_kernel(const void *__res
     __shared__ u64 s_b0[kThreads], s_b1[kThreads];
     __shared__ int s_cnt;
     const int tid = threadIdx.x;
-    const int g = pair_of_block(pairs, n_tab, (int)blockIdx.x);
+    const int g = find_pair_by_block(pairs, n_tab, (int)blockIdx.x);
     const PairDesc pd = pairs[g];
     const bool rev = g >= n_fwd;          // own rows: the forward pair's TRAIN set, in the predicate's train role
     const GuidedGeom gm = geom[rev ? g - n_fwd : g];

@@ -5,7 +5,7 @@
 // between two plain calls on a prepared buffer leaves the buffer prepared and the plain results as they were.
 #pragma once
 
-#include "match_kernels.hpp"
+#include "match_lists.hpp"   // PairDesc; the filters behind the guided tables are the plain matcher's list kernels
 
 namespace esfm {
 

@@ -6,63 +6,12 @@
 #include <vector>
 
 #include "match_kernels.hpp"
+#include "match_plan.hpp"
 
 using esfm::PairDesc;
+using esfm::PairPlan;
 
 namespace {
-
-
-struct PairPlan {
-    std::vector<PairDesc> tab;
-    std::vector<int32_t> blk_pair;   // the pair of every 512-query block of the one-product front pass (its workgroups look their work up here)
-    std::vector<int32_t> by_train;   // pair indices sorted by train set (l2_finish_kernel walks the pairs in this order: the workgroups that
-                                     // fetch rows of one train set run next to each other, on one XCD, and find them in its L2)
-    int n_blocks = 0;
-    int n_blocks2 = 0;      // workgroups of the one-product front pass
-    int max_nt = 0;
-    int64_t total_queries = 0;
-    int64_t total_rows = 0;
-};
-
-int make_plan(const int32_t *set_row_offset, int n_sets, const int32_t *pairs, int n_pairs, int query_block,
-              int64_t *out_offset, PairPlan *plan)
-{
-    ESFM_REQUIRE(set_row_offset != nullptr && n_sets >= 1, "set_row_offset/n_sets");
-    ESFM_REQUIRE(n_pairs >= 0 && (n_pairs == 0 || pairs != nullptr), "pairs/n_pairs");
-    ESFM_REQUIRE(set_row_offset[0] == 0, "set_row_offset[0] must be 0");
-    for (int s = 0; s < n_sets; ++s) ESFM_REQUIRE(set_row_offset[s + 1] >= set_row_offset[s], "set_row_offset must be non-decreasing");
-    plan->total_rows = set_row_offset[n_sets];
-    plan->tab.resize((size_t)n_pairs);
-    int64_t off = 0;
-    int64_t blk = 0, blk2 = 0;
-    const int qb2 = esfm::l2_x1_query_block();
-    for (int p = 0; p < n_pairs; ++p) {
-        const int qs = pairs[2 * p], ts = pairs[2 * p + 1];
-        ESFM_REQUIRE(qs >= 0 && qs < n_sets && ts >= 0 && ts < n_sets, "pair refers to a set out of range");
-        PairDesc &d = plan->tab[(size_t)p];
-        d.q_row0 = set_row_offset[qs]; d.nq = set_row_offset[qs + 1] - set_row_offset[qs];
-        d.t_row0 = set_row_offset[ts]; d.nt = set_row_offset[ts + 1] - set_row_offset[ts];
-        ESFM_REQUIRE(d.nt < (1 << 21), "train sets are limited to 2^21-1 rows");   // index field of the packed top-2 keys
-        ESFM_REQUIRE(d.nq < (1 << 23), "query sets are limited to 2^23-1 rows");   // 32-bit byte offsets into a set (row fetches through buffer descriptors)
-        d.out_off = off; d.blk_off = (int32_t)blk; d.blk_off2 = (int32_t)blk2;
-        plan->max_nt = std::max(plan->max_nt, (int)d.nt);
-        if (out_offset) out_offset[p] = off;
-        off += d.nq;
-        blk += (d.nq + query_block - 1) / query_block;
-        blk2 += (d.nq + qb2 - 1) / qb2;
-        ESFM_REQUIRE(blk < (int64_t)1 << 31, "too many workgroups for one launch; split the pair list");
-        plan->blk_pair.resize((size_t)blk2, p);
-    }
-    if (out_offset) out_offset[n_pairs] = off;
-    plan->by_train.resize((size_t)n_pairs);
-    for (int p = 0; p < n_pairs; ++p) plan->by_train[(size_t)p] = p;
-    std::stable_sort(plan->by_train.begin(), plan->by_train.end(),
-                     [&](int32_t a, int32_t b) { return plan->tab[(size_t)a].t_row0 < plan->tab[(size_t)b].t_row0; });
-    plan->n_blocks = (int)blk;
-    plan->n_blocks2 = (int)blk2;
-    plan->total_queries = off;
-    return ESFM_OK;
-}
 
 // Upload the pair table through a pinned staging buffer.  The context remembers the last table:
 // an identical pair list (the common case in a loop over the same frames) is not re-sent.
@@ -110,11 +59,6 @@ bool is_prepared(const esfm::MatchState &m, esfm_metric metric, const void *desc
     return m.prep_desc != nullptr && m.prep_desc == desc_dev && m.prep_metric == (int)metric && m.prep_rows == total_rows && m.prep_width == width;
 }
 
-size_t desc_bytes(esfm_metric metric, int64_t total_rows, int width)
-{
-    return (size_t)total_rows * (metric == ESFM_L2_F32 ? sizeof(float) * (size_t)width : (size_t)width);
-}
-
 // esfm_ctx_set_prepared_check(ctx, 1): a call that is about to rely on prepared operands first re-derives the buffer's fingerprint
 // and compares it with the one taken at prepare time (one read of the buffer + one host round trip per call: a debugging aid, off
 // by default).  A buffer that was rewritten in place -- or freed and replaced by another allocation at the same address -- fails
@@ -125,7 +69,7 @@ int verify_prepared(esfm_ctx *ctx, esfm_metric metric, const void *desc_dev, int
     if (!m.prep_check) return ESFM_OK;
     if (!m.prep_has_sum) { m.prep_desc = nullptr; return ESFM_OK; }      // prepared before the check was switched on: re-derive
     unsigned long long *sums = m.prep_sum.as<unsigned long long>();
-    if (int rc = esfm::launch_buffer_checksum(ctx->stream, desc_dev, desc_bytes(metric, total_rows, width), sums + 1)) return rc;
+    if (int rc = esfm::launch_buffer_checksum(ctx->stream, desc_dev, (size_t)total_rows * esfm::match_row_bytes(metric, width), sums + 1)) return rc;
     unsigned long long h[2] = {0ull, 0ull};
     ESFM_HIP_TRY(esfm::copy_d2h(h, sums, sizeof(h), ctx->stream));
     ESFM_HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -353,10 +297,7 @@ int knn2_core(esfm_ctx *ctx, esfm_metric metric, const void *desc_dev, int width
         if (int rc = verify_prepared(ctx, metric, desc_dev, plan.total_rows, width)) return rc;
     const Pass p{ctx, m, ctx->stream, desc_dev, width, plan, dev_tab, knn_idx, knn_dist, req, is_prepared(m, metric, desc_dev, plan.total_rows, width)};
     const MatchPath path = select_path(metric, width, plan.max_nt, m.l2_audit);
-    if (metric == ESFM_HAMMING && !esfm::hamming_supported(width)) {
-        esfm::set_error("hamming descriptors must be 16, 32 or 64 bytes (got %d)", width);
-        return ESFM_ERR_UNSUPPORTED;
-    }
+    if (int rc = esfm::check_hamming_width(metric, width)) return rc;
     if (metric == ESFM_L2_F32) {
         if (int rc = reserve_zeroed(m.counters, 64 * sizeof(int32_t), ctx->stream)) return rc;
         if ((m.l2_audit == 3 || m.l2_audit == 4) && path != MatchPath::L2_ONE_PRODUCT) {
@@ -382,9 +323,7 @@ int knn2_core(esfm_ctx *ctx, esfm_metric metric, const void *desc_dev, int width
 
 int check_common(esfm_ctx *ctx, esfm_metric metric, int width)
 {
-    if (!ctx) { esfm::set_error("ctx is NULL"); return ESFM_ERR_INVALID_ARG; }
-    if (metric != ESFM_L2_F32 && metric != ESFM_HAMMING) { esfm::set_error("unknown metric %d", (int)metric); return ESFM_ERR_INVALID_ARG; }
-    if (width <= 0) { esfm::set_error("descriptor width must be positive"); return ESFM_ERR_INVALID_ARG; }
+    if (int rc = esfm::check_metric_width(ctx, metric, width, "descriptor width must be positive")) return rc;
     return esfm::set_device(ctx);
 }
 
@@ -397,24 +336,15 @@ int check_cross(int use_ratio, double ratio)
 
 // The front of the pair-list entry points: context checks and the plan over `pairs`, out_offset its prefix sum.  mirror (the
 // cross-check): the plan runs over the caller's P pairs followed by (t, q) for each of them, so one pass writes both directions'
-// tables; the caller's out_offset is the first P + 1 entries of the mirrored prefix sum (the forward pairs come first).
+// tables; the caller's out_offset is the forward pairs' prefix sum (they come first).
 int plan_pairs(esfm_ctx *ctx, esfm_metric metric, int width, const int32_t *set_row_offset, int n_sets, const int32_t *pairs, int n_pairs,
                bool mirror, int64_t *out_offset, PairPlan *plan)
 {
     if (int rc = check_common(ctx, metric, width)) return rc;
     ESFM_REQUIRE(out_offset != nullptr, "out_offset is NULL");
+    if (mirror) ESFM_REQUIRE(n_pairs >= 0 && (n_pairs == 0 || pairs != nullptr), "pairs/n_pairs");      // (the mirrored form looks at the pair list first)
     const int query_block = metric == ESFM_L2_F32 ? esfm::l2_query_block(width) : esfm::hamming_query_block(width);
-    if (!mirror) return make_plan(set_row_offset, n_sets, pairs, n_pairs, query_block, out_offset, plan);
-    ESFM_REQUIRE(n_pairs >= 0 && (n_pairs == 0 || pairs != nullptr), "pairs/n_pairs");
-    std::vector<int32_t> mirrored(4 * (size_t)n_pairs);
-    for (int p = 0; p < n_pairs; ++p) {
-        mirrored[2 * (size_t)p] = pairs[2 * p]; mirrored[2 * (size_t)p + 1] = pairs[2 * p + 1];
-        mirrored[2 * ((size_t)n_pairs + p)] = pairs[2 * p + 1]; mirrored[2 * ((size_t)n_pairs + p) + 1] = pairs[2 * p];
-    }
-    std::vector<int64_t> off(2 * (size_t)n_pairs + 1);
-    if (int rc = make_plan(set_row_offset, n_sets, mirrored.data(), 2 * n_pairs, query_block, off.data(), plan)) return rc;
-    std::copy(off.begin(), off.begin() + n_pairs + 1, out_offset);
-    return ESFM_OK;
+    return esfm::make_plan(set_row_offset, n_sets, pairs, n_pairs, query_block, esfm::l2_x1_query_block(), mirror, esfm::kPlainPlanRules, out_offset, plan);
 }
 
 // esfm_knn2_pairs_dev / _screened_dev: the 2-NN tables into the caller's device arrays.
@@ -488,7 +418,7 @@ int single_pair(esfm_ctx *ctx, esfm_metric metric, const void *q, int nq, const 
     if (what == Result::CROSS) { if (int rc = check_cross(use_ratio, ratio)) return rc; }
     if (what != Result::KNN2) *n_out = 0;
     if (nq == 0) return ESFM_OK;
-    const size_t row_bytes = metric == ESFM_L2_F32 ? sizeof(float) * (size_t)width : (size_t)width;
+    const size_t row_bytes = esfm::match_row_bytes(metric, width);
     const size_t tb = row_bytes * (size_t)nt, qb = row_bytes * (size_t)nq;
     if (int rc = ctx->stage_a.reserve(tb + qb + 16)) return rc;
     hipStream_t st = ctx->stream;
@@ -510,10 +440,7 @@ int single_pair(esfm_ctx *ctx, esfm_metric metric, const void *q, int nq, const 
         ESFM_HIP_TRY(hipStreamSynchronize(st));
         return ESFM_OK;
     }
-    if (int rc = ctx->stage_b.reserve(sizeof(int32_t) * (size_t)nq)) return rc;
-    if (int rc = ctx->stage_c.reserve(sizeof(int32_t) * (size_t)nq)) return rc;
-    if (int rc = ctx->stage_d.reserve(sizeof(float) * (size_t)nq)) return rc;
-    if (int rc = ctx->stage_e.reserve(sizeof(int32_t))) return rc;
+    if (int rc = esfm::reserve_match_list_stage(ctx, (size_t)nq, 1)) return rc;
     if (int rc = match_lists_dev(ctx, metric, d, offs, 2, width, pr, 1, what == Result::CROSS, use_ratio, ratio, ctx->stage_b.as<int32_t>(),
                                  ctx->stage_c.as<int32_t>(), ctx->stage_d.as<float>(), ctx->stage_e.as<int32_t>(), out_off))
         return rc;
@@ -548,63 +475,19 @@ int match_pairs_host(esfm_ctx *ctx, esfm_metric metric, const void *desc_host, c
     ESFM_REQUIRE(desc_host && query_idx && train_idx && distance, "host pointer is NULL");
     hipStream_t st = ctx->stream;
     esfm::DevBuf &bank = ctx->match.bank;
-    const size_t row_bytes = metric == ESFM_L2_F32 ? sizeof(float) * (size_t)width : (size_t)width;
-    const size_t bytes = row_bytes * (size_t)plan.total_rows;
+    const size_t bytes = esfm::match_row_bytes(metric, width) * (size_t)plan.total_rows;
     ctx->match.prep_desc = nullptr;                // the bank below is rewritten: whatever was prepared from it is stale
     if (int rc = bank.reserve(bytes + 16)) return rc;
     ESFM_HIP_TRY(esfm::copy_h2d(bank.ptr, desc_host, bytes, st));
     if (int rc = esfm_match_prepare_dev(ctx, metric, bank.ptr, plan.total_rows, width)) return rc;
     const size_t nq = (size_t)plan.total_queries;
-    if (int rc = ctx->stage_b.reserve(sizeof(int32_t) * nq)) return rc;
-    if (int rc = ctx->stage_c.reserve(sizeof(int32_t) * nq)) return rc;
-    if (int rc = ctx->stage_d.reserve(sizeof(float) * nq)) return rc;
-    if (int rc = ctx->stage_e.reserve(sizeof(int32_t) * (size_t)n_pairs)) return rc;
+    if (int rc = esfm::reserve_match_list_stage(ctx, nq, n_pairs)) return rc;
     std::vector<int64_t> off2((size_t)n_pairs + 1);
     if (int rc = match_lists_dev(ctx, metric, bank.ptr, set_row_offset, n_sets, width, pairs, n_pairs, cross, use_ratio, ratio, ctx->stage_b.as<int32_t>(),
                                  ctx->stage_c.as<int32_t>(), ctx->stage_d.as<float>(), ctx->stage_e.as<int32_t>(), off2.data()))
         return rc;
-    ESFM_HIP_TRY(esfm::copy_d2h(n_out, ctx->stage_e.ptr, sizeof(int32_t) * (size_t)n_pairs, st));
-    ESFM_HIP_TRY(hipStreamSynchronize(st));
-    // The lists sit at out_offset[p] in arrays of sum(nq) slots; a ratio test keeps a few per cent of the queries.  When the matches
-    // are less than a quarter of the slots they are packed on the device, read back as three dense arrays and placed from a host
-    // copy (config 4's shape: 267 M slots, 4.4 M matches -- 52 MB over PCIe instead of 3.2 GB); otherwise the arrays go back whole.
-    size_t total = 0;
-    for (int p = 0; p < n_pairs; ++p) total += (size_t)n_out[p];
-    if (total == 0) return ESFM_OK;
-    if (total * 4 >= nq) {
-        ESFM_HIP_TRY(esfm::copy_d2h(query_idx, ctx->stage_b.ptr, sizeof(int32_t) * nq, st));
-        ESFM_HIP_TRY(esfm::copy_d2h(train_idx, ctx->stage_c.ptr, sizeof(int32_t) * nq, st));
-        ESFM_HIP_TRY(esfm::copy_d2h(distance, ctx->stage_d.ptr, sizeof(float) * nq, st));
-        ESFM_HIP_TRY(hipStreamSynchronize(st));
-        return ESFM_OK;
-    }
-    std::vector<long long> tab(2 * (size_t)n_pairs);
-    {
-        long long run = 0;
-        for (int p = 0; p < n_pairs; ++p) { tab[2 * (size_t)p] = off2[(size_t)p]; tab[2 * (size_t)p + 1] = run; run += n_out[p]; }
-    }
-    const size_t tab_bytes = (sizeof(long long) * tab.size() + 255) & ~(size_t)255;
-    if (int rc = ctx->stage_a.reserve(tab_bytes + 12 * total + 64)) return rc;
-    char *base = ctx->stage_a.as<char>();
-    int32_t *dq = reinterpret_cast<int32_t *>(base + tab_bytes), *dtn = dq + total;
-    float *dd = reinterpret_cast<float *>(dtn + total);
-    ESFM_HIP_TRY(esfm::copy_h2d(base, tab.data(), sizeof(long long) * tab.size(), st));
-    if (int rc = esfm::launch_pack_match_lists(st, reinterpret_cast<const long long *>(base), ctx->stage_e.as<int32_t>(), n_pairs, ctx->stage_b.as<int32_t>(),
-                                               ctx->stage_c.as<int32_t>(), ctx->stage_d.as<float>(), dq, dtn, dd))
-        return rc;
-    std::vector<int32_t> hq(2 * total);
-    std::vector<float> hd(total);
-    ESFM_HIP_TRY(esfm::copy_d2h(hq.data(), dq, sizeof(int32_t) * 2 * total, st));
-    ESFM_HIP_TRY(esfm::copy_d2h(hd.data(), dd, sizeof(float) * total, st));
-    ESFM_HIP_TRY(hipStreamSynchronize(st));
-    for (int p = 0; p < n_pairs; ++p) {
-        const size_t n = (size_t)n_out[p], so = (size_t)tab[2 * (size_t)p], dof = (size_t)tab[2 * (size_t)p + 1];
-        if (!n) continue;
-        memcpy(query_idx + so, hq.data() + dof, sizeof(int32_t) * n);
-        memcpy(train_idx + so, hq.data() + total + dof, sizeof(int32_t) * n);
-        memcpy(distance + so, hd.data() + dof, sizeof(float) * n);
-    }
-    return ESFM_OK;
+    // packed on the device when the matches are less than a quarter of the slots, otherwise the arrays go back whole
+    return esfm::read_back_match_lists(ctx, n_pairs, off2.data(), nq, true, query_idx, train_idx, distance, n_out);
 }
 
 // The first n of the last L2 call's 16 counters (zeros before any L2 call); synchronises.
@@ -735,7 +618,7 @@ int esfm_match_prepare_dev(esfm_ctx *ctx, esfm_metric metric, const void *desc_d
     m.prep_has_sum = false;
     if (m.prep_check) {
         if (int rc = m.prep_sum.reserve(2 * sizeof(unsigned long long))) return rc;
-        if (int rc = esfm::launch_buffer_checksum(st, desc_dev, desc_bytes(metric, total_rows, width), m.prep_sum.as<unsigned long long>())) return rc;
+        if (int rc = esfm::launch_buffer_checksum(st, desc_dev, (size_t)total_rows * esfm::match_row_bytes(metric, width), m.prep_sum.as<unsigned long long>())) return rc;
         m.prep_has_sum = true;
     }
     m.prep_desc = desc_dev; m.prep_metric = (int)metric; m.prep_rows = total_rows; m.prep_width = width;

@@ -1,24 +1,24 @@
-// Launch interface between match_api.cpp (host logic) and match_kernels.hip (gfx950 kernels).
+// The one launch interface between match_api.cpp (host logic) and the matcher's gfx950 kernels, grouped by the file that holds each
+// kernel family with its launchers, constants and environment switch.  match_device.hpp is what the kernels themselves share.
 #pragma once
 
+#include <algorithm>
+
 #include "common.hpp"
+#include "match_lists.hpp"   // ---- match_lists.hip: ratio test + compaction, cross-check join, list packing, buffer fingerprint
 
 namespace esfm {
 
-// One image pair of the pair loop (cpp_code/test/sfm.cpp:140-161), rows counted in the
-// concatenated descriptor buffer.
-struct PairDesc {
-    int32_t q_row0, nq;   // query set: first row, row count
-    int32_t t_row0, nt;   // train set
-    int64_t out_off;      // first output slot of this pair (exclusive prefix sum of nq)
-    int32_t blk_off;      // first workgroup of this pair in the knn launch
-    int32_t blk_off2;     // ... in the launch of the one-product front pass (l2_x1_query_block() queries per workgroup)
-};
-
+// ---- match_l2_f32.hip: row norms, f32-input MFMA pass, exact scans
 int launch_l2_norms(hipStream_t st, const float *desc, int dim, long long n_rows, float *norms);
 bool l2_mfma_supported(int dim);
 int launch_l2_knn_mfma(hipStream_t st, int dim, const float *desc, const float *norms, const PairDesc *pairs, int n_pairs,
                        int n_blocks, int32_t *knn_idx, float *knn_dist, int32_t *flagged, int32_t *counters, int flag_cap);
+int launch_l2_exact_scan(hipStream_t st, int dim, const float *desc, const PairDesc *pairs, int n_pairs,
+                         const int32_t *flagged, const int32_t *counters, long long total_queries, int grid,
+                         int32_t *knn_idx, float *knn_dist);
+
+// ---- match_l2_bf16x3.hip: split images, three-product bf16 pass, per-pair re-scan
 // 64-float descriptors: split-bf16 distance pass (needs l2_split_bytes(total_rows) of scratch; 256 queries per workgroup)
 bool l2_bf16_pass(int dim);
 int l2_query_block(int dim);
@@ -32,12 +32,25 @@ int launch_l2_split_bf16(hipStream_t st, const float *desc, long long total_rows
 int launch_l2_knn_bf16(hipStream_t st, const float *desc, const void *split, long long total_rows, const float *norms, const PairDesc *pairs,
                        int n_pairs, int n_blocks, int32_t *knn_idx, float *knn_dist, int32_t *flagged, int32_t *counters, int flag_cap,
                        int32_t *pair_cnt, int32_t *pair_list);
+// exact re-scan of the queries launch_l2_knn_bf16 binned per pair (pair_cnt[p] entries at pair_list[out_off[p]...])
+int launch_l2_rescan64_pairs(hipStream_t st, const float *desc, const PairDesc *pairs, int n_pairs, const int32_t *pair_cnt,
+                             const int32_t *pair_list, int32_t *knn_idx, float *knn_dist);
+// the one-product pass's scratch, written by launch_l2_split_bf16 (hi != NULL) and read by match_kernels.hip: part 0 the bf16(t) image,
+// 1 the bf16(-2 q) image (128 B per row each), 2 rho_t, 3 rho_q (4 B per row each), 4 per 256-row block max |row|^2 and max rho_t
+inline size_t l2_hi_bytes(long long total_rows) { const size_t n = (size_t)std::max(total_rows, 1LL); return (128 + 128 + 4 + 4) * n + 8 * ((n + 255) / 256); }
+inline char *l2_hi_part(void *hi, long long total_rows, int part)
+{
+    const size_t n = (size_t)std::max(total_rows, 1LL);
+    const size_t off[5] = {0, 128 * n, 256 * n, 260 * n, 264 * n};
+    return static_cast<char *>(hi) + off[part];
+}
+
+// ---- match_kernels.hip: one-product bf16 pass and l2_finish_kernel
 // one-product pass (64-float rows): distance pass + ratio screen.  Queries that provably fail d0 < ratio d1 get train index -2 if
 // `markers` is set -- otherwise nothing: l2_finish_kernel's ratio stage walks the survivors only -- (+inf:
 // screen off); every other query leaves a survivor entry (l2_survivor_entry_bytes() each, pair p's at surv_list + out_off[p]
 // entries, surv_cnt[p] of them; counters[2] counts them).  rejected != NULL (audit): the screen's rejections on that list, counters[0].
 // zero_a / zero_b [0, zero_n), zero_counters[0, 16): the other phase's per-pair and global counters, zeroed for the next call.
-size_t l2_hi_bytes(long long total_rows);
 size_t l2_survivor_entry_bytes();
 // blk_pair[b]: the pair of the launch's b-th 512-query block (pair p owns blocks [blk_off2[p], blk_off2[p + 1])); the grid is
 // one workgroup per block (ESFM_X1_GRID: that many persistent workgroups instead -- measurements).
@@ -57,13 +70,8 @@ int launch_l2_finish(hipStream_t st, const float *desc, const void *hi, long lon
 int l2_x1_query_block();
 bool l2_x1_supported(int max_nt);          // train sets the front pass's position code covers
 bool l2_one_product_pass();   // ESFM_L2_PASS=bf16x3 in the environment switches the one-product front pass off (measurement)
-// exact re-scan of the queries launch_l2_knn_bf16 binned per pair (pair_cnt[p] entries at pair_list[out_off[p]...])
-int launch_l2_rescan64_pairs(hipStream_t st, const float *desc, const PairDesc *pairs, int n_pairs, const int32_t *pair_cnt,
-                             const int32_t *pair_list, int32_t *knn_idx, float *knn_dist);
-int launch_l2_exact_scan(hipStream_t st, int dim, const float *desc, const PairDesc *pairs, int n_pairs,
-                         const int32_t *flagged, const int32_t *counters, long long total_queries, int grid,
-                         int32_t *knn_idx, float *knn_dist);
-bool hamming_supported(int nbytes);
+
+// ---- match_hamming.hip: XOR-popcount, i8-MFMA and FP4-MFMA kernels, their expanders
 int hamming_query_block(int nbytes);
 // 256-bit descriptors take the i8-MFMA path, which needs hamming_expanded_bytes(total_rows) of scratch (exp_scratch);
 // other widths run the XOR/popcount kernel and ignore it.
@@ -83,15 +91,5 @@ int launch_hamming_fp4(hipStream_t st, const void *desc, long long total_rows, v
 int launch_hamming_knn(hipStream_t st, int nbytes, const void *desc, long long total_rows, void *exp_scratch,
                        const PairDesc *pairs, int n_pairs, int n_blocks,
                        int32_t *knn_idx, float *knn_dist, bool expanded);
-int launch_buffer_checksum(hipStream_t st, const void *buf, size_t bytes, unsigned long long *out);
-int launch_pack_match_lists(hipStream_t st, const long long *tab, const int32_t *n_out, int n_pairs, const int32_t *sq, const int32_t *stn, const float *sd,
-                            int32_t *dq, int32_t *dtn, float *dd);
-// pairs: a mirrored table of 2 n_pairs entries (pair n_pairs + p is pair p with query and train swapped), knn_idx / knn_dist the
-// 2-NN tables of all of them with their markers.  Pair p keeps query q iff F = knn_idx[2 (out_off[p] + q)] >= 0 and the mirror's
-// nearest of row F is q (use_ratio: and ratio_ok on both records); output as launch_ratio_compact's, for the first n_pairs pairs.
-int launch_cross_check_compact(hipStream_t st, const PairDesc *pairs, int n_pairs, const int32_t *knn_idx, const float *knn_dist, int use_ratio,
-                               double ratio, int32_t *query_idx, int32_t *train_idx, float *distance, int32_t *n_out);
-int launch_ratio_compact(hipStream_t st, const PairDesc *pairs, int n_pairs, const int32_t *knn_idx, const float *knn_dist,
-                         double ratio, int32_t *query_idx, int32_t *train_idx, float *distance, int32_t *n_out);
 
 }  // namespace esfm

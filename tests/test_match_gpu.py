@@ -554,3 +554,68 @@ def test_config4_one_rank_shard_at_full_size(gpu_ctx, oracle_lib):
         m = np.isin(q, sel)
         assert np.array_equal(np.searchsorted(sel, q[m]), rq) and np.array_equal(t[m], rt) and np.array_equal(_bits(d[m]), _bits(rd))
     assert total > 0
+
+
+_FALLBACK_CHILD = r'''
+import sys; sys.path.insert(0, ".")
+import numpy as np, easysfm_amd as E, oracle
+hamming = sys.argv[1] == "hamming"
+rng = np.random.default_rng(17)
+sizes = [1500, 700, 513, 40, 1]
+sets = []
+for n in sizes:
+    if hamming:
+        x = rng.integers(0, 256, (n, 32), dtype=np.uint8)
+    else:
+        x = rng.standard_normal((n, 64)).astype(np.float32); x /= np.linalg.norm(x, axis=1, keepdims=True)
+    sets.append(x)
+for s_ in range(1, 4):                     # correspondences with set 0, so that ratio 0.6 keeps something
+    k = min(len(sets[s_]), 300)
+    if hamming:
+        flips = np.zeros((k, 32), np.uint8)
+        for r in range(k): flips[r, rng.integers(0, 32, 3)] = 1 << rng.integers(0, 8)
+        sets[s_][:k] = sets[0][:k] ^ flips
+    else:
+        sets[s_][:k] = sets[0][:k] + 0.03 * rng.standard_normal((k, 64)).astype(np.float32)
+pairs = np.array([(i, j) for i in range(len(sizes)) for j in range(len(sizes)) if i != j], np.int32)
+pm = E.PairMatcher(E.DescriptorBank(sets, E.ESFM_HAMMING if hamming else E.ESFM_L2_F32), pairs)
+ref = oracle.match_hamming if hamming else oracle.match_l2
+kept = 0
+for ratio in (0.6, 1.0):
+    res = pm.match(ratio).to_host()
+    for (i, j), (qi, ti, d) in zip(pairs, res):
+        rq, rt, rd = ref(sets[i], sets[j], ratio)
+        d, rd = np.ascontiguousarray(d, np.float32), np.ascontiguousarray(rd, np.float32)
+        assert np.array_equal(qi, rq) and np.array_equal(ti, rt) and np.array_equal(d.view(np.uint32), rd.view(np.uint32)), (i, j, ratio)
+        kept += len(rq)
+assert kept > 0
+# the switch took: the default paths leave traces the fallbacks cannot -- l2_finish_kernel's timer (K_L2_SECOND; the fallbacks time
+# their re-scan as K_L2_RESCAN), and the FP4 kernel's ratio screen (train index -2; the i8 kernel leaves every query its exact 2-NN)
+from easysfm_amd import _lib
+ctx = pm.ctx
+if hamming:
+    idx, _ = pm.knn2_screened(0.6); ctx.synchronize()
+    assert not (idx.cpu().numpy() == -2).any(), "the FP4 kernel ran"
+else:
+    ctx.synchronize(); ctx.set_kernel_timing(True); ctx.kernel_time(_lib.K_L2_RESCAN); ctx.kernel_time(_lib.K_L2_SECOND)
+    pm.match(0.6); ctx.synchronize()
+    rescans, finishes = ctx.kernel_time(_lib.K_L2_RESCAN)[1], ctx.kernel_time(_lib.K_L2_SECOND)[1]
+    ctx.set_kernel_timing(False)
+    assert rescans > 0 and finishes == 0, (rescans, finishes)
+print("ok")
+'''
+
+
+@pytest.mark.parametrize("switch,value,metric", [("ESFM_L2_PASS", "bf16x3", "l2"), ("ESFM_L2_PASS", "f32", "l2"), ("ESFM_HM_PASS", "i8", "hamming")])
+def test_fallback_kernel_families_at_small_shapes(gpu_ctx, switch, value, metric):
+    """The kernel families behind the default paths, which otherwise run only at very large train sets: ESFM_L2_PASS=bf16x3 (the
+    three-product bf16 kernel + the per-pair re-scan), ESFM_L2_PASS=f32 (the 64-wide f32 MFMA kernel + l2_rescan64_kernel) and
+    ESFM_HM_PASS=i8 (the byte-per-bit kernel and its expander).  The switches are read once per process, so each runs in a child:
+    all ordered pairs of sets of 1500, 700, 513, 40 and 1 rows -- rows beyond a 512- and a 256-row block boundary, a set smaller
+    than one 64-row tile, a train set without a second neighbour -- at ratios 0.6 and 1.0, indices and distance bit patterns
+    against the oracle."""
+    import os, subprocess, sys
+    env = dict(os.environ, **{switch: value})
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = subprocess.run([sys.executable, "-c", _FALLBACK_CHILD, metric], cwd=root, env=env, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0 and out.stdout.strip().endswith("ok"), out.stdout[-2000:] + out.stderr[-2000:]
