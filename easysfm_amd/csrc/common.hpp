@@ -80,6 +80,9 @@ struct MatchState {
     int l2_phase_pairs[2] = {0, 0};    // entries of each phase that may be non-zero
     int32_t *counters_cur = nullptr;   // the 16 counters of the last L2 call (esfm_match_last_stats / _second_pass / _flagged)
     DevBuf fin_done;   // l2_finish_kernel / hamming_fp4_kernel: per-pair arrival counters
+    DevBuf pass_done;  // l2_fused_kernel: per-pair count of finished pass blocks, the hand-over to the pair's finish workgroups (zero between calls)
+    int l2_two_launch = 0;          // esfm_ctx_set_l2_two_launch (ESFM_L2_TWO_LAUNCH at context creation): keep pass and finish as two launches
+    bool handover_pending = false;  // a fused launch has been enqueued since the failure word (counters[kHandoverFailWord]) was last read
     DevBuf knn_d2;     // exact second-best d^2 of the queries the one-product pass left uncertified (the refine pass's thresholds)
     DevBuf l2_hi;      // one-product pass: bf16(t) and bf16(-2 q) images (128 B per row each) and the two residual norms per row
     DevBuf hm_exp;     // Hamming: the FP4 form's nibble images or the i8 form's 0/1 bytes + start values (260 B per row); three-product pass: its split images
@@ -99,7 +102,7 @@ struct MatchState {
     void release()   // (every DevBuf above)
     {
         for (DevBuf *b : {&bank, &norms, &pair_tab, &knn_idx, &flagged, &counters, &pair_cnt, &pair_list, &unc_cnt[0], &unc_cnt[1], &surv_cnt[0],
-                          &surv_cnt[1], &pair_list2, &surv_list, &fin_done, &knn_d2, &l2_hi, &hm_exp, &prep_sum}) b->release();
+                          &surv_cnt[1], &pair_list2, &surv_list, &fin_done, &pass_done, &knn_d2, &l2_hi, &hm_exp, &prep_sum}) b->release();
     }
 };
 
@@ -148,6 +151,9 @@ struct KernelTimer {
     KernelTimer(esfm_ctx *ctx, int id) : c(ctx && ctx->timing ? ctx : nullptr) { if (c) c->time_begin(id); }
     ~KernelTimer() { if (c) c->time_end(); }
 };
+// match_api.cpp: after a stream synchronisation, the fused L2 launch's hand-over failure word as an error (ESFM_OK when no fused
+// launch has been enqueued since the last look: no device traffic then)
+int match_handover_check(esfm_ctx *ctx);
 inline int set_device(const esfm_ctx *ctx)
 {
     hipError_t e = hipSetDevice(ctx->device);

@@ -147,6 +147,7 @@ int esfm_ctx_create(int device, void *hip_stream, esfm_ctx **out)
     if (hipSetDevice(device) != hipSuccess) { esfm::set_error("hipSetDevice(%d) failed", device); return ESFM_ERR_NO_DEVICE; }
     esfm_ctx *c = new esfm_ctx();
     if (const char *e = getenv("ESFM_CHECK_PREPARED")) c->match.prep_check = (e[0] != '\0' && e[0] != '0') ? 1 : 0;
+    if (const char *e = getenv("ESFM_L2_TWO_LAUNCH")) c->match.l2_two_launch = (e[0] != '\0' && e[0] != '0') ? 1 : 0;
     c->device = device;
     c->num_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     if (hip_stream) {
@@ -188,7 +189,7 @@ int esfm_ctx_synchronize(esfm_ctx *ctx)
     if (!ctx) { esfm::set_error("ctx is NULL"); return ESFM_ERR_INVALID_ARG; }
     if (int rc = esfm::set_device(ctx)) return rc;
     ESFM_HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return ESFM_OK;
+    return esfm::match_handover_check(ctx);
 }
 
 void *esfm_ctx_stream(esfm_ctx *ctx) { return ctx ? reinterpret_cast<void *>(ctx->stream) : nullptr; }

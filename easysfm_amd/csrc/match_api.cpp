@@ -3,6 +3,7 @@
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
+#include <cstdlib>
 #include <vector>
 
 #include "match_kernels.hpp"
@@ -119,8 +120,10 @@ struct Pass {
     int flag_cap() const { return (int)std::min<int64_t>(plan.total_queries, (int64_t)1 << 30); }
 };
 
-// counters: [0,16) and [16,32) the two phases of the one-product path, [32,48) the other L2 passes, [48,64) scratch
-constexpr int kOtherCounters = 32, kScratchCounters = 48;
+// counters: [0,16) and [16,32) the two phases of the one-product path, [32,48) the other L2 passes, [48,64) scratch, [64] the fused
+// launch's hand-over failure word (sticky: raised by the device, cleared by match_handover_check)
+constexpr int kOtherCounters = 32, kScratchCounters = 48, kHandoverFailWord = 64, kCounterInts = 80;
+
 
 // The one-product pass's per-row operands of `desc`: bf16 images, norms, residual norms (esfm_match_prepare_dev, or a call on an
 // unprepared buffer).  Needs the context's counters.
@@ -138,6 +141,8 @@ int derive_l2_images(esfm_ctx *ctx, const float *desc, int64_t total_rows)
 // Launch 3: exact re-rank of the screen's survivors + certificate, the uncertified ones through the threshold filter, overflowed
 // chunks by brute force, ratio test + compaction (l2_finish_kernel).  Audit modes: 1 no brute force, 3 / 4 launch 3 stops after the
 // re-rank.  A prepared buffer stays prepared.
+// Match lists (outside the audit modes 3 / 4): launches 2 and 3 are ONE, l2_fused_kernel -- the finish workgroups trail the pass's
+// in the same grid (esfm_ctx_set_l2_two_launch / ESFM_X1_GRID keep the two).  The phase scheme is the same either way.
 int run_l2_one_product(const Pass &p, bool &compacted)
 {
     esfm::MatchState &m = p.m;
@@ -161,12 +166,37 @@ int run_l2_one_product(const Pass &p, bool &compacted)
         }
     }
     if (int rc = reserve_zeroed(m.fin_done, sizeof(int32_t) * (size_t)n_pairs, st)) return rc;
+    // One launch instead of two saves the fixed costs between them (about 30 us per call) and costs the finish role a third of its
+    // occupancy (two workgroups per CU instead of three): about 4 us per million queries.  Measured on all pairs of n images x 4096 rows:
+    // 3.2 M queries 1.242 against 1.286 ms, 6.3 M 2.448 against 2.472, 12.9 M 4.946 against 4.923, 25 M 9.70 against 9.63: long lists
+    // keep the two launches.
+    static const int64_t kFusedMaxQueries = [] { const char *e = getenv("ESFM_L2_FUSED_MAX_QUERIES"); return e ? (int64_t)atoll(e) : (int64_t)1 << 23; }();     // (the variable: measurement)
+    const bool one_launch = fuse && !m.l2_two_launch && esfm::l2_x1_forced_grid() <= 0 && plan.total_queries <= kFusedMaxQueries;
+    if (one_launch) { if (int rc = reserve_zeroed(m.pass_done, sizeof(int32_t) * (size_t)n_pairs, st)) return rc; }
     const int ph = m.l2_phase, oth = 1 - ph;
     int32_t *counters = m.counters.as<int32_t>();
     m.counters_cur = counters + 16 * ph;
     if (!p.prepared) {
         m.prep_desc = nullptr;          // the images below replace whatever was prepared
         if (int rc = derive_l2_images(p.ctx, desc, plan.total_rows)) return rc;
+    }
+    if (one_launch) {
+        // (timed as the pass: ESFM_K_L2_SECOND records no launch on this path)
+        esfm::KernelTimer tm(p.ctx, ESFM_K_L2_KNN);
+        if (int rc = esfm::launch_l2_fused(st, desc, m.l2_hi.ptr, plan.total_rows, m.norms.as<float>(), p.dev_tab, blk_pair_of(p.dev_tab, n_pairs),
+                                           plan.n_blocks2, pair_order_of(p.dev_tab, n_pairs), n_pairs, p.knn_idx, p.knn_dist, m.counters_cur,
+                                           m.flagged.as<int32_t>(), p.flag_cap(), m.surv_cnt[ph].as<int32_t>(), m.surv_list.ptr,
+                                           m.unc_cnt[ph].as<int32_t>(), m.pair_list2.as<int32_t>(), m.knn_d2.as<float>(), m.unc_cnt[oth].as<int32_t>(),
+                                           m.surv_cnt[oth].as<int32_t>(), m.l2_phase_pairs[oth], counters + 16 * oth, m.fin_done.as<int32_t>(),
+                                           m.pass_done.as<int32_t>(), counters + kHandoverFailWord, m.l2_audit, p.req.ratio, p.req.query_idx,
+                                           p.req.train_idx, p.req.distance, p.req.n_out))
+            return rc;
+        m.handover_pending = true;
+        m.l2_phase_pairs[oth] = 0;
+        m.l2_phase_pairs[ph] = n_pairs;
+        m.l2_phase = oth;
+        compacted = true;
+        return ESFM_OK;
     }
     {
         esfm::KernelTimer tm(p.ctx, ESFM_K_L2_KNN);
@@ -299,7 +329,7 @@ int knn2_core(esfm_ctx *ctx, esfm_metric metric, const void *desc_dev, int width
     const MatchPath path = select_path(metric, width, plan.max_nt, m.l2_audit);
     if (int rc = esfm::check_hamming_width(metric, width)) return rc;
     if (metric == ESFM_L2_F32) {
-        if (int rc = reserve_zeroed(m.counters, 64 * sizeof(int32_t), ctx->stream)) return rc;
+        if (int rc = reserve_zeroed(m.counters, kCounterInts * sizeof(int32_t), ctx->stream)) return rc;
         if ((m.l2_audit == 3 || m.l2_audit == 4) && path != MatchPath::L2_ONE_PRODUCT) {
             esfm::set_error("audit modes 3 and 4 need the one-product pass (64-float descriptors, train sets <= 65536 rows, ESFM_L2_PASS unset)");
             return ESFM_ERR_UNSUPPORTED;
@@ -447,6 +477,7 @@ int single_pair(esfm_ctx *ctx, esfm_metric metric, const void *q, int nq, const 
     int32_t n = 0;
     ESFM_HIP_TRY(esfm::copy_d2h(&n, ctx->stage_e.ptr, sizeof(int32_t), st));
     ESFM_HIP_TRY(hipStreamSynchronize(st));
+    if (int rc = esfm::match_handover_check(ctx)) return rc;
     if (n > 0) {
         ESFM_HIP_TRY(esfm::copy_d2h(o_a, ctx->stage_b.ptr, sizeof(int32_t) * (size_t)n, st));
         ESFM_HIP_TRY(esfm::copy_d2h(o_b, ctx->stage_c.ptr, sizeof(int32_t) * (size_t)n, st));
@@ -487,7 +518,8 @@ int match_pairs_host(esfm_ctx *ctx, esfm_metric metric, const void *desc_host, c
                                  ctx->stage_c.as<int32_t>(), ctx->stage_d.as<float>(), ctx->stage_e.as<int32_t>(), off2.data()))
         return rc;
     // packed on the device when the matches are less than a quarter of the slots, otherwise the arrays go back whole
-    return esfm::read_back_match_lists(ctx, n_pairs, off2.data(), nq, true, query_idx, train_idx, distance, n_out);
+    if (int rc = esfm::read_back_match_lists(ctx, n_pairs, off2.data(), nq, true, query_idx, train_idx, distance, n_out)) return rc;
+    return esfm::match_handover_check(ctx);
 }
 
 // The first n of the last L2 call's 16 counters (zeros before any L2 call); synchronises.
@@ -498,10 +530,30 @@ int read_last_counters(esfm_ctx *ctx, int32_t *dst, int n)
     if (!ctx->match.counters_cur) return ESFM_OK;
     ESFM_HIP_TRY(esfm::copy_d2h(dst, ctx->match.counters_cur, sizeof(int32_t) * (size_t)n, ctx->stream));
     ESFM_HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return ESFM_OK;
+    return esfm::match_handover_check(ctx);
 }
 
 }  // namespace
+
+// After a synchronisation of the stream: did a finish workgroup of a fused launch give up waiting for its pair's pass blocks?  (Never
+// seen; the wait is bounded so that a broken launch cannot hang the device.)  The call's lists are incomplete then, and its
+// hand-over and arrival counters are left dirty: they are cleared here, and the caller gets an error.
+int esfm::match_handover_check(esfm_ctx *ctx)
+{
+    esfm::MatchState &m = ctx->match;
+    if (!m.handover_pending || !m.counters.ptr) return ESFM_OK;
+    int32_t w = 0;
+    ESFM_HIP_TRY(esfm::copy_d2h(&w, m.counters.as<int32_t>() + kHandoverFailWord, sizeof(w), ctx->stream));
+    ESFM_HIP_TRY(hipStreamSynchronize(ctx->stream));
+    m.handover_pending = false;
+    if (w == 0) return ESFM_OK;
+    ESFM_HIP_TRY(hipMemsetAsync(m.counters.as<int32_t>() + kHandoverFailWord, 0, sizeof(int32_t), ctx->stream));
+    if (m.pass_done.ptr) ESFM_HIP_TRY(hipMemsetAsync(m.pass_done.ptr, 0, m.pass_done.cap, ctx->stream));
+    if (m.fin_done.ptr) ESFM_HIP_TRY(hipMemsetAsync(m.fin_done.ptr, 0, m.fin_done.cap, ctx->stream));
+    ESFM_HIP_TRY(hipStreamSynchronize(ctx->stream));
+    esfm::set_error("matcher: a finish workgroup of the fused L2 launch timed out waiting for its pair's distance-pass blocks; the last match lists are incomplete");
+    return ESFM_ERR_HIP;
+}
 
 extern "C" {
 
@@ -605,7 +657,7 @@ int esfm_match_prepare_dev(esfm_ctx *ctx, esfm_metric metric, const void *desc_d
     // not fit the position code re-derives (L2: its fallback writes its own operands; Hamming: the i8 form's byte image)
     const MatchPath path = select_path(metric, width, 0, 0);
     if (path == MatchPath::L2_ONE_PRODUCT) {
-        if (int rc = reserve_zeroed(m.counters, 64 * sizeof(int32_t), st)) return rc;
+        if (int rc = reserve_zeroed(m.counters, kCounterInts * sizeof(int32_t), st)) return rc;
         if (int rc = derive_l2_images(ctx, static_cast<const float *>(desc_dev), total_rows)) return rc;
     } else if (path == MatchPath::HM_FP4 || path == MatchPath::HM_I8) {
         if (int rc = m.hm_exp.reserve(esfm::hamming_expanded_bytes(width, total_rows))) return rc;
@@ -682,6 +734,13 @@ int esfm_ctx_set_l2_audit(esfm_ctx *ctx, int mode)
 {
     if (!ctx || mode < 0 || mode > 4) { esfm::set_error("esfm_ctx_set_l2_audit: bad arguments"); return ESFM_ERR_INVALID_ARG; }
     ctx->match.l2_audit = mode;
+    return ESFM_OK;
+}
+
+int esfm_ctx_set_l2_two_launch(esfm_ctx *ctx, int enable)
+{
+    if (!ctx) { esfm::set_error("ctx is NULL"); return ESFM_ERR_INVALID_ARG; }
+    ctx->match.l2_two_launch = enable ? 1 : 0;
     return ESFM_OK;
 }
 

@@ -338,7 +338,8 @@ __device__ __forceinline__ void ratio_compact_pair(const PairDesc &pd, const int
 // per query it does not store and this stage does not read -- 19.6 of 19.7 MB per step on the metric's workload).  A sweep of
 // THREADS * 16 queries: the survivors' rows set bits in an LDS bitmap, a thread looks at its 16 consecutive queries' bits and reads
 // the records of the set ones; order and compaction as above.
-template <int THREADS>
+// COH: the survivor entries too were written by other workgroups of this launch (l2_fused_kernel): their rows are read with ld_coh_f.
+template <int THREADS, bool COH = false>
 __device__ __forceinline__ void ratio_compact_pair_sparse(const PairDesc &pd, const float4 *__restrict__ ent, int nsv,
                                                           const int32_t *__restrict__ knn_idx, const float *__restrict__ knn_dist,
                                                           double ratio, int32_t *__restrict__ query_idx, int32_t *__restrict__ train_idx,
@@ -352,7 +353,8 @@ __device__ __forceinline__ void ratio_compact_pair_sparse(const PairDesc &pd, co
         for (int w = tid; w < THREADS / 2; w += THREADS) s_bits[w] = 0u;
         __syncthreads();
         for (int k = tid; k < nsv; k += THREADS) {
-            const uint32_t r = (uint32_t)(__float_as_int(ent[3 * (size_t)k + 2].x) - q0);
+            const float rowf = COH ? ld_coh_f(reinterpret_cast<const float *>(ent) + 12 * (size_t)k + 8) : ent[3 * (size_t)k + 2].x;
+            const uint32_t r = (uint32_t)(__float_as_int(rowf) - q0);
             if (r < (uint32_t)(THREADS * PER)) atomicOr(&s_bits[r >> 5], 1u << (r & 31));
         }
         __syncthreads();

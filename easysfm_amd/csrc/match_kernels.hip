@@ -4,6 +4,7 @@
 // have files of their own: match_l2_bf16x3.hip (which also writes this pass's images), match_l2_f32.hip, match_hamming.hip,
 // match_lists.hip; match_device.hpp is what all of them share.
 #include "match_kernels.hpp"
+#include "match_plan.hpp"              // fused_grid_of
 #include "match_device.hpp"
 #include "l2x1_segment_gfx950.inc"     // ESFM_L2X1_SEGMENT_ASM, ESFM_L2X1_KEEP: the one-product pass's main loop (gen_l2x1_segment_asm.py)
 
@@ -57,25 +58,41 @@ __device__ __forceinline__ float wave_max_dpp(float x)
     const float c = __int_as_float(__builtin_amdgcn_readlane(xi, 32)), d = __int_as_float(__builtin_amdgcn_readlane(xi, 48));
     return fmaxf(fmaxf(a, b), fmaxf(c, d));
 }
+// A 16-byte piece of a survivor entry.  COH: a write-through store (`sc1`), for entries that a finish workgroup of the SAME launch
+// reads (l2_fused_kernel); the caller waits for it (s_waitcnt vmcnt(0)) before it counts its block.
+template <bool COH>
+__device__ __forceinline__ void st_entry(float4 *p, float4 v)
+{
+    if (COH) {
+        const u32x4 w = {__float_as_uint(v.x), __float_as_uint(v.y), __float_as_uint(v.z), __float_as_uint(v.w)};
+        asm volatile("global_store_dwordx4 %0, %1, off sc1" : : "v"(p), "v"(w) : "memory");
+    } else {
+        *p = v;
+    }
+}
 // One unit of the one-product pass's work: 512 queries (block qblk) of pair pi against the pair's whole train set.
 struct X1Item { int32_t q_row0, nq, t_row0, nt; int64_t out_off; int32_t pi, qblk; };
 
-__global__ __launch_bounds__(256, 2) void l2_knn_bf16x1_kernel(const float *__restrict__ desc, const u32x4 *__restrict__ hi_t,
-                                                               const u32x4 *__restrict__ hi_q, const float *__restrict__ norms,
-                                                               const float *__restrict__ rho_t, const float *__restrict__ rho_q,
-                                                               const float2 *__restrict__ blkmax,
-                                                               const PairDesc *__restrict__ pairs, const int32_t *__restrict__ blk_pair, int n_blocks,
-                                                               int32_t *__restrict__ knn_idx, float *__restrict__ knn_dist,
-                                                               int32_t *__restrict__ counters, int flag_cap,
-                                                               int32_t *__restrict__ surv_cnt, float4 *__restrict__ surv_list,
-                                                               double ratio2m, int markers, int32_t *__restrict__ rejected,
-                                                               int32_t *__restrict__ zero_a, int32_t *__restrict__ zero_b, int zero_n,
-                                                               int32_t *__restrict__ zero_counters)
+// The pass's body, shared by l2_knn_bf16x1_kernel (bid = blockIdx.x, G = gridDim.x) and by the pass role of l2_fused_kernel (FUSED:
+// G = n_blocks, one block per workgroup; the survivor entries leave through write-through stores and the block ends by adding 1 to
+// pass_done[pair] -- the hand-over to the pair's finish workgroups of the same launch, see l2_fused_kernel).
+template <bool FUSED>
+__device__ __forceinline__ void l2_knn_bf16x1_body(const int bid, const int G, const float *__restrict__ desc, const u32x4 *__restrict__ hi_t,
+                                                   const u32x4 *__restrict__ hi_q, const float *__restrict__ norms,
+                                                   const float *__restrict__ rho_t, const float *__restrict__ rho_q,
+                                                   const float2 *__restrict__ blkmax,
+                                                   const PairDesc *__restrict__ pairs, const int32_t *__restrict__ blk_pair, int n_blocks,
+                                                   int32_t *__restrict__ knn_idx, float *__restrict__ knn_dist,
+                                                   int32_t *__restrict__ counters, int flag_cap,
+                                                   int32_t *__restrict__ surv_cnt, float4 *__restrict__ surv_list,
+                                                   double ratio2m, int markers, int32_t *__restrict__ rejected,
+                                                   int32_t *__restrict__ zero_a, int32_t *__restrict__ zero_b, int zero_n,
+                                                   int32_t *__restrict__ zero_counters, int32_t *__restrict__ pass_done)
 {
     // The per-pair list counters and the global counters exist twice: this launch fills one phase and zeroes the other for the NEXT
     // call (whose finish kernel needs them immutable while it runs) -- no memset launch, no zeroing pass in front of this one.
-    if (threadIdx.x == 0) for (int e = blockIdx.x; e < zero_n; e += gridDim.x) { zero_a[e] = 0; zero_b[e] = 0; }
-    if (blockIdx.x == 0 && threadIdx.x < 16) zero_counters[threadIdx.x] = 0;
+    if (threadIdx.x == 0) for (int e = bid; e < zero_n; e += G) { zero_a[e] = 0; zero_b[e] = 0; }
+    if (bid == 0 && threadIdx.x < 16) zero_counters[threadIdx.x] = 0;
     constexpr int TT = ESFM_L2X1_TT, NS = ESFM_L2X1_SETS, K = ESFM_L2X1_KEEP, RING = ESFM_L2X1_RING;
     constexpr int QB = 128 * NS, HS = 8;                         // HS: 16-B slots per row of the hi images
     constexpr int TILE_BYTES = TT * HS * 16;
@@ -111,9 +128,8 @@ __global__ __launch_bounds__(256, 2) void l2_knn_bf16x1_kernel(const float *__re
     // was hidden already; what the static schedule adds is the last round's imbalance.  (ESFM_X1_GRID sets G for measurements; what
     // the restructuring did buy is the short set-up itself: a block -> pair table instead of nine dependent loads of a binary search,
     // maxima from a per-256-row table, 5 % on the launch.)
-    const int G = gridDim.x;
     auto lb_of = [&](int k) -> int {
-        const long long v = (long long)blockIdx.x + (long long)k * G;
+        const long long v = (long long)bid + (long long)k * G;
         return v < (long long)n_blocks ? xcd_remap((int)v, n_blocks) : -1;
     };
     auto make_item = [&](int lb, int pi) -> X1Item {
@@ -326,15 +342,37 @@ __global__ __launch_bounds__(256, 2) void l2_knn_bf16x1_kernel(const float *__re
 #pragma unroll
             for (int s = 0; s < NS; ++s) {
                 if (myslot[s] >= 0) {
-                    ent[3 * myslot[s] + h] = make_float4(keys[s][0], keys[s][1], keys[s][2], keys[s][3]);
-                    if (h == 0) ent[3 * myslot[s] + 2] = make_float4(__int_as_float(qbase + 32 * s + j), qn_s[s], e1_s[s], 0.f);
+                    st_entry<FUSED>(ent + 3 * myslot[s] + h, make_float4(keys[s][0], keys[s][1], keys[s][2], keys[s][3]));
+                    if (h == 0) st_entry<FUSED>(ent + 3 * myslot[s] + 2, make_float4(__int_as_float(qbase + 32 * s + j), qn_s[s], e1_s[s], 0.f));
                 }
             }
+        }
+        if (FUSED) {
+            // hand-over: every wave's entries (write-through) and the count's atomic are acknowledged, then the block is counted
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __syncthreads();
+            if (tid == 0) __hip_atomic_fetch_add(&pass_done[pi], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
         if (!more) break;
         __syncthreads();                  // the next item's norms, maxima and query norms are in LDS, its first tile has landed
         cur = nxt; nxt = nn; lb_nn = lb_3; pi_nn = pi_3;
     }
+}
+
+__global__ __launch_bounds__(256, 2) void l2_knn_bf16x1_kernel(const float *__restrict__ desc, const u32x4 *__restrict__ hi_t,
+                                                               const u32x4 *__restrict__ hi_q, const float *__restrict__ norms,
+                                                               const float *__restrict__ rho_t, const float *__restrict__ rho_q,
+                                                               const float2 *__restrict__ blkmax,
+                                                               const PairDesc *__restrict__ pairs, const int32_t *__restrict__ blk_pair, int n_blocks,
+                                                               int32_t *__restrict__ knn_idx, float *__restrict__ knn_dist,
+                                                               int32_t *__restrict__ counters, int flag_cap,
+                                                               int32_t *__restrict__ surv_cnt, float4 *__restrict__ surv_list,
+                                                               double ratio2m, int markers, int32_t *__restrict__ rejected,
+                                                               int32_t *__restrict__ zero_a, int32_t *__restrict__ zero_b, int zero_n,
+                                                               int32_t *__restrict__ zero_counters)
+{
+    l2_knn_bf16x1_body<false>(blockIdx.x, gridDim.x, desc, hi_t, hi_q, norms, rho_t, rho_q, blkmax, pairs, blk_pair, n_blocks, knn_idx, knn_dist, counters,
+                              flag_cap, surv_cnt, surv_list, ratio2m, markers, rejected, zero_a, zero_b, zero_n, zero_counters, nullptr);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -437,6 +475,7 @@ __device__ __forceinline__ void finish_bruteforce_chunk(const float *__restrict_
 // second-best d^2 as the filter's threshold.
 struct FinRerankArgs {
     const float4 *ent;                 // the pair's survivor entries
+    __amdgpu_buffer_rsrc_t ersrc;      // ... as a buffer (COH: the entries were written by pass blocks of this launch, read with `sc1` loads)
     int nsv, per;                      // ... their number; entries per virtual set (<= kFinQV)
     PairDesc pd; int p;
     __amdgpu_buffer_rsrc_t frsrc_t, frsrc_q;   // buffer descriptors of the train / query set's float rows (rows past a set read as zeros)
@@ -458,7 +497,7 @@ constexpr int kFinPend = 112;        // pending queries of a wave (16 virtual se
 // nor out of groups afterwards is parked in the wave's LDS list (FinPending); the later rounds are run over that list, seven
 // queries at a time, each round re-packing what is still undecided.  A query's arithmetic depends on nothing but its own state, so
 // the results are bit-identical; on the metric's workload (one set per wave, 1.6 rounds) nothing changes.
-template <bool SINGLE>
+template <bool SINGLE, bool COH>
 __device__ __forceinline__ void finish_rerank_wave(const FinRerankArgs &A, int v0, int vstride, int nvs, FinPending *pend)
 {
     typedef unsigned long long u64;
@@ -541,9 +580,13 @@ __device__ __forceinline__ void finish_rerank_wave(const FinRerankArgs &A, int v
         ord = o;
     };
     auto key_number = [&](int x) {           // key number x of the query's eight (a chain of selects: a register array indexed by data would go to scratch)
-        float k = a_[0];
-        k = x == 1 ? a_[1] : k; k = x == 2 ? a_[2] : k; k = x == 3 ? a_[3] : k;
-        k = x == 4 ? b_[0] : k; k = x == 5 ? b_[1] : k; k = x == 6 ? b_[2] : k; k = x == 7 ? b_[3] : k;
+        // (through opaque copies: hipcc otherwise folds the chain into an indexed load from a stack copy of the keys, the kernel's only
+        // scratch memory -- which in l2_fused_kernel every pass workgroup would be given as well)
+        float k0 = a_[0], k1 = a_[1], k2 = a_[2], k3 = a_[3], k4 = b_[0], k5 = b_[1], k6 = b_[2], k7 = b_[3];
+        asm volatile("" : "+v"(k0), "+v"(k1), "+v"(k2), "+v"(k3), "+v"(k4), "+v"(k5), "+v"(k6), "+v"(k7));
+        float k = k0;
+        k = x == 1 ? k1 : k; k = x == 2 ? k2 : k; k = x == 3 ? k3 : k;
+        k = x == 4 ? k4 : k; k = x == 5 ? k5 : k; k = x == 6 ? k6 : k; k = x == 7 ? k7 : k;
         return k;
     };
     // rank_group from the stored order: the same (key, row0, nkey)
@@ -709,6 +752,10 @@ __device__ __forceinline__ void finish_rerank_wave(const FinRerankArgs &A, int v
     const int eq = lane >> 3 < QV ? lane >> 3 : QV - 1;
     auto entry_of = [&](int v, int part) {
         const int e = v * A.per + eq;
+        if (COH) {       // (aux 16: sc1 -- served past this XCD's L2; entries past the pair's count read as zeros)
+            const u32x4 w = __builtin_amdgcn_raw_buffer_load_b128(A.ersrc, (v < nvs && e < A.nsv) ? e * 48 + part * 16 : 0x7fffffff, 0, 16);
+            return make_float4(__uint_as_float(w[0]), __uint_as_float(w[1]), __uint_as_float(w[2]), __uint_as_float(w[3]));
+        }
         return (v < nvs && e < A.nsv) ? A.ent[3 * (size_t)e + part] : make_float4(0.f, 0.f, 0.f, 0.f);
     };
     int npend = 0;
@@ -758,8 +805,10 @@ __device__ __forceinline__ void finish_rerank_wave(const FinRerankArgs &A, int v
 // for every fragment before its MFMA -- 6.5 us per step.)  A function of its OWN, not inlined: inside l2_finish_kernel's body the
 // register allocator -- 168 registers for three workgroups per CU, cut for the re-rank -- kept the operands of this loop in scratch
 // memory and re-loaded them in front of every matrix instruction (6 us per step on M-SURF-4k-hard, round 5).
-__device__ __noinline__ void finish_filter_sweep(const u32x4 *hi_rows /* the train set's bf16 images */, const float *tn /* its |row|^2 */, int st0, int st1, int nt_, int j,
-                                                 int h, bool two, const bf16x8 (&bq_)[2][4], const float (&thr2_)[2], int *s_nhit, int *s_h)
+// (l2_fused_kernel's finish role, cut for 256 registers, takes the body INLINE: its operands then never pass through scratch memory,
+// which the fused kernel's pass role must not be made to allocate.)
+__device__ __forceinline__ void finish_filter_sweep_body(const u32x4 *hi_rows /* the train set's bf16 images */, const float *tn /* its |row|^2 */, int st0, int st1, int nt_, int j,
+                                                         int h, bool two, const bf16x8 (&bq_)[2][4], const float (&thr2_)[2], int *s_nhit, int *s_h)
 {
     constexpr int HS = 8, CAP = kFinCap;
     constexpr float kBig = 3.0e38f;
@@ -844,22 +893,41 @@ __device__ __noinline__ void finish_filter_sweep(const u32x4 *hi_rows /* the tra
     }
 }
 
+__device__ __noinline__ void finish_filter_sweep(const u32x4 *hi_rows, const float *tn, int st0, int st1, int nt_, int j, int h, bool two,
+                                                 const bf16x8 (&bq_)[2][4], const float (&thr2_)[2], int *s_nhit, int *s_h)
+{
+    finish_filter_sweep_body(hi_rows, tn, st0, st1, nt_, j, h, two, bq_, thr2_, s_nhit, s_h);
+}
+
 constexpr size_t kFinTailLds = 8192 + 8192 + (size_t)kFinWaves * 32 * 2 * 8;        // the buffers of stages (2) - (4)
 constexpr size_t kFinLdsBytes = kFinTailLds + (size_t)kFinWaves * kFinPend * sizeof(FinPending);   // + the re-rank's parked queries (its rows live in registers)
 
-constexpr int kFinOcc = 3;        // workgroups per CU the register budget is cut for: 3 = 168 registers, no spill in the re-rank (64.5 us per step;
-                                  // 1: 342 registers, 113 us; 2: 76 us; 4: 128 registers, 42 spills in the re-rank, 80 - 87 us; the query rows parked in LDS: 66 / 84 us at 3 / 4)
-__global__ __launch_bounds__(kFinThreads, kFinOcc) void l2_finish_kernel(const float *__restrict__ desc, const u32x4 *__restrict__ hi_t,
-                                                                const u32x4 *__restrict__ hi_q, const float *__restrict__ norms,
-                                                                const float *__restrict__ rho_t, const float *__restrict__ rho_q,
-                                                                const PairDesc *__restrict__ pairs, const int32_t *__restrict__ pair_order, int n_pairs, int S,
-                                                                const int32_t *__restrict__ surv_cnt, const float4 *__restrict__ surv_list,
-                                                                int32_t *__restrict__ unc_cnt, int32_t *__restrict__ unc_list, float *__restrict__ knn_d2,
-                                                                int32_t *__restrict__ knn_idx, float *__restrict__ knn_dist,
-                                                                int32_t *__restrict__ counters, int32_t *__restrict__ flagged, int flag_cap,
-                                                                int32_t *__restrict__ done, int audit, int do_ratio, double ratio, double ratio2m,
-                                                                int32_t *__restrict__ query_idx, int32_t *__restrict__ train_idx,
-                                                                float *__restrict__ distance, int32_t *__restrict__ n_out)
+// the small per-workgroup variables of the finish stages (static LDS in l2_finish_kernel; behind the dynamic part in l2_fused_kernel,
+// whose pass role wants the ring at LDS address 0 as in its own kernel)
+struct FinShared {
+    int s_nhit, s_last;
+    float s_red[2 * kFinWaves];
+    int s_qrows[64];
+    unsigned long long s_best[2][64];            // stage 2: the running (distance, index) keys of a sweep's queries
+    int s_wave[kFinWaves], s_base;
+};
+constexpr long long kHandoverTicks = 200000000;  // the fused finish role's bound on its wait for the pair's pass blocks: 2 s of the 100-MHz wall clock
+
+// The finish stages' body, shared by l2_finish_kernel (fb = blockIdx.x of nfb = gridDim.x) and the finish role of l2_fused_kernel
+// (FUSED: fb counts from the role's first workgroup; the pair's pass blocks run in the SAME launch, see the wait below).
+template <bool FUSED>
+__device__ __forceinline__ void l2_finish_body(const int fb, const int nfb, FinShared &sh, const float *__restrict__ desc, const u32x4 *__restrict__ hi_t,
+                                               const u32x4 *__restrict__ hi_q, const float *__restrict__ norms,
+                                               const float *__restrict__ rho_t, const float *__restrict__ rho_q,
+                                               const PairDesc *__restrict__ pairs, const int32_t *__restrict__ pair_order, int n_pairs, int S,
+                                               const int32_t *surv_cnt, const float4 *surv_list,
+                                               int32_t *__restrict__ unc_cnt, int32_t *__restrict__ unc_list, float *__restrict__ knn_d2,
+                                               int32_t *__restrict__ knn_idx, float *__restrict__ knn_dist,
+                                               int32_t *__restrict__ counters, int32_t *__restrict__ flagged, int flag_cap,
+                                               int32_t *__restrict__ done, int audit, int do_ratio, double ratio, double ratio2m,
+                                               int32_t *__restrict__ query_idx, int32_t *__restrict__ train_idx,
+                                               float *__restrict__ distance, int32_t *__restrict__ n_out,
+                                               int32_t *pass_done, int32_t *handover_fail)
 {
     constexpr int CAP = kFinCap, HS = 8, NW = kFinWaves;
     constexpr float kBig = 3.0e38f;
@@ -869,30 +937,60 @@ __global__ __launch_bounds__(kFinThreads, kFinOcc) void l2_finish_kernel(const f
     int *s_h = reinterpret_cast<int *>(fin_smem);                             // [CAP] hits of the sweep: (query slot in the sweep) << 21 | train row
     float4 (*s_q)[16] = reinterpret_cast<float4 (*)[16]>(fin_smem + 8192);   // [32][16]
     unsigned long long (*s_keys)[32][2] = reinterpret_cast<unsigned long long (*)[32][2]>(fin_smem + 8192 + 8192);   // [NW][32][2]
-    __shared__ int s_nhit, s_last;
-    __shared__ float s_red[2 * NW];
-    __shared__ int s_qrows[64];
-    __shared__ unsigned long long s_best[2][64];                              // stage 2: the running (distance, index) keys of a sweep's queries
-
-    __shared__ int s_wave[NW], s_base;
+    int &s_nhit = sh.s_nhit, &s_last = sh.s_last, &s_base = sh.s_base;
+    float (&s_red)[2 * NW] = sh.s_red;
+    int (&s_qrows)[64] = sh.s_qrows, (&s_wave)[NW] = sh.s_wave;
+    unsigned long long (&s_best)[2][64] = sh.s_best;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 31, h = lane >> 5;
     // Blocks are dispatched round-robin over the XCDs; xcd_remap gives every XCD a contiguous range of logical blocks, and the logical
     // order is pair-major over the pairs SORTED BY TRAIN SET: the S workgroups of a pair and the pairs of one train set run on one
     // XCD, whose L2 (4 MiB) then holds the one or two train sets their row fetches go to -- the re-rank is bound by those fetches
     // (51 k survivors x 9 rows x 256 B per step on the metric's workload).
-    const int lb = xcd_remap(blockIdx.x, gridDim.x);
+    const int lb = xcd_remap(fb, nfb);
     const int sl = lb % S, p = pair_order[lb / S];
     const PairDesc pd = pairs[p];
     const int nq = pd.nq, nt = pd.nt;
 
+    if (FUSED) {
+        // ---- (0) the HAND-OVER: this pair's pass blocks run in this launch; each adds 1 to pass_done[p] once its survivor entries
+        // (write-through stores) and its surv_cnt add are acknowledged.  One thread polls until all of the pair's 512-query blocks
+        // are counted (a pair without queries has none: ready at once).  Why no wait can stall the launch:
+        //   * every pass block has a lower workgroup id than every finish workgroup (the grid is [pass | padding | finish]);
+        //   * within an XCD workgroups start in id order, so a finish workgroup starts only after ALL of its XCD's pass blocks have
+        //     started; a waiting finish workgroup therefore never holds a slot that an unstarted pass block of its XCD needs;
+        //   * pass blocks wait for nothing, and the awaited ones sit on their own XCDs, each of which has started its pass blocks
+        //     before its finish workgroups for the same reason -- or starts them as soon as slots free up, which waiting finish
+        //     workgroups of OTHER XCDs cannot prevent;
+        //   * so every awaited pass block is running or done, or will start without this workgroup's help.
+        // The spin is still bounded by wall clock: on expiry the workgroup raises the context's failure word and leaves; the API
+        // turns the word into an error at its next synchronising call (as chol_sparse_kernel does for a lost flag).
+        // What the pass wrote is read past this XCD's L2 from here on (surv_cnt: ld_coh_i; the entries: `sc1` loads).
+        if (tid == 0) {
+            const int need = (nq + l2x1_query_block_c - 1) / l2x1_query_block_c;
+            int ok = 1;
+            if (need > 0) {
+                const long long t0 = wall_clock64();
+                while (ld_coh_i(pass_done + p) != need) {
+                    __builtin_amdgcn_s_sleep(8);
+                    if (wall_clock64() - t0 > kHandoverTicks) { st_coh_i(handover_fail, 1); ok = 0; break; }
+                }
+            }
+            s_last = ok;
+        }
+        __syncthreads();
+        if (!s_last) return;       // (s_last is next written behind the arrival's barrier)
+    }
+    const int nsv_pair = min(FUSED ? ld_coh_i(surv_cnt + p) : surv_cnt[p], nq);
+
     // ---- (1) re-rank of the survivors: virtual sets dealt out over the pair's S x NW waves
     {
         FinRerankArgs A;
-        A.nsv = min(surv_cnt[p], nq);
+        A.nsv = nsv_pair;
         // the survivors dealt out EVENLY over the pair's S x NW waves while a wave's share fits one virtual set (a set costs its
         // latency chain whatever it holds: 25 sets of seven for 20 waves made five of them -- and their workgroups -- last twice as long)
         A.per = max(1, min(kFinQV, (A.nsv + S * NW - 1) / (S * NW)));
         A.ent = surv_list + 3 * (size_t)pd.out_off;
+        A.ersrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float4 *>(A.ent), 0, A.nsv * 48, 0x00020000);
         A.pd = pd; A.p = p;
         A.frsrc_t = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(desc + (size_t)pd.t_row0 * 64), 0, nt * 256, 0x00020000);   // rows past the set read as zeros, no memory access
         A.frsrc_q = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(desc + (size_t)pd.q_row0 * 64), 0, nq * 256, 0x00020000);
@@ -902,9 +1000,9 @@ __global__ __launch_bounds__(kFinThreads, kFinOcc) void l2_finish_kernel(const f
         A.counters = counters; A.audit_unc = audit == 3 ? flagged : nullptr; A.audit_rej = audit == 4 ? flagged : nullptr; A.flag_cap = flag_cap;
         const int nvs = (A.nsv + A.per - 1) / A.per;
         if (sl * NW + wave + S * NW >= nvs)      // (wave-uniform) at most one virtual set for this wave
-            finish_rerank_wave<true>(A, sl * NW + wave, S * NW, nvs, nullptr);
+            finish_rerank_wave<true, FUSED>(A, sl * NW + wave, S * NW, nvs, nullptr);
         else
-            finish_rerank_wave<false>(A, sl * NW + wave, S * NW, nvs, reinterpret_cast<FinPending *>(fin_smem + kFinTailLds) + wave * kFinPend);
+            finish_rerank_wave<false, FUSED>(A, sl * NW + wave, S * NW, nvs, reinterpret_cast<FinPending *>(fin_smem + kFinTailLds) + wave * kFinPend);
     }
     // (Round 5, measured and not kept: every workgroup settling ITS OWN uncertified queries by exact brute force right here instead
     // of leaving them to the pair's last workgroup -- M-SURF-4k-hard: 16 695 such queries per step, the finish kernel 1.43 -> 1.71 ms:
@@ -920,6 +1018,7 @@ __global__ __launch_bounds__(kFinThreads, kFinOcc) void l2_finish_kernel(const f
         if (!s_last) return;
         if (tid == 0) __hip_atomic_store(&done[p], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // (everybody has arrived: nobody touches it again in this launch)
     }
+    if (FUSED && tid == 0) st_coh_i(pass_done + p, 0);       // (... nor the hand-over counter: every slice has seen it full)
     if (audit == 3 || audit == 4) return;          // the first pass alone: its answers, its own lists
 
     // ---- (2), (3): the pair's uncertified queries, chunks of 32, the whole train set by this workgroup's four waves
@@ -1000,7 +1099,8 @@ __global__ __launch_bounds__(kFinThreads, kFinOcc) void l2_finish_kernel(const f
                 s_best[1][tid] = key_of(ld_coh_f(knn_dist + o + 1), ld_coh_i(knn_idx + o + 1));
             }
             __syncthreads();
-            finish_filter_sweep(hi_t + (size_t)pd.t_row0 * HS, tn, st0, st1, nt, j, h, nqc > 32, bq, thr2, &s_nhit, s_h);
+            if (FUSED) finish_filter_sweep_body(hi_t + (size_t)pd.t_row0 * HS, tn, st0, st1, nt, j, h, nqc > 32, bq, thr2, &s_nhit, s_h);
+            else finish_filter_sweep(hi_t + (size_t)pd.t_row0 * HS, tn, st0, st1, nt, j, h, nqc > 32, bq, thr2, &s_nhit, s_h);
             __syncthreads();
             const int nhit = s_nhit;
             if (nhit <= CAP) {
@@ -1065,10 +1165,67 @@ __global__ __launch_bounds__(kFinThreads, kFinOcc) void l2_finish_kernel(const f
     }
     if (do_ratio) {
         if (ratio2m < 1.0e300)            // the screen ran: only its survivors have records
-            ratio_compact_pair_sparse<kFinThreads>(pd, surv_list + 3 * (size_t)pd.out_off, min(surv_cnt[p], nq), knn_idx, knn_dist, ratio, query_idx, train_idx,
+            ratio_compact_pair_sparse<kFinThreads, FUSED>(pd, surv_list + 3 * (size_t)pd.out_off, nsv_pair, knn_idx, knn_dist, ratio, query_idx, train_idx,
                                                    distance, n_out + p, reinterpret_cast<uint32_t *>(fin_smem), s_wave, &s_base);
         else
             ratio_compact_pair<kFinThreads, 4096 / kFinThreads, true>(pd, knn_idx, knn_dist, ratio, query_idx, train_idx, distance, n_out + p, s_wave, &s_base);
+    }
+}
+
+constexpr int kFinOcc = 3;        // workgroups per CU the register budget is cut for: 3 = 168 registers, no spill in the re-rank (64.5 us per step;
+                                  // 1: 342 registers, 113 us; 2: 76 us; 4: 128 registers, 42 spills in the re-rank, 80 - 87 us; the query rows parked in LDS: 66 / 84 us at 3 / 4)
+__global__ __launch_bounds__(kFinThreads, kFinOcc) void l2_finish_kernel(const float *__restrict__ desc, const u32x4 *__restrict__ hi_t,
+                                                                const u32x4 *__restrict__ hi_q, const float *__restrict__ norms,
+                                                                const float *__restrict__ rho_t, const float *__restrict__ rho_q,
+                                                                const PairDesc *__restrict__ pairs, const int32_t *__restrict__ pair_order, int n_pairs, int S,
+                                                                const int32_t *__restrict__ surv_cnt, const float4 *__restrict__ surv_list,
+                                                                int32_t *__restrict__ unc_cnt, int32_t *__restrict__ unc_list, float *__restrict__ knn_d2,
+                                                                int32_t *__restrict__ knn_idx, float *__restrict__ knn_dist,
+                                                                int32_t *__restrict__ counters, int32_t *__restrict__ flagged, int flag_cap,
+                                                                int32_t *__restrict__ done, int audit, int do_ratio, double ratio, double ratio2m,
+                                                                int32_t *__restrict__ query_idx, int32_t *__restrict__ train_idx,
+                                                                float *__restrict__ distance, int32_t *__restrict__ n_out)
+{
+    __shared__ FinShared sh;
+    l2_finish_body<false>(blockIdx.x, gridDim.x, sh, desc, hi_t, hi_q, norms, rho_t, rho_q, pairs, pair_order, n_pairs, S, surv_cnt, surv_list, unc_cnt, unc_list,
+                          knn_d2, knn_idx, knn_dist, counters, flagged, flag_cap, done, audit, do_ratio, ratio, ratio2m, query_idx, train_idx, distance, n_out,
+                          nullptr, nullptr);
+}
+
+// ---------------------------------------------------------------------------------------------
+// The pass and the finish stages in ONE launch (the match-list path outside the audit modes 3 / 4).  Grid:
+//     [ n_blocks pass blocks, padded to n_pad = a multiple of 8 | n_pairs * S finish workgroups ]
+// Workgroups below n_blocks run l2_knn_bf16x1_body, one 512-query block each; padding workgroups return at once; the others run
+// l2_finish_body, which waits for ITS pair's pass blocks only (the hand-over, stage (0) there).  Each role keeps its own xcd_remap
+// numbering over its own range, and because n_pad is a multiple of 8 a finish workgroup's XCD is (its index in the role) % 8 as in
+// a launch of its own: a pair's finish workgroups land where the pair order (sorted by train set) wants them.  The hardware's
+// dispatcher starts the finish workgroups as the pass's last round frees slots, instead of after the whole grid has drained and a
+// second launch has come up; the finish role runs at this kernel's two workgroups per CU.
+__global__ __launch_bounds__(256, 2) void l2_fused_kernel(const float *__restrict__ desc, const u32x4 *__restrict__ hi_t,
+                                                          const u32x4 *__restrict__ hi_q, const float *__restrict__ norms,
+                                                          const float *__restrict__ rho_t, const float *__restrict__ rho_q,
+                                                          const float2 *__restrict__ blkmax,
+                                                          const PairDesc *__restrict__ pairs, const int32_t *__restrict__ blk_pair, int n_blocks, int n_pad,
+                                                          const int32_t *__restrict__ pair_order, int n_pairs, int S,
+                                                          int32_t *knn_idx, float *knn_dist, int32_t *counters, int32_t *flagged, int flag_cap,
+                                                          int32_t *surv_cnt, float4 *surv_list,
+                                                          int32_t *unc_cnt, int32_t *unc_list, float *knn_d2,
+                                                          int32_t *zero_a, int32_t *zero_b, int zero_n, int32_t *zero_counters,
+                                                          int32_t *done, int32_t *pass_done, int32_t *handover_fail,
+                                                          int audit, double ratio, double ratio2m,
+                                                          int32_t *query_idx, int32_t *train_idx, float *distance, int32_t *n_out)
+{
+    static_assert(kFinThreads == 256, "both roles run 256 threads");
+    extern __shared__ __attribute__((aligned(16))) char fused_smem[];
+    const int bid = blockIdx.x;
+    if (bid < n_pad) {
+        if (bid >= n_blocks) return;
+        l2_knn_bf16x1_body<true>(bid, n_blocks, desc, hi_t, hi_q, norms, rho_t, rho_q, blkmax, pairs, blk_pair, n_blocks, knn_idx, knn_dist, counters, flag_cap,
+                                 surv_cnt, surv_list, ratio2m, 0, nullptr, zero_a, zero_b, zero_n, zero_counters, pass_done);
+    } else {
+        l2_finish_body<true>(bid - n_pad, n_pairs * S, *reinterpret_cast<FinShared *>(fused_smem + kFinLdsBytes), desc, hi_t, hi_q, norms, rho_t, rho_q, pairs,
+                             pair_order, n_pairs, S, surv_cnt, surv_list, unc_cnt, unc_list, knn_d2, knn_idx, knn_dist, counters, flagged, flag_cap, done, audit, 1,
+                             ratio, ratio2m, query_idx, train_idx, distance, n_out, pass_done, handover_fail);
     }
 }
 
@@ -1087,6 +1244,12 @@ static inline double l2_ratio2m(double ratio) { return (ratio >= 0.0 && ratio < 
 int l2_x1_query_block() { return l2x1_query_block_c; }
 bool l2_x1_supported(int max_nt) { return max_nt <= (1 << (ESFM_L2X1_CODE_BITS - (ESFM_L2X1_GRP == 4 ? 2 : 1))) * 32; }   // the position code names a 32-row step and one of its 16 / GRP groups
 
+int l2_x1_forced_grid()
+{
+    static const int forced = [] { const char *e = getenv("ESFM_X1_GRID"); return e ? atoi(e) : 0; }();     // (measurement)
+    return forced;
+}
+
 int launch_l2_knn_bf16x1(hipStream_t st, int num_cu, const float *desc, const void *hi, long long total_rows, const float *norms, const PairDesc *pairs,
                          const int32_t *blk_pair, int n_blocks, int32_t *knn_idx, float *knn_dist, int32_t *counters, int flag_cap,
                          int32_t *surv_cnt, void *surv_list, double ratio, bool markers, int32_t *rejected,
@@ -1100,7 +1263,7 @@ int launch_l2_knn_bf16x1(hipStream_t st, int num_cu, const float *desc, const vo
     ESFM_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&l2_knn_bf16x1_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     void *h = const_cast<void *>(hi);
     // one workgroup per block by default (see the kernel); ESFM_X1_GRID = persistent workgroups (a multiple of 8, e.g. 2 x CUs)
-    static const int forced = [] { const char *e = getenv("ESFM_X1_GRID"); return e ? atoi(e) : 0; }();     // (measurement)
+    const int forced = l2_x1_forced_grid();
     (void)num_cu;
     const int grid = forced > 0 && forced < n_blocks ? std::max(8, forced / 8 * 8) : n_blocks;
     hipLaunchKernelGGL(l2_knn_bf16x1_kernel, dim3(grid), dim3(256), lds, st, desc,
@@ -1113,10 +1276,14 @@ int launch_l2_knn_bf16x1(hipStream_t st, int num_cu, const float *desc, const vo
     return ESFM_OK;
 }
 
-int l2_finish_slices(int n_pairs)
+static int forced_fin_slices()
 {
     static const int forced = [] { const char *e = getenv("ESFM_FIN_SLICES"); return e ? atoi(e) : 0; }();     // (measurement)
-    if (forced > 0) return forced;
+    return forced;
+}
+int l2_finish_slices(int n_pairs)
+{
+    if (forced_fin_slices() > 0) return forced_fin_slices();
     return std::max(1, std::min(8, 2304 / std::max(n_pairs, 1)));      // (300 pairs, three workgroups per CU, survivors dealt evenly: 7 slices 60 us, 4: 70, 5: 65, 6: 66, 8: 63)
 }
 
@@ -1134,6 +1301,33 @@ int launch_l2_finish(hipStream_t st, const float *desc, const void *hi, long lon
                        reinterpret_cast<const float *>(l2_hi_part(h, total_rows, 2)), reinterpret_cast<const float *>(l2_hi_part(h, total_rows, 3)),
                        pairs, pair_order, n_pairs, S, surv_cnt, reinterpret_cast<const float4 *>(surv_list), unc_cnt, unc_list, knn_d2, knn_idx, knn_dist, counters, flagged,
                        flag_cap, done, audit, do_ratio ? 1 : 0, ratio, l2_ratio2m(ratio), query_idx, train_idx, distance, n_out);
+    ESFM_HIP_TRY(hipGetLastError());
+    return ESFM_OK;
+}
+
+int launch_l2_fused(hipStream_t st, const float *desc, const void *hi, long long total_rows, const float *norms, const PairDesc *pairs,
+                    const int32_t *blk_pair, int n_blocks, const int32_t *pair_order, int n_pairs, int32_t *knn_idx, float *knn_dist, int32_t *counters,
+                    int32_t *flagged, int flag_cap, int32_t *surv_cnt, void *surv_list, int32_t *unc_cnt, int32_t *unc_list, float *knn_d2,
+                    int32_t *zero_a, int32_t *zero_b, int zero_n, int32_t *zero_counters, int32_t *done, int32_t *pass_done, int32_t *handover_fail,
+                    int audit, double ratio, int32_t *query_idx, int32_t *train_idx, float *distance, int32_t *n_out)
+{
+    if (n_blocks <= 0 || n_pairs <= 0) return ESFM_OK;
+    const FusedGrid g = fused_grid_of(n_blocks, n_pairs, forced_fin_slices() > 0 ? forced_fin_slices() : fused_slices_default(n_pairs));
+    if (g.total >= (1LL << 31)) { set_error("too many workgroups for one launch; split the pair list"); return ESFM_ERR_INVALID_ARG; }
+    // dynamic LDS: the larger of the two roles' needs (the pass's, as in launch_l2_knn_bf16x1; the finish role's buffers + its FinShared)
+    constexpr size_t lds_pass = 4 * 128 * 128 + 4 * 128 * 4 + 64 + 4 * l2x1_query_block_c * 4;
+    constexpr size_t lds_fin = kFinLdsBytes + ((sizeof(FinShared) + 15) & ~(size_t)15);
+    constexpr size_t lds = lds_pass > lds_fin ? lds_pass : lds_fin;
+    static_assert(2 * lds <= 160 * 1024, "two workgroups per CU");
+    ESFM_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&l2_fused_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    void *h = const_cast<void *>(hi);
+    hipLaunchKernelGGL(l2_fused_kernel, dim3((unsigned)g.total), dim3(256), lds, st, desc,
+                       reinterpret_cast<const u32x4 *>(l2_hi_part(h, total_rows, 0)), reinterpret_cast<const u32x4 *>(l2_hi_part(h, total_rows, 1)), norms,
+                       reinterpret_cast<const float *>(l2_hi_part(h, total_rows, 2)), reinterpret_cast<const float *>(l2_hi_part(h, total_rows, 3)),
+                       reinterpret_cast<const float2 *>(l2_hi_part(h, total_rows, 4)),
+                       pairs, blk_pair, n_blocks, (int)g.n_pad, pair_order, n_pairs, g.slices, knn_idx, knn_dist, counters, flagged, flag_cap, surv_cnt,
+                       reinterpret_cast<float4 *>(surv_list), unc_cnt, unc_list, knn_d2, zero_a, zero_b, zero_n, zero_counters, done, pass_done, handover_fail,
+                       audit, ratio, l2_ratio2m(ratio), query_idx, train_idx, distance, n_out);
     ESFM_HIP_TRY(hipGetLastError());
     return ESFM_OK;
 }

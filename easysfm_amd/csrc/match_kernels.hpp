@@ -67,6 +67,17 @@ int launch_l2_finish(hipStream_t st, const float *desc, const void *hi, long lon
                      const int32_t *pair_order /* the pair indices sorted by train set */, int n_pairs, const int32_t *surv_cnt, const void *surv_list, int32_t *unc_cnt, int32_t *unc_list, float *knn_d2,
                      int32_t *knn_idx, float *knn_dist, int32_t *counters, int32_t *flagged, int flag_cap, int32_t *done,
                      int audit, bool do_ratio, double ratio, int32_t *query_idx, int32_t *train_idx, float *distance, int32_t *n_out);
+// The two launches above as ONE (l2_fused_kernel; match lists outside the audit modes 3 / 4): grid [pass blocks, padded to a multiple
+// of 8 | n_pairs x slices finish workgroups]; a pair's finish workgroups wait for pass_done[p] == the pair's 512-query blocks
+// ((nq + 511) / 512, as blk_off2 counts them) and the pair's last one resets it.  pass_done: n_pairs counters, zero on entry and
+// on exit like `done`.  handover_fail: one word, raised (and left raised) by a finish workgroup whose wait ran out.
+// (the grid's arithmetic is host code of its own: fused_grid_of, match_plan.hpp)
+int launch_l2_fused(hipStream_t st, const float *desc, const void *hi, long long total_rows, const float *norms, const PairDesc *pairs,
+                    const int32_t *blk_pair, int n_blocks, const int32_t *pair_order, int n_pairs, int32_t *knn_idx, float *knn_dist, int32_t *counters,
+                    int32_t *flagged, int flag_cap, int32_t *surv_cnt, void *surv_list, int32_t *unc_cnt, int32_t *unc_list, float *knn_d2,
+                    int32_t *zero_a, int32_t *zero_b, int zero_n, int32_t *zero_counters, int32_t *done, int32_t *pass_done, int32_t *handover_fail,
+                    int audit, double ratio, int32_t *query_idx, int32_t *train_idx, float *distance, int32_t *n_out);
+int l2_x1_forced_grid();      // ESFM_X1_GRID (measurement: persistent pass workgroups; such a call keeps the two launches), else 0
 int l2_x1_query_block();
 bool l2_x1_supported(int max_nt);          // train sets the front pass's position code covers
 bool l2_one_product_pass();   // ESFM_L2_PASS=bf16x3 in the environment switches the one-product front pass off (measurement)

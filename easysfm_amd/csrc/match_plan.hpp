@@ -4,6 +4,7 @@
 // list: match_plan.cpp includes no HIP header, and tests/cpp/match_plan_check.cpp states what the kernels rely on in these tables.
 #pragma once
 
+#include <algorithm>
 #include <cstddef>
 #include <vector>
 
@@ -37,6 +38,27 @@ struct PairPlan {
 // mirrored plan too, whose second half continues the numbering behind it.  *plan is overwritten as a whole.
 int make_plan(const int32_t *set_row_offset, int n_sets, const int32_t *pairs, int n_pairs, int query_block, int query_block2, bool mirror,
               const PlanRules &rules, int64_t *out_offset, PairPlan *plan);
+
+// The grid of the fused L2 launch (l2_fused_kernel, match_kernels.hip): the front pass's n_blocks2 blocks, one workgroup each, padded
+// to a multiple of 8 -- workgroups are dealt round-robin over the 8 XCDs, so the finish role's workgroup k lands on XCD k % 8 as in a
+// launch of its own -- then `slices` finish workgroups per pair.  Workgroup w: w < n_pass a pass block, w < n_pad padding (returns at
+// once), else finish workgroup w - n_pad.  A pair's finish workgroups wait until pair_blocks2() pass blocks have counted themselves:
+// that is the number of entries of blk_pair that name the pair, blk_off2[p + 1] - blk_off2[p] (tests/cpp/match_fused_grid_check.cpp).
+struct FusedGrid { int n_pass = 0, slices = 0; int64_t n_pad = 0, total = 0; };
+inline FusedGrid fused_grid_of(int n_blocks2, int n_pairs, int slices)
+{
+    FusedGrid g;
+    g.n_pass = n_blocks2;
+    g.n_pad = ((int64_t)n_blocks2 + 7) / 8 * 8;
+    g.slices = slices;
+    g.total = g.n_pad + (int64_t)n_pairs * slices;      // (the launcher refuses 2^31 and more)
+    return g;
+}
+// finish workgroups per pair of the fused launch: about two rounds of its 2 x 256 slots (measured on 300 pairs of 4096 x 4096: 1 slice
+// 0.530 ms per step, 2: 0.517, 3: 0.512, 4: 0.516, 7 -- the two-launch default -- 0.524: a finish workgroup's fixed costs weigh more at
+// two per CU, beside pass blocks, than at three per CU with the chip to itself)
+inline int fused_slices_default(int n_pairs) { return std::max(1, std::min(8, 1024 / std::max(n_pairs, 1))); }
+inline int pair_blocks2(const PairDesc &d, int query_block2) { return (int)(((int64_t)d.nq + query_block2 - 1) / query_block2); }
 
 // ctx, metric and width as every matcher entry point checks them, in this order (width_msg: the text of a width <= 0)
 int check_metric_width(const esfm_ctx *ctx, esfm_metric metric, int width, const char *width_msg);

@@ -516,6 +516,10 @@ class PairMatcher:
         """Certificate audit (tests): 0 product path, 1 skip the exact re-scan, 2 brute-force every query, 3 the one-product pass alone (esfm.h)."""
         check(lib().esfm_ctx_set_l2_audit(self.ctx.handle, int(mode)))
 
+    def set_l2_two_launch(self, enable: bool) -> None:
+        """esfm_ctx_set_l2_two_launch: run the 64-float match-list path's distance pass and finish stages as two launches instead of one (same results; A/B measurements, tests)."""
+        check(lib().esfm_ctx_set_l2_two_launch(self.ctx.handle, 1 if enable else 0))
+
     def flagged(self) -> np.ndarray:
         """(pair index, query row) of the queries the last L2 call could not certify; synchronises."""
         n = C.c_int64(0)

@@ -331,6 +331,14 @@ int esfm_match_last_second_pass(esfm_ctx *ctx, int64_t *n_second_pass);
  * Diffing the two tables row by row and removing the rows esfm_match_last_flagged() lists gives
  * the number of queries the certificate accepted with a wrong answer; it must be 0. */
 int esfm_ctx_set_l2_audit(esfm_ctx *ctx, int mode);
+/* The 64-float match-list path runs its distance pass and its finish stages as ONE launch (the finish workgroups trail the pass's
+ * in the same grid and wait, pair by pair, for the pair's pass blocks).  enable = 1 keeps them as two launches on one stream -- the
+ * same results, for A/B measurements and tests; 0 restores the default.  ESFM_L2_TWO_LAUNCH=1 in the environment sets the default
+ * of contexts created afterwards.  Pair lists of more than 8 Mi (2^23) queries keep the two launches whatever the switch says: there
+ * the finish workgroups' lower occupancy inside the fused launch costs more than the launch boundary (a limit measured on lists of
+ * 4096-row sets; ESFM_L2_FUSED_MAX_QUERIES in the environment moves it, for measurements).  Should a finish workgroup's wait ever run out (2 s; never seen), the call's lists are incomplete
+ * and the next synchronising matcher call on the context returns ESFM_ERR_HIP. */
+int esfm_ctx_set_l2_two_launch(esfm_ctx *ctx, int enable);
 /* The 16 device-side counters of the last L2 batched call ([0] re-scanned, [1] second pass, the rest: instrumented builds only). */
 int esfm_match_debug_counters(esfm_ctx *ctx, int32_t *out16);
 /* The (pair, query row) entries the last L2 batched call flagged as uncertified: writes
