@@ -13,13 +13,15 @@ from .matching import (DescriptorBank, FeatureMatching, PairMatcher, knn_match_h
 from .ba import (BAProblem, BundleAdjustment, Comm, ba_solve, ba_solve_ex, ba_sweep_bytes_per_obs, default_options, line_search_next_step, reduced_plan, shard_points,  # noqa: F401
                  torch_allreduce_callback)
 
-from .cloud import CProceesing, read_ply_vertices, sor_filter, write_ply  # noqa: F401
+from .cloud import (CProceesing, read_ply_normals, read_ply_vertices, sor_filter, voxel_merge, write_ply,  # noqa: F401
+                    write_ply_normals)
 from .motion import (MotionEstimator, find_essential_mat, find_essential_pairs, five_point_models, pixel2cam, ransac_sample_stream, recover_pose,  # noqa: F401
                      recover_pose_pairs, solve_pnp_ransac, triangulate_pairs, triangulate_points)
 
 from .features import (detectFeaturesORB, detectFeaturesSIFT, detectFeaturesSURF, import_distort, orb_detect_and_compute,  # noqa: F401
                        sift_detect_and_compute, surf_detect_and_compute, undistort)
-from .mvs import (MVSOptions, default_mvs_options, dense_reconstruct, dense_reconstruction, mvs_depth_maps, mvs_fuse,  # noqa: F401
+from .mvs import (MergeOptions, MVSNormalOptions, MVSOptions, default_mvs_normal_options, default_mvs_options, dense_merge,  # noqa: F401
+                  dense_reconstruct, dense_reconstruction, merge_arrays, merge_voxel_size, mvs_depth_maps, mvs_fuse, mvs_normals,
                   mvs_plan)
 from .pipeline import MATCH_FILTERS, FramePair, match_and_verify_all_pairs, propagate_track_ids, run_sfm  # noqa: F401
 

@@ -45,6 +45,7 @@ EXPORTED_SYMBOLS = [
     "esfm_find_essential_mat", "esfm_find_essential_pairs", "esfm_recover_pose", "esfm_recover_pose_pairs", "esfm_ransac_sample_stream", "esfm_five_point_models", "esfm_five_point_models_host",
     "esfm_solve_pnp_ransac", "esfm_surf_detect_and_compute", "esfm_orb_detect_and_compute", "esfm_sift_detect_and_compute", "esfm_undistort",
     "esfm_mvs_options_default", "esfm_mvs_plan", "esfm_mvs_depth_maps", "esfm_mvs_fuse",
+    "esfm_mvs_normal_options_default", "esfm_mvs_normals", "esfm_mvs_fuse_ex", "esfm_cloud_voxel_merge",
 ]
 
 
@@ -93,6 +94,11 @@ class MVSOptions(C.Structure):
         ("best_k", C.c_int32), ("depth_margin", C.c_float), ("max_cost", C.c_float), ("min_var", C.c_float),
         ("fuse_min_views", C.c_int32), ("fuse_reproj_px", C.c_float), ("fuse_rel_depth", C.c_float),
     ]
+
+
+class MVSNormalOptions(C.Structure):
+    """esfm_mvs_normal_options (include/esfm.h, "Dense-cloud merge")."""
+    _fields_ = [("normal_radius", C.c_int32), ("normal_min_taps", C.c_int32), ("normal_rel_step", C.c_float)]
 
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p)
@@ -200,6 +206,11 @@ def lib() -> C.CDLL:
     L.esfm_mvs_plan.argtypes = [C.c_int, vp, vp, C.c_int, vp, vp, vp, C.POINTER(MVSOptions), vp, vp]
     L.esfm_mvs_depth_maps.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.POINTER(MVSOptions), vp, vp]
     L.esfm_mvs_fuse.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.POINTER(MVSOptions), vp, vp, i32p]
+    L.esfm_mvs_normal_options_default.argtypes = [C.POINTER(MVSNormalOptions)]
+    L.esfm_mvs_normal_options_default.restype = None
+    L.esfm_mvs_normals.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.POINTER(MVSNormalOptions), vp]
+    L.esfm_mvs_fuse_ex.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.POINTER(MVSOptions), vp, vp, vp, i32p]
+    L.esfm_cloud_voxel_merge.argtypes = [vp, C.c_int, vp, vp, vp, vp, C.c_float, C.c_int, C.c_int, vp, vp, vp, vp, vp, i32p]
     L.esfm_solve_pnp_ransac.argtypes = [vp, vp, vp, C.c_int, vp, C.c_int, C.c_double, C.c_double, vp, vp, vp, vp, i32p, i32p]
     L.esfm_ba_problem_set_params.argtypes = [vp, vp, vp]
     L.esfm_ba_problem_solve.argtypes = [vp, C.POINTER(BAOptions), ALLREDUCE_FN, vp, C.POINTER(BASummary)]

@@ -28,6 +28,40 @@ def sor_filter(points, mean_k: int = 50, std_mul: float = 2.0, ctx: Optional[Con
     return keep[:n].astype(bool), md[:n], thr.value
 
 
+def voxel_merge(xyz, rgb=None, normals=None, tags=None, voxel_size: float = 1.0, min_points: int = 1, min_tags: int = 0,
+                ctx: Optional[Context] = None):
+    """esfm_cloud_voxel_merge: one point per occupied voxel of side voxel_size, in ascending voxel-key order.  xyz [n, 3] float32;
+    rgb [n, 3] uint8, normals [n, 3] float32 and tags [n] int32 (0..63) are optional.  Returns (xyz [m, 3], rgb [m, 3] or None,
+    normals [m, 3] or None, count [m] int32, tagmask [m] uint64 or None)."""
+    ctx = ctx or default_context()
+    pts = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+    n = len(pts)
+
+    def opt_in(a, dtype, width):
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a, dtype).reshape((n, width) if width else (n,))
+        return a
+
+    c, nr, tg = opt_in(rgb, np.uint8, 3), opt_in(normals, np.float32, 3), opt_in(tags, np.int32, 0)
+    cap = max(n, 1)
+    o_xyz = np.zeros((cap, 3), np.float32)
+    o_rgb = np.zeros((cap, 3), np.uint8) if c is not None else None
+    o_nrm = np.zeros((cap, 3), np.float32) if nr is not None else None
+    o_cnt = np.zeros(cap, np.int32)
+    o_msk = np.zeros(cap, np.uint64) if tg is not None else None
+    m = C.c_int32(0)
+
+    def ptr(a):
+        return C.c_void_p(a.ctypes.data) if a is not None else None
+
+    check(lib().esfm_cloud_voxel_merge(ctx.handle, n, ptr(pts), ptr(c), ptr(nr), ptr(tg), float(voxel_size), int(min_points), int(min_tags),
+                                       ptr(o_xyz), ptr(o_rgb), ptr(o_nrm), ptr(o_cnt), ptr(o_msk), C.byref(m)))
+    k = m.value
+    cut = lambda a: None if a is None else a[:k].copy()
+    return cut(o_xyz), cut(o_rgb), cut(o_nrm), cut(o_cnt), cut(o_msk)
+
+
 class CProceesing:
     """Mirror of ``CProceesing<PointT>`` (cloudprocessing.hpp:20-72; the reference's spelling), SOR filter only."""
 
@@ -84,6 +118,41 @@ def write_ply(file_name: str, cloud: SparsePointCloud) -> bool:
         return False
     print(f"Output [ {n} ] points.\nOutput ply file done.")
     return True
+
+
+def write_ply_normals(file_name: str, cloud: SparsePointCloud, normals) -> bool:
+    """ASCII PLY with oriented points: properties x y z nx ny nz red green blue (what surface reconstruction tools read)."""
+    xyz = np.asarray(cloud.xyz, np.float32).reshape(-1, 3)
+    n = xyz.shape[0]
+    nrm = np.asarray(normals, np.float32).reshape(-1, 3)
+    if len(nrm) != n:
+        raise ValueError("one normal per point")
+    rgb = np.asarray(cloud.rgb, np.uint8).reshape(-1, 3) if len(cloud.rgb) == n else np.zeros((n, 3), np.uint8)
+    head = ["ply", "format ascii 1.0", f"element vertex {n}"] + [f"property float {p}" for p in ("x", "y", "z", "nx", "ny", "nz")] + \
+           [f"property uchar {p}" for p in ("red", "green", "blue")] + ["end_header"]
+    try:
+        with open(file_name, "w") as f:
+            f.write("\n".join(head) + "\n")
+            for i in range(n):
+                f.write(" ".join(_fmt(v) for v in (*xyz[i], *nrm[i])) + f" {int(rgb[i, 0])} {int(rgb[i, 1])} {int(rgb[i, 2])}\n")
+    except OSError:
+        print("Couldn't write file ")
+        return False
+    print(f"Output [ {n} ] points.\nOutput ply file done.")
+    return True
+
+
+def read_ply_normals(file_name: str):
+    """Reader for the files write_ply_normals produces: (xyz [n, 3] f32, normals [n, 3] f32, rgb [n, 3] u8)."""
+    with open(file_name) as f:
+        lines = f.read().split("\n")
+    n = int([l for l in lines if l.startswith("element vertex")][0].split()[-1])
+    props = [l.split()[-1] for l in lines[:lines.index("end_header")] if l.startswith("property")]
+    if props != ["x", "y", "z", "nx", "ny", "nz", "red", "green", "blue"]:
+        raise ValueError(f"not a write_ply_normals file: {props}")
+    body = lines[lines.index("end_header") + 1:]
+    arr = np.array([l.split() for l in body[:n]], np.float64).reshape(n, 9)
+    return arr[:, :3].astype(np.float32), arr[:, 3:6].astype(np.float32), arr[:, 6:].astype(np.uint8)
 
 
 def read_ply_vertices(file_name: str):

@@ -102,6 +102,69 @@ void homography(const float *Kr, const float *Pr, const float *Ks, const float *
         }
 }
 
+// esfm_mvs_fuse and esfm_mvs_fuse_ex: one body; pixel_index NULL = the index is neither computed nor copied
+int fuse(esfm_ctx *ctx, int n_views, int rows, int cols, int channels, const uint8_t *images, const float *K4, const float *poses,
+         const int32_t *neighbours, const float *depth, const esfm_mvs_options *opt, float *xyz, uint8_t *rgb, int32_t *pixel_index,
+         int32_t *n_points)
+{
+    if (int rc = check_views(n_views, rows, cols, channels, images, K4, poses, neighbours, opt)) return rc;
+    ESFM_REQUIRE(depth && xyz && rgb && n_points, "NULL argument");
+    if (int rc = check_ctx(ctx)) return rc;
+    *n_points = 0;
+    hipStream_t st = ctx->stream;
+    const int nb = opt->max_neighbours;
+    std::vector<MvsCam> cams((size_t)n_views);
+    for (int v = 0; v < n_views; ++v) {
+        MvsCam &c = cams[(size_t)v];
+        memcpy(c.K, K4 + 4 * (size_t)v, sizeof(c.K));
+        memcpy(c.P, poses + 12 * (size_t)v, sizeof(c.P));
+        for (int j = 0; j < esfm::kMvsMaxNb; ++j) c.nb[j] = j < nb ? neighbours[(size_t)v * nb + j] : -1;
+    }
+    const size_t n_px = (size_t)n_views * rows * cols;
+    const size_t n_blocks = (n_px + 255) / 256;
+    auto al = [](size_t n) { return (n + 255) / 256 * 256; };
+    // stage_a: images | depth | cams | block counts + n_points; stage_b: per-pixel points | colours | keep; stage_c: output
+    const size_t img_b = al(n_px * channels), dep_b = al(sizeof(float) * n_px), cam_b = al(sizeof(MvsCam) * cams.size());
+    const size_t cnt_b = al(sizeof(int32_t) * (n_blocks + 1));
+    esfm::DevBuf &b_in = ctx->stage_a, &b_stage = ctx->stage_b, &b_out = ctx->stage_c;
+    if (int rc = b_in.reserve(img_b + dep_b + cam_b + cnt_b)) return rc;
+    if (int rc = b_stage.reserve(al(sizeof(float) * 3 * n_px) + al(3 * n_px) + al(n_px))) return rc;
+    if (int rc = b_out.reserve(al(sizeof(float) * 3 * n_px) + al(3 * n_px) + (pixel_index ? sizeof(int32_t) * n_px : 0))) return rc;
+    uint8_t *p_in = b_in.as<uint8_t>(), *p_stage = b_stage.as<uint8_t>(), *p_out = b_out.as<uint8_t>();
+    esfm::MvsFuseArgs a;
+    a.images = p_in;
+    a.depth = reinterpret_cast<const float *>(p_in + img_b);
+    a.cams = reinterpret_cast<const MvsCam *>(p_in + img_b + dep_b);
+    a.block_count = reinterpret_cast<int32_t *>(p_in + img_b + dep_b + cam_b);
+    a.n_points = a.block_count + n_blocks;
+    a.stage_xyz = reinterpret_cast<float *>(p_stage);
+    a.stage_rgb = p_stage + al(sizeof(float) * 3 * n_px);
+    a.keep = a.stage_rgb + al(3 * n_px);
+    a.xyz = reinterpret_cast<float *>(p_out);
+    a.rgb = p_out + al(sizeof(float) * 3 * n_px);
+    a.pixel_index = pixel_index ? reinterpret_cast<int32_t *>(a.rgb + al(3 * n_px)) : nullptr;
+    a.n_px = (int64_t)n_px;
+    a.rows = rows; a.cols = cols; a.channels = channels; a.n_nb = nb; a.min_views = opt->fuse_min_views;
+    a.reproj2 = opt->fuse_reproj_px * opt->fuse_reproj_px;
+    a.rel_depth = opt->fuse_rel_depth;
+    ESFM_HIP_TRY(esfm::copy_h2d(p_in, images, n_px * channels, st));
+    ESFM_HIP_TRY(esfm::copy_h2d(p_in + img_b, depth, sizeof(float) * n_px, st));
+    ESFM_HIP_TRY(esfm::copy_h2d(p_in + img_b + dep_b, cams.data(), sizeof(MvsCam) * cams.size(), st));
+    {
+        esfm::KernelTimer tm(ctx, ESFM_K_MVS_FUSE);
+        if (int rc = esfm::launch_mvs_fuse(st, a)) return rc;
+    }
+    int32_t n = 0;
+    ESFM_HIP_TRY(esfm::copy_d2h(&n, a.n_points, sizeof(int32_t), st));
+    ESFM_HIP_TRY(hipStreamSynchronize(st));
+    ESFM_HIP_TRY(esfm::copy_d2h(xyz, a.xyz, sizeof(float) * 3 * (size_t)n, st));
+    ESFM_HIP_TRY(esfm::copy_d2h(rgb, a.rgb, 3 * (size_t)n, st));
+    if (pixel_index) ESFM_HIP_TRY(esfm::copy_d2h(pixel_index, a.pixel_index, sizeof(int32_t) * (size_t)n, st));
+    ESFM_HIP_TRY(hipStreamSynchronize(st));
+    *n_points = n;
+    return ESFM_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -266,59 +329,65 @@ int esfm_mvs_depth_maps(esfm_ctx *ctx, int n_views, int rows, int cols, int chan
 int esfm_mvs_fuse(esfm_ctx *ctx, int n_views, int rows, int cols, int channels, const uint8_t *images, const float *K4, const float *poses,
                   const int32_t *neighbours, const float *depth, const esfm_mvs_options *opt, float *xyz, uint8_t *rgb, int32_t *n_points)
 {
-    if (int rc = check_views(n_views, rows, cols, channels, images, K4, poses, neighbours, opt)) return rc;
-    ESFM_REQUIRE(depth && xyz && rgb && n_points, "NULL argument");
+    return fuse(ctx, n_views, rows, cols, channels, images, K4, poses, neighbours, depth, opt, xyz, rgb, nullptr, n_points);
+}
+
+int esfm_mvs_fuse_ex(esfm_ctx *ctx, int n_views, int rows, int cols, int channels, const uint8_t *images, const float *K4, const float *poses,
+                     const int32_t *neighbours, const float *depth, const esfm_mvs_options *opt, float *xyz, uint8_t *rgb,
+                     int32_t *pixel_index, int32_t *n_points)
+{
+    return fuse(ctx, n_views, rows, cols, channels, images, K4, poses, neighbours, depth, opt, xyz, rgb, pixel_index, n_points);
+}
+
+void esfm_mvs_normal_options_default(esfm_mvs_normal_options *opt)
+{
+    if (!opt) return;
+    opt->normal_radius = 3;
+    opt->normal_min_taps = 25;
+    opt->normal_rel_step = 0.05f;
+}
+
+int esfm_mvs_normals(esfm_ctx *ctx, int n_views, int rows, int cols, const float *K4, const float *poses, const float *depth,
+                     const esfm_mvs_normal_options *opt, float *normals)
+{
+    ESFM_REQUIRE(opt, "options are NULL");
+    ESFM_REQUIRE(opt->normal_radius >= 1 && opt->normal_radius <= esfm::kMvsMaxRadius, "normal_radius must be 1..7");
+    const int win = 2 * opt->normal_radius + 1;
+    ESFM_REQUIRE(opt->normal_min_taps >= 3 && opt->normal_min_taps <= win * win, "normal_min_taps must be 3..(2 normal_radius + 1)^2");
+    ESFM_REQUIRE(opt->normal_rel_step > 0.f && std::isfinite(opt->normal_rel_step), "normal_rel_step must be finite and > 0");
+    ESFM_REQUIRE(n_views >= 1 && K4 && poses && depth && normals, "NULL argument or no views");
+    ESFM_REQUIRE(rows >= 1 && cols >= 1 && rows <= 16384 && cols <= 16384, "image sides must be 1..16384");
+    ESFM_REQUIRE((int64_t)n_views * rows * cols <= ((int64_t)1 << 31) - 256, "more than 2^31 pixels in one call");
+    for (int v = 0; v < n_views; ++v) {
+        const float *k = K4 + 4 * (size_t)v;
+        ESFM_REQUIRE(k[0] != 0.f && k[2] != 0.f && std::isfinite(k[0]) && std::isfinite(k[1]) && std::isfinite(k[2]) && std::isfinite(k[3]),
+                     "K4 must be finite with non-zero focal lengths");
+    }
     if (int rc = check_ctx(ctx)) return rc;
-    *n_points = 0;
     hipStream_t st = ctx->stream;
-    const int nb = opt->max_neighbours;
     std::vector<MvsCam> cams((size_t)n_views);
     for (int v = 0; v < n_views; ++v) {
         MvsCam &c = cams[(size_t)v];
         memcpy(c.K, K4 + 4 * (size_t)v, sizeof(c.K));
         memcpy(c.P, poses + 12 * (size_t)v, sizeof(c.P));
-        for (int j = 0; j < esfm::kMvsMaxNb; ++j) c.nb[j] = j < nb ? neighbours[(size_t)v * nb + j] : -1;
+        for (int j = 0; j < esfm::kMvsMaxNb; ++j) c.nb[j] = -1;
     }
     const size_t n_px = (size_t)n_views * rows * cols;
-    const size_t n_blocks = (n_px + 255) / 256;
-    auto al = [](size_t n) { return (n + 255) / 256 * 256; };
-    // stage_a: images | depth | cams | block counts + n_points; stage_b: per-pixel points | colours | keep; stage_c: output
-    const size_t img_b = al(n_px * channels), dep_b = al(sizeof(float) * n_px), cam_b = al(sizeof(MvsCam) * cams.size());
-    const size_t cnt_b = al(sizeof(int32_t) * (n_blocks + 1));
-    esfm::DevBuf &b_in = ctx->stage_a, &b_stage = ctx->stage_b, &b_out = ctx->stage_c;
-    if (int rc = b_in.reserve(img_b + dep_b + cam_b + cnt_b)) return rc;
-    if (int rc = b_stage.reserve(al(sizeof(float) * 3 * n_px) + al(3 * n_px) + al(n_px))) return rc;
-    if (int rc = b_out.reserve(al(sizeof(float) * 3 * n_px) + al(3 * n_px))) return rc;
-    uint8_t *p_in = b_in.as<uint8_t>(), *p_stage = b_stage.as<uint8_t>(), *p_out = b_out.as<uint8_t>();
-    esfm::MvsFuseArgs a;
-    a.images = p_in;
-    a.depth = reinterpret_cast<const float *>(p_in + img_b);
-    a.cams = reinterpret_cast<const MvsCam *>(p_in + img_b + dep_b);
-    a.block_count = reinterpret_cast<int32_t *>(p_in + img_b + dep_b + cam_b);
-    a.n_points = a.block_count + n_blocks;
-    a.stage_xyz = reinterpret_cast<float *>(p_stage);
-    a.stage_rgb = p_stage + al(sizeof(float) * 3 * n_px);
-    a.keep = a.stage_rgb + al(3 * n_px);
-    a.xyz = reinterpret_cast<float *>(p_out);
-    a.rgb = p_out + al(sizeof(float) * 3 * n_px);
-    a.n_px = (int64_t)n_px;
-    a.rows = rows; a.cols = cols; a.channels = channels; a.n_nb = nb; a.min_views = opt->fuse_min_views;
-    a.reproj2 = opt->fuse_reproj_px * opt->fuse_reproj_px;
-    a.rel_depth = opt->fuse_rel_depth;
-    ESFM_HIP_TRY(esfm::copy_h2d(p_in, images, n_px * channels, st));
-    ESFM_HIP_TRY(esfm::copy_h2d(p_in + img_b, depth, sizeof(float) * n_px, st));
-    ESFM_HIP_TRY(esfm::copy_h2d(p_in + img_b + dep_b, cams.data(), sizeof(MvsCam) * cams.size(), st));
-    {
-        esfm::KernelTimer tm(ctx, ESFM_K_MVS_FUSE);
-        if (int rc = esfm::launch_mvs_fuse(st, a)) return rc;
-    }
-    int32_t n = 0;
-    ESFM_HIP_TRY(esfm::copy_d2h(&n, a.n_points, sizeof(int32_t), st));
+    const size_t dep_b = (sizeof(float) * n_px + 255) / 256 * 256;
+    if (int rc = ctx->stage_a.reserve(dep_b + sizeof(MvsCam) * cams.size())) return rc;
+    if (int rc = ctx->stage_b.reserve(sizeof(float) * 3 * n_px)) return rc;
+    uint8_t *p_in = ctx->stage_a.as<uint8_t>();
+    ESFM_HIP_TRY(esfm::copy_h2d(p_in, depth, sizeof(float) * n_px, st));
+    ESFM_HIP_TRY(esfm::copy_h2d(p_in + dep_b, cams.data(), sizeof(MvsCam) * cams.size(), st));
+    esfm::MvsNormalArgs a;
+    a.depth = reinterpret_cast<const float *>(p_in);
+    a.cams = reinterpret_cast<const MvsCam *>(p_in + dep_b);
+    a.normals = ctx->stage_b.as<float>();
+    a.rows = rows; a.cols = cols; a.tiles_x = (cols + esfm::kMvsTile - 1) / esfm::kMvsTile;
+    a.radius = opt->normal_radius; a.min_taps = opt->normal_min_taps; a.rel_step = opt->normal_rel_step;
+    if (int rc = esfm::launch_mvs_normals(st, a, n_views)) return rc;
+    ESFM_HIP_TRY(esfm::copy_d2h(normals, a.normals, sizeof(float) * 3 * n_px, st));
     ESFM_HIP_TRY(hipStreamSynchronize(st));
-    ESFM_HIP_TRY(esfm::copy_d2h(xyz, a.xyz, sizeof(float) * 3 * (size_t)n, st));
-    ESFM_HIP_TRY(esfm::copy_d2h(rgb, a.rgb, 3 * (size_t)n, st));
-    ESFM_HIP_TRY(hipStreamSynchronize(st));
-    *n_points = n;
     return ESFM_OK;
 }
 

@@ -260,6 +260,7 @@ __global__ __launch_bounds__(256) void mvs_fuse_write_kernel(MvsFuseArgs a)
     const int64_t dst = (int64_t)a.block_count[blockIdx.x] + pre[tid] - 1;
 #pragma unroll
     for (int c = 0; c < 3; ++c) { a.xyz[3 * dst + c] = a.stage_xyz[3 * idx + c]; a.rgb[3 * dst + c] = a.stage_rgb[3 * idx + c]; }
+    if (a.pixel_index) a.pixel_index[dst] = (int32_t)idx;      // (n_px < 2^31: check_views)
 }
 
 // ---- launchers -----------------------------------------------------------------------------------------------------------
@@ -285,13 +286,19 @@ int launch_mvs_sweep(hipStream_t st, const MvsSweepArgs &a, int radius, int n_vi
     return ESFM_OK;
 }
 
+int launch_block_offsets_scan(hipStream_t st, int32_t *block_count, int n_blocks, int32_t *total)
+{
+    hipLaunchKernelGGL(mvs_fuse_scan_kernel, dim3(1), dim3(1024), 0, st, block_count, n_blocks, total);
+    LAUNCH_OK();
+    return ESFM_OK;
+}
+
 int launch_mvs_fuse(hipStream_t st, const MvsFuseArgs &a)
 {
     const int n_blocks = (int)((a.n_px + 255) / 256);
     hipLaunchKernelGGL(mvs_fuse_kernel, dim3((unsigned)n_blocks), dim3(256), 0, st, a);
     LAUNCH_OK();
-    hipLaunchKernelGGL(mvs_fuse_scan_kernel, dim3(1), dim3(1024), 0, st, a.block_count, n_blocks, a.n_points);
-    LAUNCH_OK();
+    if (int rc = launch_block_offsets_scan(st, a.block_count, n_blocks, a.n_points)) return rc;
     hipLaunchKernelGGL(mvs_fuse_write_kernel, dim3((unsigned)n_blocks), dim3(256), 0, st, a);
     LAUNCH_OK();
     return ESFM_OK;

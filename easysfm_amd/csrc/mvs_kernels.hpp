@@ -48,6 +48,7 @@ struct MvsFuseArgs {
     int32_t *block_count;   // per 256-pixel block, then its exclusive offset
     float *xyz;             // compacted output
     uint8_t *rgb;
+    int32_t *pixel_index;   // (view rows + y) cols + x of each compacted point; NULL = not wanted (esfm_mvs_fuse)
     int32_t *n_points;
     int64_t n_px;           // n_views x rows x cols
     int32_t rows, cols, channels, n_nb, min_views;
@@ -56,5 +57,16 @@ struct MvsFuseArgs {
 
 int launch_mvs_sweep(hipStream_t st, const MvsSweepArgs &a, int radius, int n_views);
 int launch_mvs_fuse(hipStream_t st, const MvsFuseArgs &a);
+// the fusion's one-workgroup exclusive scan of per-block counts (in place) and their total; the voxel merge orders its output with it too
+int launch_block_offsets_scan(hipStream_t st, int32_t *block_count, int n_blocks, int32_t *total);
+
+struct MvsNormalArgs {
+    const float *depth;     // n_views x rows x cols
+    const MvsCam *cams;     // K and P are read
+    float *normals;         // n_views x rows x cols x 3
+    int32_t rows, cols, tiles_x, radius, min_taps;
+    float rel_step;
+};
+int launch_mvs_normals(hipStream_t st, const MvsNormalArgs &a, int n_views);   // mvs_normals.hip
 
 }  // namespace esfm

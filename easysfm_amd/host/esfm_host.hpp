@@ -96,6 +96,8 @@ struct frame_t {  // utility.h:21-55
 };
 
 struct PointXYZRGB { float x = 0, y = 0, z = 0; uint8_t r = 0, g = 0, b = 0; };  // pcl::PointXYZRGB
+// a merged dense point (DenseReconstruction::reconstructMerged): normal (0, 0, 0) = none, members, bit v of views = seen by view v
+struct PointXYZRGBNormal { float x = 0, y = 0, z = 0, nx = 0, ny = 0, nz = 0; uint8_t r = 0, g = 0, b = 0; int32_t members = 0; uint64_t views = 0; };
 
 struct pointcloud_sparse_t {  // utility.h:88-102 (rgb_pointcloud->points flattened)
     std::vector<PointXYZRGB> points;
@@ -557,6 +559,22 @@ public:
         for (const PointXYZRGB &p : pointCloud)
             fs << p.x << " " << p.y << " " << p.z << " " << int(p.r) << " " << int(p.g) << " " << int(p.b) << "\n";
         fs << "0 0 0 1 0 0 0 1 0 0 0 1 0 0 0 0 0 1 " << n << " 0 0\n";
+        std::cout << "Output [ " << n << " ] points." << std::endl << "Output ply file done." << std::endl;
+        return bool(fs);
+    }
+
+    // the merged dense cloud as oriented points: ASCII, properties x y z nx ny nz red green blue (easysfm_amd.cloud.write_ply_normals)
+    bool writePlyFileNormals(const std::string &fileName, const std::vector<PointXYZRGBNormal> &pointCloud)
+    {
+        std::ofstream fs(fileName);
+        if (!fs) { std::cerr << "Couldn't write file " << std::endl; return false; }
+        const size_t n = pointCloud.size();
+        fs << "ply\nformat ascii 1.0\nelement vertex " << n
+           << "\nproperty float x\nproperty float y\nproperty float z\nproperty float nx\nproperty float ny\nproperty float nz"
+              "\nproperty uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n";
+        fs << std::setprecision(8);
+        for (const PointXYZRGBNormal &p : pointCloud)
+            fs << p.x << " " << p.y << " " << p.z << " " << p.nx << " " << p.ny << " " << p.nz << " " << int(p.r) << " " << int(p.g) << " " << int(p.b) << "\n";
         std::cout << "Output [ " << n << " ] points." << std::endl << "Output ply file done." << std::endl;
         return bool(fs);
     }
@@ -1036,14 +1054,34 @@ public:
 
 // ---- dense reconstruction (esfm.h "Dense reconstruction"; the reference README's TODO "add multi-view stereo dense
 // reconstruction"): the same CSR of observed cloud points as easysfm_amd/mvs.py, then esfm_mvs_plan, esfm_mvs_depth_maps and
-// esfm_mvs_fuse.  process_frame_id as in doSFMBA: false = registered.
+// esfm_mvs_fuse; reconstructMerged adds the merge of the dense cloud (esfm.h "Dense-cloud merge").  process_frame_id as in
+// doSFMBA: false = registered.
 class DenseReconstruction {
 public:
     // returns false (message on stderr) on a library error; n_depth_maps = views with a depth range
     bool reconstruct(const std::vector<frame_t> &frames, const std::vector<bool> &process_frame_id, const pointcloud_sparse_t &cloud,
                      std::vector<PointXYZRGB> &dense, int &n_depth_maps)
     {
+        return run(frames, process_frame_id, cloud, dense, n_depth_maps, nullptr);
+    }
+
+    // reconstruct, then the merge of the dense cloud (easysfm_amd.mvs.dense_merge): esfm_mvs_fuse_ex for each point's pixel,
+    // esfm_mvs_normals gathered by it, the view as tag, esfm_cloud_voxel_merge with dense_merge's defaults: a voxel of twice the lower
+    // median of the points' pixel footprints depth / fx, kept if two or more views support it.  dense is reconstruct's cloud.  At most
+    // 64 frames.
+    bool reconstructMerged(const std::vector<frame_t> &frames, const std::vector<bool> &process_frame_id, const pointcloud_sparse_t &cloud,
+                           std::vector<PointXYZRGB> &dense, int &n_depth_maps, std::vector<PointXYZRGBNormal> &merged)
+    {
+        if (frames.size() > 64) { std::cerr << "dense merge tags points by view: at most 64 views" << std::endl; return false; }
+        return run(frames, process_frame_id, cloud, dense, n_depth_maps, &merged);
+    }
+
+private:
+    bool run(const std::vector<frame_t> &frames, const std::vector<bool> &process_frame_id, const pointcloud_sparse_t &cloud,
+             std::vector<PointXYZRGB> &dense, int &n_depth_maps, std::vector<PointXYZRGBNormal> *merged)
+    {
         dense.clear();
+        if (merged) merged->clear();
         n_depth_maps = 0;
         const int n = int(frames.size());
         esfm_mvs_options opt;
@@ -1095,14 +1133,52 @@ public:
                                  depth.data(), cost.data());
         if (rc != ESFM_OK) { std::cerr << esfm_last_error() << std::endl; return false; }
         int32_t n_points = 0;
-        rc = esfm_mvs_fuse(default_ctx(), n, rows, cols, ch, images.data(), K4.data(), poses.data(), nb.data(), depth.data(), &opt,
-                           out_xyz.data(), out_rgb.data(), &n_points);
+        std::vector<int32_t> pixel(merged ? n_px : 0);
+        rc = merged ? esfm_mvs_fuse_ex(default_ctx(), n, rows, cols, ch, images.data(), K4.data(), poses.data(), nb.data(), depth.data(), &opt,
+                                       out_xyz.data(), out_rgb.data(), pixel.data(), &n_points)
+                    : esfm_mvs_fuse(default_ctx(), n, rows, cols, ch, images.data(), K4.data(), poses.data(), nb.data(), depth.data(), &opt,
+                                    out_xyz.data(), out_rgb.data(), &n_points);
         if (rc != ESFM_OK) { std::cerr << esfm_last_error() << std::endl; return false; }
         dense.resize(size_t(n_points));
         for (size_t k = 0; k < dense.size(); ++k) {
             PointXYZRGB &p = dense[k];
             p.x = out_xyz[3 * k]; p.y = out_xyz[3 * k + 1]; p.z = out_xyz[3 * k + 2];
             p.r = out_rgb[3 * k]; p.g = out_rgb[3 * k + 1]; p.b = out_rgb[3 * k + 2];
+        }
+        if (!merged || n_points == 0) return true;
+
+        // normals of every depth map, gathered by each point's pixel; the view as tag; footprints for the voxel size
+        const size_t N = size_t(n_points);
+        std::vector<float> normal_maps(3 * n_px), normals(3 * N), foot(N);
+        std::vector<int32_t> tags(N);
+        esfm_mvs_normal_options nopt;
+        esfm_mvs_normal_options_default(&nopt);
+        rc = esfm_mvs_normals(default_ctx(), n, rows, cols, K4.data(), poses.data(), depth.data(), &nopt, normal_maps.data());
+        if (rc != ESFM_OK) { std::cerr << esfm_last_error() << std::endl; return false; }
+        const size_t view_px = size_t(rows) * size_t(cols);
+        for (size_t k = 0; k < N; ++k) {
+            const size_t px = size_t(pixel[k]);
+            for (int c = 0; c < 3; ++c) normals[3 * k + c] = normal_maps[3 * px + c];
+            tags[k] = int32_t(px / view_px);
+            foot[k] = depth[px] / K4[size_t(4) * size_t(tags[k])];
+        }
+        std::nth_element(foot.begin(), foot.begin() + (N - 1) / 2, foot.end());         // the lower median, sorted[(n - 1) / 2]
+        const float h = 2.0f * foot[(N - 1) / 2];
+        std::vector<float> m_xyz(3 * N), m_nrm(3 * N);
+        std::vector<uint8_t> m_rgb(3 * N);
+        std::vector<int32_t> m_cnt(N);
+        std::vector<uint64_t> m_views(N);
+        int32_t n_merged = 0;
+        rc = esfm_cloud_voxel_merge(default_ctx(), n_points, out_xyz.data(), out_rgb.data(), normals.data(), tags.data(), h, /*min_points*/ 1, /*min_tags*/ 2,
+                                    m_xyz.data(), m_rgb.data(), m_nrm.data(), m_cnt.data(), m_views.data(), &n_merged);
+        if (rc != ESFM_OK) { std::cerr << esfm_last_error() << std::endl; return false; }
+        merged->resize(size_t(n_merged));
+        for (size_t k = 0; k < merged->size(); ++k) {
+            PointXYZRGBNormal &p = (*merged)[k];
+            p.x = m_xyz[3 * k]; p.y = m_xyz[3 * k + 1]; p.z = m_xyz[3 * k + 2];
+            p.nx = m_nrm[3 * k]; p.ny = m_nrm[3 * k + 1]; p.nz = m_nrm[3 * k + 2];
+            p.r = m_rgb[3 * k]; p.g = m_rgb[3 * k + 1]; p.b = m_rgb[3 * k + 2];
+            p.members = m_cnt[k]; p.views = m_views[k];
         }
         return true;
     }

@@ -10,7 +10,8 @@ from typing import Optional, Sequence, Tuple
 
 import numpy as np
 
-from ._lib import Context, MVSOptions, check, default_context, lib
+from ._lib import Context, MVSNormalOptions, MVSOptions, check, default_context, lib
+from .cloud import voxel_merge
 from .types import Frame, SparsePointCloud
 
 
@@ -18,6 +19,13 @@ def default_mvs_options() -> MVSOptions:
     """esfm_mvs_options_default: 128 planes, 7 x 7 window, 4 neighbours, best 2 costs, ..."""
     opt = MVSOptions()
     lib().esfm_mvs_options_default(C.byref(opt))
+    return opt
+
+
+def default_mvs_normal_options() -> MVSNormalOptions:
+    """esfm_mvs_normal_options_default: 7 x 7 window, at least 25 taps within 5 % of the centre's inverse depth."""
+    opt = MVSNormalOptions()
+    lib().esfm_mvs_normal_options_default(C.byref(opt))
     return opt
 
 
@@ -96,8 +104,9 @@ def mvs_depth_maps(images, K4, poses, neighbours, depth_range, opt: Optional[MVS
 
 
 def mvs_fuse(images, K4, poses, neighbours, depth, opt: Optional[MVSOptions] = None,
-             ctx: Optional[Context] = None) -> Tuple[np.ndarray, np.ndarray]:
-    """esfm_mvs_fuse.  Returns (xyz [N, 3] float32, rgb [N, 3] uint8), ordered by (view, row, col)."""
+             ctx: Optional[Context] = None, return_index: bool = False):
+    """esfm_mvs_fuse.  Returns (xyz [N, 3] float32, rgb [N, 3] uint8), ordered by (view, row, col); with return_index
+    (esfm_mvs_fuse_ex) also pixel_index [N] int32 = (view rows + y) cols + x of each point."""
     opt = opt or default_mvs_options()
     ctx = ctx or default_context()
     imgs, K, P = _views(images, K4, poses)
@@ -108,9 +117,30 @@ def mvs_fuse(images, K4, poses, neighbours, depth, opt: Optional[MVSOptions] = N
     xyz = np.zeros((cap, 3), np.float32)
     rgb = np.zeros((cap, 3), np.uint8)
     cnt = C.c_int32(0)
-    check(lib().esfm_mvs_fuse(ctx.handle, n, rows, cols, ch, _ptr(imgs), _ptr(K), _ptr(P), _ptr(nb), _ptr(d), C.byref(opt),
-                              _ptr(xyz), _ptr(rgb), C.byref(cnt)))
-    return xyz[:cnt.value].copy(), rgb[:cnt.value].copy()
+    if not return_index:
+        check(lib().esfm_mvs_fuse(ctx.handle, n, rows, cols, ch, _ptr(imgs), _ptr(K), _ptr(P), _ptr(nb), _ptr(d), C.byref(opt),
+                                  _ptr(xyz), _ptr(rgb), C.byref(cnt)))
+        return xyz[:cnt.value].copy(), rgb[:cnt.value].copy()
+    index = np.zeros(cap, np.int32)
+    check(lib().esfm_mvs_fuse_ex(ctx.handle, n, rows, cols, ch, _ptr(imgs), _ptr(K), _ptr(P), _ptr(nb), _ptr(d), C.byref(opt),
+                                 _ptr(xyz), _ptr(rgb), _ptr(index), C.byref(cnt)))
+    return xyz[:cnt.value].copy(), rgb[:cnt.value].copy(), index[:cnt.value].copy()
+
+
+def mvs_normals(K4, poses, depth, opt: Optional[MVSNormalOptions] = None, ctx: Optional[Context] = None) -> np.ndarray:
+    """esfm_mvs_normals.  depth [n, rows, cols] float32 (0 = no estimate), K4 [n, 4], poses [n, 12] (or [n, 3 | 4, 4]).
+    Returns world normals [n, rows, cols, 3] float32 facing their camera; (0, 0, 0) = no normal."""
+    opt = opt or default_mvs_normal_options()
+    ctx = ctx or default_context()
+    d = np.ascontiguousarray(depth, np.float32)
+    if d.ndim != 3:
+        raise ValueError("depth must be [n_views, rows, cols]")
+    n, rows, cols = d.shape
+    K = np.ascontiguousarray(np.asarray(K4, np.float32).reshape(n, 4))
+    P = np.ascontiguousarray(np.asarray(poses, np.float32).reshape(n, -1, 4)[:, :3, :].reshape(n, 12))
+    out = np.zeros((n, rows, cols, 3), np.float32)
+    check(lib().esfm_mvs_normals(ctx.handle, n, rows, cols, _ptr(K), _ptr(P), _ptr(d), C.byref(opt), _ptr(out)))
+    return out
 
 
 def frame_arrays(frames: Sequence[Frame], process_frame_id: Sequence[bool]):
@@ -152,3 +182,58 @@ def dense_reconstruct(frames: Sequence[Frame], process_frame_id: Sequence[bool],
     """Plan, depth maps and fusion for the registered frames (process_frame_id False) of a reconstruction; cloud is the
     sparse cloud with its track ids (before the SOR filter).  Returns the fused, coloured dense cloud."""
     return dense_reconstruction(frames, process_frame_id, cloud, opt, ctx)[0]
+
+
+class MergeOptions:
+    """Settings of dense_merge's voxel grid.  voxel_size > 0 is used as given; 0 derives it from the cloud: voxel_scale times the
+    lower median of the points' pixel footprints depth / fx.  A voxel is kept with at least min_points members from at least
+    min_tags views.  normals: esfm_mvs_normal_options, None = its defaults."""
+
+    def __init__(self, voxel_size: float = 0.0, voxel_scale: float = 2.0, min_points: int = 1, min_tags: int = 2,
+                 normals: Optional[MVSNormalOptions] = None):
+        self.voxel_size, self.voxel_scale, self.min_points, self.min_tags, self.normals = voxel_size, voxel_scale, min_points, min_tags, normals
+
+
+def merge_voxel_size(depth, K4, pixel_index, merge_opt: MergeOptions) -> np.float32:
+    """The voxel size dense_merge uses: merge_opt.voxel_size if > 0, else (f32) voxel_scale * the lower median,
+    sorted[(n - 1) // 2], of the f32 footprints depth[pixel_index] / fx_view."""
+    if merge_opt.voxel_size > 0:
+        return np.float32(merge_opt.voxel_size)
+    d = np.asarray(depth, np.float32)
+    idx = np.asarray(pixel_index, np.int64)
+    if len(idx) == 0:
+        raise ValueError("no points to derive a voxel size from")
+    fx = np.asarray(K4, np.float32).reshape(len(d), 4)[idx // (d.shape[1] * d.shape[2]), 0]
+    foot = np.sort(d.reshape(-1)[idx] / fx)
+    return np.float32(np.float32(merge_opt.voxel_scale) * foot[(len(foot) - 1) // 2])
+
+
+def dense_merge(frames: Sequence[Frame], process_frame_id: Sequence[bool], cloud: SparsePointCloud,
+                opt: Optional[MVSOptions] = None, merge_opt: Optional[MergeOptions] = None, ctx: Optional[Context] = None):
+    """Plan, depth maps, fusion with pixel indices, depth-map normals and the voxel merge: one point per occupied voxel with a
+    normal, tagged by the views that saw it.  Returns (merged cloud, normals [M, 3] float32, count [M] int32 members,
+    tagmask [M] uint64 with bit v set for view v, the unmerged dense cloud)."""
+    if len(frames) > 64:
+        raise ValueError("dense_merge tags points by view: at most 64 views")
+    opt = opt or default_mvs_options()
+    merge_opt = merge_opt or MergeOptions()
+    ctx = ctx or default_context()
+    imgs, K4, poses = frame_arrays(frames, process_frame_id)
+    nb, rng = mvs_plan(frames, process_frame_id, cloud, opt)
+    depth, _ = mvs_depth_maps(imgs, K4, poses, nb, rng, opt, ctx)
+    return merge_arrays(imgs, K4, poses, nb, depth, opt, merge_opt, ctx)
+
+
+def merge_arrays(imgs, K4, poses, nb, depth, opt: MVSOptions, merge_opt: MergeOptions, ctx: Context):
+    """dense_merge behind the depth maps (plain arrays)."""
+    if len(depth) > 64:
+        raise ValueError("dense_merge tags points by view: at most 64 views")
+    xyz, rgb, index = mvs_fuse(imgs, K4, poses, nb, depth, opt, ctx, return_index=True)
+    dense = SparsePointCloud(xyz=xyz, rgb=rgb)
+    if len(xyz) == 0:
+        return SparsePointCloud(), np.zeros((0, 3), np.float32), np.zeros(0, np.int32), np.zeros(0, np.uint64), dense
+    normals = mvs_normals(K4, poses, depth, merge_opt.normals, ctx).reshape(-1, 3)[index]
+    tags = (index // (depth.shape[1] * depth.shape[2])).astype(np.int32)
+    h = merge_voxel_size(depth, K4, index, merge_opt)
+    m_xyz, m_rgb, m_nrm, count, mask = voxel_merge(xyz, rgb, normals, tags, float(h), merge_opt.min_points, merge_opt.min_tags, ctx)
+    return SparsePointCloud(xyz=m_xyz, rgb=m_rgb), m_nrm, count, mask, dense

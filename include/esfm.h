@@ -794,6 +794,62 @@ int esfm_mvs_fuse(esfm_ctx *ctx, int n_views, int rows, int cols, int channels, 
                   const float *poses /*12 each*/, const int32_t *neighbours, const float *depth, const esfm_mvs_options *opt,
                   float *xyz, uint8_t *rgb, int32_t *n_points);
 
+/* Dense-cloud merge: per-pixel normals from the depth maps, the fusion that also reports each point's pixel, and a voxel grid
+ * that leaves one point per occupied voxel with the views that support it.  tests/merge_ref.py restates the three rules below
+ * in numpy; every accumulation across points is an integer sum, so the GPU agrees with it bit for bit whatever the order.
+ *
+ * esfm_mvs_normals: world normals, n_views x rows x cols x 3 f32, (0, 0, 0) = invalid.  A plane is exactly linear in inverse
+ * depth over pixel coordinates, w(x + dx, y + dy) = a dx + b dy + g; the rule fits that function by least squares over a window.
+ * Options (esfm_mvs_normal_options_default): normal_radius m 3 (1..7), normal_min_taps 25 (3..(2m+1)^2), normal_rel_step 0.05
+ * (> 0, finite).  Pixel (x, y) of view r with d = depth > 0: wc = 1.0f / d (f32).  Taps (dx, dy) over -m..m, row-major from
+ * the top-left tap; a tap outside the image is skipped; a tap counts if its depth dt > 0 and fabsf(wt - wc) <=
+ * normal_rel_step * wc with wt = 1.0f / dt (both sides f32).  Sums in double, in tap order, each from 0: S1 += 1, Sx += dx,
+ * Sy += dy, Sxx += dx dx, Sxy += dx dy, Syy += dy dy, Sw += (double)wt, Sxw += dx (double)wt, Syw += dy (double)wt.  Invalid if
+ * S1 < normal_min_taps.  Otherwise, in double with exactly these groupings:
+ *   c00 = Syy S1 - Sy Sy, c01 = Sxy S1 - Sy Sx, c02 = Sxy Sy - Syy Sx, det = (Sxx c00 - Sxy c01) + Sx c02,
+ *   da = (Sxw c00 - Sxy (Syw S1 - Sy Sw)) + Sx (Syw Sy - Syy Sw),
+ *   db = (Sxx (Syw S1 - Sw Sy) - Sxw c01) + Sx (Sxy Sw - Syw Sx),
+ *   dg = (Sxx (Syy Sw - Sy Syw) - Sxy (Sxy Sw - Sx Syw)) + Sxw c02.
+ * Invalid unless det > 0.  a = da / det, b = db / det, g = dg / det.  Camera normal (fx, cx, fy, cy and x, y as doubles):
+ * n0 = a fx, n1 = b fy, n2 = (g + a (cx - x)) + b (cy - y), L = sqrt((n0 n0 + n1 n1) + n2 n2); invalid unless L is finite and
+ * > 0; n = -n / L (it faces the camera).  World normal N[j] = (R[0][j] n0 + R[1][j] n1) + R[2][j] n2 with R cast from f32 to
+ * double; each component rounded to f32 once.  Arguments as esfm_mvs_fuse takes them (rows, cols 1..16384, at most 2^31 - 256
+ * pixels, K4 finite with non-zero focal lengths).
+ *
+ * esfm_mvs_fuse_ex: esfm_mvs_fuse with one more output, pixel_index (may be NULL; capacity n_views rows cols):
+ * (view rows + y) cols + x of each written point.  Points, colours and count are those of esfm_mvs_fuse, bit for bit.
+ *
+ * esfm_cloud_voxel_merge: n points (0 <= n <= 2^28), xyz f32; rgb u8 (3 each), normals f32 (3 each, finite) and tags int32 (one
+ * each, 0..63, e.g. the view) may each be NULL.  voxel_size h f32 (finite, > 0), min_points >= 1, min_tags >= 0.  Outputs of
+ * capacity n: out_xyz, and optionally out_rgb, out_normals, out_count (int32 members) and out_tagmask (uint64), plus *n_out.
+ * Rejected with ESFM_ERR_INVALID_ARG, nothing written: a tag outside 0..63; min_tags > 0 without tags; an output array
+ * requested without its input (out_rgb / rgb, out_normals / normals, out_tagmask / tags); a cell index that would reach 2^21.
+ *   A point is valid if its three coordinates are finite; others are ignored.  o_a = the f32 minimum of coordinate a over the
+ *   valid points.  Cell c_a = floorf((x_a - o_a) / h) (f32 subtract, correctly rounded f32 divide); floorf is monotone, so
+ *   the 2^21 limit is tested with the coordinate maximum.  Key = cz << 42 | cy << 21 | cx.
+ *   Member offset in double: u_a = ((double)x_a - (double)o_a) / (double)h - (double)c_a, q_a = llrint(u_a 2^30) (ties to even).
+ *   Per voxel with k members, Q_a = sum q_a (int64).  Point: (float)((double)o_a + ((double)c_a + ((double)Q_a / (double)k)
+ *   / 2^30) (double)h).  Colour per channel: (sum + k / 2) / k in integers.  Normals: members with a non-zero normal add
+ *   llrint((double)n_a 2^20) to int64 M_a; m_a = (double)M_a, L = sqrt((m0 m0 + m1 m1) + m2 m2); output (float)(m_a / L), or
+ *   (0, 0, 0) if L is 0.  tagmask = OR of 1 << tag over the members.  A voxel is kept if k >= min_points and
+ *   popcount(tagmask) >= min_tags.  Kept voxels come out in ascending key order.  Nothing depends on the order of a voxel's
+ *   members.  No valid point: *n_out = 0.
+ * All three take host pointers; without a usable device they return ESFM_ERR_NO_DEVICE (no CPU fallback). */
+typedef struct esfm_mvs_normal_options {
+    int32_t normal_radius, normal_min_taps;
+    float normal_rel_step;
+} esfm_mvs_normal_options;
+void esfm_mvs_normal_options_default(esfm_mvs_normal_options *opt);
+int esfm_mvs_normals(esfm_ctx *ctx, int n_views, int rows, int cols, const float *K4 /*4 each*/, const float *poses /*12 each*/,
+                     const float *depth, const esfm_mvs_normal_options *opt, float *normals /*3 per pixel*/);
+int esfm_mvs_fuse_ex(esfm_ctx *ctx, int n_views, int rows, int cols, int channels, const uint8_t *images, const float *K4 /*4 each*/,
+                     const float *poses /*12 each*/, const int32_t *neighbours, const float *depth, const esfm_mvs_options *opt,
+                     float *xyz, uint8_t *rgb, int32_t *pixel_index /*may be NULL*/, int32_t *n_points);
+int esfm_cloud_voxel_merge(esfm_ctx *ctx, int n, const float *xyz /*3 each*/, const uint8_t *rgb /*3 each, may be NULL*/,
+                           const float *normals /*3 each, may be NULL*/, const int32_t *tags /*may be NULL*/, float voxel_size,
+                           int min_points, int min_tags, float *out_xyz, uint8_t *out_rgb, float *out_normals, int32_t *out_count,
+                           uint64_t *out_tagmask, int32_t *n_out);
+
 #ifdef __cplusplus
 }
 #endif
