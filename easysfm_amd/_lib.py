@@ -46,6 +46,7 @@ EXPORTED_SYMBOLS = [
     "esfm_solve_pnp_ransac", "esfm_surf_detect_and_compute", "esfm_orb_detect_and_compute", "esfm_sift_detect_and_compute", "esfm_undistort",
     "esfm_mvs_options_default", "esfm_mvs_plan", "esfm_mvs_depth_maps", "esfm_mvs_fuse",
     "esfm_mvs_normal_options_default", "esfm_mvs_normals", "esfm_mvs_fuse_ex", "esfm_cloud_voxel_merge",
+    "esfm_tsdf_options_default", "esfm_tsdf_integrate", "esfm_tsdf_extract", "esfm_mvs_mesh",
 ]
 
 
@@ -99,6 +100,16 @@ class MVSOptions(C.Structure):
 class MVSNormalOptions(C.Structure):
     """esfm_mvs_normal_options (include/esfm.h, "Dense-cloud merge")."""
     _fields_ = [("normal_radius", C.c_int32), ("normal_min_taps", C.c_int32), ("normal_rel_step", C.c_float)]
+
+
+class TSDFGrid(C.Structure):
+    """esfm_tsdf_grid (include/esfm.h, "Surface reconstruction")."""
+    _fields_ = [("origin", C.c_float * 3), ("voxel_size", C.c_float), ("dims", C.c_int32 * 3)]
+
+
+class TSDFOptions(C.Structure):
+    """esfm_tsdf_options (include/esfm.h, "Surface reconstruction")."""
+    _fields_ = [("trunc", C.c_float), ("min_weight", C.c_int32)]
 
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p)
@@ -211,6 +222,12 @@ def lib() -> C.CDLL:
     L.esfm_mvs_normals.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.POINTER(MVSNormalOptions), vp]
     L.esfm_mvs_fuse_ex.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.POINTER(MVSOptions), vp, vp, vp, i32p]
     L.esfm_cloud_voxel_merge.argtypes = [vp, C.c_int, vp, vp, vp, vp, C.c_float, C.c_int, C.c_int, vp, vp, vp, vp, vp, i32p]
+    L.esfm_tsdf_options_default.argtypes = [C.POINTER(TSDFOptions)]
+    L.esfm_tsdf_options_default.restype = None
+    views = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.POINTER(TSDFGrid), C.POINTER(TSDFOptions)]   # ctx .. depth, grid, opt
+    L.esfm_tsdf_integrate.argtypes = views + [vp, vp, vp]
+    L.esfm_tsdf_extract.argtypes = [vp, C.POINTER(TSDFGrid), vp, vp, vp, C.POINTER(TSDFOptions), C.c_int, C.c_int, vp, vp, vp, vp, i32p, i32p]
+    L.esfm_mvs_mesh.argtypes = views + [C.c_int, C.c_int, vp, vp, vp, vp, i32p, i32p]
     L.esfm_solve_pnp_ransac.argtypes = [vp, vp, vp, C.c_int, vp, C.c_int, C.c_double, C.c_double, vp, vp, vp, vp, i32p, i32p]
     L.esfm_ba_problem_set_params.argtypes = [vp, vp, vp]
     L.esfm_ba_problem_solve.argtypes = [vp, C.POINTER(BAOptions), ALLREDUCE_FN, vp, C.POINTER(BASummary)]

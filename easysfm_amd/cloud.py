@@ -155,6 +155,53 @@ def read_ply_normals(file_name: str):
     return arr[:, :3].astype(np.float32), arr[:, 3:6].astype(np.float32), arr[:, 6:].astype(np.uint8)
 
 
+def write_ply_mesh(file_name: str, vertices, normals, rgb, triangles) -> bool:
+    """ASCII PLY of an indexed triangle mesh: the vertex properties of write_ply_normals (x y z nx ny nz red green blue; normals
+    or rgb None: zeros), then ``element face`` with ``property list uchar int vertex_indices``."""
+    xyz = np.asarray(vertices, np.float32).reshape(-1, 3)
+    n = xyz.shape[0]
+    nrm = np.asarray(normals, np.float32).reshape(-1, 3) if normals is not None else np.zeros((n, 3), np.float32)
+    col = np.asarray(rgb, np.uint8).reshape(-1, 3) if rgb is not None else np.zeros((n, 3), np.uint8)
+    tri = np.asarray(triangles, np.int32).reshape(-1, 3)
+    if len(nrm) != n or len(col) != n:
+        raise ValueError("one normal and one colour per vertex")
+    if len(tri) and (tri.min() < 0 or tri.max() >= n):
+        raise ValueError("a triangle index is out of range")
+    head = ["ply", "format ascii 1.0", f"element vertex {n}"] + [f"property float {p}" for p in ("x", "y", "z", "nx", "ny", "nz")] + \
+           [f"property uchar {p}" for p in ("red", "green", "blue")] + \
+           [f"element face {len(tri)}", "property list uchar int vertex_indices", "end_header"]
+    try:
+        with open(file_name, "w") as f:
+            f.write("\n".join(head) + "\n")
+            for i in range(n):
+                f.write(" ".join(_fmt(v) for v in (*xyz[i], *nrm[i])) + f" {int(col[i, 0])} {int(col[i, 1])} {int(col[i, 2])}\n")
+            for a, b, c in tri.tolist():
+                f.write(f"3 {a} {b} {c}\n")
+    except OSError:
+        print("Couldn't write file ")
+        return False
+    print(f"Output [ {n} ] vertices, [ {len(tri)} ] triangles.\nOutput ply file done.")
+    return True
+
+
+def read_ply_mesh(file_name: str):
+    """Reader for the files write_ply_mesh produces: (vertices [n, 3] f32, normals [n, 3] f32, rgb [n, 3] u8, triangles [m, 3] i32)."""
+    with open(file_name) as f:
+        lines = f.read().split("\n")
+    end = lines.index("end_header")
+    n = int([l for l in lines[:end] if l.startswith("element vertex")][0].split()[-1])
+    m = int([l for l in lines[:end] if l.startswith("element face")][0].split()[-1])
+    props = [l.split()[-1] for l in lines[:end] if l.startswith("property")]
+    if props != ["x", "y", "z", "nx", "ny", "nz", "red", "green", "blue", "vertex_indices"]:
+        raise ValueError(f"not a write_ply_mesh file: {props}")
+    body = lines[end + 1:]
+    arr = np.array([l.split() for l in body[:n]], np.float64).reshape(n, 9)
+    faces = np.array([l.split() for l in body[n:n + m]], np.int64).reshape(m, 4)
+    if m and np.any(faces[:, 0] != 3):
+        raise ValueError("not a triangle mesh")
+    return arr[:, :3].astype(np.float32), arr[:, 3:6].astype(np.float32), arr[:, 6:].astype(np.uint8), faces[:, 1:].astype(np.int32)
+
+
 def read_ply_vertices(file_name: str):
     """Minimal reader for the files write_ply produces (round-trip tests)."""
     with open(file_name) as f:

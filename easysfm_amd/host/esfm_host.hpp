@@ -98,6 +98,14 @@ struct frame_t {  // utility.h:21-55
 struct PointXYZRGB { float x = 0, y = 0, z = 0; uint8_t r = 0, g = 0, b = 0; };  // pcl::PointXYZRGB
 // a merged dense point (DenseReconstruction::reconstructMerged): normal (0, 0, 0) = none, members, bit v of views = seen by view v
 struct PointXYZRGBNormal { float x = 0, y = 0, z = 0, nx = 0, ny = 0, nz = 0; uint8_t r = 0, g = 0, b = 0; int32_t members = 0; uint64_t views = 0; };
+// an indexed triangle mesh (DenseReconstruction::reconstructMesh): oriented, coloured vertices (members and views unused), three
+// vertex indices per triangle, and the volume it was extracted from
+struct TriangleMesh {
+    std::vector<PointXYZRGBNormal> vertices;
+    std::vector<int32_t> triangles;
+    float voxel_size = 0.f;
+    int32_t dims[3] = {0, 0, 0};
+};
 
 struct pointcloud_sparse_t {  // utility.h:88-102 (rgb_pointcloud->points flattened)
     std::vector<PointXYZRGB> points;
@@ -576,6 +584,24 @@ public:
         for (const PointXYZRGBNormal &p : pointCloud)
             fs << p.x << " " << p.y << " " << p.z << " " << p.nx << " " << p.ny << " " << p.nz << " " << int(p.r) << " " << int(p.g) << " " << int(p.b) << "\n";
         std::cout << "Output [ " << n << " ] points." << std::endl << "Output ply file done." << std::endl;
+        return bool(fs);
+    }
+
+    // a triangle mesh: writePlyFileNormals' vertex properties, then the faces as vertex index lists (easysfm_amd.cloud.write_ply_mesh)
+    bool writePlyMesh(const std::string &fileName, const TriangleMesh &mesh)
+    {
+        std::ofstream fs(fileName);
+        if (!fs) { std::cerr << "Couldn't write file " << std::endl; return false; }
+        const size_t n = mesh.vertices.size(), m = mesh.triangles.size() / 3;
+        fs << "ply\nformat ascii 1.0\nelement vertex " << n
+           << "\nproperty float x\nproperty float y\nproperty float z\nproperty float nx\nproperty float ny\nproperty float nz"
+              "\nproperty uchar red\nproperty uchar green\nproperty uchar blue\nelement face " << m
+           << "\nproperty list uchar int vertex_indices\nend_header\n";
+        fs << std::setprecision(8);
+        for (const PointXYZRGBNormal &p : mesh.vertices)
+            fs << p.x << " " << p.y << " " << p.z << " " << p.nx << " " << p.ny << " " << p.nz << " " << int(p.r) << " " << int(p.g) << " " << int(p.b) << "\n";
+        for (size_t t = 0; t < m; ++t) fs << "3 " << mesh.triangles[3 * t] << " " << mesh.triangles[3 * t + 1] << " " << mesh.triangles[3 * t + 2] << "\n";
+        std::cout << "Output [ " << n << " ] vertices, [ " << m << " ] triangles." << std::endl << "Output ply file done." << std::endl;
         return bool(fs);
     }
 
@@ -1062,7 +1088,7 @@ public:
     bool reconstruct(const std::vector<frame_t> &frames, const std::vector<bool> &process_frame_id, const pointcloud_sparse_t &cloud,
                      std::vector<PointXYZRGB> &dense, int &n_depth_maps)
     {
-        return run(frames, process_frame_id, cloud, dense, n_depth_maps, nullptr);
+        return run(frames, process_frame_id, cloud, dense, n_depth_maps, nullptr, nullptr);
     }
 
     // reconstruct, then the merge of the dense cloud (easysfm_amd.mvs.dense_merge): esfm_mvs_fuse_ex for each point's pixel,
@@ -1073,15 +1099,101 @@ public:
                            std::vector<PointXYZRGB> &dense, int &n_depth_maps, std::vector<PointXYZRGBNormal> &merged)
     {
         if (frames.size() > 64) { std::cerr << "dense merge tags points by view: at most 64 views" << std::endl; return false; }
-        return run(frames, process_frame_id, cloud, dense, n_depth_maps, &merged);
+        return run(frames, process_frame_id, cloud, dense, n_depth_maps, &merged, nullptr);
+    }
+
+    // reconstruct (and the merge, if merged is not NULL), then the surface (easysfm_amd.mesh.dense_mesh with MeshOptions' defaults,
+    // esfm.h "Surface reconstruction"): the depth maps masked to the pixels the fusion kept, a voxel of twice the merge's median pixel
+    // footprint -- enlarged just enough for 2^24 voxels and 1024 per axis --, the grid around the 1st..99th percentile box of the
+    // fused points padded by the truncation distance of 4 voxels, esfm_mvs_mesh.  At most 64 frames.
+    bool reconstructMesh(const std::vector<frame_t> &frames, const std::vector<bool> &process_frame_id, const pointcloud_sparse_t &cloud,
+                         std::vector<PointXYZRGB> &dense, int &n_depth_maps, std::vector<PointXYZRGBNormal> *merged, TriangleMesh &mesh)
+    {
+        if (frames.size() > 64) { std::cerr << "dense mesh integrates at most 64 views" << std::endl; return false; }
+        return run(frames, process_frame_id, cloud, dense, n_depth_maps, merged, &mesh);
     }
 
 private:
+    // easysfm_amd.mesh.mesh_arrays behind the fusion: pixel[k] is the pixel of fused point k
+    static bool mesh_of(int n, int rows, int cols, int ch, const std::vector<uint8_t> &images, const std::vector<float> &K4,
+                        const std::vector<float> &poses, const std::vector<float> &depth, const std::vector<int32_t> &pixel, size_t N,
+                        const std::vector<float> &xyz, TriangleMesh &mesh)
+    {
+        const size_t view_px = size_t(rows) * size_t(cols);
+        std::vector<float> masked(depth.size(), 0.f), foot(N);
+        for (size_t k = 0; k < N; ++k) {
+            const size_t px = size_t(pixel[k]);
+            masked[px] = depth[px];
+            foot[k] = depth[px] / K4[size_t(4) * (px / view_px)];
+        }
+        std::nth_element(foot.begin(), foot.begin() + (N - 1) / 2, foot.end());         // the lower median, sorted[(n - 1) / 2]
+        double h = double(2.0f * foot[(N - 1) / 2]);
+        double lo[3], hi[3];
+        for (int c = 0; c < 3; ++c) {
+            std::vector<double> s;
+            for (size_t k = 0; k < N; ++k)
+                if (std::isfinite(xyz[3 * k]) && std::isfinite(xyz[3 * k + 1]) && std::isfinite(xyz[3 * k + 2])) s.push_back(double(xyz[3 * k + size_t(c)]));
+            if (s.empty()) { std::cerr << "dense mesh: no points to place a grid around" << std::endl; return false; }
+            std::sort(s.begin(), s.end());
+            const double n1 = double(s.size() - 1);
+            lo[c] = s[size_t(std::floor(0.01 * n1))]; hi[c] = s[size_t(std::ceil(0.99 * n1))];
+        }
+        const double trunc_voxels = 4.0, max_voxels = 16777216.0, max_dim = 1024.0;
+        double dims[3];
+        auto dims_of = [&](double hh) {
+            for (int c = 0; c < 3; ++c) dims[c] = std::max(std::ceil((hi[c] - lo[c] + 2.0 * trunc_voxels * hh) / hh) + 1.0, 2.0);
+        };
+        for (;;) {
+            dims_of(h);
+            const double top = std::max({dims[0], dims[1], dims[2]}), prod = dims[0] * dims[1] * dims[2];
+            if (top <= max_dim && prod <= max_voxels) break;
+            h *= std::max({top / max_dim, std::cbrt(prod / max_voxels), 1.0}) * 1.001;
+        }
+        h = double(float(h));
+        dims_of(h);
+        esfm_tsdf_grid grid;
+        for (int c = 0; c < 3; ++c) {
+            dims[c] = std::min(dims[c], max_dim);
+            grid.dims[c] = int32_t(dims[c]);
+            grid.origin[c] = float((lo[c] + hi[c]) / 2 - dims[c] * h / 2);
+        }
+        grid.voxel_size = float(h);
+        esfm_tsdf_options topt;
+        esfm_tsdf_options_default(&topt);
+        topt.trunc = float(trunc_voxels) * grid.voxel_size;
+        int32_t cap_v = 1 << 18, cap_t = 1 << 19, nv = 0, nt = 0;
+        std::vector<float> vtx, nrm;
+        std::vector<uint8_t> col;
+        for (int attempt = 0; attempt < 2; ++attempt) {         // a guess, then the counts the first call reported
+            vtx.assign(size_t(3) * size_t(cap_v), 0.f); nrm.assign(size_t(3) * size_t(cap_v), 0.f); col.assign(size_t(3) * size_t(cap_v), 0);
+            mesh.triangles.assign(size_t(3) * size_t(cap_t), 0);
+            nv = nt = -1;
+            const int rc = esfm_mvs_mesh(default_ctx(), n, rows, cols, ch, images.data(), K4.data(), poses.data(), masked.data(), &grid, &topt, cap_v,
+                                         cap_t, vtx.data(), nrm.data(), col.data(), mesh.triangles.data(), &nv, &nt);
+            if (rc == ESFM_OK) break;
+            if (attempt == 0 && rc == ESFM_ERR_INVALID_ARG && (nv > cap_v || nt > cap_t)) { cap_v = std::max(nv, 1); cap_t = std::max(nt, 1); continue; }
+            std::cerr << esfm_last_error() << std::endl;
+            return false;
+        }
+        mesh.triangles.resize(size_t(3) * size_t(nt));
+        mesh.vertices.resize(size_t(nv));
+        for (size_t k = 0; k < mesh.vertices.size(); ++k) {
+            PointXYZRGBNormal &p = mesh.vertices[k];
+            p.x = vtx[3 * k]; p.y = vtx[3 * k + 1]; p.z = vtx[3 * k + 2];
+            p.nx = nrm[3 * k]; p.ny = nrm[3 * k + 1]; p.nz = nrm[3 * k + 2];
+            p.r = col[3 * k]; p.g = col[3 * k + 1]; p.b = col[3 * k + 2];
+        }
+        mesh.voxel_size = grid.voxel_size;
+        for (int c = 0; c < 3; ++c) mesh.dims[c] = grid.dims[c];
+        return true;
+    }
+
     bool run(const std::vector<frame_t> &frames, const std::vector<bool> &process_frame_id, const pointcloud_sparse_t &cloud,
-             std::vector<PointXYZRGB> &dense, int &n_depth_maps, std::vector<PointXYZRGBNormal> *merged)
+             std::vector<PointXYZRGB> &dense, int &n_depth_maps, std::vector<PointXYZRGBNormal> *merged, TriangleMesh *mesh)
     {
         dense.clear();
         if (merged) merged->clear();
+        if (mesh) *mesh = TriangleMesh();
         n_depth_maps = 0;
         const int n = int(frames.size());
         esfm_mvs_options opt;
@@ -1133,11 +1245,11 @@ private:
                                  depth.data(), cost.data());
         if (rc != ESFM_OK) { std::cerr << esfm_last_error() << std::endl; return false; }
         int32_t n_points = 0;
-        std::vector<int32_t> pixel(merged ? n_px : 0);
-        rc = merged ? esfm_mvs_fuse_ex(default_ctx(), n, rows, cols, ch, images.data(), K4.data(), poses.data(), nb.data(), depth.data(), &opt,
-                                       out_xyz.data(), out_rgb.data(), pixel.data(), &n_points)
-                    : esfm_mvs_fuse(default_ctx(), n, rows, cols, ch, images.data(), K4.data(), poses.data(), nb.data(), depth.data(), &opt,
-                                    out_xyz.data(), out_rgb.data(), &n_points);
+        std::vector<int32_t> pixel(merged || mesh ? n_px : 0);
+        rc = merged || mesh ? esfm_mvs_fuse_ex(default_ctx(), n, rows, cols, ch, images.data(), K4.data(), poses.data(), nb.data(), depth.data(), &opt,
+                                               out_xyz.data(), out_rgb.data(), pixel.data(), &n_points)
+                            : esfm_mvs_fuse(default_ctx(), n, rows, cols, ch, images.data(), K4.data(), poses.data(), nb.data(), depth.data(), &opt,
+                                            out_xyz.data(), out_rgb.data(), &n_points);
         if (rc != ESFM_OK) { std::cerr << esfm_last_error() << std::endl; return false; }
         dense.resize(size_t(n_points));
         for (size_t k = 0; k < dense.size(); ++k) {
@@ -1145,7 +1257,9 @@ private:
             p.x = out_xyz[3 * k]; p.y = out_xyz[3 * k + 1]; p.z = out_xyz[3 * k + 2];
             p.r = out_rgb[3 * k]; p.g = out_rgb[3 * k + 1]; p.b = out_rgb[3 * k + 2];
         }
-        if (!merged || n_points == 0) return true;
+        if (n_points == 0) return true;
+        if (mesh && !mesh_of(n, rows, cols, ch, images, K4, poses, depth, pixel, size_t(n_points), out_xyz, *mesh)) return false;
+        if (!merged) return true;
 
         // normals of every depth map, gathered by each point's pixel; the view as tag; footprints for the voxel size
         const size_t N = size_t(n_points);

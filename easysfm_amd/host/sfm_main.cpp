@@ -82,17 +82,18 @@ int main(int argc, char **argv)
     // optional 14th argument: the match filter -- ratio (the reference's, default), cross (mutual nearest neighbours) or ratio+cross,
     // or one of these with +guided appended (a second, epipolar-guided pass over the verified pairs; the union is kept);
     // optional 15th (needs the 14th): a dense .ply path, or none; optional 16th (needs the 15th): a .ply path for the merged dense cloud
-    // (one oriented point per voxel), or none
+    // (one oriented point per voxel), or none; optional 17th (needs the 16th): a .ply path for the surface mesh, or none
     const std::string filter_arg = argc >= 15 ? argv[14] : "ratio";
     const std::string guided_suffix = "+guided";
     const bool guided = filter_arg.size() > guided_suffix.size() && filter_arg.compare(filter_arg.size() - guided_suffix.size(), guided_suffix.size(), guided_suffix) == 0;
     const std::string match_filter = guided ? filter_arg.substr(0, filter_arg.size() - guided_suffix.size()) : filter_arg;      // the first pass's filter
     const std::string dense_file = argc >= 16 && std::string(argv[15]) != "none" ? argv[15] : "";
-    const std::string merged_file = argc == 17 && std::string(argv[16]) != "none" ? argv[16] : "";
-    if ((argc != 14 && argc != 15 && argc != 16 && argc != 17) || (match_filter != "ratio" && match_filter != "cross" && match_filter != "ratio+cross")) {
+    const std::string merged_file = argc >= 17 && std::string(argv[16]) != "none" ? argv[16] : "";
+    const std::string mesh_file = argc == 18 && std::string(argv[17]) != "none" ? argv[17] : "";
+    if (argc < 14 || argc > 18 || (match_filter != "ratio" && match_filter != "cross" && match_filter != "ratio+cross")) {
         std::cerr << "usage: sfm_native image_folder image_list calib_K_file calib_distort_file output.ply feature_type(S | O | I) feature_parameter "
                      "repro_dis_ransac find_init_frames ba_calib_change_tolerance ba_frequency launch_viewer view_sphere [match_filter: ratio | cross | ratio+cross | "
-                     "ratio+guided | cross+guided | ratio+cross+guided [dense.ply | none [merged.ply | none]]]"
+                     "ratio+guided | cross+guided | ratio+cross+guided [dense.ply | none [merged.ply | none [mesh.ply | none]]]]"
                   << std::endl;
         return 2;
     }
@@ -382,14 +383,17 @@ int main(int argc, char **argv)
         std::cout << "stage seconds: import+undistort " << t_import << " detect " << t_detect << " match " << t_match << " verify " << t_verify << " tracks " << t_tracks
                   << " register " << t_register << " register_next_frame " << t_next << " register_pnp " << t_pnp << " ba " << t_ba << " ba_calls " << n_ba << " sor " << t_sor << " total " << total_clock.lap()
                   << " frames " << frame_number << " pairs " << frame_number * (frame_number - 1) / 2 << " batched " << (pair_by_pair ? 0 : 1) << std::endl;
-        if (!dense_file.empty() || !merged_file.empty()) {
+        if (!dense_file.empty() || !merged_file.empty() || !mesh_file.empty()) {
             // dense reconstruction after the final BA, on the cloud before the filter (it carries the track ids)
             clk.lap();
             std::vector<PointXYZRGB> dense;
             std::vector<PointXYZRGBNormal> merged;
             int n_maps = 0;
+            TriangleMesh mesh;
             DenseReconstruction dr;
-            if (!(merged_file.empty() ? dr.reconstruct(frames, todo, cloud, dense, n_maps) : dr.reconstructMerged(frames, todo, cloud, dense, n_maps, merged)))
+            if (!(!mesh_file.empty()    ? dr.reconstructMesh(frames, todo, cloud, dense, n_maps, merged_file.empty() ? nullptr : &merged, mesh)
+                  : merged_file.empty() ? dr.reconstruct(frames, todo, cloud, dense, n_maps)
+                                        : dr.reconstructMerged(frames, todo, cloud, dense, n_maps, merged)))
                 return 3;
             const double t_dense = clk.lap();
             if (!dense_file.empty()) {
@@ -406,6 +410,13 @@ int main(int argc, char **argv)
                 const std::filesystem::path merged_dir = std::filesystem::path(merged_file).parent_path();
                 if (!merged_dir.empty()) std::filesystem::create_directories(merged_dir);
                 if (!io.writePlyFileNormals(merged_file, merged)) return 3;
+            }
+            if (!mesh_file.empty()) {
+                std::cout << "Dense mesh: [" << mesh.vertices.size() << "] vertices, [" << mesh.triangles.size() / 3 << "] triangles from [" << mesh.dims[0]
+                          << "] x [" << mesh.dims[1] << "] x [" << mesh.dims[2] << "] voxels of [" << mesh.voxel_size << "]." << std::endl;
+                const std::filesystem::path mesh_dir = std::filesystem::path(mesh_file).parent_path();
+                if (!mesh_dir.empty()) std::filesystem::create_directories(mesh_dir);
+                if (!io.writePlyMesh(mesh_file, mesh)) return 3;
             }
         }
     } catch (const std::exception &e) {       // 1 is the reference's SUCCESS status: a failure must not look like one

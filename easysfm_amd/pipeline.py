@@ -15,9 +15,10 @@ import numpy as np
 
 from ._lib import Context, ESFM_HAMMING, ESFM_L2_F32, default_context
 from .ba import BundleAdjustment
-from .cloud import CProceesing, write_ply, write_ply_normals
+from .cloud import CProceesing, write_ply, write_ply_mesh, write_ply_normals
 from .matching import DescriptorBank, FeatureMatching, PairMatcher
 from .motion import MotionEstimator, _dehomogenise, find_essential_pairs, pixel2cam, recover_pose_pairs, triangulate_pairs
+from .mesh import MeshOptions, mesh_arrays
 from .mvs import MergeOptions, default_mvs_options, dense_reconstruction, frame_arrays, merge_arrays
 from .types import DMatch, Frame, SparsePointCloud
 
@@ -160,12 +161,15 @@ def propagate_track_ids(frames: Sequence[Frame], graph: List[List[FramePair]]):
 def run_sfm(frames: List[Frame], output_file: Optional[str] = None, use_feature: str = "S", ransac_reproj_distance: float = 1.0,
             use_track_frames_as_init: bool = True, fix_calib_tolerance_BA: float = 0.0, frequency_BA: int = 4,
             ctx: Optional[Context] = None, verbose: bool = False, match_filter: str = "ratio", dense_output_file: Optional[str] = None,
-            dense_merged_output_file: Optional[str] = None):
+            dense_merged_output_file: Optional[str] = None, dense_mesh_output_file: Optional[str] = None):
     """sfm.cpp:128-339.  Returns (sparse cloud before the final filter, filtered cloud, img_match_graph).
     dense_output_file: after the final BA and the sparse .ply, run dense_reconstruct on the registered frames and the cloud
     before the filter (it carries the track ids) and write the dense cloud there (esfm.h "Dense reconstruction").
     dense_merged_output_file: merge that dense cloud into one oriented point per voxel that two or more views support (esfm.h
-    "Dense-cloud merge", mvs.dense_merge's defaults) and write it there with write_ply_normals."""
+    "Dense-cloud merge", mvs.dense_merge's defaults) and write it there with write_ply_normals.
+    dense_mesh_output_file: integrate the depth maps, masked to the pixels the fusion kept, into a signed distance volume and
+    write the triangle mesh extracted from it there with write_ply_mesh (esfm.h "Surface reconstruction", mesh.dense_mesh's
+    defaults); prints one "Dense mesh:" line."""
     ctx = ctx or default_context()
     fm, ee = FeatureMatching(ctx), MotionEstimator(ctx)
     for f in frames:
@@ -222,7 +226,7 @@ def run_sfm(frames: List[Frame], output_file: Optional[str] = None, use_feature:
     out = CProceesing(ctx).SORFilter(cloud)
     if output_file:
         write_ply(output_file, out)
-    if dense_output_file or dense_merged_output_file:
+    if dense_output_file or dense_merged_output_file or dense_mesh_output_file:
         dense, nb, rng, depth, _ = dense_reconstruction(frames, todo, cloud, ctx=ctx)
         if dense_output_file:
             if verbose:
@@ -235,4 +239,10 @@ def run_sfm(frames: List[Frame], output_file: Optional[str] = None, use_feature:
                 print(f"Dense merge: [{len(dense.xyz)}] points into [{len(merged.xyz)}] voxels, "
                       f"[{int(np.count_nonzero(np.any(normals != 0, axis=1)))}] with a normal.")
             write_ply_normals(dense_merged_output_file, merged, normals)
+        if dense_mesh_output_file:
+            imgs, K4, poses = frame_arrays(frames, todo)
+            vertices, normals, rgb, triangles, grid = mesh_arrays(imgs, K4, poses, nb, depth, default_mvs_options(), MeshOptions(), ctx)
+            print(f"Dense mesh: [{len(vertices)}] vertices, [{len(triangles)}] triangles from [{grid.dims[0]}] x [{grid.dims[1]}] x "
+                  f"[{grid.dims[2]}] voxels of [{grid.voxel_size:g}].")
+            write_ply_mesh(dense_mesh_output_file, vertices, normals, rgb, triangles)
     return cloud, out, graph

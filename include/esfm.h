@@ -850,6 +850,85 @@ int esfm_cloud_voxel_merge(esfm_ctx *ctx, int n, const float *xyz /*3 each*/, co
                            int min_points, int min_tags, float *out_xyz, uint8_t *out_rgb, float *out_normals, int32_t *out_count,
                            uint64_t *out_tagmask, int32_t *n_out);
 
+/* ---- Surface reconstruction: TSDF volume and watertight triangle mesh --------------------------------
+ * Depth maps (e.g. esfm_mvs_depth_maps masked to the pixels esfm_mvs_fuse_ex kept) are integrated into a truncated signed
+ * distance volume, and an indexed triangle mesh is extracted from it by marching tetrahedra on the Kuhn decomposition: a
+ * translation-invariant rule, so neighbouring cells agree on every shared face and there are no ambiguity cases.  One voxel
+ * is one thread's work and every ordering is by linear index, so nothing depends on scheduling; tests/tsdf_ref.py restates
+ * this text in numpy and the GPU reproduces it bit for bit.  Conventions are those of the dense section (poses, K4, depth 0 =
+ * none, colour order as esfm_mvs_fuse).  All arithmetic is f32 unless said otherwise, no mul + add contraction, correctly
+ * rounded division and sqrtf.
+ *
+ * Grid (esfm_tsdf_grid): dims (nx, ny, nz) each 2..1024, product at most 2^27; voxel_size h finite and > 0; origin finite.
+ * Voxel (i, j, k) has linear index (k ny + j) nx + i and centre X_a = origin_a + ((float)i_a + 0.5f) * h.
+ * Options (esfm_tsdf_options_default: trunc 0, min_weight 2): trunc 0 means 4.0f * h, otherwise finite and >= h;
+ * min_weight >= 1.
+ *
+ * esfm_tsdf_integrate: n_views 1..64, images may be NULL (then rgb must be NULL).  Per voxel, the views v = 0 .. n - 1 in that
+ * order (a view without a positive depth contributes nothing), S (f32) and W, Wc, colour sums (integers) from 0:
+ *   p_i = ((R[i][0] X0 + R[i][1] X1) + R[i][2] X2) + t[i]; skip unless p2 > 0;
+ *   u = fx (p0 / p2) + cx, v = fy (p1 / p2) + cy, px = floorf(u + 0.5f), py = floorf(v + 0.5f); skip unless 0 <= px < cols,
+ *   0 <= py < rows and d = depth[v][py][px] > 0;
+ *   s = d - p2; skip if s < -trunc;  S += fminf(1.0f, s / trunc), W += 1;
+ *   with images, if s <= trunc: add the pixel's R, G, B (grey: a grey triple) to the colour sums, Wc += 1.
+ * Outputs, one per voxel: tsdf = W > 0 ? S / (float)W : 1.0f; weight = W; rgb = (sum + Wc / 2) / Wc in integers per channel,
+ * (0, 0, 0) if Wc is 0.
+ *
+ * esfm_tsdf_extract: tsdf, weight and rgb (may be NULL) as above, from any source.
+ *   A voxel is valid if weight >= min_weight, inside if valid and tsdf < 0.  Cell (i, j, k), i < nx - 1 and so on, has the
+ *   eight corner voxels (i + dx, j + dy, k + dz); it is live if all eight are valid.
+ *   A live cell splits into six tetrahedra, one per permutation (a, b, c) of the axes in lexicographic order (xyz, xzy, yxz,
+ *   yzx, zxy, zyx), with the ordered corners q0 = (0,0,0), q1 = q0 + e_a, q2 = q1 + e_b, q3 = (1,1,1).
+ *   Edges: every tetrahedron edge runs from a voxel v to v + delta, delta a non-zero vector of {0,1}^3; v owns it, its
+ *   direction id is e = (dx | dy << 1 | dz << 2) - 1 in 0..6.  The edge is used if exactly one end is inside and at least one
+ *   cell that holds both ends is live (4 cells for an axis edge, 2 for a face diagonal, 1 for the body diagonal).
+ *   Vertices: one per used edge, numbered in ascending (owner linear index, e).  fa = tsdf at the owner, fb at the other end:
+ *   tt = fa / (fa - fb); position P_a = Xa_a + tt * ((float)delta_a * h) with Xa the owner's centre; colour per channel
+ *   (uint8)floorf((ca + tt * (cb - ca)) + 0.5f), ca and cb as f32.
+ *   Gradient at a voxel, per axis, with f+ / f- the tsdf of the axis neighbours that are in the grid and valid:
+ *   0.5f * (f+ - f-) if both qualify, f+ - f or f - f- if one does, 0 if none.  g = ga + tt * (gb - ga) per component,
+ *   L = sqrtf((g0 g0 + g1 g1) + g2 g2); normal = g / L, or (0, 0, 0) if L is 0 or not finite.  It points to the outside
+ *   (towards positive distance: free space).
+ *   Triangles: by ascending cell linear index (that of the cell's origin voxel), then tetrahedron 0..5, then as listed, with
+ *   local corner indices 0..3 and edges written as corner pairs.  One corner a alone inside or alone outside, the others
+ *   b < c < d: (ab, ac, ad).  Two inside a < b, two outside c < d: (ac, ad, bd) and (ac, bd, bc).  None or all four inside:
+ *   nothing.  Winding, in integers on lattice coordinates: m_i = the sum of the two corners of edge i, n = (m1 - m0) x
+ *   (m2 - m0), s = n_in * (sum of the outside corners) - n_out * (sum of the inside corners); if n . s < 0 the second and
+ *   third vertex are swapped (n . s is never 0).  (v1 - v0) x (v2 - v0) then points to the outside.  Where a tsdf value is
+ *   exactly 0, tt is 0 or 1 and triangles of zero area occur; they are kept, the topology relies on them.
+ *   Capacities: *n_vertices and *n_triangles always receive the needed counts (both below 2^31); if either exceeds
+ *   max_vertices / max_triangles no geometry is written and the call returns ESFM_ERR_INVALID_ARG with both counts in the
+ *   message.  vertices, normals (may be NULL): 3 f32 each; vertex_rgb (may be NULL, needs rgb): 3 u8; triangles: 3 int32.
+ *
+ * esfm_mvs_mesh: esfm_tsdf_integrate then esfm_tsdf_extract with the volume staying on the device; the mesh equals the
+ * two-step result bit for bit (colours are integrated only if vertex_rgb is requested, which needs images).
+ * Rejected with ESFM_ERR_INVALID_ARG, before the device is looked at: a non-finite grid value, dims out of range, more than
+ * 2^27 voxels, a trunc that is non-zero and below h or not finite, min_weight < 1, an output requested without its input,
+ * a negative capacity.  All three take host pointers; without a usable device they return ESFM_ERR_NO_DEVICE (no CPU
+ * fallback). */
+typedef struct esfm_tsdf_grid {
+    float origin[3];
+    float voxel_size;
+    int32_t dims[3];
+} esfm_tsdf_grid;
+typedef struct esfm_tsdf_options {
+    float trunc;
+    int32_t min_weight;
+} esfm_tsdf_options;
+void esfm_tsdf_options_default(esfm_tsdf_options *opt);
+int esfm_tsdf_integrate(esfm_ctx *ctx, int n_views, int rows, int cols, int channels, const uint8_t *images /*may be NULL*/,
+                        const float *K4 /*4 each*/, const float *poses /*12 each*/, const float *depth, const esfm_tsdf_grid *grid,
+                        const esfm_tsdf_options *opt, float *tsdf, int32_t *weight, uint8_t *rgb /*3 each, may be NULL; needs images*/);
+int esfm_tsdf_extract(esfm_ctx *ctx, const esfm_tsdf_grid *grid, const float *tsdf, const int32_t *weight,
+                      const uint8_t *rgb /*may be NULL*/, const esfm_tsdf_options *opt, int max_vertices, int max_triangles,
+                      float *vertices, float *normals /*may be NULL*/, uint8_t *vertex_rgb /*may be NULL; needs rgb*/,
+                      int32_t *triangles /*3 each*/, int32_t *n_vertices, int32_t *n_triangles);
+int esfm_mvs_mesh(esfm_ctx *ctx, int n_views, int rows, int cols, int channels, const uint8_t *images /*may be NULL*/,
+                  const float *K4 /*4 each*/, const float *poses /*12 each*/, const float *depth, const esfm_tsdf_grid *grid,
+                  const esfm_tsdf_options *opt, int max_vertices, int max_triangles, float *vertices, float *normals /*may be NULL*/,
+                  uint8_t *vertex_rgb /*may be NULL; needs images*/, int32_t *triangles /*3 each*/, int32_t *n_vertices,
+                  int32_t *n_triangles);
+
 #ifdef __cplusplus
 }
 #endif
