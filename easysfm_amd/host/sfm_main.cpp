@@ -82,18 +82,21 @@ int main(int argc, char **argv)
     // optional 14th argument: the match filter -- ratio (the reference's, default), cross (mutual nearest neighbours) or ratio+cross,
     // or one of these with +guided appended (a second, epipolar-guided pass over the verified pairs; the union is kept);
     // optional 15th (needs the 14th): a dense .ply path, or none; optional 16th (needs the 15th): a .ply path for the merged dense cloud
-    // (one oriented point per voxel), or none; optional 17th (needs the 16th): a .ply path for the surface mesh, or none
+    // (one oriented point per voxel), or none; optional 17th (needs the 16th): a .ply path for the surface mesh, or none; clean:mesh.ply
+    // cleans the mesh with the defaults of esfm.h "Mesh clean-up" before it is written to mesh.ply
     const std::string filter_arg = argc >= 15 ? argv[14] : "ratio";
     const std::string guided_suffix = "+guided";
     const bool guided = filter_arg.size() > guided_suffix.size() && filter_arg.compare(filter_arg.size() - guided_suffix.size(), guided_suffix.size(), guided_suffix) == 0;
     const std::string match_filter = guided ? filter_arg.substr(0, filter_arg.size() - guided_suffix.size()) : filter_arg;      // the first pass's filter
     const std::string dense_file = argc >= 16 && std::string(argv[15]) != "none" ? argv[15] : "";
     const std::string merged_file = argc >= 17 && std::string(argv[16]) != "none" ? argv[16] : "";
-    const std::string mesh_file = argc == 18 && std::string(argv[17]) != "none" ? argv[17] : "";
+    const std::string mesh_arg = argc == 18 && std::string(argv[17]) != "none" ? argv[17] : "";
+    const bool clean_mesh = mesh_arg.compare(0, 6, "clean:") == 0;
+    const std::string mesh_file = clean_mesh ? mesh_arg.substr(6) : mesh_arg;
     if (argc < 14 || argc > 18 || (match_filter != "ratio" && match_filter != "cross" && match_filter != "ratio+cross")) {
         std::cerr << "usage: sfm_native image_folder image_list calib_K_file calib_distort_file output.ply feature_type(S | O | I) feature_parameter "
                      "repro_dis_ransac find_init_frames ba_calib_change_tolerance ba_frequency launch_viewer view_sphere [match_filter: ratio | cross | ratio+cross | "
-                     "ratio+guided | cross+guided | ratio+cross+guided [dense.ply | none [merged.ply | none [mesh.ply | none]]]]"
+                     "ratio+guided | cross+guided | ratio+cross+guided [dense.ply | none [merged.ply | none [mesh.ply | clean:mesh.ply | none]]]]"
                   << std::endl;
         return 2;
     }
@@ -414,6 +417,12 @@ int main(int argc, char **argv)
             if (!mesh_file.empty()) {
                 std::cout << "Dense mesh: [" << mesh.vertices.size() << "] vertices, [" << mesh.triangles.size() / 3 << "] triangles from [" << mesh.dims[0]
                           << "] x [" << mesh.dims[1] << "] x [" << mesh.dims[2] << "] voxels of [" << mesh.voxel_size << "]." << std::endl;
+                if (clean_mesh) {
+                    int n_before = 0, n_after = 0;
+                    if (!dr.cleanMesh(mesh, &n_before, &n_after)) return 3;
+                    std::cout << "Mesh clean: [" << n_after << "] of [" << n_before << "] components kept, [" << mesh.vertices.size() << "] vertices, ["
+                              << mesh.triangles.size() / 3 << "] triangles." << std::endl;
+                }
                 const std::filesystem::path mesh_dir = std::filesystem::path(mesh_file).parent_path();
                 if (!mesh_dir.empty()) std::filesystem::create_directories(mesh_dir);
                 if (!io.writePlyMesh(mesh_file, mesh)) return 3;

@@ -1,7 +1,8 @@
 """Surface reconstruction over the C ABI (include/esfm.h, "Surface reconstruction"): depth maps into a truncated signed
 distance volume (``tsdf_integrate``), an indexed triangle mesh out of it by marching tetrahedra (``tsdf_extract``), and both
 with the volume staying on the device (``mvs_mesh``).  ``dense_mesh`` takes what the pipeline holds after its final bundle
-adjustment, as ``mvs.dense_merge`` does, and ends in a mesh instead of a point cloud."""
+adjustment, as ``mvs.dense_merge`` does, and ends in a mesh instead of a point cloud.  ``mesh_components`` and ``mesh_clean``
+(esfm.h, "Mesh clean-up") label a mesh's connected pieces, drop the small ones, smooth the rest and recompute its normals."""
 from __future__ import annotations
 
 import ctypes as C
@@ -9,7 +10,7 @@ from typing import Optional, Sequence, Tuple
 
 import numpy as np
 
-from ._lib import Context, MVSOptions, TSDFGrid, TSDFOptions, check, default_context, lib
+from ._lib import Context, MeshCleanOptions, MVSOptions, TSDFGrid, TSDFOptions, check, default_context, lib
 from .mvs import MergeOptions, _views, default_mvs_options, frame_arrays, merge_voxel_size, mvs_depth_maps, mvs_fuse, mvs_plan
 from .types import Frame, SparsePointCloud
 
@@ -209,5 +210,57 @@ def dense_mesh(frames: Sequence[Frame], process_frame_id: Sequence[bool], cloud:
     return mesh_arrays(imgs, K4, poses, nb, depth, opt, mesh_opt, ctx)
 
 
-__all__ = ["TSDFGrid", "TSDFOptions", "MeshOptions", "default_tsdf_options", "tsdf_grid", "tsdf_integrate", "tsdf_extract", "mvs_mesh",
-           "masked_depth", "mesh_grid", "mesh_arrays", "dense_mesh"]
+def default_mesh_clean_options() -> MeshCleanOptions:
+    """esfm_mesh_clean_options_default: components of at least 64 triangles and 1 % of the largest, 5 Taubin iterations with
+    lambda 0.5 and mu -0.53, border vertices pinned."""
+    opt = MeshCleanOptions()
+    lib().esfm_mesh_clean_options_default(C.byref(opt))
+    return opt
+
+
+def _triangle_array(triangles) -> np.ndarray:
+    t = np.ascontiguousarray(triangles, np.int32)
+    if t.size % 3:
+        raise ValueError("triangles must hold 3 indices each")
+    return t.reshape(-1, 3)
+
+
+def mesh_components(triangles, n_vertices: int, ctx: Optional[Context] = None):
+    """esfm_mesh_components.  Returns (labels [V] int32: the smallest vertex index of each vertex's component, tri_count [V]
+    int32: a component's triangle count at its label vertex and 0 elsewhere, the number of components)."""
+    ctx = ctx or default_context()
+    t = _triangle_array(triangles)
+    labels = np.zeros(max(int(n_vertices), 0), np.int32)
+    count = np.zeros(max(int(n_vertices), 0), np.int32)
+    n = C.c_int32(0)
+    check(lib().esfm_mesh_components(ctx.handle, int(n_vertices), len(t), _ptr(t), _ptr(labels), _ptr(count), C.byref(n)))
+    return labels, count, n.value
+
+
+def mesh_clean(vertices, rgb, triangles, opt: Optional[MeshCleanOptions] = None, ctx: Optional[Context] = None, return_maps: bool = False):
+    """esfm_mesh_clean on vertices [V, 3] float32, rgb [V, 3] uint8 or None and triangles [T, 3] int32.  Returns (vertices,
+    normals, rgb or None, triangles) of the cleaned mesh, and with return_maps also (vertex_map, triangle_map): the old index of
+    every new vertex and triangle."""
+    opt = opt or default_mesh_clean_options()
+    ctx = ctx or default_context()
+    v = np.ascontiguousarray(vertices, np.float32).reshape(-1, 3)
+    c = np.ascontiguousarray(rgb, np.uint8).reshape(-1, 3) if rgb is not None else None
+    if c is not None and len(c) != len(v):
+        raise ValueError("rgb must hold one colour per vertex")
+    t = _triangle_array(triangles)
+    out_v, out_n = np.zeros_like(v), np.zeros_like(v)
+    out_c = np.zeros_like(c) if c is not None else None
+    out_t = np.zeros_like(t)
+    vmap = np.zeros(len(v), np.int32) if return_maps else None
+    tmap = np.zeros(len(t), np.int32) if return_maps else None
+    nv, nt = C.c_int32(0), C.c_int32(0)
+    check(lib().esfm_mesh_clean(ctx.handle, len(v), len(t), _ptr(v), _ptr(c), _ptr(t), C.byref(opt), _ptr(out_v), _ptr(out_n), _ptr(out_c),
+                                _ptr(out_t), _ptr(vmap), _ptr(tmap), C.byref(nv), C.byref(nt)))
+    cut = lambda a, m: None if a is None else a[:m].copy()
+    out = (cut(out_v, nv.value), cut(out_n, nv.value), cut(out_c, nv.value), cut(out_t, nt.value))
+    return out + (cut(vmap, nv.value), cut(tmap, nt.value)) if return_maps else out
+
+
+__all__ = ["TSDFGrid", "TSDFOptions", "MeshOptions", "MeshCleanOptions", "default_tsdf_options", "default_mesh_clean_options", "tsdf_grid",
+           "tsdf_integrate", "tsdf_extract", "mvs_mesh", "masked_depth", "mesh_grid", "mesh_arrays", "dense_mesh", "mesh_components",
+           "mesh_clean"]

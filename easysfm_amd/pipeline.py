@@ -18,7 +18,7 @@ from .ba import BundleAdjustment
 from .cloud import CProceesing, write_ply, write_ply_mesh, write_ply_normals
 from .matching import DescriptorBank, FeatureMatching, PairMatcher
 from .motion import MotionEstimator, _dehomogenise, find_essential_pairs, pixel2cam, recover_pose_pairs, triangulate_pairs
-from .mesh import MeshOptions, mesh_arrays
+from .mesh import MeshCleanOptions, MeshOptions, mesh_arrays, mesh_clean, mesh_components
 from .mvs import MergeOptions, default_mvs_options, dense_reconstruction, frame_arrays, merge_arrays
 from .types import DMatch, Frame, SparsePointCloud
 
@@ -161,7 +161,8 @@ def propagate_track_ids(frames: Sequence[Frame], graph: List[List[FramePair]]):
 def run_sfm(frames: List[Frame], output_file: Optional[str] = None, use_feature: str = "S", ransac_reproj_distance: float = 1.0,
             use_track_frames_as_init: bool = True, fix_calib_tolerance_BA: float = 0.0, frequency_BA: int = 4,
             ctx: Optional[Context] = None, verbose: bool = False, match_filter: str = "ratio", dense_output_file: Optional[str] = None,
-            dense_merged_output_file: Optional[str] = None, dense_mesh_output_file: Optional[str] = None):
+            dense_merged_output_file: Optional[str] = None, dense_mesh_output_file: Optional[str] = None,
+            dense_mesh_clean: Optional[MeshCleanOptions] = None):
     """sfm.cpp:128-339.  Returns (sparse cloud before the final filter, filtered cloud, img_match_graph).
     dense_output_file: after the final BA and the sparse .ply, run dense_reconstruct on the registered frames and the cloud
     before the filter (it carries the track ids) and write the dense cloud there (esfm.h "Dense reconstruction").
@@ -169,7 +170,10 @@ def run_sfm(frames: List[Frame], output_file: Optional[str] = None, use_feature:
     "Dense-cloud merge", mvs.dense_merge's defaults) and write it there with write_ply_normals.
     dense_mesh_output_file: integrate the depth maps, masked to the pixels the fusion kept, into a signed distance volume and
     write the triangle mesh extracted from it there with write_ply_mesh (esfm.h "Surface reconstruction", mesh.dense_mesh's
-    defaults); prints one "Dense mesh:" line."""
+    defaults); prints one "Dense mesh:" line.
+    dense_mesh_clean: with dense_mesh_output_file, clean that mesh with these options before it is written (esfm.h "Mesh
+    clean-up": small components dropped, Taubin smoothing, normals from the faces); prints one "Mesh clean:" line.  None: the
+    mesh is written as extracted."""
     ctx = ctx or default_context()
     fm, ee = FeatureMatching(ctx), MotionEstimator(ctx)
     for f in frames:
@@ -244,5 +248,10 @@ def run_sfm(frames: List[Frame], output_file: Optional[str] = None, use_feature:
             vertices, normals, rgb, triangles, grid = mesh_arrays(imgs, K4, poses, nb, depth, default_mvs_options(), MeshOptions(), ctx)
             print(f"Dense mesh: [{len(vertices)}] vertices, [{len(triangles)}] triangles from [{grid.dims[0]}] x [{grid.dims[1]}] x "
                   f"[{grid.dims[2]}] voxels of [{grid.voxel_size:g}].")
+            if dense_mesh_clean is not None:
+                n_before = mesh_components(triangles, len(vertices), ctx)[2]
+                vertices, normals, rgb, triangles = mesh_clean(vertices, rgb, triangles, dense_mesh_clean, ctx)
+                n_after = mesh_components(triangles, len(vertices), ctx)[2]
+                print(f"Mesh clean: [{n_after}] of [{n_before}] components kept, [{len(vertices)}] vertices, [{len(triangles)}] triangles.")
             write_ply_mesh(dense_mesh_output_file, vertices, normals, rgb, triangles)
     return cloud, out, graph

@@ -929,6 +929,64 @@ int esfm_mvs_mesh(esfm_ctx *ctx, int n_views, int rows, int cols, int channels, 
                   uint8_t *vertex_rgb /*may be NULL; needs images*/, int32_t *triangles /*3 each*/, int32_t *n_vertices,
                   int32_t *n_triangles);
 
+/* ---- Mesh clean-up: component filter, Taubin smoothing, face normals ----------------------------------
+ * An indexed triangle mesh (e.g. esfm_mvs_mesh's) loses its small connected pieces, is low-pass filtered without shrinking,
+ * and gets vertex normals from its faces.  Every step is a rule on sorted key lists with a fixed operation order, so nothing
+ * depends on scheduling; tests/mesh_clean_ref.py restates this text in numpy and the GPU reproduces it bit for bit.  All
+ * arithmetic is f32, no mul + add contraction, correctly rounded division and sqrtf.
+ *
+ * Input: V vertices (3 f32 each), vertex_rgb optional (3 u8 each), T triangles (3 int32 each); 0 <= V <= 2^30,
+ * 0 <= T <= 2^28.  A triangle index outside 0 .. V - 1 is rejected.  Triangles that repeat an index are legal: the rules
+ * below are stated on key lists and so say what happens to them.
+ *
+ * Components: two vertices are connected if a triangle holds both; label[v] is the smallest vertex index of v's component (a
+ * vertex in no triangle is its own component).  A triangle belongs to the component of its first corner; count[c] is the
+ * component's number of triangles, largest the maximum count.  A component is kept iff count >= min_component_triangles and
+ * 1000 * (int64)count >= (int64)min_component_permille * largest.
+ * Compaction: kept vertices and kept triangles keep their ascending order, indices are remapped, colours are carried through;
+ * vertex_map / triangle_map (may be NULL) receive the old index of every new vertex / triangle.  The outputs have capacity V
+ * and T; *n_out_vertices and *n_out_triangles are always written.  T == 0 or nothing kept: ESFM_OK with 0 and 0.
+ *
+ * Adjacency, on the output mesh: the multiset of directed keys (a << 32) | b over the six ordered corner pairs (0,1), (1,0),
+ * (1,2), (2,1), (2,0), (0,2) of every triangle, without the keys that have a == b.  N(i) is the ascending list of the distinct
+ * b with a key (i, b); the multiplicity of (i, b) is the number of triangle sides on the edge {i, b}.  Vertex i is pinned iff
+ * some key (i, b) has a multiplicity other than 2 (borders and non-manifold edges).
+ *
+ * Smoothing (Taubin lambda | mu): passes s = 0 .. 2 smooth_iterations - 1 with w = smooth_lambda on even s, smooth_mu on odd
+ * s; every vertex reads the positions p the previous pass left (Jacobi).  k = |N(i)|.  If k == 0, or pin_boundary is set and i
+ * is pinned: q_i = p_i.  Otherwise per coordinate a: m = p[n_0]_a, then m += p[n_j]_a for j = 1 .. k - 1 in list order;
+ * c = m / (float)k; q_ia = p_ia + w * (c - p_ia).
+ *
+ * Normals, always recomputed from the output mesh: the face vector of triangle t is e1 = p1 - p0, e2 = p2 - p0,
+ * f = (e1_1 e2_2 - e1_2 e2_1, e1_2 e2_0 - e1_0 e2_2, e1_0 e2_1 - e1_1 e2_0), every product rounded.  For vertex i, n is the
+ * sequential f32 sum, starting from the first, of f over the keys (i << 32) | (3 t + corner) in ascending key order;
+ * L = sqrtf((n0 n0 + n1 n1) + n2 n2); the normal is n / L, or (0, 0, 0) if L is 0 or not finite.  With esfm_tsdf_extract's
+ * winding it points to free space as the gradient normals do; a caller who wants those indexes them with vertex_map.
+ *
+ * Options (esfm_mesh_clean_options_default): min_component_triangles 64 (>= 1), min_component_permille 10 (0..1000),
+ * smooth_iterations 5 (0..1000), smooth_lambda 0.5 (finite, in (0, 1]), smooth_mu -0.53 (finite, in [-1.5, 0]), pin_boundary 1
+ * (0 or 1).
+ *
+ * esfm_mesh_components: the labelling alone.  labels: V int32; tri_count (may be NULL): V int32, a component's count at its
+ * label vertex and 0 elsewhere; *n_components.
+ * esfm_mesh_clean: the whole chain.  out_normals, out_rgb (needs vertex_rgb), vertex_map and triangle_map may be NULL.
+ * Rejected with ESFM_ERR_INVALID_ARG, before the device is looked at and with nothing written: an option out of range, a
+ * negative count or one above the limits, a triangle index outside 0 .. V - 1, a required pointer that is NULL, out_rgb
+ * without vertex_rgb.  Both take host pointers; without a usable device they return ESFM_ERR_NO_DEVICE (no CPU fallback). */
+typedef struct esfm_mesh_clean_options {
+    int32_t min_component_triangles, min_component_permille, smooth_iterations;
+    float smooth_lambda, smooth_mu;
+    int32_t pin_boundary;
+} esfm_mesh_clean_options;
+void esfm_mesh_clean_options_default(esfm_mesh_clean_options *opt);
+int esfm_mesh_components(esfm_ctx *ctx, int n_vertices, int n_triangles, const int32_t *triangles /*3 each*/, int32_t *labels /*V*/,
+                         int32_t *tri_count /*V, may be NULL*/, int32_t *n_components);
+int esfm_mesh_clean(esfm_ctx *ctx, int n_vertices, int n_triangles, const float *vertices /*3 each*/,
+                    const uint8_t *vertex_rgb /*3 each, may be NULL*/, const int32_t *triangles /*3 each*/,
+                    const esfm_mesh_clean_options *opt, float *out_vertices, float *out_normals /*may be NULL*/,
+                    uint8_t *out_rgb /*may be NULL; needs vertex_rgb*/, int32_t *out_triangles, int32_t *vertex_map /*may be NULL*/,
+                    int32_t *triangle_map /*may be NULL*/, int32_t *n_out_vertices, int32_t *n_out_triangles);
+
 #ifdef __cplusplus
 }
 #endif
