@@ -23,9 +23,9 @@ from .features import (detectFeaturesORB, detectFeaturesSIFT, detectFeaturesSURF
 from .mvs import (MergeOptions, MVSNormalOptions, MVSOptions, default_mvs_normal_options, default_mvs_options, dense_merge,  # noqa: F401
                   dense_reconstruct, dense_reconstruction, merge_arrays, merge_voxel_size, mvs_depth_maps, mvs_fuse, mvs_normals,
                   mvs_plan)
-from .mesh import (MeshCleanOptions, MeshOptions, TSDFGrid, TSDFOptions, default_mesh_clean_options, default_tsdf_options,  # noqa: F401
-                   dense_mesh, masked_depth, mesh_arrays, mesh_clean, mesh_components, mesh_grid, mvs_mesh, tsdf_extract, tsdf_grid,
-                   tsdf_integrate)
+from .mesh import (MeshCleanOptions, MeshOptions, MeshSimplifyOptions, TSDFGrid, TSDFOptions, default_mesh_clean_options,  # noqa: F401
+                   default_mesh_simplify_options, default_tsdf_options, dense_mesh, masked_depth, mesh_arrays, mesh_clean,
+                   mesh_components, mesh_grid, mesh_simplify, mvs_mesh, tsdf_extract, tsdf_grid, tsdf_integrate)
 from .pipeline import MATCH_FILTERS, FramePair, match_and_verify_all_pairs, propagate_track_ids, run_sfm  # noqa: F401
 
 __version__ = "0.1.0"

@@ -48,6 +48,7 @@ EXPORTED_SYMBOLS = [
     "esfm_mvs_normal_options_default", "esfm_mvs_normals", "esfm_mvs_fuse_ex", "esfm_cloud_voxel_merge",
     "esfm_tsdf_options_default", "esfm_tsdf_integrate", "esfm_tsdf_extract", "esfm_mvs_mesh",
     "esfm_mesh_clean_options_default", "esfm_mesh_components", "esfm_mesh_clean",
+    "esfm_mesh_simplify_options_default", "esfm_mesh_simplify",
 ]
 
 
@@ -117,6 +118,11 @@ class MeshCleanOptions(C.Structure):
     """esfm_mesh_clean_options (include/esfm.h, "Mesh clean-up")."""
     _fields_ = [("min_component_triangles", C.c_int32), ("min_component_permille", C.c_int32), ("smooth_iterations", C.c_int32),
                 ("smooth_lambda", C.c_float), ("smooth_mu", C.c_float), ("pin_boundary", C.c_int32)]
+
+
+class MeshSimplifyOptions(C.Structure):
+    """esfm_mesh_simplify_options (include/esfm.h, "Mesh simplification")."""
+    _fields_ = [("regularisation", C.c_float), ("use_quadric", C.c_int32)]
 
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p)
@@ -239,6 +245,10 @@ def lib() -> C.CDLL:
     L.esfm_mesh_clean_options_default.restype = None
     L.esfm_mesh_components.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, i32p]
     L.esfm_mesh_clean.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, C.POINTER(MeshCleanOptions), vp, vp, vp, vp, vp, vp, i32p, i32p]
+    L.esfm_mesh_simplify_options_default.argtypes = [C.POINTER(MeshSimplifyOptions)]
+    L.esfm_mesh_simplify_options_default.restype = None
+    L.esfm_mesh_simplify.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, C.c_float, C.POINTER(MeshSimplifyOptions), vp, vp, vp, vp, vp, vp,
+                                     i32p, i32p]
     L.esfm_solve_pnp_ransac.argtypes = [vp, vp, vp, C.c_int, vp, C.c_int, C.c_double, C.c_double, vp, vp, vp, vp, i32p, i32p]
     L.esfm_ba_problem_set_params.argtypes = [vp, vp, vp]
     L.esfm_ba_problem_solve.argtypes = [vp, C.POINTER(BAOptions), ALLREDUCE_FN, vp, C.POINTER(BASummary)]

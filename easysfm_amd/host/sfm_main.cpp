@@ -83,7 +83,8 @@ int main(int argc, char **argv)
     // or one of these with +guided appended (a second, epipolar-guided pass over the verified pairs; the union is kept);
     // optional 15th (needs the 14th): a dense .ply path, or none; optional 16th (needs the 15th): a .ply path for the merged dense cloud
     // (one oriented point per voxel), or none; optional 17th (needs the 16th): a .ply path for the surface mesh, or none; clean:mesh.ply
-    // cleans the mesh with the defaults of esfm.h "Mesh clean-up" before it is written to mesh.ply
+    // cleans the mesh with the defaults of esfm.h "Mesh clean-up" before it is written to mesh.ply, simplify:mesh.ply merges the
+    // vertices of every cell of two voxels' side (esfm.h "Mesh simplification"), clean+simplify:mesh.ply does both in that order
     const std::string filter_arg = argc >= 15 ? argv[14] : "ratio";
     const std::string guided_suffix = "+guided";
     const bool guided = filter_arg.size() > guided_suffix.size() && filter_arg.compare(filter_arg.size() - guided_suffix.size(), guided_suffix.size(), guided_suffix) == 0;
@@ -91,12 +92,15 @@ int main(int argc, char **argv)
     const std::string dense_file = argc >= 16 && std::string(argv[15]) != "none" ? argv[15] : "";
     const std::string merged_file = argc >= 17 && std::string(argv[16]) != "none" ? argv[16] : "";
     const std::string mesh_arg = argc == 18 && std::string(argv[17]) != "none" ? argv[17] : "";
-    const bool clean_mesh = mesh_arg.compare(0, 6, "clean:") == 0;
-    const std::string mesh_file = clean_mesh ? mesh_arg.substr(6) : mesh_arg;
+    const bool both_mesh = mesh_arg.compare(0, 15, "clean+simplify:") == 0;
+    const bool clean_mesh = both_mesh || mesh_arg.compare(0, 6, "clean:") == 0;
+    const bool simplify_mesh = both_mesh || mesh_arg.compare(0, 9, "simplify:") == 0;
+    const std::string mesh_file = mesh_arg.substr(both_mesh ? 15 : clean_mesh ? 6 : simplify_mesh ? 9 : 0);
     if (argc < 14 || argc > 18 || (match_filter != "ratio" && match_filter != "cross" && match_filter != "ratio+cross")) {
         std::cerr << "usage: sfm_native image_folder image_list calib_K_file calib_distort_file output.ply feature_type(S | O | I) feature_parameter "
                      "repro_dis_ransac find_init_frames ba_calib_change_tolerance ba_frequency launch_viewer view_sphere [match_filter: ratio | cross | ratio+cross | "
-                     "ratio+guided | cross+guided | ratio+cross+guided [dense.ply | none [merged.ply | none [mesh.ply | clean:mesh.ply | none]]]]"
+                     "ratio+guided | cross+guided | ratio+cross+guided [dense.ply | none [merged.ply | none [simplify:mesh.ply | "
+                     "clean+simplify:mesh.ply | mesh.ply | clean:mesh.ply | none]]]]"
                   << std::endl;
         return 2;
     }
@@ -422,6 +426,13 @@ int main(int argc, char **argv)
                     if (!dr.cleanMesh(mesh, &n_before, &n_after)) return 3;
                     std::cout << "Mesh clean: [" << n_after << "] of [" << n_before << "] components kept, [" << mesh.vertices.size() << "] vertices, ["
                               << mesh.triangles.size() / 3 << "] triangles." << std::endl;
+                }
+                if (simplify_mesh) {
+                    const size_t n_v = mesh.vertices.size(), n_t = mesh.triangles.size() / 3;
+                    float cell = 0.f;
+                    if (!dr.simplifyMesh(mesh, 2.0f, &cell)) return 3;
+                    std::cout << "Mesh simplify: [" << n_v << "] vertices, [" << n_t << "] triangles into [" << mesh.vertices.size() << "] vertices, ["
+                              << mesh.triangles.size() / 3 << "] triangles, cells of [" << cell << "]." << std::endl;
                 }
                 const std::filesystem::path mesh_dir = std::filesystem::path(mesh_file).parent_path();
                 if (!mesh_dir.empty()) std::filesystem::create_directories(mesh_dir);

@@ -2,7 +2,8 @@
 distance volume (``tsdf_integrate``), an indexed triangle mesh out of it by marching tetrahedra (``tsdf_extract``), and both
 with the volume staying on the device (``mvs_mesh``).  ``dense_mesh`` takes what the pipeline holds after its final bundle
 adjustment, as ``mvs.dense_merge`` does, and ends in a mesh instead of a point cloud.  ``mesh_components`` and ``mesh_clean``
-(esfm.h, "Mesh clean-up") label a mesh's connected pieces, drop the small ones, smooth the rest and recompute its normals."""
+(esfm.h, "Mesh clean-up") label a mesh's connected pieces, drop the small ones, smooth the rest and recompute its normals;
+``mesh_simplify`` (esfm.h, "Mesh simplification") merges the vertices of each cell of a regular grid into one."""
 from __future__ import annotations
 
 import ctypes as C
@@ -10,7 +11,7 @@ from typing import Optional, Sequence, Tuple
 
 import numpy as np
 
-from ._lib import Context, MeshCleanOptions, MVSOptions, TSDFGrid, TSDFOptions, check, default_context, lib
+from ._lib import Context, MeshCleanOptions, MeshSimplifyOptions, MVSOptions, TSDFGrid, TSDFOptions, check, default_context, lib
 from .mvs import MergeOptions, _views, default_mvs_options, frame_arrays, merge_voxel_size, mvs_depth_maps, mvs_fuse, mvs_plan
 from .types import Frame, SparsePointCloud
 
@@ -261,6 +262,42 @@ def mesh_clean(vertices, rgb, triangles, opt: Optional[MeshCleanOptions] = None,
     return out + (cut(vmap, nv.value), cut(tmap, nt.value)) if return_maps else out
 
 
-__all__ = ["TSDFGrid", "TSDFOptions", "MeshOptions", "MeshCleanOptions", "default_tsdf_options", "default_mesh_clean_options", "tsdf_grid",
-           "tsdf_integrate", "tsdf_extract", "mvs_mesh", "masked_depth", "mesh_grid", "mesh_arrays", "dense_mesh", "mesh_components",
-           "mesh_clean"]
+def default_mesh_simplify_options() -> MeshSimplifyOptions:
+    """esfm_mesh_simplify_options_default: regularisation 1e-3, quadric placement on."""
+    opt = MeshSimplifyOptions()
+    lib().esfm_mesh_simplify_options_default(C.byref(opt))
+    return opt
+
+
+def mesh_simplify(vertices, rgb, triangles, cell: float, origin=None, opt: Optional[MeshSimplifyOptions] = None,
+                  ctx: Optional[Context] = None, return_maps: bool = False):
+    """esfm_mesh_simplify on vertices [V, 3] float32, rgb [V, 3] uint8 or None and triangles [T, 3] int32: all vertices of one
+    grid cell of side `cell` (the grid starts at `origin`; None = the per-axis minimum of the vertices) become one.  Returns
+    (vertices, normals, rgb or None, triangles) of the simplified mesh, and with return_maps also (vertex_map [V]: the new vertex
+    of every old vertex or -1, triangle_map: the old index of every new triangle)."""
+    opt = opt or default_mesh_simplify_options()
+    ctx = ctx or default_context()
+    v = np.ascontiguousarray(vertices, np.float32).reshape(-1, 3)
+    c = np.ascontiguousarray(rgb, np.uint8).reshape(-1, 3) if rgb is not None else None
+    if c is not None and len(c) != len(v):
+        raise ValueError("rgb must hold one colour per vertex")
+    t = _triangle_array(triangles)
+    if origin is None:
+        origin = v.min(axis=0) if len(v) else np.zeros(3, np.float32)
+    o = np.ascontiguousarray(origin, np.float32).reshape(3)
+    out_v, out_n = np.zeros_like(v), np.zeros_like(v)
+    out_c = np.zeros_like(c) if c is not None else None
+    out_t = np.zeros_like(t)
+    vmap = np.zeros(len(v), np.int32) if return_maps else None
+    tmap = np.zeros(len(t), np.int32) if return_maps else None
+    nv, nt = C.c_int32(0), C.c_int32(0)
+    check(lib().esfm_mesh_simplify(ctx.handle, len(v), len(t), _ptr(v), _ptr(c), _ptr(t), _ptr(o), float(cell), C.byref(opt), _ptr(out_v),
+                                   _ptr(out_n), _ptr(out_c), _ptr(out_t), _ptr(vmap), _ptr(tmap), C.byref(nv), C.byref(nt)))
+    cut = lambda a, m: None if a is None else a[:m].copy()
+    out = (cut(out_v, nv.value), cut(out_n, nv.value), cut(out_c, nv.value), cut(out_t, nt.value))
+    return out + (vmap, cut(tmap, nt.value)) if return_maps else out
+
+
+__all__ = ["TSDFGrid", "TSDFOptions", "MeshOptions", "MeshCleanOptions", "MeshSimplifyOptions", "default_tsdf_options",
+           "default_mesh_clean_options", "default_mesh_simplify_options", "tsdf_grid", "tsdf_integrate", "tsdf_extract", "mvs_mesh",
+           "masked_depth", "mesh_grid", "mesh_arrays", "dense_mesh", "mesh_components", "mesh_clean", "mesh_simplify"]

@@ -18,7 +18,7 @@ from .ba import BundleAdjustment
 from .cloud import CProceesing, write_ply, write_ply_mesh, write_ply_normals
 from .matching import DescriptorBank, FeatureMatching, PairMatcher
 from .motion import MotionEstimator, _dehomogenise, find_essential_pairs, pixel2cam, recover_pose_pairs, triangulate_pairs
-from .mesh import MeshCleanOptions, MeshOptions, mesh_arrays, mesh_clean, mesh_components
+from .mesh import MeshCleanOptions, MeshOptions, mesh_arrays, mesh_clean, mesh_components, mesh_simplify
 from .mvs import MergeOptions, default_mvs_options, dense_reconstruction, frame_arrays, merge_arrays
 from .types import DMatch, Frame, SparsePointCloud
 
@@ -162,7 +162,7 @@ def run_sfm(frames: List[Frame], output_file: Optional[str] = None, use_feature:
             use_track_frames_as_init: bool = True, fix_calib_tolerance_BA: float = 0.0, frequency_BA: int = 4,
             ctx: Optional[Context] = None, verbose: bool = False, match_filter: str = "ratio", dense_output_file: Optional[str] = None,
             dense_merged_output_file: Optional[str] = None, dense_mesh_output_file: Optional[str] = None,
-            dense_mesh_clean: Optional[MeshCleanOptions] = None):
+            dense_mesh_clean: Optional[MeshCleanOptions] = None, dense_mesh_simplify: Optional[float] = None):
     """sfm.cpp:128-339.  Returns (sparse cloud before the final filter, filtered cloud, img_match_graph).
     dense_output_file: after the final BA and the sparse .ply, run dense_reconstruct on the registered frames and the cloud
     before the filter (it carries the track ids) and write the dense cloud there (esfm.h "Dense reconstruction").
@@ -173,7 +173,10 @@ def run_sfm(frames: List[Frame], output_file: Optional[str] = None, use_feature:
     defaults); prints one "Dense mesh:" line.
     dense_mesh_clean: with dense_mesh_output_file, clean that mesh with these options before it is written (esfm.h "Mesh
     clean-up": small components dropped, Taubin smoothing, normals from the faces); prints one "Mesh clean:" line.  None: the
-    mesh is written as extracted."""
+    mesh is written as extracted.
+    dense_mesh_simplify: with dense_mesh_output_file, the side of a simplification cell in voxels of the signed distance volume:
+    after the optional clean-up all vertices of one cell, counted from the volume's origin, are merged into one (esfm.h "Mesh
+    simplification", default options); prints one "Mesh simplify:" line.  None: no simplification."""
     ctx = ctx or default_context()
     fm, ee = FeatureMatching(ctx), MotionEstimator(ctx)
     for f in frames:
@@ -253,5 +256,11 @@ def run_sfm(frames: List[Frame], output_file: Optional[str] = None, use_feature:
                 vertices, normals, rgb, triangles = mesh_clean(vertices, rgb, triangles, dense_mesh_clean, ctx)
                 n_after = mesh_components(triangles, len(vertices), ctx)[2]
                 print(f"Mesh clean: [{n_after}] of [{n_before}] components kept, [{len(vertices)}] vertices, [{len(triangles)}] triangles.")
+            if dense_mesh_simplify is not None:
+                n_v, n_t = len(vertices), len(triangles)
+                cell = float(np.float32(dense_mesh_simplify) * np.float32(grid.voxel_size))
+                vertices, normals, rgb, triangles = mesh_simplify(vertices, rgb, triangles, cell, np.array(grid.origin, np.float32), None, ctx)
+                print(f"Mesh simplify: [{n_v}] vertices, [{n_t}] triangles into [{len(vertices)}] vertices, [{len(triangles)}] triangles, "
+                      f"cells of [{cell:g}].")
             write_ply_mesh(dense_mesh_output_file, vertices, normals, rgb, triangles)
     return cloud, out, graph

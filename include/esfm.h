@@ -987,6 +987,70 @@ int esfm_mesh_clean(esfm_ctx *ctx, int n_vertices, int n_triangles, const float 
                     uint8_t *out_rgb /*may be NULL; needs vertex_rgb*/, int32_t *out_triangles, int32_t *vertex_map /*may be NULL*/,
                     int32_t *triangle_map /*may be NULL*/, int32_t *n_out_vertices, int32_t *n_out_triangles);
 
+/* ---- Mesh simplification: grid vertex clustering with quadric placement --------------------------------
+ * An indexed triangle mesh (e.g. esfm_mesh_clean's) is reduced by merging all vertices of one cell of a regular grid into one
+ * representative, placed where the cell's summed plane quadrics are smallest (Lindstrom's out-of-core simplification).  Every
+ * step is a rule on sorted key lists with a fixed operation order, so nothing depends on scheduling; tests/simplify_ref.py
+ * restates this text in numpy and the GPU reproduces it bit for bit.  No mul + add contraction anywhere, correctly rounded
+ * division and square root; sums are f64, start from +0.0 and add their terms one by one in the stated order.
+ *
+ * Input: V vertices (3 f32 each), vertex_rgb optional (3 u8 each), T triangles (3 int32 each), with the limits of the clean-up
+ * (0 <= V <= 2^30, 0 <= T <= 2^28, indices in 0 .. V - 1, repeated indices legal); origin[3] and cell, f32.
+ *
+ * Cells: per axis a, i_a = (int)floorf((p_a - origin_a) / cell) in f32.  Every index must lie in 0 .. 2^21 - 1 (a coordinate
+ * that is not finite fails this too).  key = (i_0 << 42) | (i_1 << 21) | i_2; the distinct keys in ascending order number the
+ * cells 0 .. C - 1, cell_of[v] is vertex v's cell number.  The cell centre is cc_a = origin_a + (i_a + 0.5) * cell in f64 from
+ * the f32 inputs.
+ *
+ * Per-cell sums.  Over the cell's n vertices in ascending vertex index: s_a += (double)p_a - cc_a; m_a = s_a / n.  Colours: the
+ * integer sum S per channel, the cell's colour is (2 S + n) / (2 n) in integer division.  Over the cell's triangle corners in
+ * ascending 3 t + corner -- the keys (cell_of[vertex] << 32) | (3 t + corner) in ascending order --, with p0, p1, p2 the
+ * corners of triangle t in its own order, in f64: e1 = p1 - p0, e2 = p2 - p0,
+ * N = (e1_1 e2_2 - e1_2 e2_1, e1_2 e2_0 - e1_0 e2_2, e1_0 e2_1 - e1_1 e2_0), L = sqrt((N_0 N_0 + N_1 N_1) + N_2 N_2).  A corner
+ * with L > 0 false adds nothing.  Otherwise D = -((N_0 d_0 + N_1 d_1) + N_2 d_2) with d = p0 - cc, and
+ * A_ab += (N_a N_b) / L for ab = 00, 01, 02, 11, 12, 22;  b_a += (N_a D) / L.  This is the area-weighted plane quadric about
+ * the cell centre.  A triangle with two or three corners in one cell is added once per corner.
+ *
+ * Placement: tau = (A_00 + A_11) + A_22.  If use_quadric is 0 or tau > 0 is false, x = m.  Otherwise r = (double)regularisation
+ * * tau, M = A + r I, g_a = r m_a - b_a, and (M x = g) by LDL^T without pivoting:
+ *   d0 = M_00; l10 = M_01 / d0; l20 = M_02 / d0; d1 = M_11 - l10 M_01; u = M_12 - l20 M_01; l21 = u / d1;
+ *   d2 = (M_22 - l20 M_02) - l21 u; y0 = g_0; y1 = g_1 - l10 y0; y2 = (g_2 - l20 y0) - l21 y1;
+ *   x_2 = y2 / d2; x_1 = y1 / d1 - l21 x_2; x_0 = (y0 / d0 - l10 x_1) - l20 x_2.
+ * If |x_a| <= (double)cell fails for some a (NaN and infinities fail it), x = m.  The representative is (float)(cc + x).
+ *
+ * Triangles: every corner is remapped through cell_of; a triangle that names a cell twice is dropped.  A survivor is rotated so
+ * that its smallest cell number comes first, (c, p, q); it is odd if p > q, even otherwise.  Survivors with the same unordered
+ * triple form a group.  A group with more members of one orientation than of the other keeps its lowest-numbered triangle of
+ * the majority orientation; a group with equal counts keeps nothing (two opposite faces on the same three vertices: removing
+ * both keeps a closed mesh closed).  Kept triangles keep their ascending input order and their input corner order.  Cells in no
+ * kept triangle are dropped; the others keep their ascending order and are renumbered.
+ *
+ * Normals: recomputed on the output mesh by the rule of "Mesh clean-up" (face-vector sums in incidence-key order).
+ *
+ * Outputs, capacities V and T: out_vertices, out_normals (may be NULL), out_rgb (may be NULL, needs vertex_rgb), out_triangles;
+ * vertex_map (may be NULL): V int32, the new vertex of every old vertex or -1; triangle_map (may be NULL): the old index of
+ * every new triangle; *n_out_vertices and *n_out_triangles are always written on ESFM_OK.  T == 0 or nothing kept: ESFM_OK with
+ * 0 and 0 (vertex_map is all -1).
+ *
+ * Options (esfm_mesh_simplify_options_default): regularisation 1e-3 (finite, in (0, 1]), use_quadric 1 (0 or 1; 0 places every
+ * representative at the cell mean cc + m).
+ *
+ * Rejected with ESFM_ERR_INVALID_ARG, before the device is looked at and with nothing written: an option out of range, cell not
+ * finite or <= 0, an origin that is not finite, a vertex outside the 2^21 cells per axis, a negative count or one above the
+ * limits, a triangle index outside 0 .. V - 1, a required pointer that is NULL, out_rgb without vertex_rgb.  The grouping of
+ * triangles holds three cell numbers in one 64-bit key: more than 2^21 occupied cells is ESFM_ERR_UNSUPPORTED, with nothing
+ * written (use a larger cell).  Host pointers; without a usable device ESFM_ERR_NO_DEVICE (no CPU fallback). */
+typedef struct esfm_mesh_simplify_options {
+    float regularisation;
+    int32_t use_quadric;
+} esfm_mesh_simplify_options;
+void esfm_mesh_simplify_options_default(esfm_mesh_simplify_options *opt);
+int esfm_mesh_simplify(esfm_ctx *ctx, int n_vertices, int n_triangles, const float *vertices /*3 each*/,
+                       const uint8_t *vertex_rgb /*3 each, may be NULL*/, const int32_t *triangles /*3 each*/, const float *origin /*3*/,
+                       float cell, const esfm_mesh_simplify_options *opt, float *out_vertices, float *out_normals /*may be NULL*/,
+                       uint8_t *out_rgb /*may be NULL; needs vertex_rgb*/, int32_t *out_triangles, int32_t *vertex_map /*V, may be NULL*/,
+                       int32_t *triangle_map /*may be NULL*/, int32_t *n_out_vertices, int32_t *n_out_triangles);
+
 #ifdef __cplusplus
 }
 #endif
