@@ -13,8 +13,8 @@ from .matching import (DescriptorBank, FeatureMatching, PairMatcher, knn_match_h
 from .ba import (BAProblem, BundleAdjustment, Comm, ba_solve, ba_solve_ex, ba_sweep_bytes_per_obs, default_options, line_search_next_step, reduced_plan, shard_points,  # noqa: F401
                  torch_allreduce_callback)
 
-from .cloud import (CProceesing, read_ply_mesh, read_ply_normals, read_ply_vertices, sor_filter, voxel_merge, write_ply,  # noqa: F401
-                    write_ply_mesh, write_ply_normals)
+from .cloud import (CProceesing, read_ply_mesh, read_ply_normals, read_ply_textured_mesh, read_ply_vertices, sor_filter,  # noqa: F401
+                    voxel_merge, write_ply, write_ply_mesh, write_ply_normals, write_ply_textured_mesh, write_png_rgb)
 from .motion import (MotionEstimator, find_essential_mat, find_essential_pairs, five_point_models, pixel2cam, ransac_sample_stream, recover_pose,  # noqa: F401
                      recover_pose_pairs, solve_pnp_ransac, triangulate_pairs, triangulate_points)
 
@@ -23,9 +23,10 @@ from .features import (detectFeaturesORB, detectFeaturesSIFT, detectFeaturesSURF
 from .mvs import (MergeOptions, MVSNormalOptions, MVSOptions, default_mvs_normal_options, default_mvs_options, dense_merge,  # noqa: F401
                   dense_reconstruct, dense_reconstruction, merge_arrays, merge_voxel_size, mvs_depth_maps, mvs_fuse, mvs_normals,
                   mvs_plan)
-from .mesh import (MeshCleanOptions, MeshOptions, MeshSimplifyOptions, TSDFGrid, TSDFOptions, default_mesh_clean_options,  # noqa: F401
-                   default_mesh_simplify_options, default_tsdf_options, dense_mesh, masked_depth, mesh_arrays, mesh_clean,
-                   mesh_components, mesh_grid, mesh_simplify, mvs_mesh, tsdf_extract, tsdf_grid, tsdf_integrate)
+from .mesh import (MeshCleanOptions, MeshOptions, MeshSimplifyOptions, MeshTextureOptions, TSDFGrid, TSDFOptions,  # noqa: F401
+                   default_mesh_clean_options, default_mesh_simplify_options, default_mesh_texture_options, default_tsdf_options,
+                   dense_mesh, masked_depth, mesh_arrays, mesh_clean, mesh_components, mesh_grid, mesh_simplify, mesh_texture,
+                   mesh_texture_bake, mesh_texture_views, mvs_mesh, tsdf_extract, tsdf_grid, tsdf_integrate)
 from .pipeline import MATCH_FILTERS, FramePair, match_and_verify_all_pairs, propagate_track_ids, run_sfm  # noqa: F401
 
 __version__ = "0.1.0"

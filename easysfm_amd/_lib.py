@@ -49,6 +49,7 @@ EXPORTED_SYMBOLS = [
     "esfm_tsdf_options_default", "esfm_tsdf_integrate", "esfm_tsdf_extract", "esfm_mvs_mesh",
     "esfm_mesh_clean_options_default", "esfm_mesh_components", "esfm_mesh_clean",
     "esfm_mesh_simplify_options_default", "esfm_mesh_simplify",
+    "esfm_mesh_texture_options_default", "esfm_mesh_texture_views", "esfm_mesh_texture_bake",
 ]
 
 
@@ -123,6 +124,11 @@ class MeshCleanOptions(C.Structure):
 class MeshSimplifyOptions(C.Structure):
     """esfm_mesh_simplify_options (include/esfm.h, "Mesh simplification")."""
     _fields_ = [("regularisation", C.c_float), ("use_quadric", C.c_int32)]
+
+
+class MeshTextureOptions(C.Structure):
+    """esfm_mesh_texture_options (include/esfm.h, "Mesh texturing")."""
+    _fields_ = [("min_cos", C.c_float), ("occlusion_tol", C.c_float)]
 
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p)
@@ -249,6 +255,11 @@ def lib() -> C.CDLL:
     L.esfm_mesh_simplify_options_default.restype = None
     L.esfm_mesh_simplify.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, C.c_float, C.POINTER(MeshSimplifyOptions), vp, vp, vp, vp, vp, vp,
                                      i32p, i32p]
+    L.esfm_mesh_texture_options_default.argtypes = [C.POINTER(MeshTextureOptions)]
+    L.esfm_mesh_texture_options_default.restype = None
+    L.esfm_mesh_texture_views.argtypes = [vp, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.POINTER(MeshTextureOptions), vp, vp, vp]
+    L.esfm_mesh_texture_bake.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, C.c_int,
+                                         C.c_int, vp, vp, i32p]
     L.esfm_solve_pnp_ransac.argtypes = [vp, vp, vp, C.c_int, vp, C.c_int, C.c_double, C.c_double, vp, vp, vp, vp, i32p, i32p]
     L.esfm_ba_problem_set_params.argtypes = [vp, vp, vp]
     L.esfm_ba_problem_solve.argtypes = [vp, C.POINTER(BAOptions), ALLREDUCE_FN, vp, C.POINTER(BASummary)]

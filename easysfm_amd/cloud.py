@@ -5,6 +5,7 @@
 from __future__ import annotations
 
 import ctypes as C
+import os
 from typing import Optional, Tuple
 
 import numpy as np
@@ -200,6 +201,92 @@ def read_ply_mesh(file_name: str):
     if m and np.any(faces[:, 0] != 3):
         raise ValueError("not a triangle mesh")
     return arr[:, :3].astype(np.float32), arr[:, 3:6].astype(np.float32), arr[:, 6:].astype(np.uint8), faces[:, 1:].astype(np.int32)
+
+
+def write_png_rgb(file_name: str, image) -> bool:
+    """An 8-bit RGB PNG of image [rows, cols, 3] uint8: one IDAT chunk, scanline filter 0 (the host layer's C++ writer stores the
+    same scanlines without compression; both decode to the same pixels)."""
+    import struct
+    import zlib
+    img = np.ascontiguousarray(image, np.uint8)
+    if img.ndim != 3 or img.shape[2] != 3 or img.shape[0] < 1 or img.shape[1] < 1:
+        raise ValueError("image must be [rows, cols, 3] with at least one pixel")
+    rows, cols = img.shape[:2]
+    raw = np.concatenate([np.zeros((rows, 1), np.uint8), img.reshape(rows, cols * 3)], axis=1).tobytes()
+
+    def chunk(kind: bytes, data: bytes) -> bytes:
+        return struct.pack(">I", len(data)) + kind + data + struct.pack(">I", zlib.crc32(kind + data) & 0xFFFFFFFF)
+    try:
+        with open(file_name, "wb") as f:
+            f.write(b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", cols, rows, 8, 2, 0, 0, 0)) + chunk(b"IDAT", zlib.compress(raw, 6)) +
+                    chunk(b"IEND", b""))
+    except OSError:
+        print("Couldn't write file ")
+        return False
+    return True
+
+
+def texture_file_name(file_name: str) -> str:
+    """The atlas of mesh.ply goes beside it as mesh.png."""
+    return os.path.splitext(file_name)[0] + ".png"
+
+
+def write_ply_textured_mesh(file_name: str, vertices, normals, triangles, uv, atlas) -> bool:
+    """ASCII PLY of a textured triangle mesh as MeshLab and Blender read it: ``comment TextureFile <name>.png`` in the header, the
+    vertex properties x y z nx ny nz (normals None: zeros), and per face ``property list uchar int vertex_indices`` and
+    ``property list uchar float texcoord`` with the six values u0 v0 u1 v1 u2 v2.  uv [T, 3, 2] is mesh_texture's (v down the atlas
+    rows); the file holds (u, 1 - v), the readers' convention with v up.  The atlas [H, W, 3] uint8 RGB goes beside the file as an
+    8-bit RGB PNG of the same stem."""
+    xyz = np.asarray(vertices, np.float32).reshape(-1, 3)
+    n = xyz.shape[0]
+    nrm = np.asarray(normals, np.float32).reshape(-1, 3) if normals is not None else np.zeros((n, 3), np.float32)
+    tri = np.asarray(triangles, np.int32).reshape(-1, 3)
+    tex = np.asarray(uv, np.float32).reshape(-1, 3, 2)
+    if len(nrm) != n or len(tex) != len(tri):
+        raise ValueError("one normal per vertex and three texture coordinates per triangle")
+    if len(tri) and (tri.min() < 0 or tri.max() >= n):
+        raise ValueError("a triangle index is out of range")
+    png = texture_file_name(file_name)
+    head = ["ply", "format ascii 1.0", f"comment TextureFile {os.path.basename(png)}", f"element vertex {n}"] + \
+           [f"property float {p}" for p in ("x", "y", "z", "nx", "ny", "nz")] + \
+           [f"element face {len(tri)}", "property list uchar int vertex_indices", "property list uchar float texcoord", "end_header"]
+    flipped = np.stack([tex[..., 0], np.float32(1.0) - tex[..., 1]], axis=-1).reshape(-1, 6)
+    try:
+        with open(file_name, "w") as f:
+            f.write("\n".join(head) + "\n")
+            for i in range(n):
+                f.write(" ".join(_fmt(v) for v in (*xyz[i], *nrm[i])) + "\n")
+            for (a, b, c), t in zip(tri.tolist(), flipped):
+                f.write(f"3 {a} {b} {c} 6 " + " ".join(_fmt(v) for v in t) + "\n")
+    except OSError:
+        print("Couldn't write file ")
+        return False
+    if not write_png_rgb(png, atlas):
+        return False
+    print(f"Output [ {n} ] vertices, [ {len(tri)} ] triangles, texture [ {np.asarray(atlas).shape[1]} x {np.asarray(atlas).shape[0]} ].\nOutput ply file done.")
+    return True
+
+
+def read_ply_textured_mesh(file_name: str):
+    """Reader for the files write_ply_textured_mesh produces: (vertices [n, 3] f32, normals [n, 3] f32, triangles [m, 3] i32, uv
+    [m, 3, 2] f32 with v down the atlas rows again, the texture's file name as the header gives it)."""
+    with open(file_name) as f:
+        lines = f.read().split("\n")
+    end = lines.index("end_header")
+    n = int([l for l in lines[:end] if l.startswith("element vertex")][0].split()[-1])
+    m = int([l for l in lines[:end] if l.startswith("element face")][0].split()[-1])
+    props = [l.split()[-1] for l in lines[:end] if l.startswith("property")]
+    if props != ["x", "y", "z", "nx", "ny", "nz", "vertex_indices", "texcoord"]:
+        raise ValueError(f"not a write_ply_textured_mesh file: {props}")
+    texture = [l for l in lines[:end] if l.startswith("comment TextureFile ")][0][len("comment TextureFile "):]
+    body = lines[end + 1:]
+    arr = np.array([l.split() for l in body[:n]], np.float64).reshape(n, 6)
+    faces = np.array([l.split() for l in body[n:n + m]], np.float64).reshape(m, 11)
+    if m and (np.any(faces[:, 0] != 3) or np.any(faces[:, 4] != 6)):
+        raise ValueError("not a textured triangle mesh")
+    uv = faces[:, 5:].astype(np.float32).reshape(m, 3, 2)
+    uv[..., 1] = np.float32(1.0) - uv[..., 1]
+    return arr[:, :3].astype(np.float32), arr[:, 3:].astype(np.float32), faces[:, 1:4].astype(np.int32), uv, texture
 
 
 def read_ply_vertices(file_name: str):

@@ -16,6 +16,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <filesystem>
 #include <fstream>
 #include <iomanip>
 #include <iostream>
@@ -606,6 +607,35 @@ public:
         return bool(fs);
     }
 
+    // easysfm_amd.cloud.write_ply_textured_mesh: the header names the texture (comment TextureFile <stem>.png), vertices carry x y z nx
+    // ny nz, faces their indices and six texture coordinates (u, 1 - v: v runs up in the file, down the atlas rows in uv); the atlas
+    // (rows x cols x 3 RGB) goes beside the file as an 8-bit RGB PNG of the same stem.
+    bool writePlyTexturedMesh(const std::string &fileName, const TriangleMesh &mesh, const std::vector<float> &uv, int atlas_rows, int atlas_cols,
+                              const std::vector<uint8_t> &atlas)
+    {
+        const std::filesystem::path png = std::filesystem::path(fileName).replace_extension(".png");
+        std::ofstream fs(fileName);
+        if (!fs) { std::cerr << "Couldn't write file " << std::endl; return false; }
+        const size_t n = mesh.vertices.size(), m = mesh.triangles.size() / 3;
+        if (uv.size() != 6 * m || atlas.size() != size_t(atlas_rows) * size_t(atlas_cols) * 3) { std::cerr << "texture coordinates or atlas of the wrong size" << std::endl; return false; }
+        fs << "ply\nformat ascii 1.0\ncomment TextureFile " << png.filename().string() << "\nelement vertex " << n
+           << "\nproperty float x\nproperty float y\nproperty float z\nproperty float nx\nproperty float ny\nproperty float nz\nelement face " << m
+           << "\nproperty list uchar int vertex_indices\nproperty list uchar float texcoord\nend_header\n";
+        fs << std::setprecision(8);
+        for (const PointXYZRGBNormal &p : mesh.vertices) fs << p.x << " " << p.y << " " << p.z << " " << p.nx << " " << p.ny << " " << p.nz << "\n";
+        for (size_t t = 0; t < m; ++t) {
+            fs << "3 " << mesh.triangles[3 * t] << " " << mesh.triangles[3 * t + 1] << " " << mesh.triangles[3 * t + 2] << " 6";
+            for (int k = 0; k < 3; ++k) fs << " " << uv[6 * t + 2 * k] << " " << 1.0f - uv[6 * t + 2 * k + 1];
+            fs << "\n";
+        }
+        if (!fs) return false;
+        const std::string e = png::write_rgb(png.string(), atlas_rows, atlas_cols, atlas.data());
+        if (!e.empty()) { std::cerr << e << std::endl; return false; }
+        std::cout << "Output [ " << n << " ] vertices, [ " << m << " ] triangles, texture [ " << atlas_cols << " x " << atlas_rows << " ]." << std::endl
+                  << "Output ply file done." << std::endl;
+        return true;
+    }
+
     // DataIO::importDistort (data_io.cpp:97-125): up to three groups of k1 k2 p1 p2 are extracted as floats, then stored with
     // at<float>(0, i) into the CV_64FC1 matrix -- i.e. into its first 16 bytes.  Reproduced: cv::undistort
     // sees v[0] = the double made of the bits of (k1, k2), v[1] = that of (p1, p2), v[2] = v[3] = 0.
@@ -1180,6 +1210,78 @@ public:
             p.r = out_col[3 * k]; p.g = out_col[3 * k + 1]; p.b = out_col[3 * k + 2];
         }
         if (cell_used) *cell_used = cell;
+        return true;
+    }
+
+    // esfm.h "Mesh texturing" with its default options, as run_sfm(dense_mesh_texture=...) runs it: every triangle chooses one of the
+    // registered frames (process_frame_id false; at most 64, in frame order), then a square atlas of ceil(sqrt(ceil(T / 2))) squares per
+    // row is baked.  texels 0 derives the chart size: the median over the labelled triangles of sqrt(2 score), rounded up, clamped to
+    // 4 .. 64.  uv: T x 3 x 2; atlas: atlas_rows x atlas_cols x 3 RGB; texels_used: the chart size.
+    bool textureMesh(const TriangleMesh &mesh, const std::vector<frame_t> &frames, const std::vector<bool> &process_frame_id, int texels,
+                     std::vector<float> &uv, std::vector<uint8_t> &atlas, int &atlas_rows, int &atlas_cols, int &n_labelled, int &n_views, int &texels_used)
+    {
+        uv.clear(); atlas.clear();
+        atlas_rows = atlas_cols = n_labelled = n_views = texels_used = 0;
+        int rows = -1, cols = -1, ch = -1;
+        std::vector<uint8_t> images;
+        std::vector<float> K4, poses;
+        for (size_t v = 0; v < frames.size(); ++v) {
+            if (process_frame_id[v]) continue;
+            const frame_t &f = frames[v];
+            const ImageMat &im = f.rgb_image;
+            if (im.empty()) { std::cerr << "mesh texture: registered frame " << v << " has no image" << std::endl; return false; }
+            if (rows < 0) { rows = im.rows; cols = im.cols; ch = im.channels; }
+            if (im.rows != rows || im.cols != cols || im.channels != ch) { std::cerr << "mesh texture: frames differ in size" << std::endl; return false; }
+            images.insert(images.end(), im.data.begin(), im.data.end());
+            const float k4[4] = {f.K_cam(0, 0), f.K_cam(0, 2), f.K_cam(1, 1), f.K_cam(1, 2)};
+            K4.insert(K4.end(), k4, k4 + 4);
+            for (int i = 0; i < 3; ++i) for (int j = 0; j < 4; ++j) poses.push_back(f.pose_cam(i, j));
+            ++n_views;
+        }
+        const int nv = int(mesh.vertices.size()), nt = int(mesh.triangles.size() / 3);
+        std::vector<float> vtx(size_t(3) * mesh.vertices.size());
+        std::vector<uint8_t> col(vtx.size());
+        for (size_t k = 0; k < mesh.vertices.size(); ++k) {
+            const PointXYZRGBNormal &p = mesh.vertices[k];
+            vtx[3 * k] = p.x; vtx[3 * k + 1] = p.y; vtx[3 * k + 2] = p.z;
+            col[3 * k] = p.r; col[3 * k + 1] = p.g; col[3 * k + 2] = p.b;
+        }
+        esfm_mesh_texture_options opt;
+        esfm_mesh_texture_options_default(&opt);
+        std::vector<int32_t> label(size_t(nt), -1);
+        std::vector<float> score(size_t(nt), 0.f);
+        int rc = esfm_mesh_texture_views(default_ctx(), nv, nt, vtx.data(), mesh.triangles.data(), n_views, rows, cols, K4.data(), poses.data(), &opt,
+                                         label.data(), score.data(), nullptr);
+        if (rc != ESFM_OK) { std::cerr << esfm_last_error() << std::endl; return false; }
+        std::vector<double> legs;
+        for (int t = 0; t < nt; ++t)
+            if (label[size_t(t)] >= 0) { ++n_labelled; legs.push_back(std::sqrt(2.0 * double(score[size_t(t)]))); }
+        texels_used = texels;
+        if (texels == 0) {
+            texels_used = 4;
+            if (!legs.empty()) {
+                std::sort(legs.begin(), legs.end());
+                const size_t h = legs.size() / 2;
+                const double median = legs.size() % 2 ? legs[h] : (legs[h - 1] + legs[h]) / 2.0;
+                texels_used = int(std::min(64.0, std::max(4.0, std::ceil(median))));
+            }
+        }
+        const int squares = (nt + 1) / 2;
+        int width = int(std::ceil(std::sqrt(double(squares))));
+        while (width * width < squares) ++width;
+        if (width < 1) width = 1;
+        int32_t need = 0;
+        uv.assign(size_t(6) * size_t(nt), 0.f);
+        rc = esfm_mesh_texture_bake(default_ctx(), nv, nt, vtx.data(), col.data(), mesh.triangles.data(), label.data(), n_views, rows, cols, ch, images.data(),
+                                    K4.data(), poses.data(), texels_used, width, 0, nullptr, uv.data(), &need);       // the height first
+        if (rc != ESFM_OK && need <= 0) { std::cerr << esfm_last_error() << std::endl; return false; }
+        atlas_rows = need; atlas_cols = width * texels_used;
+        atlas.assign(size_t(atlas_rows) * size_t(atlas_cols) * 3, 0);
+        if (need > 0) {
+            rc = esfm_mesh_texture_bake(default_ctx(), nv, nt, vtx.data(), col.data(), mesh.triangles.data(), label.data(), n_views, rows, cols, ch,
+                                        images.data(), K4.data(), poses.data(), texels_used, width, atlas_rows, atlas.data(), uv.data(), &need);
+            if (rc != ESFM_OK) { std::cerr << esfm_last_error() << std::endl; return false; }
+        }
         return true;
     }
 

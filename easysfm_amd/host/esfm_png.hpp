@@ -4,6 +4,8 @@
 // their high byte (as libpng's strip-16 does for imread), sub-byte gray expanded by bit replication, non-interlaced.  Adam7 files are reported as unsupported (JPEG: esfm_jpeg.hpp) -- image decoding is host
 // I/O outside the hot path, this reader exists so that the C++ executable needs no Python.
 // Needs zlib (-lz) for the inflate step; everything else (chunk walk, CRC check, the five scanline filters) is here.
+// write_rgb is the writer of the textured mesh's atlas: 8-bit RGB, scanline filter 0, the zlib stream made of stored (uncompressed)
+// deflate blocks, so that it needs nothing of zlib but its two checksums.
 #pragma once
 #include <zlib.h>
 
@@ -135,6 +137,53 @@ inline std::string read_bgr(const std::string &path, int &rows, int &cols, std::
         }
     }
     return std::string();
+}
+
+// Writes rgb (rows x cols x 3, at least one pixel) as an 8-bit RGB PNG.  Returns an empty string on success.
+inline std::string write_rgb(const std::string &path, int rows, int cols, const uint8_t *rgb)
+{
+    if (rows < 1 || cols < 1 || rows > (1 << 16) || cols > (1 << 16) || !rgb) return path + ": image dimensions out of range";
+    const size_t stride = size_t(cols) * 3;
+    std::vector<uint8_t> raw((stride + 1) * size_t(rows));
+    for (int y = 0; y < rows; ++y) {
+        raw[(stride + 1) * size_t(y)] = 0;                                   // filter type 0: the bytes as they are
+        std::memcpy(&raw[(stride + 1) * size_t(y) + 1], rgb + stride * size_t(y), stride);
+    }
+    auto put32 = [](std::vector<uint8_t> &v, uint32_t x) { for (int s = 24; s >= 0; s -= 8) v.push_back(uint8_t(x >> s)); };
+    std::vector<uint8_t> z;                                                  // zlib header, stored blocks of at most 65535 bytes, Adler-32
+    z.reserve(raw.size() + raw.size() / 65535 * 5 + 16);
+    z.push_back(0x78); z.push_back(0x01);
+    for (size_t at = 0; at < raw.size(); at += 65535) {
+        const size_t n = raw.size() - at < 65535 ? raw.size() - at : 65535;
+        z.push_back(at + n == raw.size() ? 1 : 0);
+        z.push_back(uint8_t(n & 255)); z.push_back(uint8_t(n >> 8)); z.push_back(uint8_t(~n & 255)); z.push_back(uint8_t((~n >> 8) & 255));
+        z.insert(z.end(), raw.begin() + at, raw.begin() + at + n);
+    }
+    uLong adler = adler32(0L, Z_NULL, 0);
+    for (size_t at = 0; at < raw.size(); at += size_t(1) << 30)             // (uInt lengths)
+        adler = adler32(adler, raw.data() + at, uInt(raw.size() - at < (size_t(1) << 30) ? raw.size() - at : size_t(1) << 30));
+    put32(z, uint32_t(adler));
+    std::vector<uint8_t> file{0x89, 'P', 'N', 'G', 0x0D, 0x0A, 0x1A, 0x0A};
+    auto chunk = [&file, &put32](const char *type, const std::vector<uint8_t> &data) {
+        put32(file, uint32_t(data.size()));
+        const size_t start = file.size();
+        file.insert(file.end(), type, type + 4);
+        file.insert(file.end(), data.begin(), data.end());
+        uLong crc = crc32(0L, Z_NULL, 0);
+        for (size_t at = start; at < file.size(); at += size_t(1) << 30)
+            crc = crc32(crc, file.data() + at, uInt(file.size() - at < (size_t(1) << 30) ? file.size() - at : size_t(1) << 30));
+        put32(file, uint32_t(crc));
+    };
+    std::vector<uint8_t> ihdr;
+    put32(ihdr, uint32_t(cols)); put32(ihdr, uint32_t(rows));
+    ihdr.push_back(8); ihdr.push_back(2); ihdr.push_back(0); ihdr.push_back(0); ihdr.push_back(0);
+    chunk("IHDR", ihdr);
+    chunk("IDAT", z);
+    chunk("IEND", std::vector<uint8_t>());
+    FILE *f = std::fopen(path.c_str(), "wb");
+    if (!f) return "cannot write " + path;
+    const bool ok = std::fwrite(file.data(), 1, file.size(), f) == file.size();
+    return (std::fclose(f) == 0 && ok) ? std::string() : "cannot write " + path;
 }
 
 }  // namespace png

@@ -84,7 +84,9 @@ int main(int argc, char **argv)
     // optional 15th (needs the 14th): a dense .ply path, or none; optional 16th (needs the 15th): a .ply path for the merged dense cloud
     // (one oriented point per voxel), or none; optional 17th (needs the 16th): a .ply path for the surface mesh, or none; clean:mesh.ply
     // cleans the mesh with the defaults of esfm.h "Mesh clean-up" before it is written to mesh.ply, simplify:mesh.ply merges the
-    // vertices of every cell of two voxels' side (esfm.h "Mesh simplification"), clean+simplify:mesh.ply does both in that order
+    // vertices of every cell of two voxels' side (esfm.h "Mesh simplification"), clean+simplify:mesh.ply does both in that order; with
+    // +texture in the prefix (texture:, clean+texture:, simplify+texture:, clean+simplify+texture:) the mesh is then textured from the
+    // registered frames (esfm.h "Mesh texturing") and written with texture coordinates, its atlas beside it as mesh.png
     const std::string filter_arg = argc >= 15 ? argv[14] : "ratio";
     const std::string guided_suffix = "+guided";
     const bool guided = filter_arg.size() > guided_suffix.size() && filter_arg.compare(filter_arg.size() - guided_suffix.size(), guided_suffix.size(), guided_suffix) == 0;
@@ -92,15 +94,28 @@ int main(int argc, char **argv)
     const std::string dense_file = argc >= 16 && std::string(argv[15]) != "none" ? argv[15] : "";
     const std::string merged_file = argc >= 17 && std::string(argv[16]) != "none" ? argv[16] : "";
     const std::string mesh_arg = argc == 18 && std::string(argv[17]) != "none" ? argv[17] : "";
-    const bool both_mesh = mesh_arg.compare(0, 15, "clean+simplify:") == 0;
-    const bool clean_mesh = both_mesh || mesh_arg.compare(0, 6, "clean:") == 0;
-    const bool simplify_mesh = both_mesh || mesh_arg.compare(0, 9, "simplify:") == 0;
-    const std::string mesh_file = mesh_arg.substr(both_mesh ? 15 : clean_mesh ? 6 : simplify_mesh ? 9 : 0);
+    bool clean_mesh = false, simplify_mesh = false, texture_mesh = false;
+    std::string mesh_file = mesh_arg;
+    {
+        struct Form { const char *prefix; bool clean, simplify, texture; };
+        const Form forms[] = {{"clean+simplify+texture:", true, true, true}, {"clean+texture:", true, false, true}, {"simplify+texture:", false, true, true},
+                              {"texture:", false, false, true}, {"clean+simplify:", true, true, false}, {"clean:", true, false, false},
+                              {"simplify:", false, true, false}};
+        for (const Form &f : forms) {
+            const size_t len = std::strlen(f.prefix);
+            if (mesh_arg.compare(0, len, f.prefix) == 0) {
+                clean_mesh = f.clean; simplify_mesh = f.simplify; texture_mesh = f.texture;
+                mesh_file = mesh_arg.substr(len);
+                break;
+            }
+        }
+    }
     if (argc < 14 || argc > 18 || (match_filter != "ratio" && match_filter != "cross" && match_filter != "ratio+cross")) {
         std::cerr << "usage: sfm_native image_folder image_list calib_K_file calib_distort_file output.ply feature_type(S | O | I) feature_parameter "
                      "repro_dis_ransac find_init_frames ba_calib_change_tolerance ba_frequency launch_viewer view_sphere [match_filter: ratio | cross | ratio+cross | "
                      "ratio+guided | cross+guided | ratio+cross+guided [dense.ply | none [merged.ply | none [simplify:mesh.ply | "
-                     "clean+simplify:mesh.ply | mesh.ply | clean:mesh.ply | none]]]]"
+                     "clean+simplify:mesh.ply | mesh.ply | clean:mesh.ply | none]]]] (the 17th's prefix also takes +texture: texture:, clean+texture:, "
+                     "simplify+texture:, clean+simplify+texture:)"
                   << std::endl;
         return 2;
     }
@@ -436,7 +451,15 @@ int main(int argc, char **argv)
                 }
                 const std::filesystem::path mesh_dir = std::filesystem::path(mesh_file).parent_path();
                 if (!mesh_dir.empty()) std::filesystem::create_directories(mesh_dir);
-                if (!io.writePlyMesh(mesh_file, mesh)) return 3;
+                if (texture_mesh) {
+                    std::vector<float> uv;
+                    std::vector<uint8_t> atlas;
+                    int atlas_rows = 0, atlas_cols = 0, n_labelled = 0, n_views = 0, texels = 0;
+                    if (!dr.textureMesh(mesh, frames, todo, 0, uv, atlas, atlas_rows, atlas_cols, n_labelled, n_views, texels)) return 3;
+                    std::cout << "Mesh texture: [" << mesh.triangles.size() / 3 << "] triangles, [" << n_labelled << "] labelled from [" << n_views
+                              << "] views, charts of [" << texels << "] texels, atlas [" << atlas_cols << "] x [" << atlas_rows << "]." << std::endl;
+                    if (!io.writePlyTexturedMesh(mesh_file, mesh, uv, atlas_rows, atlas_cols, atlas)) return 3;
+                } else if (!io.writePlyMesh(mesh_file, mesh)) return 3;
             }
         }
     } catch (const std::exception &e) {       // 1 is the reference's SUCCESS status: a failure must not look like one

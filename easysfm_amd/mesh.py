@@ -3,7 +3,8 @@ distance volume (``tsdf_integrate``), an indexed triangle mesh out of it by marc
 with the volume staying on the device (``mvs_mesh``).  ``dense_mesh`` takes what the pipeline holds after its final bundle
 adjustment, as ``mvs.dense_merge`` does, and ends in a mesh instead of a point cloud.  ``mesh_components`` and ``mesh_clean``
 (esfm.h, "Mesh clean-up") label a mesh's connected pieces, drop the small ones, smooth the rest and recompute its normals;
-``mesh_simplify`` (esfm.h, "Mesh simplification") merges the vertices of each cell of a regular grid into one."""
+``mesh_simplify`` (esfm.h, "Mesh simplification") merges the vertices of each cell of a regular grid into one;
+``mesh_texture`` (esfm.h, "Mesh texturing") lets every triangle choose the view that sees it best and bakes a texture atlas."""
 from __future__ import annotations
 
 import ctypes as C
@@ -11,7 +12,7 @@ from typing import Optional, Sequence, Tuple
 
 import numpy as np
 
-from ._lib import Context, MeshCleanOptions, MeshSimplifyOptions, MVSOptions, TSDFGrid, TSDFOptions, check, default_context, lib
+from ._lib import Context, MeshCleanOptions, MeshSimplifyOptions, MeshTextureOptions, MVSOptions, TSDFGrid, TSDFOptions, check, default_context, lib
 from .mvs import MergeOptions, _views, default_mvs_options, frame_arrays, merge_voxel_size, mvs_depth_maps, mvs_fuse, mvs_plan
 from .types import Frame, SparsePointCloud
 
@@ -298,6 +299,111 @@ def mesh_simplify(vertices, rgb, triangles, cell: float, origin=None, opt: Optio
     return out + (vmap, cut(tmap, nt.value)) if return_maps else out
 
 
+def default_mesh_texture_options() -> MeshTextureOptions:
+    """esfm_mesh_texture_options_default: min_cos 0.2, occlusion_tol 0.02."""
+    opt = MeshTextureOptions()
+    lib().esfm_mesh_texture_options_default(C.byref(opt))
+    return opt
+
+
+def _cameras(K4, poses):
+    K = np.ascontiguousarray(np.asarray(K4, np.float32).reshape(-1, 4))
+    n = len(K)
+    P = np.ascontiguousarray(np.asarray(poses, np.float32).reshape(n, -1, 4)[:, :3, :].reshape(n, 12))
+    return K, P
+
+
+def mesh_texture_views(vertices, triangles, rows: int, cols: int, K4, poses, opt: Optional[MeshTextureOptions] = None,
+                       ctx: Optional[Context] = None, return_buffers: bool = False):
+    """esfm_mesh_texture_views on vertices [V, 3] float32 and triangles [T, 3] int32 under n views of rows x cols pixels (K4 [n, 4],
+    poses [n, 12] or [n, 3 | 4, 4]).  Returns (label [T] int32: the chosen view or -1, score [T] float32: half the triangle's
+    screen area there in pixels), and with return_buffers also the views' buffers [n, rows, cols] uint32 (the bit pattern of the
+    largest inverse depth at each pixel, 0 = nothing)."""
+    opt = opt or default_mesh_texture_options()
+    ctx = ctx or default_context()
+    v = np.ascontiguousarray(vertices, np.float32).reshape(-1, 3)
+    t = _triangle_array(triangles)
+    K, P = _cameras(K4, poses)
+    label, score = np.full(len(t), -1, np.int32), np.zeros(len(t), np.float32)
+    buffers = np.zeros((len(K), max(int(rows), 0), max(int(cols), 0)), np.uint32) if return_buffers else None
+    check(lib().esfm_mesh_texture_views(ctx.handle, len(v), len(t), _ptr(v), _ptr(t), len(K), int(rows), int(cols), _ptr(K), _ptr(P),
+                                        C.byref(opt), _ptr(label), _ptr(score), _ptr(buffers)))
+    return (label, score, buffers) if return_buffers else (label, score)
+
+
+def default_atlas_width(n_triangles: int) -> int:
+    """ceil(sqrt(ceil(T / 2))) squares per atlas row, at least 1: a square atlas."""
+    squares = (int(n_triangles) + 1) // 2
+    a = int(np.ceil(np.sqrt(squares)))
+    while a * a < squares:
+        a += 1
+    return max(a, 1)
+
+
+def mesh_texture_bake(vertices, rgb, triangles, label, images, K4, poses, texels: int, atlas_width: Optional[int] = None,
+                      ctx: Optional[Context] = None):
+    """esfm_mesh_texture_bake: every triangle gets a chart of `texels` x `texels` / 2 texels, two per square and `atlas_width`
+    squares per atlas row (None = a square atlas), filled from the view label[t] names (images [n, rows, cols(, 1 | 3)] uint8, BGR)
+    or, for label -1, from the vertex colours (grey without them).  Returns (atlas [H, W, 3] uint8 RGB, uv [T, 3, 2] float32,
+    normalised, origin at the outer corner of the atlas's first texel, v down the rows)."""
+    ctx = ctx or default_context()
+    v = np.ascontiguousarray(vertices, np.float32).reshape(-1, 3)
+    c = np.ascontiguousarray(rgb, np.uint8).reshape(-1, 3) if rgb is not None else None
+    if c is not None and len(c) != len(v):
+        raise ValueError("rgb must hold one colour per vertex")
+    t = _triangle_array(triangles)
+    lab = np.ascontiguousarray(label, np.int32).reshape(-1)
+    if len(lab) != len(t):
+        raise ValueError("label must hold one view per triangle")
+    imgs = np.ascontiguousarray(images, np.uint8)
+    if imgs.ndim == 3:
+        imgs = imgs[..., None]
+    if imgs.ndim != 4:
+        raise ValueError("images must be [n_views, rows, cols(, channels)]")
+    n, rows, cols, ch = imgs.shape
+    K, P = _cameras(K4, poses)
+    if len(K) != n:
+        raise ValueError("one K4 and one pose per image")
+    width = default_atlas_width(len(t)) if atlas_width is None else int(atlas_width)
+    uv = np.zeros((len(t), 3, 2), np.float32)
+    need = C.c_int32(-1)
+    cap = 0
+    atlas = np.zeros((0, 0, 3), np.uint8)
+    for attempt in range(2):                                            # the first call asks for the height, the second bakes
+        status = lib().esfm_mesh_texture_bake(ctx.handle, len(v), len(t), _ptr(v), _ptr(c), _ptr(t), _ptr(lab), n, rows, cols, ch, _ptr(imgs),
+                                              _ptr(K), _ptr(P), int(texels), width, cap, _ptr(atlas) if cap else None, _ptr(uv), C.byref(need))
+        if attempt == 0 and status == -1 and need.value > cap:
+            cap = need.value
+            atlas = np.zeros((cap, width * int(texels), 3), np.uint8)
+            continue
+        check(status)
+        break
+    return atlas.reshape(cap, max(width, 0) * max(int(texels), 0), 3), uv
+
+
+def auto_texels(label, score) -> int:
+    """The chart size mesh_texture derives: the median over the labelled triangles of sqrt(2 score) -- the leg in pixels of an
+    equal-legged right triangle of that screen area --, rounded up and clamped to 4 .. 64 (4 if nothing is labelled)."""
+    s = np.asarray(score, np.float64)[np.asarray(label) >= 0]
+    if len(s) == 0:
+        return 4
+    return int(min(64, max(4, np.ceil(np.median(np.sqrt(2.0 * s))))))
+
+
+def mesh_texture(vertices, rgb, triangles, images, K4, poses, texels: Optional[int] = None, atlas_width: Optional[int] = None,
+                 opt: Optional[MeshTextureOptions] = None, ctx: Optional[Context] = None):
+    """View choice and bake in one: returns (atlas [H, W, 3] uint8 RGB, uv [T, 3, 2] float32, label [T] int32, score [T] float32).
+    texels=None derives the chart size from the triangles' screen areas (auto_texels)."""
+    ctx = ctx or default_context()
+    imgs = np.asarray(images)
+    label, score = mesh_texture_views(vertices, triangles, imgs.shape[1], imgs.shape[2], K4, poses, opt, ctx)
+    S = auto_texels(label, score) if texels is None else int(texels)
+    atlas, uv = mesh_texture_bake(vertices, rgb, triangles, label, imgs, K4, poses, S, atlas_width, ctx)
+    return atlas, uv, label, score
+
+
 __all__ = ["TSDFGrid", "TSDFOptions", "MeshOptions", "MeshCleanOptions", "MeshSimplifyOptions", "default_tsdf_options",
            "default_mesh_clean_options", "default_mesh_simplify_options", "tsdf_grid", "tsdf_integrate", "tsdf_extract", "mvs_mesh",
-           "masked_depth", "mesh_grid", "mesh_arrays", "dense_mesh", "mesh_components", "mesh_clean", "mesh_simplify"]
+           "masked_depth", "mesh_grid", "mesh_arrays", "dense_mesh", "mesh_components", "mesh_clean", "mesh_simplify",
+           "MeshTextureOptions", "default_mesh_texture_options", "default_atlas_width", "auto_texels", "mesh_texture_views",
+           "mesh_texture_bake", "mesh_texture"]

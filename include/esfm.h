@@ -1051,6 +1051,92 @@ int esfm_mesh_simplify(esfm_ctx *ctx, int n_vertices, int n_triangles, const flo
                        uint8_t *out_rgb /*may be NULL; needs vertex_rgb*/, int32_t *out_triangles, int32_t *vertex_map /*V, may be NULL*/,
                        int32_t *triangle_map /*may be NULL*/, int32_t *n_out_vertices, int32_t *n_out_triangles);
 
+/* ---- Mesh texturing: per-triangle view choice, z-buffer, atlas bake ---------------------------------------
+ * An indexed triangle mesh (e.g. esfm_mesh_simplify's) gets a texture atlas from the photographs: every view rasterises the mesh
+ * into a buffer of inverse depths, every triangle chooses the view that sees it largest and unoccluded, and every atlas texel
+ * fetches its colour from its triangle's view.  The only combination across threads is an integer maximum, the views are tried in
+ * view order and one texel is one thread's work, so nothing depends on scheduling; tests/texture_ref.py restates this text in numpy
+ * and the GPU reproduces it bit for bit.  All arithmetic is f32, no mul + add contraction, correctly rounded division and sqrtf;
+ * fminf / fmaxf return the other operand where one is NaN.  Conventions are those of the dense section (poses, K4, pixel centres,
+ * images n_views x rows x cols x channels u8 with 3 = BGR and 1 = grey; colours come out as RGB, grey as a grey triple).
+ *
+ * Input: V vertices (3 f32 each, finite), T triangles (3 int32 each, indices in 0 .. V - 1, repeated indices legal), 0 <= V <= 2^30,
+ * 0 <= T <= 2^25; n_views 1..64 of rows x cols pixels, both 2..16384; K4 and poses finite, focal lengths not 0.
+ *
+ * Projection of a world point X into view v: p_i = ((R[i][0] X0 + R[i][1] X1) + R[i][2] X2) + t[i]; u = fx (p0 / p2) + cx,
+ * w = fy (p1 / p2) + cy, z = 1.0f / p2 (the inverse depth).  X is in front of v if p2 > 0, |u| <= 2^20 and |w| <= 2^20 (a NaN fails).
+ * Its nearest pixel is (floorf(u + 0.5f), floorf(w + 0.5f)), as in esfm_tsdf_integrate.
+ *
+ * Screen triangle of triangle t in view v: its vertices' (x_k, y_k, z_k) = (u, w, z), k = 0, 1, 2 in the triangle's own order; it
+ * exists only if all three are in front.  A triangle with a vertex at p2 <= 0 in a view (or otherwise not in front) is skipped in
+ * that view: there it neither occludes nor can be labelled.  area2 = (x1 - x0) (y2 - y0) - (y1 - y0) (x2 - x0).
+ *
+ * esfm_mesh_texture_views.
+ *   Depth buffer of view v, rows x cols uint32, 0 = nothing covers the pixel: each cell is the largest bit pattern (a positive f32
+ *   orders like a uint32) of the inverse depths that the screen triangles with area2 != 0 give the pixel.  With s = 1.0f if
+ *   area2 > 0, else -1.0f, a triangle gives a value to pixel (px, py) if
+ *     fmaxf(ceilf(xmin - 0.5f), 0) <= px <= fminf(floorf(xmax + 0.5f), cols - 1), likewise py with ymin, ymax and rows (xmin =
+ *     fminf(fminf(x0, x1), x2) and so on), and for the three edges k, from vertex k to vertex k' = (k + 1) mod 3, with
+ *     ex = x_k' - x_k, ey = y_k' - y_k, e_k = ex (py - y_k) - ey (px - x_k):  s e_k >= -0.5f (|ex| + |ey|).
+ *   That is coverage widened by half a pixel, because the later look-up is by nearest pixel; both windings occlude.  The value is
+ *   b0 = e_1 / area2, b1 = e_2 / area2, b2 = e_0 / area2, z = (b0 z0 + b1 z1) + b2 z2, then z = fminf(fmaxf(z, zmin), zmax) with zmin
+ *   and zmax the smallest and largest of z0, z1, z2, so that the half-pixel rim does not extrapolate.
+ *   View choice of triangle t: views 0 .. n - 1 in order; best = 0.0f, label = -1.  View v is admissible if
+ *     - the screen triangle exists, every vertex has 1 <= x_k <= cols - 2 and 1 <= y_k <= rows - 2, and score = 0.5f |area2| > 0;
+ *     - with P0, P1, P2 the world corners, N = (P1 - P0) x (P2 - P0) (products rounded, as the clean-up's face vector; it points
+ *       outside by the extractor's convention), G_a = ((P0_a + P1_a) + P2_a) / 3.0f, the camera centre C_j = -((R[0][j] t0 +
+ *       R[1][j] t1) + R[2][j] t2), D = C - G, d = (N0 D0 + N1 D1) + N2 D2, |N| = sqrtf((N0 N0 + N1 N1) + N2 N2), |D| likewise:
+ *       d > 0 and d >= min_cos * (|N| * |D|);
+ *     - each of four test points, the three vertices (x_k, y_k, z_k) and the projection of G (which must be in front), has its
+ *       nearest pixel inside the image and z >= (float)buffer[v][py][px] * (1.0f - occlusion_tol), the buffer's bits read as f32.
+ *   If v is admissible and score > best: best = score, label = v.  So the label is the admissible view of greatest score (half the
+ *   screen area in pixels), the lowest index on a tie, and -1 with score 0 if none is admissible.
+ *   Outputs: label [T] int32, score [T] f32 (best), depth_buffers [n_views, rows, cols] uint32 (may be NULL).
+ *
+ * esfm_mesh_texture_bake.  texels S 4..64, atlas_width A >= 1 squares.  The atlas is W = A S texels wide and
+ * H = ceil(ceil(T / 2) / A) S texels high (0 for T = 0), both at most 16384; atlas [H, W, 3] u8 RGB, row 0 first.
+ *   Layout: square q = t / 2 has its first texel at column (q % A) S and row (q / A) S.  Texel (i, j) of a square, column i and row
+ *   j, has its centre at (i + 0.5, j + 0.5) in the square's texel units and belongs to triangle 2 q if i + j <= S - 1, else to
+ *   2 q + 1.  Chart corners, for the triangle's vertices 0, 1, 2: even (0.5, 0.5), (S - 1.5, 0.5), (0.5, S - 1.5); odd
+ *   (S - 0.5, S - 0.5), (2.5, S - 0.5), (S - 0.5, 2.5).  With bilinear filtering between texel centres, every texel that has a
+ *   non-zero weight for a point inside a chart belongs to that chart's triangle and lies in its square.
+ *   uv [T, 3, 2] f32: corner (cx, cy) of a triangle in the square at column X0, row Y0 is (((float)X0 + cx) / (float)W,
+ *   ((float)Y0 + cy) / (float)H): normalised, origin at the outer corner of the atlas's first texel, u along a row, v down the rows.
+ *   Texel of triangle t >= T: (0, 0, 0).  Otherwise its barycentrics: even b1 = (float)i / (float)(S - 2), b2 = (float)j /
+ *   (float)(S - 2); odd b1 = (float)(S - 1 - i) / (float)(S - 3), b2 = (float)(S - 1 - j) / (float)(S - 3); b0 = (1.0f - b1) - b2.
+ *   Texels outside the chart extrapolate: that is the gutter fill.
+ *   Fallback colour: with vertex_rgb, per channel c = (b0 c0 + b1 c1) + b2 c2 of the three vertex colours as f32,
+ *   c = fminf(fmaxf(c, 0.0f), 255.0f), (uint8)floorf(c + 0.5f); without, (128, 128, 128).
+ *   label[t] = -1: the fallback colour.  Otherwise X_a = (b0 P0_a + b1 P1_a) + b2 P2_a is projected into view label[t]; if p2 > 0 is
+ *   false, the fallback colour; else uc = fminf(fmaxf(u, 0.0f), (float)(cols - 1)), x0 = fminf(floorf(uc), (float)(cols - 2)),
+ *   ax = uc - x0, likewise wc, y0, ay with rows, and per channel, with I the image of that view,
+ *   c = (1.0f - ay) * ((1.0f - ax) * I[y0][x0] + ax * I[y0][x0 + 1]) + ay * ((1.0f - ax) * I[y0 + 1][x0] + ax * I[y0 + 1][x0 + 1]),
+ *   the texel's channel (uint8)floorf(c + 0.5f).
+ *   Capacity: *atlas_rows receives H whenever the arguments are otherwise valid; if H > max_atlas_rows nothing else is written and
+ *   the call returns ESFM_ERR_INVALID_ARG with H in the message.
+ *
+ * Options (esfm_mesh_texture_options_default): min_cos 0.2 (in [0, 1)), occlusion_tol 0.02 (in [0, 1)).
+ * Rejected with ESFM_ERR_INVALID_ARG, before the device is looked at and with nothing written: a vertex, K4 or pose value that is
+ * not finite, a focal length of 0, a triangle index outside 0 .. V - 1, a count, n_views, rows or cols out of range, channels other
+ * than 1 or 3, texels outside 4..64, atlas_width < 1, an atlas above 16384 texels per side, a label outside -1 .. n_views - 1, an
+ * option out of range, a required pointer that is NULL.  Host pointers; without a usable device ESFM_ERR_NO_DEVICE (no CPU
+ * fallback). */
+typedef struct esfm_mesh_texture_options {
+    float min_cos;
+    float occlusion_tol;
+} esfm_mesh_texture_options;
+void esfm_mesh_texture_options_default(esfm_mesh_texture_options *opt);
+int esfm_mesh_texture_views(esfm_ctx *ctx, int n_vertices, int n_triangles, const float *vertices /*3 each*/,
+                            const int32_t *triangles /*3 each*/, int n_views, int rows, int cols, const float *K4 /*4 each*/,
+                            const float *poses /*12 each*/, const esfm_mesh_texture_options *opt, int32_t *label /*T*/,
+                            float *score /*T*/, uint32_t *depth_buffers /*n_views x rows x cols, may be NULL*/);
+int esfm_mesh_texture_bake(esfm_ctx *ctx, int n_vertices, int n_triangles, const float *vertices /*3 each*/,
+                           const uint8_t *vertex_rgb /*3 each, may be NULL*/, const int32_t *triangles /*3 each*/,
+                           const int32_t *label /*T*/, int n_views, int rows, int cols, int channels, const uint8_t *images,
+                           const float *K4 /*4 each*/, const float *poses /*12 each*/, int texels, int atlas_width,
+                           int max_atlas_rows, uint8_t *atlas /*max_atlas_rows x W x 3*/, float *uv /*T x 3 x 2*/,
+                           int32_t *atlas_rows);
+
 #ifdef __cplusplus
 }
 #endif
