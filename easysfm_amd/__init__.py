@@ -23,10 +23,12 @@ from .features import (detectFeaturesORB, detectFeaturesSIFT, detectFeaturesSURF
 from .mvs import (MergeOptions, MVSNormalOptions, MVSOptions, default_mvs_normal_options, default_mvs_options, dense_merge,  # noqa: F401
                   dense_reconstruct, dense_reconstruction, merge_arrays, merge_voxel_size, mvs_depth_maps, mvs_fuse, mvs_normals,
                   mvs_plan)
-from .mesh import (MeshCleanOptions, MeshOptions, MeshSimplifyOptions, MeshTextureOptions, TSDFGrid, TSDFOptions,  # noqa: F401
-                   default_mesh_clean_options, default_mesh_simplify_options, default_mesh_texture_options, default_tsdf_options,
+from .mesh import (MeshCleanOptions, MeshOptions, MeshSimplifyOptions, MeshTextureLevelOptions, MeshTextureLevelStats,  # noqa: F401
+                   MeshTextureOptions, TSDFGrid, TSDFOptions,
+                   default_mesh_clean_options, default_mesh_simplify_options, default_mesh_texture_level_options,
+                   default_mesh_texture_options, default_tsdf_options,
                    dense_mesh, masked_depth, mesh_arrays, mesh_clean, mesh_components, mesh_grid, mesh_simplify, mesh_texture,
-                   mesh_texture_bake, mesh_texture_views, mvs_mesh, tsdf_extract, tsdf_grid, tsdf_integrate)
+                   mesh_texture_bake, mesh_texture_level, mesh_texture_views, mvs_mesh, tsdf_extract, tsdf_grid, tsdf_integrate)
 from .pipeline import MATCH_FILTERS, FramePair, match_and_verify_all_pairs, propagate_track_ids, run_sfm  # noqa: F401
 
 __version__ = "0.1.0"

@@ -50,6 +50,7 @@ EXPORTED_SYMBOLS = [
     "esfm_mesh_clean_options_default", "esfm_mesh_components", "esfm_mesh_clean",
     "esfm_mesh_simplify_options_default", "esfm_mesh_simplify",
     "esfm_mesh_texture_options_default", "esfm_mesh_texture_views", "esfm_mesh_texture_bake",
+    "esfm_mesh_texture_level_options_default", "esfm_mesh_texture_level", "esfm_mesh_texture_bake_ex",
 ]
 
 
@@ -129,6 +130,16 @@ class MeshSimplifyOptions(C.Structure):
 class MeshTextureOptions(C.Structure):
     """esfm_mesh_texture_options (include/esfm.h, "Mesh texturing")."""
     _fields_ = [("min_cos", C.c_float), ("occlusion_tol", C.c_float)]
+
+
+class MeshTextureLevelOptions(C.Structure):
+    """esfm_mesh_texture_level_options (include/esfm.h, "Mesh texturing", seam levelling)."""
+    _fields_ = [("lam", C.c_double), ("mu", C.c_double), ("tolerance", C.c_double), ("max_iterations", C.c_int32)]
+
+
+class MeshTextureLevelStats(C.Structure):
+    """esfm_mesh_texture_level_stats."""
+    _fields_ = [("nodes", C.c_int32), ("seam_vertices", C.c_int32), ("iterations", C.c_int32), ("converged", C.c_int32)]
 
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p)
@@ -260,6 +271,11 @@ def lib() -> C.CDLL:
     L.esfm_mesh_texture_views.argtypes = [vp, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.POINTER(MeshTextureOptions), vp, vp, vp]
     L.esfm_mesh_texture_bake.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, C.c_int,
                                          C.c_int, vp, vp, i32p]
+    L.esfm_mesh_texture_level_options_default.argtypes = [C.POINTER(MeshTextureLevelOptions)]
+    L.esfm_mesh_texture_level_options_default.restype = None
+    L.esfm_mesh_texture_level.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp,
+                                          C.POINTER(MeshTextureLevelOptions), vp, vp, C.POINTER(MeshTextureLevelStats)]
+    L.esfm_mesh_texture_bake_ex.argtypes = L.esfm_mesh_texture_bake.argtypes + [vp]
     L.esfm_solve_pnp_ransac.argtypes = [vp, vp, vp, C.c_int, vp, C.c_int, C.c_double, C.c_double, vp, vp, vp, vp, i32p, i32p]
     L.esfm_ba_problem_set_params.argtypes = [vp, vp, vp]
     L.esfm_ba_problem_solve.argtypes = [vp, C.POINTER(BAOptions), ALLREDUCE_FN, vp, C.POINTER(BASummary)]

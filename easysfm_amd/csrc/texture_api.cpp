@@ -1,7 +1,8 @@
-// C-ABI entry points of the mesh texturing (include/esfm.h, "Mesh texturing"): esfm_mesh_texture_views and
-// esfm_mesh_texture_bake.  Host side: the argument checks on the caller's arrays, the atlas layout with its uv corners and the
+// C-ABI entry points of the mesh texturing (include/esfm.h, "Mesh texturing"): esfm_mesh_texture_views, esfm_mesh_texture_bake and
+// esfm_mesh_texture_bake_ex (the bake with the seam levelling's offsets; level_api.cpp computes them).  Host side: the argument checks on the caller's arrays, the atlas layout with its uv corners and the
 // scratch layout (texture_check.hpp), uploads, launches and the copies back.  The work runs in texture_kernels.hip;
 // tests/texture_ref.py restates the rule.
+#include "level_check.hpp"
 #include "texture_kernels.hpp"
 
 namespace {
@@ -80,9 +81,20 @@ int esfm_mesh_texture_bake(esfm_ctx *ctx, int n_vertices, int n_triangles, const
                            const int32_t *label, int n_views, int rows, int cols, int channels, const uint8_t *images, const float *K4,
                            const float *poses, int texels, int atlas_width, int max_atlas_rows, uint8_t *atlas, float *uv, int32_t *atlas_rows)
 {
+    return esfm_mesh_texture_bake_ex(ctx, n_vertices, n_triangles, vertices, vertex_rgb, triangles, label, n_views, rows, cols, channels, images, K4, poses,
+                                     texels, atlas_width, max_atlas_rows, atlas, uv, atlas_rows, nullptr);
+}
+
+// offsets == NULL: the plain bake (the kernel's variant without offsets, nothing more uploaded)
+int esfm_mesh_texture_bake_ex(esfm_ctx *ctx, int n_vertices, int n_triangles, const float *vertices, const uint8_t *vertex_rgb, const int32_t *triangles,
+                              const int32_t *label, int n_views, int rows, int cols, int channels, const uint8_t *images, const float *K4,
+                              const float *poses, int texels, int atlas_width, int max_atlas_rows, uint8_t *atlas, float *uv, int32_t *atlas_rows,
+                              const float *offsets)
+{
     int H = 0;
     if (int rc = esfm::texture_check_bake_args(n_vertices, n_triangles, vertices, triangles, label, n_views, rows, cols, channels, images, K4, poses, texels,
                                                atlas_width, max_atlas_rows, atlas, uv, atlas_rows, &H)) return rc;
+    if (int rc = esfm::level_check_offsets(n_triangles, offsets)) return rc;
     *atlas_rows = H;
     if (H > max_atlas_rows) {
         esfm::set_error("esfm_mesh_texture_bake: the atlas needs %d rows of %d texels, the buffer holds %d", H, atlas_width * texels, max_atlas_rows);
@@ -98,6 +110,7 @@ int esfm_mesh_texture_bake(esfm_ctx *ctx, int n_vertices, int n_triangles, const
     if (int rc = ctx->stage_a.reserve(l.a_bytes)) return rc;
     if (int rc = ctx->stage_c.reserve(l.c_bytes)) return rc;
     if (int rc = ctx->stage_d.reserve(l.d_bytes)) return rc;
+    if (offsets) { if (int rc = ctx->stage_b.reserve(sizeof(float) * 9 * T)) return rc; }
     if (int rc = ctx->pin(sizeof(esfm::TextureCam) * n)) return rc;
     uint8_t *p_a = ctx->stage_a.as<uint8_t>(), *p_c = ctx->stage_c.as<uint8_t>(), *p_d = ctx->stage_d.as<uint8_t>();
     fill_cams(static_cast<esfm::TextureCam *>(ctx->pinned), n_views, K4, poses);
@@ -117,6 +130,10 @@ int esfm_mesh_texture_bake(esfm_ctx *ctx, int n_vertices, int n_triangles, const
     a.cams = reinterpret_cast<const esfm::TextureCam *>(p_a + l.cams);
     a.images = p_c + l.images;
     a.atlas = p_d + l.atlas;
+    if (offsets) {                                                     // stage_b: the bake's only use of it
+        ESFM_HIP_TRY(esfm::copy_h2d(ctx->stage_b.ptr, offsets, sizeof(float) * 9 * T, st));
+        a.offsets = ctx->stage_b.as<float>();
+    }
     a.T = n_triangles; a.rows = rows; a.cols = cols; a.channels = channels; a.S = texels; a.A = atlas_width; a.H = H;
     if (int rc = esfm::launch_texture_bake(st, a)) return rc;
     ESFM_HIP_TRY(hipStreamSynchronize(st));

@@ -3,24 +3,13 @@
 // per-texel bake.  The only combination across threads is atomicMax on a uint32 (a positive f32 orders like its bit pattern), so
 // the buffers do not depend on the order in which the pairs arrive; the list of large boxes is filled in arrival order, which the
 // maximum does not see.  Every f32 expression is the header's, in its order (the build has no mul + add contraction).
-#include "texture_kernels.hpp"
+#include "texture_device.hpp"     // texture_project, texture_taps, texture_fetch
 
 namespace esfm {
 
 #define LAUNCH_OK() ESFM_HIP_TRY(hipGetLastError())
 
 static unsigned blocks_of(int64_t n) { return (unsigned)((n + 255) / 256); }
-
-// u, w, p2 of a world point; true if it is in front of the view
-__device__ inline bool texture_project(const TextureCam &c, float X0, float X1, float X2, float &u, float &w, float &p2)
-{
-    const float p0 = ((c.P[0] * X0 + c.P[1] * X1) + c.P[2] * X2) + c.P[3];
-    const float p1 = ((c.P[4] * X0 + c.P[5] * X1) + c.P[6] * X2) + c.P[7];
-    p2 = ((c.P[8] * X0 + c.P[9] * X1) + c.P[10] * X2) + c.P[11];
-    u = c.K[0] * (p0 / p2) + c.K[1];
-    w = c.K[2] * (p1 / p2) + c.K[3];
-    return p2 > 0.f && fabsf(u) <= 1048576.f && fabsf(w) <= 1048576.f;
-}
 
 __global__ __launch_bounds__(256) void texture_project_kernel(TextureViewsArgs a)
 {
@@ -156,6 +145,8 @@ __global__ __launch_bounds__(256) void texture_choose_kernel(TextureViewsArgs a)
 
 // One thread per texel, numbered square by square (S S consecutive threads fill one square), so a wave covers whole squares or whole
 // rows of one: its image reads stay inside the two triangles' footprints instead of running along an atlas row over many charts.
+// kOffsets: the levelled bake of esfm_mesh_texture_bake_ex, a variant of its own so that the plain one keeps its code.
+template <bool kOffsets>
 __global__ __launch_bounds__(256) void texture_bake_kernel(TextureBakeArgs a)
 {
     const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -178,15 +169,14 @@ __global__ __launch_bounds__(256) void texture_bake_kernel(TextureBakeArgs a)
         float u, w, p2;
         texture_project(a.cams[label], X[0], X[1], X[2], u, w, p2);
         if (p2 > 0.f) {
-            const float uc = fminf(fmaxf(u, 0.0f), (float)(a.cols - 1)), wc = fminf(fmaxf(w, 0.0f), (float)(a.rows - 1));
-            const float x0 = fminf(floorf(uc), (float)(a.cols - 2)), y0 = fminf(floorf(wc), (float)(a.rows - 2));
-            const float ax = uc - x0, ay = wc - y0;
-            const uint8_t *I = a.images + (((int64_t)label * a.rows + (int)y0) * a.cols + (int)x0) * a.channels;
-            const int64_t right = a.channels, down = (int64_t)a.cols * a.channels;
+            const TextureTaps taps = texture_taps(a.images, label, a.rows, a.cols, a.channels, u, w);
             for (int c = 0; c < 3; ++c) {
-                const int ch = a.channels == 3 ? 2 - c : 0;
-                const float v = (1.0f - ay) * ((1.0f - ax) * (float)I[ch] + ax * (float)I[right + ch]) +
-                                ay * ((1.0f - ax) * (float)I[down + ch] + ax * (float)I[down + right + ch]);
+                float v = texture_fetch(taps, a.channels == 3 ? 2 - c : 0);
+                if constexpr (kOffsets) {
+                    const float *o = a.offsets + 9 * t + c;          // the three corners' offsets of this channel
+                    v = v + ((b0 * o[0] + b1 * o[3]) + b2 * o[6]);
+                    v = fminf(fmaxf(v, 0.0f), 255.0f);
+                }
                 out[c] = (uint8_t)floorf(v + 0.5f);
             }
             return;
@@ -230,7 +220,8 @@ int launch_texture_choose(hipStream_t st, const TextureViewsArgs &a)
 
 int launch_texture_bake(hipStream_t st, const TextureBakeArgs &a)
 {
-    hipLaunchKernelGGL(texture_bake_kernel, dim3(blocks_of((int64_t)a.H * a.A * a.S)), dim3(256), 0, st, a);
+    if (a.offsets) hipLaunchKernelGGL(texture_bake_kernel<true>, dim3(blocks_of((int64_t)a.H * a.A * a.S)), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(texture_bake_kernel<false>, dim3(blocks_of((int64_t)a.H * a.A * a.S)), dim3(256), 0, st, a);
     LAUNCH_OK();
     return ESFM_OK;
 }

@@ -28,6 +28,7 @@ struct TextureBakeArgs {
     const TextureCam *cams;
     const uint8_t *images;       // n x rows x cols x channels
     uint8_t *atlas;              // H x W x 3
+    const float *offsets;        // T x 3 corners x 3 channels, finite (checked on the host); NULL: the plain bake
     int32_t T, rows, cols, channels, S, A, H;   // W = A S
 };
 

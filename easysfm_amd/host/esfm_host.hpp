@@ -1217,8 +1217,11 @@ public:
     // registered frames (process_frame_id false; at most 64, in frame order), then a square atlas of ceil(sqrt(ceil(T / 2))) squares per
     // row is baked.  texels 0 derives the chart size: the median over the labelled triangles of sqrt(2 score), rounded up, clamped to
     // 4 .. 64.  uv: T x 3 x 2; atlas: atlas_rows x atlas_cols x 3 RGB; texels_used: the chart size.
+    // level: not NULL runs levelTexture between the view choice and the bake, as run_sfm(dense_mesh_texture_level=True) does, and
+    // receives its counts.
     bool textureMesh(const TriangleMesh &mesh, const std::vector<frame_t> &frames, const std::vector<bool> &process_frame_id, int texels,
-                     std::vector<float> &uv, std::vector<uint8_t> &atlas, int &atlas_rows, int &atlas_cols, int &n_labelled, int &n_views, int &texels_used)
+                     std::vector<float> &uv, std::vector<uint8_t> &atlas, int &atlas_rows, int &atlas_cols, int &n_labelled, int &n_views, int &texels_used,
+                     esfm_mesh_texture_level_stats *level = nullptr)
     {
         uv.clear(); atlas.clear();
         atlas_rows = atlas_cols = n_labelled = n_views = texels_used = 0;
@@ -1272,16 +1275,35 @@ public:
         if (width < 1) width = 1;
         int32_t need = 0;
         uv.assign(size_t(6) * size_t(nt), 0.f);
-        rc = esfm_mesh_texture_bake(default_ctx(), nv, nt, vtx.data(), col.data(), mesh.triangles.data(), label.data(), n_views, rows, cols, ch, images.data(),
-                                    K4.data(), poses.data(), texels_used, width, 0, nullptr, uv.data(), &need);       // the height first
+        std::vector<float> offsets;
+        if (level && !levelTexture(vtx, mesh.triangles, label, n_views, rows, cols, ch, images, K4, poses, offsets, *level)) return false;
+        const float *off = level ? offsets.data() : nullptr;              // NULL: esfm_mesh_texture_bake itself
+        rc = esfm_mesh_texture_bake_ex(default_ctx(), nv, nt, vtx.data(), col.data(), mesh.triangles.data(), label.data(), n_views, rows, cols, ch, images.data(),
+                                       K4.data(), poses.data(), texels_used, width, 0, nullptr, uv.data(), &need, off);      // the height first
         if (rc != ESFM_OK && need <= 0) { std::cerr << esfm_last_error() << std::endl; return false; }
         atlas_rows = need; atlas_cols = width * texels_used;
         atlas.assign(size_t(atlas_rows) * size_t(atlas_cols) * 3, 0);
         if (need > 0) {
-            rc = esfm_mesh_texture_bake(default_ctx(), nv, nt, vtx.data(), col.data(), mesh.triangles.data(), label.data(), n_views, rows, cols, ch,
-                                        images.data(), K4.data(), poses.data(), texels_used, width, atlas_rows, atlas.data(), uv.data(), &need);
+            rc = esfm_mesh_texture_bake_ex(default_ctx(), nv, nt, vtx.data(), col.data(), mesh.triangles.data(), label.data(), n_views, rows, cols, ch,
+                                           images.data(), K4.data(), poses.data(), texels_used, width, atlas_rows, atlas.data(), uv.data(), &need, off);
             if (rc != ESFM_OK) { std::cerr << esfm_last_error() << std::endl; return false; }
         }
+        return true;
+    }
+
+    // esfm.h "Mesh texturing", esfm_mesh_texture_level with its default options: one colour offset per triangle corner and channel
+    // (T x 3 x 3) that takes the steps out of the seams between triangles of different labels; the bake adds them.
+    bool levelTexture(const std::vector<float> &vtx, const std::vector<int32_t> &triangles, const std::vector<int32_t> &label, int n_views, int rows,
+                      int cols, int ch, const std::vector<uint8_t> &images, const std::vector<float> &K4, const std::vector<float> &poses,
+                      std::vector<float> &offsets, esfm_mesh_texture_level_stats &stats)
+    {
+        const int nv = int(vtx.size() / 3), nt = int(triangles.size() / 3);
+        esfm_mesh_texture_level_options opt;
+        esfm_mesh_texture_level_options_default(&opt);
+        offsets.assign(size_t(9) * size_t(nt), 0.f);
+        const int rc = esfm_mesh_texture_level(default_ctx(), nv, nt, vtx.data(), triangles.data(), label.data(), n_views, rows, cols, ch, images.data(),
+                                               K4.data(), poses.data(), &opt, offsets.data(), nullptr, &stats);
+        if (rc != ESFM_OK) { std::cerr << esfm_last_error() << std::endl; return false; }
         return true;
     }
 

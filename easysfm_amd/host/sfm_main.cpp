@@ -86,7 +86,8 @@ int main(int argc, char **argv)
     // cleans the mesh with the defaults of esfm.h "Mesh clean-up" before it is written to mesh.ply, simplify:mesh.ply merges the
     // vertices of every cell of two voxels' side (esfm.h "Mesh simplification"), clean+simplify:mesh.ply does both in that order; with
     // +texture in the prefix (texture:, clean+texture:, simplify+texture:, clean+simplify+texture:) the mesh is then textured from the
-    // registered frames (esfm.h "Mesh texturing") and written with texture coordinates, its atlas beside it as mesh.png
+    // registered frames (esfm.h "Mesh texturing") and written with texture coordinates, its atlas beside it as mesh.png; +level behind
+    // +texture (e.g. clean+simplify+texture+level:mesh.ply) levels the seams between the frames first, +level without +texture is an error
     const std::string filter_arg = argc >= 15 ? argv[14] : "ratio";
     const std::string guided_suffix = "+guided";
     const bool guided = filter_arg.size() > guided_suffix.size() && filter_arg.compare(filter_arg.size() - guided_suffix.size(), guided_suffix.size(), guided_suffix) == 0;
@@ -94,7 +95,7 @@ int main(int argc, char **argv)
     const std::string dense_file = argc >= 16 && std::string(argv[15]) != "none" ? argv[15] : "";
     const std::string merged_file = argc >= 17 && std::string(argv[16]) != "none" ? argv[16] : "";
     const std::string mesh_arg = argc == 18 && std::string(argv[17]) != "none" ? argv[17] : "";
-    bool clean_mesh = false, simplify_mesh = false, texture_mesh = false;
+    bool clean_mesh = false, simplify_mesh = false, texture_mesh = false, level_mesh = false, level_alone = mesh_arg.compare(0, 6, "level:") == 0;
     std::string mesh_file = mesh_arg;
     {
         struct Form { const char *prefix; bool clean, simplify, texture; };
@@ -103,6 +104,13 @@ int main(int argc, char **argv)
                               {"simplify:", false, true, false}};
         for (const Form &f : forms) {
             const size_t len = std::strlen(f.prefix);
+            const std::string levelled = std::string(f.prefix, len - 1) + "+level:";
+            if (mesh_arg.compare(0, levelled.size(), levelled) == 0) {
+                clean_mesh = f.clean; simplify_mesh = f.simplify; texture_mesh = f.texture;
+                level_mesh = f.texture; level_alone = !f.texture;
+                mesh_file = mesh_arg.substr(levelled.size());
+                break;
+            }
             if (mesh_arg.compare(0, len, f.prefix) == 0) {
                 clean_mesh = f.clean; simplify_mesh = f.simplify; texture_mesh = f.texture;
                 mesh_file = mesh_arg.substr(len);
@@ -110,12 +118,13 @@ int main(int argc, char **argv)
             }
         }
     }
-    if (argc < 14 || argc > 18 || (match_filter != "ratio" && match_filter != "cross" && match_filter != "ratio+cross")) {
+    if (argc < 14 || argc > 18 || (match_filter != "ratio" && match_filter != "cross" && match_filter != "ratio+cross") || level_alone) {
         std::cerr << "usage: sfm_native image_folder image_list calib_K_file calib_distort_file output.ply feature_type(S | O | I) feature_parameter "
                      "repro_dis_ransac find_init_frames ba_calib_change_tolerance ba_frequency launch_viewer view_sphere [match_filter: ratio | cross | ratio+cross | "
                      "ratio+guided | cross+guided | ratio+cross+guided [dense.ply | none [merged.ply | none [simplify:mesh.ply | "
                      "clean+simplify:mesh.ply | mesh.ply | clean:mesh.ply | none]]]] (the 17th's prefix also takes +texture: texture:, clean+texture:, "
-                     "simplify+texture:, clean+simplify+texture:)"
+                     "simplify+texture:, clean+simplify+texture:) (and +level behind +texture: texture+level:, clean+texture+level:, simplify+texture+level:, "
+                     "clean+simplify+texture+level:)"
                   << std::endl;
         return 2;
     }
@@ -455,7 +464,11 @@ int main(int argc, char **argv)
                     std::vector<float> uv;
                     std::vector<uint8_t> atlas;
                     int atlas_rows = 0, atlas_cols = 0, n_labelled = 0, n_views = 0, texels = 0;
-                    if (!dr.textureMesh(mesh, frames, todo, 0, uv, atlas, atlas_rows, atlas_cols, n_labelled, n_views, texels)) return 3;
+                    esfm_mesh_texture_level_stats level = {0, 0, 0, 0};
+                    if (!dr.textureMesh(mesh, frames, todo, 0, uv, atlas, atlas_rows, atlas_cols, n_labelled, n_views, texels, level_mesh ? &level : nullptr)) return 3;
+                    if (level_mesh)
+                        std::cout << "Mesh texture level: [" << level.nodes << "] nodes, [" << level.seam_vertices << "] seam vertices, [" << level.iterations
+                                  << "] iterations" << std::endl;
                     std::cout << "Mesh texture: [" << mesh.triangles.size() / 3 << "] triangles, [" << n_labelled << "] labelled from [" << n_views
                               << "] views, charts of [" << texels << "] texels, atlas [" << atlas_cols << "] x [" << atlas_rows << "]." << std::endl;
                     if (!io.writePlyTexturedMesh(mesh_file, mesh, uv, atlas_rows, atlas_cols, atlas)) return 3;

@@ -4,7 +4,8 @@ with the volume staying on the device (``mvs_mesh``).  ``dense_mesh`` takes what
 adjustment, as ``mvs.dense_merge`` does, and ends in a mesh instead of a point cloud.  ``mesh_components`` and ``mesh_clean``
 (esfm.h, "Mesh clean-up") label a mesh's connected pieces, drop the small ones, smooth the rest and recompute its normals;
 ``mesh_simplify`` (esfm.h, "Mesh simplification") merges the vertices of each cell of a regular grid into one;
-``mesh_texture`` (esfm.h, "Mesh texturing") lets every triangle choose the view that sees it best and bakes a texture atlas."""
+``mesh_texture`` (esfm.h, "Mesh texturing") lets every triangle choose the view that sees it best and bakes a texture atlas;
+``mesh_texture_level`` solves for per-vertex colour offsets that take the steps out of the seams between views."""
 from __future__ import annotations
 
 import ctypes as C
@@ -12,7 +13,8 @@ from typing import Optional, Sequence, Tuple
 
 import numpy as np
 
-from ._lib import Context, MeshCleanOptions, MeshSimplifyOptions, MeshTextureOptions, MVSOptions, TSDFGrid, TSDFOptions, check, default_context, lib
+from ._lib import (Context, MeshCleanOptions, MeshSimplifyOptions, MeshTextureLevelOptions, MeshTextureLevelStats, MeshTextureOptions, MVSOptions,
+                   TSDFGrid, TSDFOptions, check, default_context, lib)
 from .mvs import MergeOptions, _views, default_mvs_options, frame_arrays, merge_voxel_size, mvs_depth_maps, mvs_fuse, mvs_plan
 from .types import Frame, SparsePointCloud
 
@@ -340,9 +342,50 @@ def default_atlas_width(n_triangles: int) -> int:
     return max(a, 1)
 
 
+def default_mesh_texture_level_options() -> MeshTextureLevelOptions:
+    """esfm_mesh_texture_level_options_default: lam (lambda) 0.1, mu 0.001, tolerance 1e-4, max_iterations 200."""
+    opt = MeshTextureLevelOptions()
+    lib().esfm_mesh_texture_level_options_default(C.byref(opt))
+    return opt
+
+
+def _image_array(images):
+    imgs = np.ascontiguousarray(images, np.uint8)
+    if imgs.ndim == 3:
+        imgs = imgs[..., None]
+    if imgs.ndim != 4:
+        raise ValueError("images must be [n_views, rows, cols(, channels)]")
+    return imgs
+
+
+def mesh_texture_level(vertices, triangles, label, images, K4, poses, opt: Optional[MeshTextureLevelOptions] = None,
+                       ctx: Optional[Context] = None):
+    """esfm_mesh_texture_level: one additive colour offset per (vertex, view) such that the views agree where triangles of
+    different labels meet.  Returns (offsets [T, 3, 3] float32: corner x RGB, for mesh_texture_bake(offsets=...), samples [T, 3, 3]
+    float32: the unrounded image values at the corners, stats: MeshTextureLevelStats with nodes, seam_vertices, iterations,
+    converged)."""
+    opt = opt or default_mesh_texture_level_options()
+    ctx = ctx or default_context()
+    v = np.ascontiguousarray(vertices, np.float32).reshape(-1, 3)
+    t = _triangle_array(triangles)
+    lab = np.ascontiguousarray(label, np.int32).reshape(-1)
+    if len(lab) != len(t):
+        raise ValueError("label must hold one view per triangle")
+    imgs = _image_array(images)
+    n, rows, cols, ch = imgs.shape
+    K, P = _cameras(K4, poses)
+    if len(K) != n:
+        raise ValueError("one K4 and one pose per image")
+    offsets, samples = np.zeros((len(t), 3, 3), np.float32), np.zeros((len(t), 3, 3), np.float32)
+    stats = MeshTextureLevelStats()
+    check(lib().esfm_mesh_texture_level(ctx.handle, len(v), len(t), _ptr(v), _ptr(t), _ptr(lab), n, rows, cols, ch, _ptr(imgs), _ptr(K), _ptr(P),
+                                        C.byref(opt), _ptr(offsets), _ptr(samples), C.byref(stats)))
+    return offsets, samples, stats
+
+
 def mesh_texture_bake(vertices, rgb, triangles, label, images, K4, poses, texels: int, atlas_width: Optional[int] = None,
-                      ctx: Optional[Context] = None):
-    """esfm_mesh_texture_bake: every triangle gets a chart of `texels` x `texels` / 2 texels, two per square and `atlas_width`
+                      ctx: Optional[Context] = None, offsets=None):
+    """esfm_mesh_texture_bake, or with offsets [T, 3, 3] float32 (mesh_texture_level's) esfm_mesh_texture_bake_ex: every triangle gets a chart of `texels` x `texels` / 2 texels, two per square and `atlas_width`
     squares per atlas row (None = a square atlas), filled from the view label[t] names (images [n, rows, cols(, 1 | 3)] uint8, BGR)
     or, for label -1, from the vertex colours (grey without them).  Returns (atlas [H, W, 3] uint8 RGB, uv [T, 3, 2] float32,
     normalised, origin at the outer corner of the atlas's first texel, v down the rows)."""
@@ -365,13 +408,17 @@ def mesh_texture_bake(vertices, rgb, triangles, label, images, K4, poses, texels
     if len(K) != n:
         raise ValueError("one K4 and one pose per image")
     width = default_atlas_width(len(t)) if atlas_width is None else int(atlas_width)
+    off = np.ascontiguousarray(offsets, np.float32).reshape(-1, 3, 3) if offsets is not None else None
+    if off is not None and len(off) != len(t):
+        raise ValueError("offsets must hold three corners of three channels per triangle")
     uv = np.zeros((len(t), 3, 2), np.float32)
     need = C.c_int32(-1)
     cap = 0
     atlas = np.zeros((0, 0, 3), np.uint8)
     for attempt in range(2):                                            # the first call asks for the height, the second bakes
-        status = lib().esfm_mesh_texture_bake(ctx.handle, len(v), len(t), _ptr(v), _ptr(c), _ptr(t), _ptr(lab), n, rows, cols, ch, _ptr(imgs),
-                                              _ptr(K), _ptr(P), int(texels), width, cap, _ptr(atlas) if cap else None, _ptr(uv), C.byref(need))
+        args = (ctx.handle, len(v), len(t), _ptr(v), _ptr(c), _ptr(t), _ptr(lab), n, rows, cols, ch, _ptr(imgs), _ptr(K), _ptr(P), int(texels), width,
+                cap, _ptr(atlas) if cap else None, _ptr(uv), C.byref(need))
+        status = lib().esfm_mesh_texture_bake(*args) if off is None else lib().esfm_mesh_texture_bake_ex(*args, _ptr(off))
         if attempt == 0 and status == -1 and need.value > cap:
             cap = need.value
             atlas = np.zeros((cap, width * int(texels), 3), np.uint8)
@@ -391,14 +438,18 @@ def auto_texels(label, score) -> int:
 
 
 def mesh_texture(vertices, rgb, triangles, images, K4, poses, texels: Optional[int] = None, atlas_width: Optional[int] = None,
-                 opt: Optional[MeshTextureOptions] = None, ctx: Optional[Context] = None):
+                 opt: Optional[MeshTextureOptions] = None, ctx: Optional[Context] = None, level=False):
     """View choice and bake in one: returns (atlas [H, W, 3] uint8 RGB, uv [T, 3, 2] float32, label [T] int32, score [T] float32).
-    texels=None derives the chart size from the triangles' screen areas (auto_texels)."""
+    texels=None derives the chart size from the triangles' screen areas (auto_texels).  level=True (or a MeshTextureLevelOptions)
+    levels the seams between the views before the bake (mesh_texture_level)."""
     ctx = ctx or default_context()
     imgs = np.asarray(images)
     label, score = mesh_texture_views(vertices, triangles, imgs.shape[1], imgs.shape[2], K4, poses, opt, ctx)
     S = auto_texels(label, score) if texels is None else int(texels)
-    atlas, uv = mesh_texture_bake(vertices, rgb, triangles, label, imgs, K4, poses, S, atlas_width, ctx)
+    offsets = None
+    if level:
+        offsets = mesh_texture_level(vertices, triangles, label, imgs, K4, poses, level if isinstance(level, MeshTextureLevelOptions) else None, ctx)[0]
+    atlas, uv = mesh_texture_bake(vertices, rgb, triangles, label, imgs, K4, poses, S, atlas_width, ctx, offsets)
     return atlas, uv, label, score
 
 
@@ -406,4 +457,5 @@ __all__ = ["TSDFGrid", "TSDFOptions", "MeshOptions", "MeshCleanOptions", "MeshSi
            "default_mesh_clean_options", "default_mesh_simplify_options", "tsdf_grid", "tsdf_integrate", "tsdf_extract", "mvs_mesh",
            "masked_depth", "mesh_grid", "mesh_arrays", "dense_mesh", "mesh_components", "mesh_clean", "mesh_simplify",
            "MeshTextureOptions", "default_mesh_texture_options", "default_atlas_width", "auto_texels", "mesh_texture_views",
-           "mesh_texture_bake", "mesh_texture"]
+           "mesh_texture_bake", "mesh_texture", "MeshTextureLevelOptions", "MeshTextureLevelStats", "default_mesh_texture_level_options",
+           "mesh_texture_level"]

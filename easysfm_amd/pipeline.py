@@ -19,7 +19,7 @@ from .cloud import CProceesing, write_ply, write_ply_mesh, write_ply_normals, wr
 from .matching import DescriptorBank, FeatureMatching, PairMatcher
 from .motion import MotionEstimator, _dehomogenise, find_essential_pairs, pixel2cam, recover_pose_pairs, triangulate_pairs
 from .mesh import (MeshCleanOptions, MeshOptions, auto_texels, default_atlas_width, mesh_arrays, mesh_clean, mesh_components, mesh_simplify,
-                   mesh_texture_bake, mesh_texture_views)
+                   mesh_texture_bake, mesh_texture_level, mesh_texture_views)
 from .mvs import MergeOptions, default_mvs_options, dense_reconstruction, frame_arrays, merge_arrays
 from .types import DMatch, Frame, SparsePointCloud
 
@@ -164,7 +164,7 @@ def run_sfm(frames: List[Frame], output_file: Optional[str] = None, use_feature:
             ctx: Optional[Context] = None, verbose: bool = False, match_filter: str = "ratio", dense_output_file: Optional[str] = None,
             dense_merged_output_file: Optional[str] = None, dense_mesh_output_file: Optional[str] = None,
             dense_mesh_clean: Optional[MeshCleanOptions] = None, dense_mesh_simplify: Optional[float] = None,
-            dense_mesh_texture: Optional[int] = None):
+            dense_mesh_texture: Optional[int] = None, dense_mesh_texture_level: bool = False):
     """sfm.cpp:128-339.  Returns (sparse cloud before the final filter, filtered cloud, img_match_graph).
     dense_output_file: after the final BA and the sparse .ply, run dense_reconstruct on the registered frames and the cloud
     before the filter (it carries the track ids) and write the dense cloud there (esfm.h "Dense reconstruction").
@@ -182,7 +182,9 @@ def run_sfm(frames: List[Frame], output_file: Optional[str] = None, use_feature:
     dense_mesh_texture: with dense_mesh_output_file, the chart size in texels (4..64), or 0 to derive it from the triangles' screen
     areas: after the optional clean-up and simplification every triangle chooses one of the registered frames (at most 64, in
     frame order) and a texture atlas is baked from them (esfm.h "Mesh texturing", default options, a square atlas); the mesh is
-    written with texture coordinates and the atlas beside it as a .png; prints one "Mesh texture:" line.  None: vertex colours only."""
+    written with texture coordinates and the atlas beside it as a .png; prints one "Mesh texture:" line.  None: vertex colours only.
+    dense_mesh_texture_level: with dense_mesh_texture, level the seams between triangles that chose different frames before the bake
+    (esfm.h "Mesh texturing", esfm_mesh_texture_level, default options); prints one "Mesh texture level:" line."""
     ctx = ctx or default_context()
     fm, ee = FeatureMatching(ctx), MotionEstimator(ctx)
     for f in frames:
@@ -272,7 +274,12 @@ def run_sfm(frames: List[Frame], output_file: Optional[str] = None, use_feature:
                 reg = ~np.asarray(todo, bool)
                 label, score = mesh_texture_views(vertices, triangles, imgs.shape[1], imgs.shape[2], K4[reg], poses[reg], None, ctx)
                 texels = int(dense_mesh_texture) if dense_mesh_texture else auto_texels(label, score)
-                atlas, uv = mesh_texture_bake(vertices, rgb, triangles, label, imgs[reg], K4[reg], poses[reg], texels, default_atlas_width(len(triangles)), ctx)
+                offsets = None
+                if dense_mesh_texture_level:
+                    offsets, _, level = mesh_texture_level(vertices, triangles, label, imgs[reg], K4[reg], poses[reg], None, ctx)
+                    print(f"Mesh texture level: [{level.nodes}] nodes, [{level.seam_vertices}] seam vertices, [{level.iterations}] iterations")
+                atlas, uv = mesh_texture_bake(vertices, rgb, triangles, label, imgs[reg], K4[reg], poses[reg], texels, default_atlas_width(len(triangles)), ctx,
+                                              offsets)
                 print(f"Mesh texture: [{len(triangles)}] triangles, [{int(np.count_nonzero(label >= 0))}] labelled from [{int(reg.sum())}] views, charts of "
                       f"[{texels}] texels, atlas [{atlas.shape[1]}] x [{atlas.shape[0]}].")
                 write_ply_textured_mesh(dense_mesh_output_file, vertices, normals, triangles, uv, atlas)

@@ -1115,12 +1115,47 @@ int esfm_mesh_simplify(esfm_ctx *ctx, int n_vertices, int n_triangles, const flo
  *   Capacity: *atlas_rows receives H whenever the arguments are otherwise valid; if H > max_atlas_rows nothing else is written and
  *   the call returns ESFM_ERR_INVALID_ARG with H in the message.
  *
+ * esfm_mesh_texture_level: seam levelling.  Where neighbouring triangles chose different views the atlas shows a step in colour
+ * (exposure, vignetting, small pose errors).  Every (vertex, label) pair gets one additive offset per colour channel such that the
+ * views agree at the vertices they share and the offsets vary smoothly inside each view's region: the global adjustment of Waechter,
+ * Moehrle and Goesele (2014), restricted to vertex samples.  Steps 2 to 5 are f64, no mul + add contraction, correctly rounded
+ * division; no sum depends on thread order, so tests/level_ref.py restates this text and the GPU reproduces it bit for bit.
+ *   1. Samples.  Triangle t takes part if label[t] >= 0 and all three of its vertices have p2 > 0 in view label[t].  Corner k of
+ *      such a triangle projects its vertex into that view; per RGB channel f is the bake's bilinear c at (u, w) -- the same clamps,
+ *      x0, y0, ax, ay and operation order --, kept as f32 and not rounded.  3 channels: BGR as in the bake; 1 channel: the three
+ *      colour channels are equal.  Every other triangle gets offsets and samples 0 and contributes nothing.
+ *   2. Nodes.  A node is a distinct (vertex, label) among the corners that take part, its key vertex * 64 + label; nodes are numbered
+ *      in ascending key order (all corners of a node sample the same pixel position, so a node has one f).  seam(a): the other nodes
+ *      with a's vertex (a contiguous run).  smooth(a): the nodes b != a that share a triangle that takes part with a, each once
+ *      however many triangles share the edge; a repeated index in a triangle gives no pair.  A seam vertex has two or more nodes.
+ *   3. System, per channel: minimise  sum over seam pairs ((g_a + f_a) - (g_b + f_b))^2 + lambda sum over smooth pairs (g_a - g_b)^2
+ *      + mu sum g_a^2.  Its normal equations, per node:  (A g)_a = (s + lambda * m) + mu * g_a  with s = sum over b in seam(a) of
+ *      (g_a - g_b), m = sum over b in smooth(a) of (g_a - g_b), both in ascending b and starting from 0.0;  rhs_a = sum over b in
+ *      seam(a), ascending, of ((double)f_b - (double)f_a), from 0.0;  d_a = ((double)|seam(a)| + lambda * (double)|smooth(a)|) + mu.
+ *   4. tree_sum(x[0 .. n)): 0.0 for n = 0; otherwise x is padded with +0.0 to a multiple of 256, in every block of 256, for h = 128,
+ *      64, .., 1: x[i] += x[i + h] for i < h, block j's x[0] is element j of the next level, until one value is left.  dot(x, y) is
+ *      the tree_sum of the rounded products x_a * y_a, per channel.
+ *   5. Jacobi-preconditioned conjugate gradients, the three channels in one loop, each with its own scalars:
+ *        g = 0, r = rhs, z = r / d, p = z, rz = dot(r, z), bb = dot(rhs, rhs).  No node, or bb == 0 in every channel: iterations 0,
+ *        converged 1.  Otherwise, for k = 1 .. max_iterations (none for 0: iterations 0, converged 0):
+ *          q = A p;  pq = dot(p, q);  alpha = rz / pq (0.0 if pq == 0);  g = g + alpha * p;  r = r - alpha * q;  rr = dot(r, r);
+ *          if rr <= (tolerance * tolerance) * bb in every channel: iterations = k, converged = 1, stop;
+ *          z = r / d;  rz' = dot(r, z);  beta = rz' / rz (0.0 if rz == 0);  p = z + beta * p;  rz = rz'.
+ *        Never stopped: iterations = max_iterations, converged = 0.  The count is part of the result.
+ *   6. Outputs: offsets [T, 3 corners, 3 RGB] f32 = (float)g of the corner's node, samples (same shape, may be NULL) = f, stats.
+ * esfm_mesh_texture_bake_ex is esfm_mesh_texture_bake with offsets [T, 3, 3] (NULL: the same call, bit for bit).  A texel that takes
+ * its colour from a view gets, per channel and on the unrounded bilinear c, c = c + ((b0 * o0 + b1 * o1) + b2 * o2) in f32 with its
+ * own barycentrics and its triangle's three corner offsets (the gutter extrapolates), c = fminf(fmaxf(c, 0.0f), 255.0f), then
+ * (uint8)floorf(c + 0.5f).  Texels with the fallback colour are untouched.
+ *
  * Options (esfm_mesh_texture_options_default): min_cos 0.2 (in [0, 1)), occlusion_tol 0.02 (in [0, 1)).
+ * (esfm_mesh_texture_level_options_default): lambda 0.1 (finite, > 0), mu 0.001 (finite, > 0), tolerance 1e-4 (in [0, 1)),
+ * max_iterations 200 (0..10000).
  * Rejected with ESFM_ERR_INVALID_ARG, before the device is looked at and with nothing written: a vertex, K4 or pose value that is
  * not finite, a focal length of 0, a triangle index outside 0 .. V - 1, a count, n_views, rows or cols out of range, channels other
  * than 1 or 3, texels outside 4..64, atlas_width < 1, an atlas above 16384 texels per side, a label outside -1 .. n_views - 1, an
- * option out of range, a required pointer that is NULL.  Host pointers; without a usable device ESFM_ERR_NO_DEVICE (no CPU
- * fallback). */
+ * option out of range, an offset that is not finite, a required pointer that is NULL.  Host pointers; without a usable device
+ * ESFM_ERR_NO_DEVICE (no CPU fallback). */
 typedef struct esfm_mesh_texture_options {
     float min_cos;
     float occlusion_tol;
@@ -1136,6 +1171,30 @@ int esfm_mesh_texture_bake(esfm_ctx *ctx, int n_vertices, int n_triangles, const
                            const float *K4 /*4 each*/, const float *poses /*12 each*/, int texels, int atlas_width,
                            int max_atlas_rows, uint8_t *atlas /*max_atlas_rows x W x 3*/, float *uv /*T x 3 x 2*/,
                            int32_t *atlas_rows);
+typedef struct esfm_mesh_texture_level_options {
+    double lambda;
+    double mu;
+    double tolerance;
+    int32_t max_iterations;
+} esfm_mesh_texture_level_options;
+typedef struct esfm_mesh_texture_level_stats {
+    int32_t nodes;
+    int32_t seam_vertices;
+    int32_t iterations;
+    int32_t converged;
+} esfm_mesh_texture_level_stats;
+void esfm_mesh_texture_level_options_default(esfm_mesh_texture_level_options *opt);
+int esfm_mesh_texture_level(esfm_ctx *ctx, int n_vertices, int n_triangles, const float *vertices /*3 each*/,
+                            const int32_t *triangles /*3 each*/, const int32_t *label /*T*/, int n_views, int rows, int cols,
+                            int channels, const uint8_t *images, const float *K4 /*4 each*/, const float *poses /*12 each*/,
+                            const esfm_mesh_texture_level_options *opt, float *offsets /*T x 3 x 3*/,
+                            float *samples /*T x 3 x 3, may be NULL*/, esfm_mesh_texture_level_stats *stats);
+int esfm_mesh_texture_bake_ex(esfm_ctx *ctx, int n_vertices, int n_triangles, const float *vertices /*3 each*/,
+                              const uint8_t *vertex_rgb /*3 each, may be NULL*/, const int32_t *triangles /*3 each*/,
+                              const int32_t *label /*T*/, int n_views, int rows, int cols, int channels, const uint8_t *images,
+                              const float *K4 /*4 each*/, const float *poses /*12 each*/, int texels, int atlas_width,
+                              int max_atlas_rows, uint8_t *atlas /*max_atlas_rows x W x 3*/, float *uv /*T x 3 x 2*/,
+                              int32_t *atlas_rows, const float *offsets /*T x 3 x 3, may be NULL*/);
 
 #ifdef __cplusplus
 }
