@@ -32,7 +32,7 @@ int esfm_mesh_texture_level(esfm_ctx *ctx, int n_vertices, int n_triangles, cons
     const int64_t n_corners = 3 * (int64_t)T, n_edges = 6 * (int64_t)T;
 
     // all scratch before the first launch: the number of nodes is not known yet, so the layout takes its bound, the corners
-    const int corner_bits = 6 + esfm::level_bit_width((uint64_t)V), edge_bits_max = 32 + esfm::level_bit_width((uint64_t)n_corners);
+    const int corner_bits = 6 + esfm::bit_width((uint64_t)V), edge_bits_max = esfm::mesh_key_bits(n_corners);
     size_t sort_corners = 0, sort_edges = 0;
     if (int rc = esfm::mesh_sort_scratch_bytes(n_corners, corner_bits, &sort_corners, st)) return rc;
     if (int rc = esfm::mesh_sort_scratch_bytes(n_edges, edge_bits_max, &sort_edges, st)) return rc;
@@ -42,7 +42,7 @@ int esfm_mesh_texture_level(esfm_ctx *ctx, int n_vertices, int n_triangles, cons
     if (int rc = ctx->stage_b.reserve(l.b_bytes)) return rc;
     if (int rc = ctx->stage_c.reserve(l.c_bytes)) return rc;
     if (int rc = ctx->stage_d.reserve(l.d_bytes)) return rc;
-    const size_t cams_b = esfm::texture_align(sizeof(esfm::TextureCam) * n);
+    const size_t cams_b = esfm::align256(sizeof(esfm::TextureCam) * n);
     if (int rc = ctx->pin(cams_b + 256)) return rc;
     uint8_t *p_a = ctx->stage_a.as<uint8_t>(), *p_b = ctx->stage_b.as<uint8_t>(), *p_c = ctx->stage_c.as<uint8_t>(), *p_d = ctx->stage_d.as<uint8_t>();
     esfm::TextureCam *cams = static_cast<esfm::TextureCam *>(ctx->pinned);
@@ -119,9 +119,7 @@ int esfm_mesh_texture_level(esfm_ctx *ctx, int n_vertices, int n_triangles, cons
     g.col = const_cast<int32_t *>(a.col);
     g.row_start = const_cast<int32_t *>(a.row_start);
     g.pinned = p_d + l.pinned;
-    if (int rc = esfm::launch_mesh_edge_keys(st, g)) return rc;
-    if (int rc = esfm::mesh_sort_keys(p_b + l.sort, sort_b, g.keys, const_cast<uint64_t *>(g.sorted), n_edges, 32 + esfm::level_bit_width((uint64_t)N), st)) return rc;
-    if (int rc = esfm::launch_mesh_adjacency(st, g)) return rc;
+    if (int rc = esfm::mesh_build_adjacency(st, g, p_b + l.sort, sort_b)) return rc;
 
     // conjugate gradients: rz and bb, then per iteration five launches and 24 bytes back
     if (int rc = esfm::launch_level_start(st, a)) return rc;

@@ -65,8 +65,6 @@ inline bool level_converged(const double rr[3], const double bb[3], double toler
     return rr[0] <= t2 * bb[0] && rr[1] <= t2 * bb[1] && rr[2] <= t2 * bb[2];
 }
 
-inline int level_bit_width(uint64_t x) { int n = 0; while (x) { ++n; x >>= 1; } return n; }
-
 // Byte offsets of the arrays inside the context's scratch buffers; every array starts on a multiple of 256 bytes.  The number of
 // nodes is known only on the device, so everything per node is laid out for its bound, the 3 T corners.
 struct LevelLayout {
@@ -92,45 +90,41 @@ inline LevelLayout level_layout(size_t V, size_t T, size_t n_views, size_t image
     l.corners = 3 * T;
     l.stride = (l.corners + 255) / 256 * 256;
     l.partials = (l.stride / 256 + 255) / 256 * 256;
-    size_t at = 0;
-    auto take = [&at](size_t bytes) { const size_t here = at; at += texture_align(bytes); return here; };
-    l.vertices = take(sizeof(float) * 3 * V);
-    l.tri = take(sizeof(int32_t) * 3 * T);
-    l.label = take(sizeof(int32_t) * T);
-    l.cams = take(sizeof(TextureCam) * n_views);
-    l.a_bytes = at;
-    at = 0;
-    l.keys = take(sizeof(uint64_t) * 6 * T);
-    l.sorted = take(sizeof(uint64_t) * 6 * T);
-    l.head_rank = take(sizeof(int32_t) * (6 * T + 1));
-    l.head_blocks = take(sizeof(int32_t) * ((6 * T + 255) / 256 + 1));
-    l.sort = take(sort_bytes);
-    l.b_bytes = at;
-    at = 0;
-    l.images = take(image_bytes);
-    l.c_bytes = at;
-    at = 0;
-    l.corner_keys = take(sizeof(uint64_t) * l.corners);
-    l.node_keys = take(sizeof(uint64_t) * l.corners);
-    l.corner_node = take(sizeof(int32_t) * l.corners);
-    l.seam_first = take(sizeof(int32_t) * l.corners);
-    l.seam_last = take(sizeof(int32_t) * l.corners);
-    l.col = take(sizeof(int32_t) * 6 * T);
-    l.row_start = take(sizeof(int32_t) * (l.corners + 1));
-    l.pinned = take(l.corners);
-    l.f = take(sizeof(float) * 3 * l.stride);
-    l.d = take(sizeof(double) * l.stride);
-    l.g = take(sizeof(double) * 3 * l.stride);
-    l.r = take(sizeof(double) * 3 * l.stride);
-    l.p = take(sizeof(double) * 3 * l.stride);
-    l.q = take(sizeof(double) * 3 * l.stride);
-    l.part_a = take(sizeof(double) * 3 * l.partials);
-    l.part_b = take(sizeof(double) * 3 * l.partials);
-    l.scalars = take(sizeof(double) * kLevelScalars);
-    l.counters = take(sizeof(int32_t) * 4);
-    l.offsets = take(sizeof(float) * 9 * T);
-    l.samples = take(sizeof(float) * 9 * T);
-    l.d_bytes = at;
+    ScratchCarver a, b, c, d;
+    l.vertices = a.take(sizeof(float) * 3 * V);
+    l.tri = a.take(sizeof(int32_t) * 3 * T);
+    l.label = a.take(sizeof(int32_t) * T);
+    l.cams = a.take(sizeof(TextureCam) * n_views);
+    l.a_bytes = a.at;
+    l.keys = b.take(sizeof(uint64_t) * 6 * T);
+    l.sorted = b.take(sizeof(uint64_t) * 6 * T);
+    l.head_rank = b.take(sizeof(int32_t) * (6 * T + 1));
+    l.head_blocks = b.take(sizeof(int32_t) * ((6 * T + 255) / 256 + 1));
+    l.sort = b.take(sort_bytes);
+    l.b_bytes = b.at;
+    l.images = c.take(image_bytes);
+    l.c_bytes = c.at;
+    l.corner_keys = d.take(sizeof(uint64_t) * l.corners);
+    l.node_keys = d.take(sizeof(uint64_t) * l.corners);
+    l.corner_node = d.take(sizeof(int32_t) * l.corners);
+    l.seam_first = d.take(sizeof(int32_t) * l.corners);
+    l.seam_last = d.take(sizeof(int32_t) * l.corners);
+    l.col = d.take(sizeof(int32_t) * 6 * T);
+    l.row_start = d.take(sizeof(int32_t) * (l.corners + 1));
+    l.pinned = d.take(l.corners);
+    l.f = d.take(sizeof(float) * 3 * l.stride);
+    l.d = d.take(sizeof(double) * l.stride);
+    l.g = d.take(sizeof(double) * 3 * l.stride);
+    l.r = d.take(sizeof(double) * 3 * l.stride);
+    l.p = d.take(sizeof(double) * 3 * l.stride);
+    l.q = d.take(sizeof(double) * 3 * l.stride);
+    l.part_a = d.take(sizeof(double) * 3 * l.partials);
+    l.part_b = d.take(sizeof(double) * 3 * l.partials);
+    l.scalars = d.take(sizeof(double) * kLevelScalars);
+    l.counters = d.take(sizeof(int32_t) * 4);
+    l.offsets = d.take(sizeof(float) * 9 * T);
+    l.samples = d.take(sizeof(float) * 9 * T);
+    l.d_bytes = d.at;
     return l;
 }
 

@@ -6,39 +6,11 @@
 // integer count, so the result does not depend on scheduling; tests/level_ref.py restates the rule and the output is compared bit
 // for bit (-ffp-contract=off; HIP's f64 division is correctly rounded).  Nothing waits for another workgroup: every hand-over is
 // the end of a launch.  Vectors are stored channel by channel, so a wave's 64 nodes read 512 contiguous bytes per channel.
+#include "block_scan.hpp"
 #include "level_kernels.hpp"
-#include "mvs_kernels.hpp"        // launch_block_offsets_scan
 #include "texture_device.hpp"     // texture_project, texture_taps, texture_fetch
 
 namespace esfm {
-
-#define LAUNCH_OK() ESFM_HIP_TRY(hipGetLastError())
-
-static unsigned blocks_of(int64_t n) { return (unsigned)((n + 255) / 256); }
-
-// The number of threads of the 256-thread workgroup up to and including this one for which `flag` holds (every thread calls).
-__device__ inline int level_inclusive_count(bool flag)
-{
-    __shared__ int32_t per_wave[4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const unsigned long long b = __ballot(flag);
-    if (lane == 0) per_wave[wave] = __popcll(b);
-    __syncthreads();
-    int before = 0;
-    for (int w = 0; w < wave; ++w) before += per_wave[w];
-    return before + __popcll(b & ((2ull << lane) - 1ull));        // (lane 63: 2 << 63 wraps to 0, the mask is all ones)
-}
-
-// First index in sorted[0 .. n) whose key is >= key.
-__device__ inline int64_t level_lower_bound(const uint64_t *sorted, int64_t n, uint64_t key)
-{
-    int64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const int64_t mid = lo + ((hi - lo) >> 1);
-        if (sorted[mid] < key) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
 
 // One level of tree_sum for K sums at once: every thread of the workgroup brings K values (+0.0 where it has no element), thread 0
 // leaves with the K block sums.  x[i] += x[i + h] for h = 128 .. 1, as the header writes it.
@@ -85,24 +57,22 @@ __global__ __launch_bounds__(256) void level_corner_keys_kernel(LevelArgs a)
     for (int k = 0; k < 3; ++k) a.corner_keys[3 * t + k] = part ? (uint64_t)i[k] << 6 | (uint64_t)label : none;
 }
 
-__device__ inline bool level_is_head(const LevelArgs &a, int64_t i, int64_t n)
-{
-    if (i >= n) return false;
-    const uint64_t key = a.sorted[i];
-    return key < (uint64_t)a.V << 6 && (i == 0 || a.sorted[i - 1] != key);
-}
-
-__global__ __launch_bounds__(256) void level_heads_kernel(LevelArgs a)
-{
-    const int n = __syncthreads_count(level_is_head(a, (int64_t)blockIdx.x * 256 + threadIdx.x, 3 * (int64_t)a.T));
-    if (threadIdx.x == 0) a.head_blocks[blockIdx.x] = n;
-}
+// A run head of the 3 T sorted corner keys that is a node's.
+struct LevelIsHead {
+    LevelArgs a;
+    __device__ bool operator()(int64_t i) const
+    {
+        if (i >= 3 * (int64_t)a.T) return false;
+        const uint64_t key = a.sorted[i];
+        return key < (uint64_t)a.V << 6 && (i == 0 || a.sorted[i - 1] != key);
+    }
+};
 
 __global__ __launch_bounds__(256) void level_node_keys_kernel(LevelArgs a)
 {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const bool head = level_is_head(a, i, 3 * (int64_t)a.T);
-    const int incl = level_inclusive_count(head);
+    const bool head = LevelIsHead{a}(i);
+    const int incl = block_inclusive_count(head);
     if (head) a.node_keys[a.head_blocks[blockIdx.x] + incl - 1] = a.sorted[i];
 }
 
@@ -121,8 +91,8 @@ __global__ __launch_bounds__(256) void level_nodes_kernel(LevelArgs a)
         const TextureTaps taps = texture_taps(a.images, label, a.rows, a.cols, a.channels, u, w);
 #pragma unroll
         for (int c = 0; c < 3; ++c) a.f[c * a.stride + n] = texture_fetch(taps, a.channels == 3 ? 2 - c : 0);
-        const int32_t first = (int32_t)level_lower_bound(a.node_keys, a.N, (uint64_t)vertex << 6);
-        const int32_t last = (int32_t)level_lower_bound(a.node_keys, a.N, (uint64_t)(vertex + 1) << 6);
+        const int32_t first = (int32_t)lower_bound(a.node_keys, a.N, (uint64_t)vertex << 6);
+        const int32_t last = (int32_t)lower_bound(a.node_keys, a.N, (uint64_t)(vertex + 1) << 6);
         a.seam_first[n] = first;
         a.seam_last[n] = last;
         seam_vertex = first == n && last - first >= 2;
@@ -136,7 +106,7 @@ __global__ __launch_bounds__(256) void level_corner_node_kernel(LevelArgs a)
     const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;       // 3 t + corner
     if (j >= 3 * (int64_t)a.T) return;
     const uint64_t key = a.corner_keys[j];
-    a.corner_node[j] = key < (uint64_t)a.V << 6 ? (int32_t)level_lower_bound(a.node_keys, a.N, key) : 0;
+    a.corner_node[j] = key < (uint64_t)a.V << 6 ? (int32_t)lower_bound(a.node_keys, a.N, key) : 0;
 }
 
 // ---- the scalars -----------------------------------------------------------------------------------------------------------
@@ -327,11 +297,9 @@ int launch_level_corner_keys(hipStream_t st, const LevelArgs &a)
 
 int launch_level_node_keys(hipStream_t st, const LevelArgs &a)
 {
-    const unsigned nb = blocks_of(3 * (int64_t)a.T);
-    hipLaunchKernelGGL(level_heads_kernel, dim3(nb), dim3(256), 0, st, a);
-    LAUNCH_OK();
-    if (int rc = launch_block_offsets_scan(st, a.head_blocks, (int)nb, a.head_blocks + nb)) return rc;
-    hipLaunchKernelGGL(level_node_keys_kernel, dim3(nb), dim3(256), 0, st, a);
+    const int64_t n = 3 * (int64_t)a.T;
+    if (int rc = launch_flag_offsets(st, n, LevelIsHead{a}, a.head_blocks)) return rc;
+    hipLaunchKernelGGL(level_node_keys_kernel, dim3(blocks_of(n)), dim3(256), 0, st, a);
     LAUNCH_OK();
     return ESFM_OK;
 }

@@ -4,20 +4,12 @@
 // tests/mesh_clean_ref.py restates the rules.
 #include <cmath>
 
+#include "mesh_check.hpp"
 #include "mesh_kernels.hpp"
 
 namespace {
 
-size_t al(size_t b) { return (b + 255) / 256 * 256; }
-
-int check_mesh(int V, int T, const int32_t *triangles)
-{
-    ESFM_REQUIRE(V >= 0 && V <= (1 << 30), "n_vertices must be 0..2^30");
-    ESFM_REQUIRE(T >= 0 && T <= (1 << 28), "n_triangles must be 0..2^28");
-    ESFM_REQUIRE(T == 0 || triangles, "NULL argument");
-    for (size_t i = 0; i < 3 * (size_t)T; ++i) ESFM_REQUIRE(triangles[i] >= 0 && triangles[i] < V, "a triangle index is outside 0..n_vertices-1");
-    return ESFM_OK;
-}
+using esfm::check_mesh;
 
 int check_options(const esfm_mesh_clean_options *o)
 {
@@ -37,21 +29,32 @@ int check_ctx(esfm_ctx *ctx)
     return esfm::set_device(ctx);
 }
 
-int bit_width(uint32_t x) { int n = 0; while (x) { ++n; x >>= 1; } return n; }
+// the labelling's device arrays in stage_a, behind whatever the caller has carved before them: triangles | parent | label |
+// tri_count | stats
+struct LabelLayout { size_t tri, parent, label, tri_count, stats; };
 
-// the labelling's device arrays behind `head` bytes of stage_a: triangles | parent | label | tri_count | stats
-int place_labels(esfm_ctx *ctx, size_t head, size_t tail, int V, int T, const int32_t *triangles, esfm::MeshLabelArgs *a)
+LabelLayout carve_labels(esfm::ScratchCarver *at, size_t V, size_t T)
 {
-    const size_t tri_b = al(sizeof(int32_t) * 3 * (size_t)T), v_b = al(sizeof(int32_t) * (size_t)V);
-    if (int rc = ctx->stage_a.reserve(head + tri_b + 3 * v_b + 256 + tail)) return rc;
-    uint8_t *p = ctx->stage_a.as<uint8_t>() + head;
-    a->tri = reinterpret_cast<const int32_t *>(p);
-    a->parent = reinterpret_cast<int32_t *>(p + tri_b);
-    a->label = reinterpret_cast<int32_t *>(p + tri_b + v_b);
-    a->tri_count = reinterpret_cast<int32_t *>(p + tri_b + 2 * v_b);
-    a->stats = reinterpret_cast<int32_t *>(p + tri_b + 3 * v_b);
+    LabelLayout l;
+    l.tri = at->take(sizeof(int32_t) * 3 * T);
+    l.parent = at->take(sizeof(int32_t) * V);
+    l.label = at->take(sizeof(int32_t) * V);
+    l.tri_count = at->take(sizeof(int32_t) * V);
+    l.stats = at->take(sizeof(int32_t) * 2);
+    return l;
+}
+
+// (stage_a is reserved) points the arguments at the arrays and uploads the triangles
+int place_labels(esfm_ctx *ctx, const LabelLayout &l, int V, int T, const int32_t *triangles, esfm::MeshLabelArgs *a)
+{
+    uint8_t *p = ctx->stage_a.as<uint8_t>();
+    a->tri = reinterpret_cast<const int32_t *>(p + l.tri);
+    a->parent = reinterpret_cast<int32_t *>(p + l.parent);
+    a->label = reinterpret_cast<int32_t *>(p + l.label);
+    a->tri_count = reinterpret_cast<int32_t *>(p + l.tri_count);
+    a->stats = reinterpret_cast<int32_t *>(p + l.stats);
     a->V = V; a->T = T;
-    if (T) ESFM_HIP_TRY(esfm::copy_h2d(p, triangles, sizeof(int32_t) * 3 * (size_t)T, ctx->stream));
+    if (T) ESFM_HIP_TRY(esfm::copy_h2d(p + l.tri, triangles, sizeof(int32_t) * 3 * (size_t)T, ctx->stream));
     return ESFM_OK;
 }
 
@@ -78,8 +81,11 @@ int esfm_mesh_components(esfm_ctx *ctx, int n_vertices, int n_triangles, const i
     if (int rc = check_ctx(ctx)) return rc;
     if (n_vertices == 0) { *n_components = 0; return ESFM_OK; }
     hipStream_t st = ctx->stream;
+    esfm::ScratchCarver in;
+    const LabelLayout l = carve_labels(&in, (size_t)n_vertices, (size_t)n_triangles);
+    if (int rc = ctx->stage_a.reserve(in.at)) return rc;
     esfm::MeshLabelArgs a;
-    if (int rc = place_labels(ctx, 0, 0, n_vertices, n_triangles, triangles, &a)) return rc;
+    if (int rc = place_labels(ctx, l, n_vertices, n_triangles, triangles, &a)) return rc;
     if (int rc = esfm::launch_mesh_labels(st, a)) return rc;
     const size_t V = (size_t)n_vertices;
     int32_t stats[2] = {0, 0};
@@ -108,38 +114,44 @@ int esfm_mesh_clean(esfm_ctx *ctx, int n_vertices, int n_triangles, const float 
     const size_t V = (size_t)n_vertices, T = (size_t)n_triangles, vb = (V + 255) / 256, tb = (T + 255) / 256;
 
     // stage_a: vertices | colours, then the labelling's arrays, then remap | vertex block counts | triangle block counts
-    const size_t vtx_b = al(sizeof(float) * 3 * V), col_b = out_rgb ? al(3 * V) : 0, map_b = al(sizeof(int32_t) * V),
-                 vcnt_b = al(sizeof(int32_t) * (vb + 1)), tcnt_b = al(sizeof(int32_t) * (tb + 1));
+    esfm::ScratchCarver in;
+    const size_t in_vertices = in.take(sizeof(float) * 3 * V), in_rgb = in.take(out_rgb ? 3 * V : 0);
+    const LabelLayout labels_at = carve_labels(&in, V, T);
+    const size_t remap = in.take(sizeof(int32_t) * V), vertex_blocks = in.take(sizeof(int32_t) * (vb + 1)),
+                 triangle_blocks = in.take(sizeof(int32_t) * (tb + 1));
+    if (int rc = ctx->stage_a.reserve(in.at)) return rc;
     esfm::MeshLabelArgs lab;
-    if (int rc = place_labels(ctx, vtx_b + col_b, map_b + vcnt_b + tcnt_b, n_vertices, n_triangles, triangles, &lab)) return rc;
+    if (int rc = place_labels(ctx, labels_at, n_vertices, n_triangles, triangles, &lab)) return rc;
     uint8_t *p_a = ctx->stage_a.as<uint8_t>();
-    ESFM_HIP_TRY(esfm::copy_h2d(p_a, vertices, sizeof(float) * 3 * V, st));
-    if (out_rgb) ESFM_HIP_TRY(esfm::copy_h2d(p_a + vtx_b, vertex_rgb, 3 * V, st));
+    ESFM_HIP_TRY(esfm::copy_h2d(p_a + in_vertices, vertices, sizeof(float) * 3 * V, st));
+    if (out_rgb) ESFM_HIP_TRY(esfm::copy_h2d(p_a + in_rgb, vertex_rgb, 3 * V, st));
     if (int rc = esfm::launch_mesh_labels(st, lab)) return rc;
 
     // stage_d: positions (two buffers) | normals | colours | triangles | vertex_map | triangle_map
-    const size_t nrm_b = out_normals ? vtx_b : 0, otri_b = al(sizeof(int32_t) * 3 * T), vmap_b = vertex_map ? map_b : 0,
-                 tmap_b = triangle_map ? al(sizeof(int32_t) * T) : 0;
-    if (int rc = ctx->stage_d.reserve(2 * vtx_b + nrm_b + col_b + otri_b + vmap_b + tmap_b)) return rc;
+    esfm::ScratchCarver out;
+    const size_t pos0 = out.take(sizeof(float) * 3 * V), pos1 = out.take(sizeof(float) * 3 * V),
+                 o_normals = out.take(out_normals ? sizeof(float) * 3 * V : 0), o_rgb = out.take(out_rgb ? 3 * V : 0),
+                 o_tri = out.take(sizeof(int32_t) * 3 * T), o_vmap = out.take(vertex_map ? sizeof(int32_t) * V : 0),
+                 o_tmap = out.take(triangle_map ? sizeof(int32_t) * T : 0);
+    if (int rc = ctx->stage_d.reserve(out.at)) return rc;
     uint8_t *p_d = ctx->stage_d.as<uint8_t>();
-    float *pos[2] = {reinterpret_cast<float *>(p_d), reinterpret_cast<float *>(p_d + vtx_b)};
-    float *d_normals = reinterpret_cast<float *>(p_d + 2 * vtx_b);
+    float *pos[2] = {reinterpret_cast<float *>(p_d + pos0), reinterpret_cast<float *>(p_d + pos1)};
+    float *d_normals = reinterpret_cast<float *>(p_d + o_normals);
     esfm::MeshCompactArgs c;
     memset(&c, 0, sizeof(c));
     c.tri = lab.tri; c.label = lab.label; c.tri_count = lab.tri_count; c.stats = lab.stats;
-    c.vertices = reinterpret_cast<const float *>(p_a);
-    c.rgb = out_rgb ? p_a + vtx_b : nullptr;
+    c.vertices = reinterpret_cast<const float *>(p_a + in_vertices);
+    c.rgb = out_rgb ? p_a + in_rgb : nullptr;
     c.V = n_vertices; c.T = n_triangles;
     c.min_triangles = opt->min_component_triangles; c.min_permille = opt->min_component_permille;
-    uint8_t *p_tail = reinterpret_cast<uint8_t *>(lab.stats) + 256;
-    c.remap = reinterpret_cast<int32_t *>(p_tail);
-    c.vertex_blocks = reinterpret_cast<int32_t *>(p_tail + map_b);
-    c.triangle_blocks = reinterpret_cast<int32_t *>(p_tail + map_b + vcnt_b);
+    c.remap = reinterpret_cast<int32_t *>(p_a + remap);
+    c.vertex_blocks = reinterpret_cast<int32_t *>(p_a + vertex_blocks);
+    c.triangle_blocks = reinterpret_cast<int32_t *>(p_a + triangle_blocks);
     c.out_vertices = pos[0];
-    c.out_rgb = out_rgb ? p_d + 2 * vtx_b + nrm_b : nullptr;
-    c.out_tri = reinterpret_cast<int32_t *>(p_d + 2 * vtx_b + nrm_b + col_b);
-    c.vertex_map = vertex_map ? reinterpret_cast<int32_t *>(p_d + 2 * vtx_b + nrm_b + col_b + otri_b) : nullptr;
-    c.triangle_map = triangle_map ? reinterpret_cast<int32_t *>(p_d + 2 * vtx_b + nrm_b + col_b + otri_b + vmap_b) : nullptr;
+    c.out_rgb = out_rgb ? p_d + o_rgb : nullptr;
+    c.out_tri = reinterpret_cast<int32_t *>(p_d + o_tri);
+    c.vertex_map = vertex_map ? reinterpret_cast<int32_t *>(p_d + o_vmap) : nullptr;
+    c.triangle_map = triangle_map ? reinterpret_cast<int32_t *>(p_d + o_tmap) : nullptr;
     if (int rc = esfm::launch_mesh_compact(st, c)) return rc;
     int32_t nv = 0, nt = 0;
     ESFM_HIP_TRY(esfm::copy_d2h(&nv, c.vertex_blocks + vb, sizeof(int32_t), st));
@@ -154,44 +166,41 @@ int esfm_mesh_clean(esfm_ctx *ctx, int n_vertices, int n_triangles, const float 
 
     // stage_b: keys | sorted keys | run heads before each key | head block counts | sort scratch;  stage_c: columns | row starts |
     // incidence starts | face vectors | pinned bytes
-    const int end_bit = 32 + bit_width((uint32_t)nv);
-    const int64_t n_keys = 6 * (int64_t)To;
-    const size_t kb = ((size_t)n_keys + 255) / 256;
+    const size_t n_keys = 6 * To;
     size_t sort_b = 0;
-    if (int rc = esfm::mesh_sort_scratch_bytes(n_keys, end_bit, &sort_b, st)) return rc;
-    const size_t key_b = al(sizeof(uint64_t) * (size_t)n_keys), rank_b = al(sizeof(int32_t) * ((size_t)n_keys + 1)), kcnt_b = al(sizeof(int32_t) * (kb + 1));
-    if (int rc = ctx->stage_b.reserve(2 * key_b + rank_b + kcnt_b + sort_b)) return rc;
+    if (int rc = esfm::mesh_sort_scratch_bytes((int64_t)n_keys, esfm::mesh_key_bits(nv), &sort_b, st)) return rc;
+    esfm::ScratchCarver sorting, graph;
+    const size_t keys = sorting.take(sizeof(uint64_t) * n_keys), sorted = sorting.take(sizeof(uint64_t) * n_keys),
+                 head_rank = sorting.take(sizeof(int32_t) * (n_keys + 1)), head_blocks = sorting.take(sizeof(int32_t) * ((n_keys + 255) / 256 + 1)),
+                 sort = sorting.take(sort_b);
+    if (int rc = ctx->stage_b.reserve(sorting.at)) return rc;
     uint8_t *p_b = ctx->stage_b.as<uint8_t>();
-    const size_t ncol_b = al(sizeof(int32_t) * (size_t)n_keys), row_b = al(sizeof(int32_t) * (Vo + 1)), face_b = al(sizeof(float) * 3 * To);
-    if (int rc = ctx->stage_c.reserve(ncol_b + 2 * row_b + face_b + al(Vo))) return rc;
+    const size_t col = graph.take(sizeof(int32_t) * n_keys), row_start = graph.take(sizeof(int32_t) * (Vo + 1)),
+                 inc_start = graph.take(sizeof(int32_t) * (Vo + 1)), face = graph.take(sizeof(float) * 3 * To), pinned = graph.take(Vo);
+    if (int rc = ctx->stage_c.reserve(graph.at)) return rc;
     uint8_t *p_c = ctx->stage_c.as<uint8_t>();
     esfm::MeshGraphArgs g;
     memset(&g, 0, sizeof(g));
     g.tri = c.out_tri; g.V = nv; g.T = nt;
-    g.keys = reinterpret_cast<uint64_t *>(p_b);
-    g.sorted = reinterpret_cast<const uint64_t *>(p_b + key_b);
-    g.head_rank = reinterpret_cast<int32_t *>(p_b + 2 * key_b);
-    g.head_blocks = reinterpret_cast<int32_t *>(p_b + 2 * key_b + rank_b);
-    void *d_sort = p_b + 2 * key_b + rank_b + kcnt_b;
-    g.col = reinterpret_cast<int32_t *>(p_c);
-    g.row_start = reinterpret_cast<int32_t *>(p_c + ncol_b);
-    g.inc_start = reinterpret_cast<int32_t *>(p_c + ncol_b + row_b);
-    g.face = reinterpret_cast<float *>(p_c + ncol_b + 2 * row_b);
-    g.pinned = p_c + ncol_b + 2 * row_b + face_b;
+    g.keys = reinterpret_cast<uint64_t *>(p_b + keys);
+    g.sorted = reinterpret_cast<const uint64_t *>(p_b + sorted);
+    g.head_rank = reinterpret_cast<int32_t *>(p_b + head_rank);
+    g.head_blocks = reinterpret_cast<int32_t *>(p_b + head_blocks);
+    void *d_sort = p_b + sort;
+    g.col = reinterpret_cast<int32_t *>(p_c + col);
+    g.row_start = reinterpret_cast<int32_t *>(p_c + row_start);
+    g.inc_start = reinterpret_cast<int32_t *>(p_c + inc_start);
+    g.face = reinterpret_cast<float *>(p_c + face);
+    g.pinned = p_c + pinned;
 
     int cur = 0;
     if (opt->smooth_iterations > 0) {
-        if (int rc = esfm::launch_mesh_edge_keys(st, g)) return rc;
-        if (int rc = esfm::mesh_sort_keys(d_sort, sort_b, g.keys, const_cast<uint64_t *>(g.sorted), n_keys, end_bit, st)) return rc;
-        if (int rc = esfm::launch_mesh_adjacency(st, g)) return rc;
+        if (int rc = esfm::mesh_build_adjacency(st, g, d_sort, sort_b)) return rc;
         for (int s = 0; s < 2 * opt->smooth_iterations; ++s, cur ^= 1)
             if (int rc = esfm::launch_mesh_smooth(st, g, pos[cur], pos[cur ^ 1], s % 2 == 0 ? opt->smooth_lambda : opt->smooth_mu, opt->pin_boundary)) return rc;
     }
-    if (out_normals) {
-        if (int rc = esfm::launch_mesh_incidence_keys(st, g)) return rc;
-        if (int rc = esfm::mesh_sort_keys(d_sort, sort_b, g.keys, const_cast<uint64_t *>(g.sorted), 3 * (int64_t)To, end_bit, st)) return rc;
-        if (int rc = esfm::launch_mesh_normals(st, g, pos[cur], d_normals)) return rc;
-    }
+    if (out_normals)
+        if (int rc = esfm::mesh_build_normals(st, g, d_sort, sort_b, pos[cur], d_normals)) return rc;
     ESFM_HIP_TRY(esfm::copy_d2h(out_vertices, pos[cur], sizeof(float) * 3 * Vo, st));
     if (out_normals) ESFM_HIP_TRY(esfm::copy_d2h(out_normals, d_normals, sizeof(float) * 3 * Vo, st));
     if (out_rgb) ESFM_HIP_TRY(esfm::copy_d2h(out_rgb, c.out_rgb, 3 * Vo, st));

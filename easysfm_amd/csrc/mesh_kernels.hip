@@ -5,38 +5,10 @@
 // compared bit for bit (-ffp-contract=off; HIP's default f32 division and sqrtf are correctly rounded).
 #include <cmath>
 
+#include "block_scan.hpp"
 #include "mesh_kernels.hpp"
-#include "mvs_kernels.hpp"     // launch_block_offsets_scan
 
 namespace esfm {
-
-#define LAUNCH_OK() ESFM_HIP_TRY(hipGetLastError())
-
-static unsigned blocks_of(int64_t n) { return (unsigned)((n + 255) / 256); }
-
-// The number of threads of the 256-thread workgroup up to and including this one for which `flag` holds (every thread calls).
-__device__ inline int mesh_inclusive_count(bool flag)
-{
-    __shared__ int32_t per_wave[4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const unsigned long long b = __ballot(flag);
-    if (lane == 0) per_wave[wave] = __popcll(b);
-    __syncthreads();
-    int before = 0;
-    for (int w = 0; w < wave; ++w) before += per_wave[w];
-    return before + __popcll(b & ((2ull << lane) - 1ull));        // (lane 63: 2 << 63 wraps to 0, the mask is all ones)
-}
-
-// First index in sorted[0 .. n) whose key is >= key.
-__device__ inline int64_t mesh_lower_bound(const uint64_t *sorted, int64_t n, uint64_t key)
-{
-    int64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const int64_t mid = lo + ((hi - lo) >> 1);
-        if (sorted[mid] < key) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
 
 // ---- components ----------------------------------------------------------------------------------------------------------
 // A forest over the vertices in which a parent is always SMALLER than its child: a root is only ever linked under a smaller
@@ -155,26 +127,20 @@ __device__ inline bool mesh_component_kept(const MeshCompactArgs &a, int32_t c)
     const int64_t n = a.tri_count[c];
     return n >= a.min_triangles && 1000 * n >= (int64_t)a.min_permille * a.stats[0];
 }
-__device__ inline bool mesh_vertex_kept(const MeshCompactArgs &a, int64_t v) { return v < a.V && mesh_component_kept(a, a.label[v]); }
-__device__ inline bool mesh_triangle_kept(const MeshCompactArgs &a, int64_t t) { return t < a.T && mesh_component_kept(a, a.label[a.tri[3 * t]]); }
-
-__global__ __launch_bounds__(256) void mesh_keep_vertices_kernel(MeshCompactArgs a)
-{
-    const int n = __syncthreads_count(mesh_vertex_kept(a, (int64_t)blockIdx.x * 256 + threadIdx.x));
-    if (threadIdx.x == 0) a.vertex_blocks[blockIdx.x] = n;
-}
-
-__global__ __launch_bounds__(256) void mesh_keep_triangles_kernel(MeshCompactArgs a)
-{
-    const int n = __syncthreads_count(mesh_triangle_kept(a, (int64_t)blockIdx.x * 256 + threadIdx.x));
-    if (threadIdx.x == 0) a.triangle_blocks[blockIdx.x] = n;
-}
+struct MeshVertexKept {
+    MeshCompactArgs a;
+    __device__ bool operator()(int64_t v) const { return v < a.V && mesh_component_kept(a, a.label[v]); }
+};
+struct MeshTriangleKept {
+    MeshCompactArgs a;
+    __device__ bool operator()(int64_t t) const { return t < a.T && mesh_component_kept(a, a.label[a.tri[3 * t]]); }
+};
 
 __global__ __launch_bounds__(256) void mesh_write_vertices_kernel(MeshCompactArgs a)
 {
     const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const bool keep = mesh_vertex_kept(a, v);
-    const int incl = mesh_inclusive_count(keep);
+    const bool keep = MeshVertexKept{a}(v);
+    const int incl = block_inclusive_count(keep);
     if (!keep) return;
     const int64_t dst = (int64_t)a.vertex_blocks[blockIdx.x] + incl - 1;
 #pragma unroll
@@ -191,8 +157,8 @@ __global__ __launch_bounds__(256) void mesh_write_vertices_kernel(MeshCompactArg
 __global__ __launch_bounds__(256) void mesh_write_triangles_kernel(MeshCompactArgs a)
 {
     const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const bool keep = mesh_triangle_kept(a, t);
-    const int incl = mesh_inclusive_count(keep);
+    const bool keep = MeshTriangleKept{a}(t);
+    const int incl = block_inclusive_count(keep);
     if (!keep) return;
     const int64_t dst = (int64_t)a.triangle_blocks[blockIdx.x] + incl - 1;
 #pragma unroll
@@ -202,16 +168,11 @@ __global__ __launch_bounds__(256) void mesh_write_triangles_kernel(MeshCompactAr
 
 int launch_mesh_compact(hipStream_t st, const MeshCompactArgs &a)
 {
-    const unsigned vb = blocks_of(a.V), tb = blocks_of(a.T);
-    hipLaunchKernelGGL(mesh_keep_vertices_kernel, dim3(vb), dim3(256), 0, st, a);
+    if (int rc = launch_flag_offsets(st, a.V, MeshVertexKept{a}, a.vertex_blocks)) return rc;
+    if (int rc = launch_flag_offsets(st, a.T, MeshTriangleKept{a}, a.triangle_blocks)) return rc;
+    hipLaunchKernelGGL(mesh_write_vertices_kernel, dim3(blocks_of(a.V)), dim3(256), 0, st, a);
     LAUNCH_OK();
-    hipLaunchKernelGGL(mesh_keep_triangles_kernel, dim3(tb), dim3(256), 0, st, a);
-    LAUNCH_OK();
-    if (int rc = launch_block_offsets_scan(st, a.vertex_blocks, (int)vb, a.vertex_blocks + vb)) return rc;
-    if (int rc = launch_block_offsets_scan(st, a.triangle_blocks, (int)tb, a.triangle_blocks + tb)) return rc;
-    hipLaunchKernelGGL(mesh_write_vertices_kernel, dim3(vb), dim3(256), 0, st, a);
-    LAUNCH_OK();
-    hipLaunchKernelGGL(mesh_write_triangles_kernel, dim3(tb), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(mesh_write_triangles_kernel, dim3(blocks_of(a.T)), dim3(256), 0, st, a);
     LAUNCH_OK();
     return ESFM_OK;
 }
@@ -232,26 +193,24 @@ __global__ __launch_bounds__(256) void mesh_edge_keys_kernel(MeshGraphArgs a)
     }
 }
 
-__device__ inline bool mesh_is_head(const MeshGraphArgs &a, int64_t i, int64_t n)
-{
-    if (i >= n) return false;
-    const uint64_t key = a.sorted[i];
-    return (int64_t)(key >> 32) < a.V && (i == 0 || a.sorted[i - 1] != key);
-}
-
-__global__ __launch_bounds__(256) void mesh_heads_kernel(MeshGraphArgs a)
-{
-    const int n = __syncthreads_count(mesh_is_head(a, (int64_t)blockIdx.x * 256 + threadIdx.x, 6 * (int64_t)a.T));
-    if (threadIdx.x == 0) a.head_blocks[blockIdx.x] = n;
-}
+// A run head of the 6 T sorted keys that names a row.
+struct MeshIsHead {
+    MeshGraphArgs a;
+    __device__ bool operator()(int64_t i) const
+    {
+        if (i >= 6 * (int64_t)a.T) return false;
+        const uint64_t key = a.sorted[i];
+        return (int64_t)(key >> 32) < a.V && (i == 0 || a.sorted[i - 1] != key);
+    }
+};
 
 // One thread per sorted key and one more: the number of run heads before each key (so the first key of a row names the row's
 // first column), the column of each head, and a row's pinned byte wherever a run is not exactly two keys long.
 __global__ __launch_bounds__(256) void mesh_columns_kernel(MeshGraphArgs a, int n_blocks)
 {
     const int64_t n = 6 * (int64_t)a.T, i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const bool head = mesh_is_head(a, i, n);
-    const int incl = mesh_inclusive_count(head);
+    const bool head = MeshIsHead{a}(i);
+    const int incl = block_inclusive_count(head);
     if (i > n) return;
     if (i == n) { a.head_rank[n] = a.head_blocks[n_blocks]; return; }
     const int32_t rank = a.head_blocks[blockIdx.x] + incl - (head ? 1 : 0);
@@ -267,26 +226,19 @@ __global__ __launch_bounds__(256) void mesh_rows_kernel(const uint64_t *sorted, 
 {
     const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (v > V) return;
-    const int64_t j = mesh_lower_bound(sorted, n, (uint64_t)v << 32);
+    const int64_t j = lower_bound(sorted, n, (uint64_t)v << 32);
     start[v] = rank ? rank[j] : (int32_t)j;
 }
 
-int launch_mesh_edge_keys(hipStream_t st, const MeshGraphArgs &a)
-{
-    hipLaunchKernelGGL(mesh_edge_keys_kernel, dim3(blocks_of(a.T)), dim3(256), 0, st, a);
-    LAUNCH_OK();
-    return ESFM_OK;
-}
-
-int launch_mesh_adjacency(hipStream_t st, const MeshGraphArgs &a)
+int mesh_build_adjacency(hipStream_t st, const MeshGraphArgs &a, void *sort_tmp, size_t sort_bytes)
 {
     const int64_t n = 6 * (int64_t)a.T;
-    const unsigned nb = blocks_of(n);
-    ESFM_HIP_TRY(hipMemsetAsync(a.pinned, 0, (size_t)a.V, st));
-    hipLaunchKernelGGL(mesh_heads_kernel, dim3(nb), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(mesh_edge_keys_kernel, dim3(blocks_of(a.T)), dim3(256), 0, st, a);
     LAUNCH_OK();
-    if (int rc = launch_block_offsets_scan(st, a.head_blocks, (int)nb, a.head_blocks + nb)) return rc;
-    hipLaunchKernelGGL(mesh_columns_kernel, dim3(blocks_of(n + 1)), dim3(256), 0, st, a, (int)nb);
+    if (int rc = mesh_sort_keys(sort_tmp, sort_bytes, a.keys, const_cast<uint64_t *>(a.sorted), n, mesh_key_bits(a.V), st)) return rc;
+    ESFM_HIP_TRY(hipMemsetAsync(a.pinned, 0, (size_t)a.V, st));
+    if (int rc = launch_flag_offsets(st, n, MeshIsHead{a}, a.head_blocks)) return rc;
+    hipLaunchKernelGGL(mesh_columns_kernel, dim3(blocks_of(n + 1)), dim3(256), 0, st, a, (int)blocks_of(n));
     LAUNCH_OK();
     hipLaunchKernelGGL(mesh_rows_kernel, dim3(blocks_of((int64_t)a.V + 1)), dim3(256), 0, st, a.sorted, n, (const int32_t *)a.head_rank, a.V, a.row_start);
     LAUNCH_OK();
@@ -366,18 +318,15 @@ __global__ __launch_bounds__(256) void mesh_normals_kernel(MeshGraphArgs a, floa
     normals[3 * i + 2] = ok ? n[2] / L : 0.f;
 }
 
-int launch_mesh_incidence_keys(hipStream_t st, const MeshGraphArgs &a)
+int mesh_build_normals(hipStream_t st, const MeshGraphArgs &a, void *sort_tmp, size_t sort_bytes, const float *p, float *normals)
 {
-    hipLaunchKernelGGL(mesh_incidence_keys_kernel, dim3(blocks_of(3 * (int64_t)a.T)), dim3(256), 0, st, a);
+    const int64_t n = 3 * (int64_t)a.T;
+    hipLaunchKernelGGL(mesh_incidence_keys_kernel, dim3(blocks_of(n)), dim3(256), 0, st, a);
     LAUNCH_OK();
-    return ESFM_OK;
-}
-
-int launch_mesh_normals(hipStream_t st, const MeshGraphArgs &a, const float *p, float *normals)
-{
+    if (int rc = mesh_sort_keys(sort_tmp, sort_bytes, a.keys, const_cast<uint64_t *>(a.sorted), n, mesh_key_bits(a.V), st)) return rc;
     hipLaunchKernelGGL(mesh_faces_kernel, dim3(blocks_of(a.T)), dim3(256), 0, st, a, p);
     LAUNCH_OK();
-    hipLaunchKernelGGL(mesh_rows_kernel, dim3(blocks_of((int64_t)a.V + 1)), dim3(256), 0, st, a.sorted, 3 * (int64_t)a.T, (const int32_t *)nullptr, a.V, a.inc_start);
+    hipLaunchKernelGGL(mesh_rows_kernel, dim3(blocks_of((int64_t)a.V + 1)), dim3(256), 0, st, a.sorted, n, (const int32_t *)nullptr, a.V, a.inc_start);
     LAUNCH_OK();
     hipLaunchKernelGGL(mesh_normals_kernel, dim3(blocks_of(a.V)), dim3(256), 0, st, a, normals);
     LAUNCH_OK();

@@ -2,6 +2,7 @@
 #pragma once
 
 #include "common.hpp"
+#include "scratch_layout.hpp"   // bit_width
 
 namespace esfm {
 
@@ -44,11 +45,16 @@ struct MeshGraphArgs {         // adjacency, smoothing and normals of the output
 
 int launch_mesh_labels(hipStream_t st, const MeshLabelArgs &a);          // init, hook, flatten, counts, largest
 int launch_mesh_compact(hipStream_t st, const MeshCompactArgs &a);       // keep counts, scans, ordered writes
-int launch_mesh_edge_keys(hipStream_t st, const MeshGraphArgs &a);       // the 6 T directed keys (a == b: behind every other key)
-int launch_mesh_adjacency(hipStream_t st, const MeshGraphArgs &a);       // from the sorted keys: columns, row starts, pinned bytes
+// The key width of both sorts below: the high word is a vertex index, or V itself for a key that names no row.  The callers size
+// the sorts' scratch with it (mesh_sort_scratch_bytes), for V or for a bound of it.
+inline int mesh_key_bits(int64_t V) { return 32 + bit_width((uint64_t)V); }
+
+// the adjacency of a mesh with T >= 1: the 6 T directed keys (a == b: behind every other key), their sort, then columns, row starts
+// and pinned bytes
+int mesh_build_adjacency(hipStream_t st, const MeshGraphArgs &g, void *sort_tmp, size_t sort_bytes);
 int launch_mesh_smooth(hipStream_t st, const MeshGraphArgs &a, const float *p, float *q, float w, int pin_boundary);
-int launch_mesh_incidence_keys(hipStream_t st, const MeshGraphArgs &a);  // the 3 T (vertex, 3 t + corner) keys
-int launch_mesh_normals(hipStream_t st, const MeshGraphArgs &a, const float *p, float *normals);   // from the sorted incidence keys
+// the vertex normals of a mesh with T >= 1: the 3 T (vertex, 3 t + corner) keys, their sort, the face vectors summed in incidence order
+int mesh_build_normals(hipStream_t st, const MeshGraphArgs &g, void *sort_tmp, size_t sort_bytes, const float *p, float *normals);
 
 // mesh_sort.hip: hipCUB's device radix sort of 64-bit keys, bits 0 .. end_bit - 1
 int mesh_sort_scratch_bytes(int64_t n, int end_bit, size_t *bytes, hipStream_t st);

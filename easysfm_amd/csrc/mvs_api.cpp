@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "mvs_kernels.hpp"
+#include "scratch_layout.hpp"
 #include "surf_kernels.hpp"
 
 using esfm::MvsCam;
@@ -122,14 +123,13 @@ int fuse(esfm_ctx *ctx, int n_views, int rows, int cols, int channels, const uin
     }
     const size_t n_px = (size_t)n_views * rows * cols;
     const size_t n_blocks = (n_px + 255) / 256;
-    auto al = [](size_t n) { return (n + 255) / 256 * 256; };
     // stage_a: images | depth | cams | block counts + n_points; stage_b: per-pixel points | colours | keep; stage_c: output
-    const size_t img_b = al(n_px * channels), dep_b = al(sizeof(float) * n_px), cam_b = al(sizeof(MvsCam) * cams.size());
-    const size_t cnt_b = al(sizeof(int32_t) * (n_blocks + 1));
+    const size_t img_b = esfm::align256(n_px * channels), dep_b = esfm::align256(sizeof(float) * n_px), cam_b = esfm::align256(sizeof(MvsCam) * cams.size());
+    const size_t cnt_b = esfm::align256(sizeof(int32_t) * (n_blocks + 1));
     esfm::DevBuf &b_in = ctx->stage_a, &b_stage = ctx->stage_b, &b_out = ctx->stage_c;
     if (int rc = b_in.reserve(img_b + dep_b + cam_b + cnt_b)) return rc;
-    if (int rc = b_stage.reserve(al(sizeof(float) * 3 * n_px) + al(3 * n_px) + al(n_px))) return rc;
-    if (int rc = b_out.reserve(al(sizeof(float) * 3 * n_px) + al(3 * n_px) + (pixel_index ? sizeof(int32_t) * n_px : 0))) return rc;
+    if (int rc = b_stage.reserve(esfm::align256(sizeof(float) * 3 * n_px) + esfm::align256(3 * n_px) + esfm::align256(n_px))) return rc;
+    if (int rc = b_out.reserve(esfm::align256(sizeof(float) * 3 * n_px) + esfm::align256(3 * n_px) + (pixel_index ? sizeof(int32_t) * n_px : 0))) return rc;
     uint8_t *p_in = b_in.as<uint8_t>(), *p_stage = b_stage.as<uint8_t>(), *p_out = b_out.as<uint8_t>();
     esfm::MvsFuseArgs a;
     a.images = p_in;
@@ -138,11 +138,11 @@ int fuse(esfm_ctx *ctx, int n_views, int rows, int cols, int channels, const uin
     a.block_count = reinterpret_cast<int32_t *>(p_in + img_b + dep_b + cam_b);
     a.n_points = a.block_count + n_blocks;
     a.stage_xyz = reinterpret_cast<float *>(p_stage);
-    a.stage_rgb = p_stage + al(sizeof(float) * 3 * n_px);
-    a.keep = a.stage_rgb + al(3 * n_px);
+    a.stage_rgb = p_stage + esfm::align256(sizeof(float) * 3 * n_px);
+    a.keep = a.stage_rgb + esfm::align256(3 * n_px);
     a.xyz = reinterpret_cast<float *>(p_out);
-    a.rgb = p_out + al(sizeof(float) * 3 * n_px);
-    a.pixel_index = pixel_index ? reinterpret_cast<int32_t *>(a.rgb + al(3 * n_px)) : nullptr;
+    a.rgb = p_out + esfm::align256(sizeof(float) * 3 * n_px);
+    a.pixel_index = pixel_index ? reinterpret_cast<int32_t *>(a.rgb + esfm::align256(3 * n_px)) : nullptr;
     a.n_px = (int64_t)n_px;
     a.rows = rows; a.cols = cols; a.channels = channels; a.n_nb = nb; a.min_views = opt->fuse_min_views;
     a.reproj2 = opt->fuse_reproj_px * opt->fuse_reproj_px;

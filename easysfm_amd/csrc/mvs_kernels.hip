@@ -4,6 +4,7 @@
 // tests/mvs_ref.py restates both and the output is compared bit for bit.
 #include <cmath>
 
+#include "block_scan.hpp"
 #include "mvs_kernels.hpp"
 
 namespace esfm {
@@ -220,52 +221,20 @@ __global__ __launch_bounds__(256) void mvs_fuse_kernel(MvsFuseArgs a)
     if (threadIdx.x == 0) a.block_count[blockIdx.x] = n;
 }
 
-// One workgroup: the exclusive scan of the block counts (in place) and the total.
-__global__ __launch_bounds__(1024) void mvs_fuse_scan_kernel(int32_t *block_count, int n_blocks, int32_t *n_points)
-{
-    __shared__ int32_t part[1024];
-    const int tid = threadIdx.x;
-    const int per = (n_blocks + 1023) / 1024, b0 = tid * per, b1 = min(b0 + per, n_blocks);
-    int32_t s = 0;
-    for (int b = b0; b < b1; ++b) s += block_count[b];
-    part[tid] = s;
-    __syncthreads();
-    for (int o = 1; o < 1024; o <<= 1) {
-        const int32_t v = tid >= o ? part[tid - o] : 0;
-        __syncthreads();
-        part[tid] += v;
-        __syncthreads();
-    }
-    int32_t run = part[tid] - s;                     // exclusive prefix of this thread's chunk
-    for (int b = b0; b < b1; ++b) { const int32_t c = block_count[b]; block_count[b] = run; run += c; }
-    if (tid == 1023) *n_points = part[1023];
-}
-
 // The ordered write: a kept pixel goes to its block's offset plus the kept pixels before it in the block.
 __global__ __launch_bounds__(256) void mvs_fuse_write_kernel(MvsFuseArgs a)
 {
-    __shared__ int32_t pre[256];
     const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const int tid = threadIdx.x;
-    const int32_t k = (idx < a.n_px && a.keep[idx]) ? 1 : 0;
-    pre[tid] = k;
-    __syncthreads();
-    for (int o = 1; o < 256; o <<= 1) {
-        const int32_t v = tid >= o ? pre[tid - o] : 0;
-        __syncthreads();
-        pre[tid] += v;
-        __syncthreads();
-    }
+    const bool k = idx < a.n_px && a.keep[idx];
+    const int incl = block_inclusive_count(k);
     if (!k) return;
-    const int64_t dst = (int64_t)a.block_count[blockIdx.x] + pre[tid] - 1;
+    const int64_t dst = (int64_t)a.block_count[blockIdx.x] + incl - 1;
 #pragma unroll
     for (int c = 0; c < 3; ++c) { a.xyz[3 * dst + c] = a.stage_xyz[3 * idx + c]; a.rgb[3 * dst + c] = a.stage_rgb[3 * idx + c]; }
     if (a.pixel_index) a.pixel_index[dst] = (int32_t)idx;      // (n_px < 2^31: check_views)
 }
 
 // ---- launchers -----------------------------------------------------------------------------------------------------------
-#define LAUNCH_OK() ESFM_HIP_TRY(hipGetLastError())
-
 int launch_mvs_sweep(hipStream_t st, const MvsSweepArgs &a, int radius, int n_views)
 {
     const int tiles_y = (a.rows + kMvsTile - 1) / kMvsTile;
@@ -282,13 +251,6 @@ int launch_mvs_sweep(hipStream_t st, const MvsSweepArgs &a, int radius, int n_vi
     case 7: hipLaunchKernelGGL(mvs_sweep_kernel<7>, grid, dim3(256), lds, st, a); break;
     default: set_error("window radius %d is outside 1..7", radius); return ESFM_ERR_INVALID_ARG;
     }
-    LAUNCH_OK();
-    return ESFM_OK;
-}
-
-int launch_block_offsets_scan(hipStream_t st, int32_t *block_count, int n_blocks, int32_t *total)
-{
-    hipLaunchKernelGGL(mvs_fuse_scan_kernel, dim3(1), dim3(1024), 0, st, block_count, n_blocks, total);
     LAUNCH_OK();
     return ESFM_OK;
 }

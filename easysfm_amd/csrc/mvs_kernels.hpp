@@ -57,8 +57,6 @@ struct MvsFuseArgs {
 
 int launch_mvs_sweep(hipStream_t st, const MvsSweepArgs &a, int radius, int n_views);
 int launch_mvs_fuse(hipStream_t st, const MvsFuseArgs &a);
-// the fusion's one-workgroup exclusive scan of per-block counts (in place) and their total; the voxel merge orders its output with it too
-int launch_block_offsets_scan(hipStream_t st, int32_t *block_count, int n_blocks, int32_t *total);
 
 struct MvsNormalArgs {
     const float *depth;     // n_views x rows x cols

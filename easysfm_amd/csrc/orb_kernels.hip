@@ -13,6 +13,7 @@
 //   orb_harris_kernel    Harris response of the candidates that survived the first selection
 //   orb_angle_kernel     intensity-centroid orientation (one wave per keypoint)
 //   orb_describe_kernel  256 rotated intensity tests on the blurred level (one thread per descriptor byte)
+#include "block_scan.hpp"   // LAUNCH_OK
 #include "orb_kernels.hpp"
 
 #include <float.h>
@@ -213,8 +214,6 @@ __global__ __launch_bounds__(256) void orb_describe_kernel(OrbLevels L, const Or
 }
 
 // ---- launchers ---------------------------------------------------------------------------------------------------------
-#define LAUNCH_OK() ESFM_HIP_TRY(hipGetLastError())
-
 int launch_orb_resize(hipStream_t st, const uint8_t *src, int sr, int sc, uint8_t *dst, int dr, int dc)
 {
     hipLaunchKernelGGL(orb_resize_kernel, dim3((dc + 255) / 256, dr), dim3(256), 0, st, src, sr, sc, dst, dr, dc);

@@ -12,6 +12,7 @@
 //                       epnp_core.hpp routines
 // The sample stream and the best-model / adaptive-iteration bookkeeping are replayed on the host exactly as for the
 // essential-matrix RANSAC (ransac_api.cpp).
+#include "block_scan.hpp"   // LAUNCH_OK
 #include "pnp_kernels.hpp"
 
 #include <float.h>
@@ -239,8 +240,6 @@ __global__ __launch_bounds__(256) void pnp_reproj_sums_kernel(PnpProblem pb, con
 }
 
 // ---- launchers ---------------------------------------------------------------------------------------------------------
-#define LAUNCH_OK() ESFM_HIP_TRY(hipGetLastError())
-
 int launch_pnp_chunk(hipStream_t st, const PnpProblem &pb, const float *p3, const float *p2, const int32_t *samples, int n_hyp, double *poses,
                      int32_t *valid, int32_t *counts, int sweep_cap, bool only_unfinished, esfm_ctx *timing_ctx)
 {

@@ -6,12 +6,6 @@
 #include "simplify_kernels.hpp"
 #include "voxel_kernels.hpp"   // voxel_sort_pairs
 
-namespace {
-
-int bit_width(uint32_t x) { int n = 0; while (x) { ++n; x >>= 1; } return n; }
-
-}  // namespace
-
 extern "C" {
 
 void esfm_mesh_simplify_options_default(esfm_mesh_simplify_options *opt)
@@ -39,7 +33,7 @@ int esfm_mesh_simplify(esfm_ctx *ctx, int n_vertices, int n_triangles, const flo
     const size_t V = (size_t)n_vertices, T = (size_t)n_triangles, vb = (V + 255) / 256, tb = (T + 255) / 256;
 
     // the corner keys' high word is a cell number below V; the pair sorts run over all 64 bits (voxel_sort.hip's entry point)
-    const int corner_bits = 32 + bit_width((uint32_t)n_vertices);
+    const int corner_bits = esfm::mesh_key_bits(n_vertices);
     size_t pair_b = 0, corner_b = 0;
     if (int rc = esfm::voxel_sort_scratch_bytes((int)(V > T ? V : T), &pair_b, st)) return rc;
     if (int rc = esfm::mesh_sort_scratch_bytes(3 * (int64_t)T, corner_bits, &corner_b, st)) return rc;
@@ -116,9 +110,7 @@ int esfm_mesh_simplify(esfm_ctx *ctx, int n_vertices, int n_triangles, const flo
         g.keys = key_in; g.sorted = key_out;
         g.inc_start = reinterpret_cast<int32_t *>(p_c + l.inc_start);
         g.face = reinterpret_cast<float *>(p_c + l.face);
-        if (int rc = esfm::launch_mesh_incidence_keys(st, g)) return rc;
-        if (int rc = esfm::mesh_sort_keys(d_sort, sort_b, key_in, key_out, 3 * (int64_t)To, 32 + bit_width((uint32_t)nv), st)) return rc;
-        if (int rc = esfm::launch_mesh_normals(st, g, a.out_vertices, d_normals)) return rc;
+        if (int rc = esfm::mesh_build_normals(st, g, d_sort, sort_b, a.out_vertices, d_normals)) return rc;
     }
     if (nt > 0) {
         ESFM_HIP_TRY(esfm::copy_d2h(out_vertices, a.out_vertices, sizeof(float) * 3 * Vo, st));

@@ -7,7 +7,8 @@
 #include <cstddef>
 #include <cstdint>
 
-#include "error.hpp"
+#include "mesh_check.hpp"
+#include "scratch_layout.hpp"
 
 namespace esfm {
 
@@ -35,10 +36,7 @@ inline int simplify_check_args(int V, int T, const float *vertices, const uint8_
     ESFM_REQUIRE(V <= 0 || (vertices && out_vertices), "NULL argument");
     ESFM_REQUIRE(T <= 0 || out_triangles, "NULL argument");
     ESFM_REQUIRE(!out_rgb || vertex_rgb, "an output array is requested without its input");
-    ESFM_REQUIRE(V >= 0 && V <= (1 << 30), "n_vertices must be 0..2^30");
-    ESFM_REQUIRE(T >= 0 && T <= (1 << 28), "n_triangles must be 0..2^28");
-    ESFM_REQUIRE(T == 0 || triangles, "NULL argument");
-    for (size_t i = 0; i < 3 * (size_t)T; ++i) ESFM_REQUIRE(triangles[i] >= 0 && triangles[i] < V, "a triangle index is outside 0..n_vertices-1");
+    if (int rc = check_mesh(V, T, triangles)) return rc;
     ESFM_REQUIRE(std::isfinite(cell) && cell > 0.f, "cell must be finite and > 0");
     ESFM_REQUIRE(std::isfinite(origin[0]) && std::isfinite(origin[1]) && std::isfinite(origin[2]), "origin must be finite");
     for (size_t i = 0; i < 3 * (size_t)V; ++i) {
@@ -60,48 +58,42 @@ struct SimplifyLayout {
     size_t out_vertices, out_normals, out_rgb, out_tri, vertex_map, triangle_map, d_bytes;
 };
 
-inline size_t simplify_align(size_t b) { return (b + 255) / 256 * 256; }
-
 inline SimplifyLayout simplify_layout(size_t V, size_t T, bool rgb, bool normals, bool vertex_map, bool triangle_map, size_t sort_bytes)
 {
     SimplifyLayout l;
     const size_t vb = (V + 255) / 256, tb = (T + 255) / 256, keys = 3 * T > V ? 3 * T : V, vals = T > V ? T : V;
-    size_t at = 0;
-    auto take = [&at](size_t bytes) { const size_t here = at; at += simplify_align(bytes); return here; };
-    l.vertices = take(sizeof(float) * 3 * V);
-    l.rgb = take(rgb ? 3 * V : 0);
-    l.tri = take(sizeof(int32_t) * 3 * T);
-    l.cell_of = take(sizeof(int32_t) * V);
-    l.cell_start = take(sizeof(int32_t) * (V + 1));
-    l.cell_key = take(sizeof(uint64_t) * V);
-    l.new_of_cell = take(sizeof(int32_t) * V);
-    l.used = take(V);
-    l.keep = take(T);
-    l.cell_blocks = take(sizeof(int32_t) * (vb + 1));
-    l.used_blocks = take(sizeof(int32_t) * (vb + 1));
-    l.tri_blocks = take(sizeof(int32_t) * (tb + 1));
-    l.rep = take(sizeof(float) * 3 * V);
-    l.rep_rgb = take(rgb ? 3 * V : 0);
-    l.a_bytes = at;
-    at = 0;
-    l.key_in = take(sizeof(uint64_t) * keys);
-    l.key_out = take(sizeof(uint64_t) * keys);
-    l.val_in = take(sizeof(int32_t) * vals);
-    l.val_out = take(sizeof(int32_t) * vals);
-    l.sort = take(sort_bytes);
-    l.b_bytes = at;
-    at = 0;
-    l.inc_start = take(normals ? sizeof(int32_t) * (V + 1) : 0);
-    l.face = take(normals ? sizeof(float) * 3 * T : 0);
-    l.c_bytes = at;
-    at = 0;
-    l.out_vertices = take(sizeof(float) * 3 * V);
-    l.out_normals = take(normals ? sizeof(float) * 3 * V : 0);
-    l.out_rgb = take(rgb ? 3 * V : 0);
-    l.out_tri = take(sizeof(int32_t) * 3 * T);
-    l.vertex_map = take(vertex_map ? sizeof(int32_t) * V : 0);
-    l.triangle_map = take(triangle_map ? sizeof(int32_t) * T : 0);
-    l.d_bytes = at;
+    ScratchCarver a, b, c, d;
+    l.vertices = a.take(sizeof(float) * 3 * V);
+    l.rgb = a.take(rgb ? 3 * V : 0);
+    l.tri = a.take(sizeof(int32_t) * 3 * T);
+    l.cell_of = a.take(sizeof(int32_t) * V);
+    l.cell_start = a.take(sizeof(int32_t) * (V + 1));
+    l.cell_key = a.take(sizeof(uint64_t) * V);
+    l.new_of_cell = a.take(sizeof(int32_t) * V);
+    l.used = a.take(V);
+    l.keep = a.take(T);
+    l.cell_blocks = a.take(sizeof(int32_t) * (vb + 1));
+    l.used_blocks = a.take(sizeof(int32_t) * (vb + 1));
+    l.tri_blocks = a.take(sizeof(int32_t) * (tb + 1));
+    l.rep = a.take(sizeof(float) * 3 * V);
+    l.rep_rgb = a.take(rgb ? 3 * V : 0);
+    l.a_bytes = a.at;
+    l.key_in = b.take(sizeof(uint64_t) * keys);
+    l.key_out = b.take(sizeof(uint64_t) * keys);
+    l.val_in = b.take(sizeof(int32_t) * vals);
+    l.val_out = b.take(sizeof(int32_t) * vals);
+    l.sort = b.take(sort_bytes);
+    l.b_bytes = b.at;
+    l.inc_start = c.take(normals ? sizeof(int32_t) * (V + 1) : 0);
+    l.face = c.take(normals ? sizeof(float) * 3 * T : 0);
+    l.c_bytes = c.at;
+    l.out_vertices = d.take(sizeof(float) * 3 * V);
+    l.out_normals = d.take(normals ? sizeof(float) * 3 * V : 0);
+    l.out_rgb = d.take(rgb ? 3 * V : 0);
+    l.out_tri = d.take(sizeof(int32_t) * 3 * T);
+    l.vertex_map = d.take(vertex_map ? sizeof(int32_t) * V : 0);
+    l.triangle_map = d.take(triangle_map ? sizeof(int32_t) * T : 0);
+    l.d_bytes = d.at;
     return l;
 }
 

@@ -7,40 +7,12 @@
 // for bit (-ffp-contract=off; HIP's default f32 / f64 division and f64 sqrt are correctly rounded).
 #include <cmath>
 
-#include "mvs_kernels.hpp"     // launch_block_offsets_scan
+#include "block_scan.hpp"
 #include "simplify_kernels.hpp"
 
 namespace esfm {
 
-#define LAUNCH_OK() ESFM_HIP_TRY(hipGetLastError())
-
-static unsigned blocks_of(int64_t n) { return (unsigned)((n + 255) / 256); }
-
 constexpr uint64_t kNoGroup = ~0ull;          // grouping key of a triangle that names a cell twice: behind every other key
-
-// The number of threads of the 256-thread workgroup up to and including this one for which `flag` holds (every thread calls).
-__device__ inline int simplify_inclusive_count(bool flag)
-{
-    __shared__ int32_t per_wave[4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const unsigned long long b = __ballot(flag);
-    if (lane == 0) per_wave[wave] = __popcll(b);
-    __syncthreads();
-    int before = 0;
-    for (int w = 0; w < wave; ++w) before += per_wave[w];
-    return before + __popcll(b & ((2ull << lane) - 1ull));        // (lane 63: 2 << 63 wraps to 0, the mask is all ones)
-}
-
-// First index in sorted[0 .. n) whose key is >= key.
-__device__ inline int64_t simplify_lower_bound(const uint64_t *sorted, int64_t n, uint64_t key)
-{
-    int64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const int64_t mid = lo + ((hi - lo) >> 1);
-        if (sorted[mid] < key) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
 
 // ---- cells -----------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void simplify_cell_keys_kernel(SimplifyArgs a)
@@ -57,21 +29,18 @@ __global__ __launch_bounds__(256) void simplify_cell_keys_kernel(SimplifyArgs a)
     a.val_in[v] = (int32_t)v;
 }
 
-__device__ inline bool simplify_is_cell_head(const SimplifyArgs &a, int64_t i) { return i < a.V && (i == 0 || a.key_out[i - 1] != a.key_out[i]); }
-
-__global__ __launch_bounds__(256) void simplify_cell_heads_kernel(SimplifyArgs a)
-{
-    const int n = __syncthreads_count(simplify_is_cell_head(a, (int64_t)blockIdx.x * 256 + threadIdx.x));
-    if (threadIdx.x == 0) a.cell_blocks[blockIdx.x] = n;
-}
+struct SimplifyIsCellHead {
+    SimplifyArgs a;
+    __device__ bool operator()(int64_t i) const { return i < a.V && (i == 0 || a.key_out[i - 1] != a.key_out[i]); }
+};
 
 // One thread per sorted vertex: the run heads up to and including it number its cell (position 0 is a head, so the number is
 // never negative); a head also records where its run starts and its key, the last position closes the last run.
 __global__ __launch_bounds__(256) void simplify_cell_numbers_kernel(SimplifyArgs a)
 {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const bool head = simplify_is_cell_head(a, i);
-    const int incl = simplify_inclusive_count(head);
+    const bool head = SimplifyIsCellHead{a}(i);
+    const int incl = block_inclusive_count(head);
     if (i >= a.V) return;
     const int32_t cell = a.cell_blocks[blockIdx.x] + incl - 1;
     a.cell_of[a.val_out[i]] = cell;
@@ -88,11 +57,8 @@ int launch_simplify_cell_keys(hipStream_t st, const SimplifyArgs &a)
 
 int launch_simplify_cells(hipStream_t st, const SimplifyArgs &a)
 {
-    const unsigned vb = blocks_of(a.V);
-    hipLaunchKernelGGL(simplify_cell_heads_kernel, dim3(vb), dim3(256), 0, st, a);
-    LAUNCH_OK();
-    if (int rc = launch_block_offsets_scan(st, a.cell_blocks, (int)vb, a.cell_blocks + vb)) return rc;
-    hipLaunchKernelGGL(simplify_cell_numbers_kernel, dim3(vb), dim3(256), 0, st, a);
+    if (int rc = launch_flag_offsets(st, a.V, SimplifyIsCellHead{a}, a.cell_blocks)) return rc;
+    hipLaunchKernelGGL(simplify_cell_numbers_kernel, dim3(blocks_of(a.V)), dim3(256), 0, st, a);
     LAUNCH_OK();
     return ESFM_OK;
 }
@@ -141,7 +107,7 @@ __global__ __launch_bounds__(256) void simplify_place_kernel(SimplifyArgs a, con
     // the area-weighted plane quadric about the cell centre over the cell's corners in ascending 3 t + corner
     double A00 = 0.0, A01 = 0.0, A02 = 0.0, A11 = 0.0, A12 = 0.0, A22 = 0.0, b0 = 0.0, b1 = 0.0, b2 = 0.0;
     const int64_t n_keys = 3 * (int64_t)a.T;
-    const int64_t j0 = simplify_lower_bound(a.key_out, n_keys, (uint64_t)c << 32), j1 = simplify_lower_bound(a.key_out, n_keys, (uint64_t)(c + 1) << 32);
+    const int64_t j0 = lower_bound(a.key_out, n_keys, (uint64_t)c << 32), j1 = lower_bound(a.key_out, n_keys, (uint64_t)(c + 1) << 32);
     for (int64_t j = j0; j < j1; ++j) {
         const int64_t t = (int64_t)(a.key_out[j] & 0xFFFFFFFFull) / 3;
         const int64_t v0 = a.tri[3 * t], v1 = a.tri[3 * t + 1], v2 = a.tri[3 * t + 2];
@@ -260,25 +226,20 @@ int launch_simplify_vote(hipStream_t st, const SimplifyArgs &a)
 
 // ---- ordered compaction ------------------------------------------------------------------------------------------------------
 // (used[] is zero from the cell count on, so the cell kernels run over V without knowing the count)
-__global__ __launch_bounds__(256) void simplify_count_cells_kernel(SimplifyArgs a)
-{
-    const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const int n = __syncthreads_count(c < a.V && a.used[c]);
-    if (threadIdx.x == 0) a.used_blocks[blockIdx.x] = n;
-}
-
-__global__ __launch_bounds__(256) void simplify_count_triangles_kernel(SimplifyArgs a)
-{
-    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const int n = __syncthreads_count(t < a.T && a.keep[t]);
-    if (threadIdx.x == 0) a.tri_blocks[blockIdx.x] = n;
-}
+struct SimplifyCellUsed {
+    SimplifyArgs a;
+    __device__ bool operator()(int64_t c) const { return c < a.V && a.used[c]; }
+};
+struct SimplifyTriangleKept {
+    SimplifyArgs a;
+    __device__ bool operator()(int64_t t) const { return t < a.T && a.keep[t]; }
+};
 
 __global__ __launch_bounds__(256) void simplify_write_vertices_kernel(SimplifyArgs a)
 {
     const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const bool keep = c < a.V && a.used[c];
-    const int incl = simplify_inclusive_count(keep);
+    const bool keep = SimplifyCellUsed{a}(c);
+    const int incl = block_inclusive_count(keep);
     if (!keep) return;
     const int64_t dst = (int64_t)a.used_blocks[blockIdx.x] + incl - 1;
 #pragma unroll
@@ -294,8 +255,8 @@ __global__ __launch_bounds__(256) void simplify_write_vertices_kernel(SimplifyAr
 __global__ __launch_bounds__(256) void simplify_write_triangles_kernel(SimplifyArgs a)
 {
     const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const bool keep = t < a.T && a.keep[t];
-    const int incl = simplify_inclusive_count(keep);
+    const bool keep = SimplifyTriangleKept{a}(t);
+    const int incl = block_inclusive_count(keep);
     if (!keep) return;
     const int64_t dst = (int64_t)a.tri_blocks[blockIdx.x] + incl - 1;
 #pragma unroll
@@ -314,12 +275,8 @@ __global__ __launch_bounds__(256) void simplify_vertex_map_kernel(SimplifyArgs a
 int launch_simplify_compact(hipStream_t st, const SimplifyArgs &a)
 {
     const unsigned vb = blocks_of(a.V), tb = blocks_of(a.T);
-    hipLaunchKernelGGL(simplify_count_cells_kernel, dim3(vb), dim3(256), 0, st, a);
-    LAUNCH_OK();
-    hipLaunchKernelGGL(simplify_count_triangles_kernel, dim3(tb), dim3(256), 0, st, a);
-    LAUNCH_OK();
-    if (int rc = launch_block_offsets_scan(st, a.used_blocks, (int)vb, a.used_blocks + vb)) return rc;
-    if (int rc = launch_block_offsets_scan(st, a.tri_blocks, (int)tb, a.tri_blocks + tb)) return rc;
+    if (int rc = launch_flag_offsets(st, a.V, SimplifyCellUsed{a}, a.used_blocks)) return rc;
+    if (int rc = launch_flag_offsets(st, a.T, SimplifyTriangleKept{a}, a.tri_blocks)) return rc;
     hipLaunchKernelGGL(simplify_write_vertices_kernel, dim3(vb), dim3(256), 0, st, a);
     LAUNCH_OK();
     hipLaunchKernelGGL(simplify_write_triangles_kernel, dim3(tb), dim3(256), 0, st, a);

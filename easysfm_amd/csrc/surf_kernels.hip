@@ -13,6 +13,7 @@
 //   surf_window_kernel        rotated window, one thread per chunk of a window row (all keypoints in one grid)
 //   surf_rowsum_kernel        horizontal pass of the area shrink to 21 x 21, one thread per (window row, output column)
 //   surf_vector_kernel        one workgroup per keypoint: vertical pass, weighted gradients, 4 x 4 x 4 sums, normalisation
+#include "block_scan.hpp"   // LAUNCH_OK
 #include "surf_kernels.hpp"
 #include "feature_math.hpp"
 
@@ -413,8 +414,6 @@ __global__ __launch_bounds__(kSurfVecThreads) void surf_vector_kernel(const Surf
 }
 
 // ---- launchers ---------------------------------------------------------------------------------------------------------
-#define LAUNCH_OK() ESFM_HIP_TRY(hipGetLastError())
-
 int launch_surf_gray(hipStream_t st, const uint8_t *bgr, int n_pixels, uint8_t *gray)
 {
     if (n_pixels <= 0) return ESFM_OK;

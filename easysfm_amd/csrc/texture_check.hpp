@@ -8,6 +8,7 @@
 #include <cstdint>
 
 #include "error.hpp"
+#include "scratch_layout.hpp"
 
 namespace esfm {
 
@@ -111,33 +112,27 @@ struct TextureLayout {
     size_t images, c_bytes, atlas, d_bytes;
 };
 
-inline size_t texture_align(size_t b) { return (b + 255) / 256 * 256; }
-
 // views: pixels = rows * cols, the bake's fields empty; bake: image_bytes and atlas_bytes, the views' fields empty
 inline TextureLayout texture_layout(size_t V, size_t T, size_t n_views, bool rgb, size_t pixels, size_t image_bytes, size_t atlas_bytes)
 {
     TextureLayout l;
-    size_t at = 0;
-    auto take = [&at](size_t bytes) { const size_t here = at; at += texture_align(bytes); return here; };
-    l.vertices = take(sizeof(float) * 3 * V);
-    l.tri = take(sizeof(int32_t) * 3 * T);
-    l.rgb = take(rgb ? 3 * V : 0);
-    l.cams = take(sizeof(TextureCam) * n_views);
-    l.label = take(sizeof(int32_t) * T);
-    l.score = take(sizeof(float) * T);
-    l.a_bytes = at;
-    at = 0;
-    l.proj = take(pixels ? 16 * n_views * V : 0);
-    l.buffers = take(sizeof(uint32_t) * n_views * pixels);
-    l.list = take(pixels ? sizeof(uint32_t) * n_views * T : 0);
-    l.count = take(pixels ? sizeof(uint32_t) : 0);
-    l.b_bytes = at;
-    at = 0;
-    l.images = take(image_bytes);
-    l.c_bytes = at;
-    at = 0;
-    l.atlas = take(atlas_bytes);
-    l.d_bytes = at;
+    ScratchCarver a, b, c, d;
+    l.vertices = a.take(sizeof(float) * 3 * V);
+    l.tri = a.take(sizeof(int32_t) * 3 * T);
+    l.rgb = a.take(rgb ? 3 * V : 0);
+    l.cams = a.take(sizeof(TextureCam) * n_views);
+    l.label = a.take(sizeof(int32_t) * T);
+    l.score = a.take(sizeof(float) * T);
+    l.a_bytes = a.at;
+    l.proj = b.take(pixels ? 16 * n_views * V : 0);
+    l.buffers = b.take(sizeof(uint32_t) * n_views * pixels);
+    l.list = b.take(pixels ? sizeof(uint32_t) * n_views * T : 0);
+    l.count = b.take(pixels ? sizeof(uint32_t) : 0);
+    l.b_bytes = b.at;
+    l.images = c.take(image_bytes);
+    l.c_bytes = c.at;
+    l.atlas = d.take(atlas_bytes);
+    l.d_bytes = d.at;
     return l;
 }
 

@@ -3,13 +3,10 @@
 // per-texel bake.  The only combination across threads is atomicMax on a uint32 (a positive f32 orders like its bit pattern), so
 // the buffers do not depend on the order in which the pairs arrive; the list of large boxes is filled in arrival order, which the
 // maximum does not see.  Every f32 expression is the header's, in its order (the build has no mul + add contraction).
+#include "block_scan.hpp"         // blocks_of, LAUNCH_OK
 #include "texture_device.hpp"     // texture_project, texture_taps, texture_fetch
 
 namespace esfm {
-
-#define LAUNCH_OK() ESFM_HIP_TRY(hipGetLastError())
-
-static unsigned blocks_of(int64_t n) { return (unsigned)((n + 255) / 256); }
 
 __global__ __launch_bounds__(256) void texture_project_kernel(TextureViewsArgs a)
 {

@@ -5,11 +5,10 @@
 #include <cmath>
 #include <vector>
 
+#include "scratch_layout.hpp"
 #include "tsdf_kernels.hpp"
 
 namespace {
-
-size_t al(size_t b) { return (b + 255) / 256 * 256; }
 
 int check_grid(const esfm_tsdf_grid *g, const esfm_tsdf_options *o)
 {
@@ -57,15 +56,16 @@ int check_ctx(esfm_ctx *ctx)
 int place_volume(esfm_ctx *ctx, const esfm_tsdf_grid *g, bool with_rgb, esfm::TsdfVolume *vol)
 {
     const size_t N = (size_t)g->dims[0] * g->dims[1] * g->dims[2];
-    const size_t f_b = al(sizeof(float) * N), w_b = al(sizeof(int32_t) * N), c_b = with_rgb ? al(3 * N) : 0;
-    if (int rc = ctx->stage_b.reserve(f_b + w_b + c_b)) return rc;
+    esfm::ScratchCarver at;
+    const size_t tsdf = at.take(sizeof(float) * N), weight = at.take(sizeof(int32_t) * N), rgb = at.take(with_rgb ? 3 * N : 0);
+    if (int rc = ctx->stage_b.reserve(at.at)) return rc;
     uint8_t *p = ctx->stage_b.as<uint8_t>();
     for (int c = 0; c < 3; ++c) vol->origin[c] = g->origin[c];
     vol->h = g->voxel_size;
     vol->nx = g->dims[0]; vol->ny = g->dims[1]; vol->nz = g->dims[2]; vol->n = (int32_t)N;
-    vol->tsdf = reinterpret_cast<float *>(p);
-    vol->weight = reinterpret_cast<int32_t *>(p + f_b);
-    vol->rgb = with_rgb ? p + f_b + w_b : nullptr;
+    vol->tsdf = reinterpret_cast<float *>(p + tsdf);
+    vol->weight = reinterpret_cast<int32_t *>(p + weight);
+    vol->rgb = with_rgb ? p + rgb : nullptr;
     return ESFM_OK;
 }
 
@@ -87,20 +87,21 @@ int integrate(esfm_ctx *ctx, int n_views, int rows, int cols, int channels, cons
         c.view = v;
         cams.push_back(c);
     }
-    const size_t dep_b = al(sizeof(float) * n_px), img_b = images ? al(n_px * channels) : 0;
-    if (int rc = ctx->stage_a.reserve(dep_b + img_b + sizeof(esfm::TsdfCam) * esfm::kTsdfMaxViews)) return rc;
+    esfm::ScratchCarver at;
+    const size_t dep = at.take(sizeof(float) * n_px), img = at.take(images ? n_px * channels : 0), cam = at.take(sizeof(esfm::TsdfCam) * esfm::kTsdfMaxViews);
+    if (int rc = ctx->stage_a.reserve(at.at)) return rc;
     uint8_t *p = ctx->stage_a.as<uint8_t>();
     esfm::TsdfIntegrateArgs a;
     a.vol = vol;
-    a.depth = reinterpret_cast<const float *>(p);
-    a.images = images ? p + dep_b : nullptr;
-    a.cams = reinterpret_cast<const esfm::TsdfCam *>(p + dep_b + img_b);
+    a.depth = reinterpret_cast<const float *>(p + dep);
+    a.images = images ? p + img : nullptr;
+    a.cams = reinterpret_cast<const esfm::TsdfCam *>(p + cam);
     a.n_cams = (int32_t)cams.size(); a.rows = rows; a.cols = cols; a.channels = images ? channels : 1;
     a.trunc = opt->trunc == 0.f ? 4.0f * vol.h : opt->trunc;
     if (!cams.empty()) {
-        ESFM_HIP_TRY(esfm::copy_h2d(p, depth, sizeof(float) * n_px, st));
-        if (images) ESFM_HIP_TRY(esfm::copy_h2d(p + dep_b, images, n_px * channels, st));
-        ESFM_HIP_TRY(esfm::copy_h2d(p + dep_b + img_b, cams.data(), sizeof(esfm::TsdfCam) * cams.size(), st));
+        ESFM_HIP_TRY(esfm::copy_h2d(p + dep, depth, sizeof(float) * n_px, st));
+        if (images) ESFM_HIP_TRY(esfm::copy_h2d(p + img, images, n_px * channels, st));
+        ESFM_HIP_TRY(esfm::copy_h2d(p + cam, cams.data(), sizeof(esfm::TsdfCam) * cams.size(), st));
     }
     return esfm::launch_tsdf_integrate(st, a);
 }
@@ -112,17 +113,19 @@ int extract(esfm_ctx *ctx, const esfm::TsdfVolume &vol, const esfm_tsdf_options 
 {
     hipStream_t st = ctx->stream;
     const size_t N = (size_t)vol.n, n_blocks = (N + 255) / 256;
-    const size_t byte_b = al(N), base_b = al(sizeof(int32_t) * N), cnt_b = al(sizeof(int32_t) * (n_blocks + 1));
-    if (int rc = ctx->stage_c.reserve(3 * byte_b + base_b + 2 * cnt_b)) return rc;
+    esfm::ScratchCarver work;
+    const size_t state = work.take(N), edge_mask = work.take(N), tri_count = work.take(N), vertex_base = work.take(sizeof(int32_t) * N),
+                 block_vertices = work.take(sizeof(int32_t) * (n_blocks + 1)), block_triangles = work.take(sizeof(int32_t) * (n_blocks + 1));
+    if (int rc = ctx->stage_c.reserve(work.at)) return rc;
     uint8_t *p = ctx->stage_c.as<uint8_t>();
     esfm::TsdfExtractArgs a;
     memset(&a, 0, sizeof(a));
     a.vol = vol;
     a.min_weight = opt->min_weight; a.n_blocks = (int32_t)n_blocks;
-    a.state = p; a.edge_mask = p + byte_b; a.tri_count = p + 2 * byte_b;
-    a.vertex_base = reinterpret_cast<int32_t *>(p + 3 * byte_b);
-    a.block_vertices = reinterpret_cast<int32_t *>(p + 3 * byte_b + base_b);
-    a.block_triangles = reinterpret_cast<int32_t *>(p + 3 * byte_b + base_b + cnt_b);
+    a.state = p + state; a.edge_mask = p + edge_mask; a.tri_count = p + tri_count;
+    a.vertex_base = reinterpret_cast<int32_t *>(p + vertex_base);
+    a.block_vertices = reinterpret_cast<int32_t *>(p + block_vertices);
+    a.block_triangles = reinterpret_cast<int32_t *>(p + block_triangles);
     if (int rc = esfm::launch_tsdf_classify(st, a)) return rc;
     int32_t nv = 0, nt = 0;
     ESFM_HIP_TRY(esfm::copy_d2h(&nv, a.block_vertices + n_blocks, sizeof(int32_t), st));
@@ -136,13 +139,15 @@ int extract(esfm_ctx *ctx, const esfm::TsdfVolume &vol, const esfm_tsdf_options 
     }
     if (nv == 0) return ESFM_OK;                               // (no vertex: no triangle either)
     const size_t V = (size_t)nv, T = (size_t)nt;
-    const size_t vtx_b = al(sizeof(float) * 3 * V), nrm_b = normals ? vtx_b : 0, col_b = vertex_rgb ? al(3 * V) : 0;
-    if (int rc = ctx->stage_d.reserve(vtx_b + nrm_b + col_b + sizeof(int32_t) * 3 * T)) return rc;
+    esfm::ScratchCarver out;
+    const size_t o_vtx = out.take(sizeof(float) * 3 * V), o_nrm = out.take(normals ? sizeof(float) * 3 * V : 0), o_rgb = out.take(vertex_rgb ? 3 * V : 0),
+                 o_tri = out.take(sizeof(int32_t) * 3 * T);
+    if (int rc = ctx->stage_d.reserve(out.at)) return rc;
     uint8_t *o = ctx->stage_d.as<uint8_t>();
-    a.vertices = reinterpret_cast<float *>(o);
-    a.normals = normals ? reinterpret_cast<float *>(o + vtx_b) : nullptr;
-    a.vertex_rgb = vertex_rgb ? o + vtx_b + nrm_b : nullptr;
-    a.triangles = reinterpret_cast<int32_t *>(o + vtx_b + nrm_b + col_b);
+    a.vertices = reinterpret_cast<float *>(o + o_vtx);
+    a.normals = normals ? reinterpret_cast<float *>(o + o_nrm) : nullptr;
+    a.vertex_rgb = vertex_rgb ? o + o_rgb : nullptr;
+    a.triangles = reinterpret_cast<int32_t *>(o + o_tri);
     if (int rc = esfm::launch_tsdf_mesh(st, a)) return rc;
     ESFM_HIP_TRY(esfm::copy_d2h(vertices, a.vertices, sizeof(float) * 3 * V, st));
     if (normals) ESFM_HIP_TRY(esfm::copy_d2h(normals, a.normals, sizeof(float) * 3 * V, st));

@@ -4,12 +4,10 @@
 // is compared bit for bit (-ffp-contract=off; HIP's default f32 division and sqrtf are correctly rounded).
 #include <cmath>
 
-#include "mvs_kernels.hpp"     // launch_block_offsets_scan
+#include "block_scan.hpp"
 #include "tsdf_kernels.hpp"
 
 namespace esfm {
-
-#define LAUNCH_OK() ESFM_HIP_TRY(hipGetLastError())
 
 __device__ inline void tsdf_voxel_of(const TsdfVolume &g, int idx, int &i, int &j, int &k)
 {

@@ -5,12 +5,10 @@
 // division and f64 sqrt are correctly rounded).
 #include <cmath>
 
-#include "mvs_kernels.hpp"     // launch_block_offsets_scan
+#include "block_scan.hpp"
 #include "voxel_kernels.hpp"
 
 namespace esfm {
-
-#define LAUNCH_OK() ESFM_HIP_TRY(hipGetLastError())
 
 // ---- bounds --------------------------------------------------------------------------------------------------------------
 // Grid-stride over the points; each workgroup leaves the min / max of the finite points it saw and their number (min and max are
@@ -70,26 +68,10 @@ __global__ __launch_bounds__(256) void voxel_keys_kernel(VoxelArgs a, uint64_t *
 }
 
 // ---- run heads -----------------------------------------------------------------------------------------------------------
-__device__ inline bool voxel_is_head(const VoxelArgs &a, int64_t i) { return i < a.n_valid && (i == 0 || a.keys[i] != a.keys[i - 1]); }
-
-__global__ __launch_bounds__(256) void voxel_heads_kernel(VoxelArgs a)
-{
-    const int n = __syncthreads_count(voxel_is_head(a, (int64_t)blockIdx.x * 256 + threadIdx.x));
-    if (threadIdx.x == 0) a.head_count[blockIdx.x] = n;
-}
-
-// The number of threads of the 256-thread workgroup up to and including this one for which `flag` holds (every thread calls).
-__device__ inline int block_inclusive_count(bool flag)
-{
-    __shared__ int32_t per_wave[4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const unsigned long long b = __ballot(flag);
-    if (lane == 0) per_wave[wave] = __popcll(b);
-    __syncthreads();
-    int before = 0;
-    for (int w = 0; w < wave; ++w) before += per_wave[w];
-    return before + __popcll(b & ((2ull << lane) - 1ull));        // (lane 63: 2 << 63 wraps to 0, the mask is all ones)
-}
+struct VoxelIsHead {
+    VoxelArgs a;
+    __device__ bool operator()(int64_t i) const { return i < a.n_valid && (i == 0 || a.keys[i] != a.keys[i - 1]); }
+};
 
 // ---- accumulation --------------------------------------------------------------------------------------------------------
 // One thread per sorted entry; a voxel's members are contiguous.  Each wave folds its entries by voxel with a segmented scan over
@@ -103,7 +85,7 @@ __global__ __launch_bounds__(256) void voxel_accumulate_kernel(VoxelArgs a)
     const int lane = threadIdx.x & 63;
     const bool in = i < a.n_valid;
     const uint64_t key = in ? a.keys[i] : kVoxelNoKey;
-    const bool head = voxel_is_head(a, i);
+    const bool head = VoxelIsHead{a}(i);
     const bool tail = in && (i + 1 == a.n_valid || a.keys[i + 1] != key);
     const int incl = block_inclusive_count(head);
     const int vid = in ? a.head_count[blockIdx.x] + incl - 1 : -1;       // (entry 0 is a head: vid >= 0 for every entry)
@@ -163,24 +145,21 @@ __global__ __launch_bounds__(256) void voxel_accumulate_kernel(VoxelArgs a)
 }
 
 // ---- finalise, filter, ordered compaction -----------------------------------------------------------------------------------
-__device__ inline bool voxel_is_kept(const VoxelArgs &a, int64_t v)
-{
-    if (v >= a.n_vox) return false;
-    const int64_t *acc = a.acc + v * kVoxelAccWords;
-    return acc[9] >= a.min_points && __popcll((unsigned long long)acc[10]) >= a.min_tags;
-}
-
-__global__ __launch_bounds__(256) void voxel_keep_kernel(VoxelArgs a)
-{
-    const int n = __syncthreads_count(voxel_is_kept(a, (int64_t)blockIdx.x * 256 + threadIdx.x));
-    if (threadIdx.x == 0) a.keep_count[blockIdx.x] = n;
-}
+struct VoxelIsKept {
+    VoxelArgs a;
+    __device__ bool operator()(int64_t v) const
+    {
+        if (v >= a.n_vox) return false;
+        const int64_t *acc = a.acc + v * kVoxelAccWords;
+        return acc[9] >= a.min_points && __popcll((unsigned long long)acc[10]) >= a.min_tags;
+    }
+};
 
 // Voxel ids ascend with the key, so the block offsets plus the kept voxels before this one in the block give the key order.
 __global__ __launch_bounds__(256) void voxel_write_kernel(VoxelArgs a)
 {
     const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const bool keep = voxel_is_kept(a, v);
+    const bool keep = VoxelIsKept{a}(v);
     const int incl = block_inclusive_count(keep);
     if (!keep) return;
     const int64_t dst = (int64_t)a.keep_count[blockIdx.x] + incl - 1;
@@ -209,8 +188,6 @@ __global__ __launch_bounds__(256) void voxel_write_kernel(VoxelArgs a)
 }
 
 // ---- launchers -----------------------------------------------------------------------------------------------------------
-static unsigned blocks_of(int64_t n) { return (unsigned)((n + 255) / 256); }
-
 int launch_voxel_bounds(hipStream_t st, const float *xyz, int n, VoxelBounds *partials, int *n_partials)
 {
     const unsigned g = blocks_of(n) < (unsigned)kVoxelBoundsBlocks ? blocks_of(n) : (unsigned)kVoxelBoundsBlocks;
@@ -229,9 +206,7 @@ int launch_voxel_keys(hipStream_t st, const VoxelArgs &a, uint64_t *keys, int32_
 
 int launch_voxel_heads(hipStream_t st, const VoxelArgs &a)
 {
-    hipLaunchKernelGGL(voxel_heads_kernel, dim3(blocks_of(a.n_valid)), dim3(256), 0, st, a);
-    LAUNCH_OK();
-    return launch_block_offsets_scan(st, a.head_count, (int)blocks_of(a.n_valid), a.n_voxels);
+    return launch_flag_offsets(st, a.n_valid, VoxelIsHead{a}, a.head_count);
 }
 
 int launch_voxel_accumulate(hipStream_t st, const VoxelArgs &a)
@@ -243,9 +218,7 @@ int launch_voxel_accumulate(hipStream_t st, const VoxelArgs &a)
 
 int launch_voxel_finalise(hipStream_t st, const VoxelArgs &a)
 {
-    hipLaunchKernelGGL(voxel_keep_kernel, dim3(blocks_of(a.n_vox)), dim3(256), 0, st, a);
-    LAUNCH_OK();
-    if (int rc = launch_block_offsets_scan(st, a.keep_count, (int)blocks_of(a.n_vox), a.n_out)) return rc;
+    if (int rc = launch_flag_offsets(st, a.n_vox, VoxelIsKept{a}, a.keep_count)) return rc;
     hipLaunchKernelGGL(voxel_write_kernel, dim3(blocks_of(a.n_vox)), dim3(256), 0, st, a);
     LAUNCH_OK();
     return ESFM_OK;

@@ -25,14 +25,12 @@ struct VoxelArgs {
     // sorted (key, point) pairs
     const uint64_t *keys;
     const int32_t *order;
-    int32_t *head_count;   // per 256-entry block: run heads, then their exclusive offset
-    int32_t *n_voxels;
+    int32_t *head_count;   // per 256-entry block: run heads, then their exclusive offset; the total (the voxels) behind them
     // per voxel
     uint64_t *vox_key;
     int64_t *acc;          // kVoxelAccWords each, zero before the accumulation
     int32_t n_vox, min_points, min_tags;
-    int32_t *keep_count;   // per 256-voxel block: kept voxels, then their exclusive offset
-    int32_t *n_out;
+    int32_t *keep_count;   // per 256-voxel block: kept voxels, then their exclusive offset; the total behind them
     // compacted output (out_rgb, out_normals, out_count, out_tagmask may be NULL)
     float *out_xyz;
     uint8_t *out_rgb;
@@ -43,9 +41,9 @@ struct VoxelArgs {
 
 int launch_voxel_bounds(hipStream_t st, const float *xyz, int n, VoxelBounds *partials, int *n_partials);
 int launch_voxel_keys(hipStream_t st, const VoxelArgs &a, uint64_t *keys, int32_t *index);
-int launch_voxel_heads(hipStream_t st, const VoxelArgs &a);          // head counts, their scan, *n_voxels
+int launch_voxel_heads(hipStream_t st, const VoxelArgs &a);          // head counts, their scan, the total
 int launch_voxel_accumulate(hipStream_t st, const VoxelArgs &a);
-int launch_voxel_finalise(hipStream_t st, const VoxelArgs &a);       // keep counts, their scan, the ordered write, *n_out
+int launch_voxel_finalise(hipStream_t st, const VoxelArgs &a);       // keep counts, their scan, the total, the ordered write
 
 // voxel_sort.hip: hipCUB's device radix sort of (64-bit key, point index)
 int voxel_sort_scratch_bytes(int n, size_t *bytes, hipStream_t st);

@@ -139,7 +139,7 @@ int main()
         EXPECT(esfm::level_converged(ok, bb, 1e-4) && !esfm::level_converged(one, bb, 1e-4) && !esfm::level_converged(bad, bb, 1e-4));
         EXPECT(!esfm::level_converged(ok, bb, 0.0));
     }
-    EXPECT(esfm::level_bit_width(0) == 0 && esfm::level_bit_width(1) == 1 && esfm::level_bit_width(255) == 8 && esfm::level_bit_width(256) == 9);
+    EXPECT(esfm::bit_width(0) == 0 && esfm::bit_width(1) == 1 && esfm::bit_width(255) == 8 && esfm::bit_width(256) == 9);
 
     // the layout: arrays in order, 256-byte aligned, apart, inside the totals
     for (size_t V : {size_t(1), size_t(255), size_t(70001)})
