@@ -17,7 +17,8 @@
 //   null_space             orthonormal basis of the null space of the 5 x 9 epipolar system (Householder QR of its transpose)
 //   determinant_polynomial the ten cubic constraints -> 10 x 20 system -> Gauss-Jordan -> B(z) -> det B(z), degree 10
 //   dk_*                   its ten roots by the simultaneous Durand-Kerner iteration
-//   model_from_root        z -> (x, y) from the null vector of B(z) -> E, unit norm, canonical sign
+//   model_from_root        z -> (x, y) from the null vector of B(z) -> refine_solution -> E, unit norm, canonical sign
+//   refine_solution        up to six Gauss-Newton steps on (x, y, z) against the ten constraints evaluated on E itself
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -310,9 +311,93 @@ ESFM_FP_HD bool dk_moving(Rest &st, double qr, double qi, double re, double im)
 }
 constexpr int kMaxSweeps = 300;
 
+// ---- refinement of a solution (x, y, z) against the ten constraints themselves ---------------------------------------------------
+// Forming det B(z) loses accuracy (the elimination and the products of its rows: roots off by 1e-8 .. 1e-3 on one RANSAC sample in
+// eight, tests/test_five_point_census.py), and a model built from such a root misses the constraints by as much.  The constraints
+// evaluated directly on E = x N0 + y N1 + z N2 + N3 lose nothing, so a few Gauss-Newton steps on them repair the model wherever the
+// root was near a solution at all.  F(E) = (2 E E'E - tr(E E')E [9], det E); E stays inside the null space, so x2'E x1 = 0 holds as before.
+constexpr int kRefineSteps = 6;
+
+// G = E E', tr = its trace, F[10] = the constraints' values
+ESFM_FP_HD void constraint_values(const double *E, double *G, double &tr, double *F)
+{
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) G[3 * r + c] = E[3 * r] * E[3 * c] + E[3 * r + 1] * E[3 * c + 1] + E[3 * r + 2] * E[3 * c + 2];
+    tr = G[0] + G[4] + G[8];
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) F[3 * r + c] = 2.0 * (G[3 * r] * E[c] + G[3 * r + 1] * E[3 + c] + G[3 * r + 2] * E[6 + c]) - tr * E[3 * r + c];
+    F[9] = E[0] * (E[4] * E[8] - E[5] * E[7]) - E[1] * (E[3] * E[8] - E[5] * E[6]) + E[2] * (E[3] * E[7] - E[4] * E[6]);
+}
+// D[10] = the derivative of F at E along H: 2 (H E'E + E H'E + E E'H) - 2 tr(H E')E - tr(E E')H, and the cofactor sum for det
+ESFM_FP_HD void constraint_derivative(const double *E, const double *G, double tr, const double *H, double *D)
+{
+    double A[9];                                           // A = H E'
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) A[3 * r + c] = H[3 * r] * E[3 * c] + H[3 * r + 1] * E[3 * c + 1] + H[3 * r + 2] * E[3 * c + 2];
+    const double trA = A[0] + A[4] + A[8];
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+            D[3 * r + c] = 2.0 * ((A[3 * r] + A[r]) * E[c] + (A[3 * r + 1] + A[3 + r]) * E[3 + c] + (A[3 * r + 2] + A[6 + r]) * E[6 + c]
+                                  + G[3 * r] * H[c] + G[3 * r + 1] * H[3 + c] + G[3 * r + 2] * H[6 + c])
+                           - 2.0 * trA * E[3 * r + c] - tr * H[3 * r + c];
+    D[9] = H[0] * (E[4] * E[8] - E[5] * E[7]) - H[1] * (E[3] * E[8] - E[5] * E[6]) + H[2] * (E[3] * E[7] - E[4] * E[6])
+           - H[3] * (E[1] * E[8] - E[2] * E[7]) + H[4] * (E[0] * E[8] - E[2] * E[6]) - H[5] * (E[0] * E[7] - E[1] * E[6])
+           + H[6] * (E[1] * E[5] - E[2] * E[4]) - H[7] * (E[0] * E[5] - E[2] * E[3]) + H[8] * (E[0] * E[4] - E[1] * E[3]);
+}
+// At most kRefineSteps Gauss-Newton steps on (x, y, z); N = the basis N[4][9].  What a step is measured by: q = |F|^2 / |E|^6, the squared
+// residual of the unit-norm E (F is cubic in E).  A step that does not lower q is taken back and ends the refinement (a spurious root
+// is near no solution and the steps from it go anywhere; a non-finite value fails every comparison and ends it the same way), so the
+// model that comes out is never worse than the one that went in.  The 3 x 3 normal equations by elimination without pivoting (the
+// matrix is positive definite where the solution is isolated; a pivot that is not positive ends the refinement).
+ESFM_FP_HD void refine_solution(const double *N, double &x, double &y, double &z)
+{
+    double kx = x, ky = y, kz = z, kq = 0.0;               // the best point so far and its q
+#pragma unroll 1
+    for (int step = 0; step <= kRefineSteps; ++step) {
+        double E[9], G[9], F[10], tr, nn = 0.0, ss = 0.0;
+#pragma unroll
+        for (int a = 0; a < 9; ++a) { E[a] = x * N[a] + y * N[9 + a] + z * N[18 + a] + N[27 + a]; nn += E[a] * E[a]; }
+        constraint_values(E, G, tr, F);
+#pragma unroll
+        for (int a = 0; a < 10; ++a) ss += F[a] * F[a];
+        const double q = ss / (nn * nn * nn);
+        if (!(step == 0 || q < kq)) { x = kx; y = ky; z = kz; break; }
+        kx = x; ky = y; kz = z; kq = q;
+        if (step == kRefineSteps) break;
+        double D0[10], D1[10], D2[10];
+        constraint_derivative(E, G, tr, N, D0);
+        constraint_derivative(E, G, tr, N + 9, D1);
+        constraint_derivative(E, G, tr, N + 18, D2);
+        double a00 = 0.0, a01 = 0.0, a02 = 0.0, a11 = 0.0, a12 = 0.0, a22 = 0.0, b0 = 0.0, b1 = 0.0, b2 = 0.0;      // J'J d = J'F
+#pragma unroll
+        for (int a = 0; a < 10; ++a) {
+            a00 += D0[a] * D0[a]; a01 += D0[a] * D1[a]; a02 += D0[a] * D2[a]; a11 += D1[a] * D1[a]; a12 += D1[a] * D2[a]; a22 += D2[a] * D2[a];
+            b0 += D0[a] * F[a]; b1 += D1[a] * F[a]; b2 += D2[a] * F[a];
+        }
+        if (!(a00 > 0.0)) break;
+        const double l10 = a01 / a00, l20 = a02 / a00;
+        const double c11 = a11 - l10 * a01, c12 = a12 - l10 * a02, c22 = a22 - l20 * a02, e1 = b1 - l10 * b0, e2 = b2 - l20 * b0;
+        if (!(c11 > 0.0)) break;
+        const double l21 = c12 / c11;
+        const double f22 = c22 - l21 * c12, g2 = e2 - l21 * e1;
+        if (!(f22 > 0.0)) break;
+        const double d2 = g2 / f22, d1 = (e1 - c12 * d2) / c11, d0 = (b0 - a01 * d1 - a02 * d2) / a00;
+        x -= d0; y -= d1; z -= d2;
+    }
+}
+
 // Root estimate (re, im) -> model: Newton on the real axis if it is real to 1e-8, x, y from the null vector of B(z) (the largest of the
-// cross products of two of its rows; OpenCV: SVD::solveZ), E = x N0 + y N1 + z N2 + N3 scaled to unit Frobenius norm with its
-// largest-magnitude entry positive.  Ev and z are written in every case (the device ranks lanes by them under `valid`).
+// cross products of two of its rows; OpenCV: SVD::solveZ), (x, y, z) refined against the constraints (refine_solution; z from then on
+// is the refined one), E = x N0 + y N1 + z N2 + N3 scaled to unit Frobenius norm with its largest-magnitude entry positive.  Ev and z
+// are written in every case (the device ranks lanes by them under `valid`).
 ESFM_FP_HD bool model_from_root(const double *cc, const double *w, double re, double im, double *Ev, double &z)
 {
     const bool is_real = !(fabs(im) > 1e-8 * fmax(1.0, fabs(re)));
@@ -342,7 +427,8 @@ ESFM_FP_HD bool model_from_root(const double *cc, const double *w, double re, do
         if (nn > bn) { bn = nn; bx = cx; by = cy; bw = cw; }
     }
     const bool valid = is_real && bn > 0.0 && !(fabs(bw) < 1e-10 * sqrt(bn));
-    const double x = bx / bw, y = by / bw;
+    double x = bx / bw, y = by / bw;
+    if (valid) refine_solution(w + kSetupN, x, y, z);
     double nrm = 0.0;
 #pragma unroll
     for (int a = 0; a < 9; ++a) {

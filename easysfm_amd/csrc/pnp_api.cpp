@@ -160,7 +160,10 @@ int esfm_solve_pnp_ransac(esfm_ctx *ctx, const float *pts3d, const float *pts2d,
     {
         int m_host = 0;
         for (size_t i = 0; i < nn; ++i) m_host += mask[i] ? 1 : 0;
-        if (m_host >= rs::kModelPoints && m_host <= kPnpHostRefit) {
+        // (ESFM_PNP_HOST_REFIT=0: every re-fit through the device reductions below, whatever its size -- tests; read on each call)
+        const char *env_refit = getenv("ESFM_PNP_HOST_REFIT");
+        const int host_refit = env_refit ? std::max(0, atoi(env_refit)) : kPnpHostRefit;
+        if (m_host >= rs::kModelPoints && m_host <= host_refit) {
             std::vector<double> w(3 * (size_t)m_host), px(2 * (size_t)m_host), al(4 * (size_t)m_host), pc(3 * (size_t)m_host);
             for (size_t i = 0, k = 0; i < nn; ++i)
                 if (mask[i]) { for (int c = 0; c < 3; ++c) w[3 * k + c] = (double)pts3d[3 * i + c]; px[2 * k] = (double)pts2d[2 * i]; px[2 * k + 1] = (double)pts2d[2 * i + 1]; ++k; }
