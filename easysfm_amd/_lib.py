@@ -51,6 +51,7 @@ EXPORTED_SYMBOLS = [
     "esfm_mesh_simplify_options_default", "esfm_mesh_simplify",
     "esfm_mesh_texture_options_default", "esfm_mesh_texture_views", "esfm_mesh_texture_bake",
     "esfm_mesh_texture_level_options_default", "esfm_mesh_texture_level", "esfm_mesh_texture_bake_ex",
+    "esfm_mesh_render_options_default", "esfm_mesh_render",
 ]
 
 
@@ -140,6 +141,11 @@ class MeshTextureLevelOptions(C.Structure):
 class MeshTextureLevelStats(C.Structure):
     """esfm_mesh_texture_level_stats."""
     _fields_ = [("nodes", C.c_int32), ("seam_vertices", C.c_int32), ("iterations", C.c_int32), ("converged", C.c_int32)]
+
+
+class MeshRenderOptions(C.Structure):
+    """esfm_mesh_render_options (include/esfm.h, "Mesh rendering")."""
+    _fields_ = [("background", C.c_uint8 * 3), ("reserved", C.c_uint8)]
 
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p)
@@ -276,6 +282,10 @@ def lib() -> C.CDLL:
     L.esfm_mesh_texture_level.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp,
                                           C.POINTER(MeshTextureLevelOptions), vp, vp, C.POINTER(MeshTextureLevelStats)]
     L.esfm_mesh_texture_bake_ex.argtypes = L.esfm_mesh_texture_bake.argtypes + [vp]
+    L.esfm_mesh_render_options_default.argtypes = [C.POINTER(MeshRenderOptions)]
+    L.esfm_mesh_render_options_default.restype = None
+    L.esfm_mesh_render.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp,
+                                   C.POINTER(MeshRenderOptions), vp, vp, vp]
     L.esfm_solve_pnp_ransac.argtypes = [vp, vp, vp, C.c_int, vp, C.c_int, C.c_double, C.c_double, vp, vp, vp, vp, i32p, i32p]
     L.esfm_ba_problem_set_params.argtypes = [vp, vp, vp]
     L.esfm_ba_problem_solve.argtypes = [vp, C.POINTER(BAOptions), ALLREDUCE_FN, vp, C.POINTER(BASummary)]

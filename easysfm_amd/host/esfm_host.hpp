@@ -1307,6 +1307,71 @@ public:
         return true;
     }
 
+    // esfm.h "Mesh rendering" with its default options, as run_sfm(dense_mesh_render_dir=...) runs it: the mesh is drawn into every
+    // registered frame (process_frame_id false; in frame order, 64 views per call), with the atlas if uv and atlas are given (textureMesh's),
+    // else with the vertex colours, and each picture is written to dir/render_%04d.png, numbered by frame index; dir must exist.  covered: the pixels
+    // some triangle owns; sum_abs: the sum over them and the three channels of |picture - photograph| (a grey photograph counts as a
+    // grey triple).  Integer arithmetic: the mean sum_abs / (3 covered) prints with the digits of easysfm_amd.mesh_render_error's.
+    bool renderMesh(const TriangleMesh &mesh, const std::vector<frame_t> &frames, const std::vector<bool> &process_frame_id, const std::vector<float> *uv,
+                    int atlas_rows, int atlas_cols, const std::vector<uint8_t> *atlas, const std::string &dir, int &n_views, long long &covered,
+                    long long &sum_abs)
+    {
+        n_views = 0; covered = 0; sum_abs = 0;
+        const int nv = int(mesh.vertices.size()), nt = int(mesh.triangles.size() / 3);
+        std::vector<float> vtx(size_t(3) * mesh.vertices.size());
+        std::vector<uint8_t> col(vtx.size());
+        for (size_t k = 0; k < mesh.vertices.size(); ++k) {
+            const PointXYZRGBNormal &p = mesh.vertices[k];
+            vtx[3 * k] = p.x; vtx[3 * k + 1] = p.y; vtx[3 * k + 2] = p.z;
+            col[3 * k] = p.r; col[3 * k + 1] = p.g; col[3 * k + 2] = p.b;
+        }
+        const bool textured = uv && atlas && !atlas->empty();
+        const float no_uv[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};             // (no triangle: a pointer that is not NULL goes with the atlas)
+        esfm_mesh_render_options opt;
+        esfm_mesh_render_options_default(&opt);
+        std::vector<size_t> registered;
+        for (size_t v = 0; v < frames.size(); ++v) if (!process_frame_id[v]) registered.push_back(v);
+        for (size_t first = 0; first < registered.size(); first += 64) {
+            const int n = int(std::min<size_t>(64, registered.size() - first));
+            const ImageMat &im0 = frames[registered[first]].rgb_image;
+            const int rows = im0.rows, cols = im0.cols;
+            std::vector<float> K4, poses;
+            for (int k = 0; k < n; ++k) {
+                const frame_t &f = frames[registered[first + size_t(k)]];
+                if (f.rgb_image.empty() || f.rgb_image.rows != rows || f.rgb_image.cols != cols) { std::cerr << "mesh render: frames differ in size or have no image" << std::endl; return false; }
+                const float k4[4] = {f.K_cam(0, 0), f.K_cam(0, 2), f.K_cam(1, 1), f.K_cam(1, 2)};
+                K4.insert(K4.end(), k4, k4 + 4);
+                for (int i = 0; i < 3; ++i) for (int j = 0; j < 4; ++j) poses.push_back(f.pose_cam(i, j));
+            }
+            const size_t pixels = size_t(rows) * size_t(cols);
+            std::vector<uint8_t> rgb(size_t(n) * pixels * 3);
+            std::vector<int32_t> id(size_t(n) * pixels);
+            const int rc = esfm_mesh_render(default_ctx(), nv, nt, vtx.data(), mesh.triangles.data(), textured ? nullptr : col.data(),
+                                            textured ? (nt ? uv->data() : no_uv) : nullptr, textured ? atlas_rows : 0, textured ? atlas_cols : 0,
+                                            textured ? atlas->data() : nullptr, n, rows, cols, K4.data(), poses.data(), &opt, rgb.data(), nullptr, id.data());
+            if (rc != ESFM_OK) { std::cerr << esfm_last_error() << std::endl; return false; }
+            for (int k = 0; k < n; ++k) {
+                const size_t frame = registered[first + size_t(k)];
+                const ImageMat &im = frames[frame].rgb_image;
+                const uint8_t *pic = rgb.data() + size_t(k) * pixels * 3;
+                for (size_t p = 0; p < pixels; ++p) {
+                    if (id[size_t(k) * pixels + p] < 0) continue;
+                    ++covered;
+                    for (int c = 0; c < 3; ++c) {
+                        const int photo = im.channels == 3 ? im.data[3 * p + size_t(2 - c)] : im.data[p];      // BGR photographs, RGB pictures
+                        sum_abs += std::abs(int(pic[3 * p + size_t(c)]) - photo);
+                    }
+                }
+                char name[32];
+                std::snprintf(name, sizeof(name), "render_%04d.png", int(frame));
+                const std::string e = png::write_rgb((std::filesystem::path(dir) / name).string(), rows, cols, pic);
+                if (!e.empty()) { std::cerr << e << std::endl; return false; }
+                ++n_views;
+            }
+        }
+        return true;
+    }
+
 private:
     // easysfm_amd.mesh.mesh_arrays behind the fusion: pixel[k] is the pixel of fused point k
     static bool mesh_of(int n, int rows, int cols, int ch, const std::vector<uint8_t> &images, const std::vector<float> &K4,

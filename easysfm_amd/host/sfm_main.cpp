@@ -74,6 +74,19 @@ int dump_image(const char *in, const char *out)
     return f ? 0 : 3;
 }
 
+// the re-render of the written mesh into the registered frames and its "Mesh render:" line (bin/sfm prints the same form)
+bool render_mesh(DenseReconstruction &dr, const TriangleMesh &mesh, const std::vector<frame_t> &frames, const std::vector<bool> &todo,
+                 const std::vector<float> *uv, int atlas_rows, int atlas_cols, const std::vector<uint8_t> *atlas, const std::string &dir)
+{
+    int n_views = 0;
+    long long covered = 0, sum_abs = 0;
+    if (!dr.renderMesh(mesh, frames, todo, uv, atlas_rows, atlas_cols, atlas, dir, n_views, covered, sum_abs)) return false;
+    char mean[64];
+    std::snprintf(mean, sizeof(mean), "%.3f", covered ? double(sum_abs) / (3.0 * double(covered)) : 0.0);
+    std::cout << "Mesh render: [" << n_views << "] views, [" << covered << "] covered pixels, mean absolute error [" << mean << "]" << std::endl;
+    return true;
+}
+
 }  // namespace
 
 int main(int argc, char **argv)
@@ -87,14 +100,19 @@ int main(int argc, char **argv)
     // vertices of every cell of two voxels' side (esfm.h "Mesh simplification"), clean+simplify:mesh.ply does both in that order; with
     // +texture in the prefix (texture:, clean+texture:, simplify+texture:, clean+simplify+texture:) the mesh is then textured from the
     // registered frames (esfm.h "Mesh texturing") and written with texture coordinates, its atlas beside it as mesh.png; +level behind
-    // +texture (e.g. clean+simplify+texture+level:mesh.ply) levels the seams between the frames first, +level without +texture is an error
+    // +texture (e.g. clean+simplify+texture+level:mesh.ply) levels the seams between the frames first, +level without +texture is an error;
+    // optional 18th (needs a mesh as the 17th): an existing directory, or none: the mesh is drawn into every registered frame (esfm.h "Mesh
+    // rendering"; with the atlas if it was textured, else with its vertex colours), the pictures go there as render_%04d.png and one
+    // "Mesh render:" line states their mean absolute error against the photographs
     const std::string filter_arg = argc >= 15 ? argv[14] : "ratio";
     const std::string guided_suffix = "+guided";
     const bool guided = filter_arg.size() > guided_suffix.size() && filter_arg.compare(filter_arg.size() - guided_suffix.size(), guided_suffix.size(), guided_suffix) == 0;
     const std::string match_filter = guided ? filter_arg.substr(0, filter_arg.size() - guided_suffix.size()) : filter_arg;      // the first pass's filter
     const std::string dense_file = argc >= 16 && std::string(argv[15]) != "none" ? argv[15] : "";
     const std::string merged_file = argc >= 17 && std::string(argv[16]) != "none" ? argv[16] : "";
-    const std::string mesh_arg = argc == 18 && std::string(argv[17]) != "none" ? argv[17] : "";
+    const std::string mesh_arg = argc >= 18 && std::string(argv[17]) != "none" ? argv[17] : "";
+    const std::string render_dir = argc == 19 && std::string(argv[18]) != "none" ? argv[18] : "";
+    const bool render_alone = !render_dir.empty() && (mesh_arg.empty() || !std::filesystem::is_directory(render_dir));
     bool clean_mesh = false, simplify_mesh = false, texture_mesh = false, level_mesh = false, level_alone = mesh_arg.compare(0, 6, "level:") == 0;
     std::string mesh_file = mesh_arg;
     {
@@ -118,13 +136,14 @@ int main(int argc, char **argv)
             }
         }
     }
-    if (argc < 14 || argc > 18 || (match_filter != "ratio" && match_filter != "cross" && match_filter != "ratio+cross") || level_alone) {
+    if (argc < 14 || argc > 19 || (match_filter != "ratio" && match_filter != "cross" && match_filter != "ratio+cross") || level_alone || render_alone) {
         std::cerr << "usage: sfm_native image_folder image_list calib_K_file calib_distort_file output.ply feature_type(S | O | I) feature_parameter "
                      "repro_dis_ransac find_init_frames ba_calib_change_tolerance ba_frequency launch_viewer view_sphere [match_filter: ratio | cross | ratio+cross | "
                      "ratio+guided | cross+guided | ratio+cross+guided [dense.ply | none [merged.ply | none [simplify:mesh.ply | "
-                     "clean+simplify:mesh.ply | mesh.ply | clean:mesh.ply | none]]]] (the 17th's prefix also takes +texture: texture:, clean+texture:, "
+                     "clean+simplify:mesh.ply | mesh.ply | clean:mesh.ply | none [render_dir | none]]]]] (the 17th's prefix also takes +texture: texture:, clean+texture:, "
                      "simplify+texture:, clean+simplify+texture:) (and +level behind +texture: texture+level:, clean+texture+level:, simplify+texture+level:, "
-                     "clean+simplify+texture+level:)"
+                     "clean+simplify+texture+level:) (render_dir, the 18th: an existing directory for render_%04d.png, one re-render of the mesh per "
+                     "registered frame; it needs a mesh)"
                   << std::endl;
         return 2;
     }
@@ -472,7 +491,11 @@ int main(int argc, char **argv)
                     std::cout << "Mesh texture: [" << mesh.triangles.size() / 3 << "] triangles, [" << n_labelled << "] labelled from [" << n_views
                               << "] views, charts of [" << texels << "] texels, atlas [" << atlas_cols << "] x [" << atlas_rows << "]." << std::endl;
                     if (!io.writePlyTexturedMesh(mesh_file, mesh, uv, atlas_rows, atlas_cols, atlas)) return 3;
-                } else if (!io.writePlyMesh(mesh_file, mesh)) return 3;
+                    if (!render_dir.empty() && !render_mesh(dr, mesh, frames, todo, &uv, atlas_rows, atlas_cols, &atlas, render_dir)) return 3;
+                } else {
+                    if (!io.writePlyMesh(mesh_file, mesh)) return 3;
+                    if (!render_dir.empty() && !render_mesh(dr, mesh, frames, todo, nullptr, 0, 0, nullptr, render_dir)) return 3;
+                }
             }
         }
     } catch (const std::exception &e) {       // 1 is the reference's SUCCESS status: a failure must not look like one

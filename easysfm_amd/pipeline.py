@@ -9,17 +9,19 @@ the track bookkeeping that does depend on it runs in the reference's order."""
 from __future__ import annotations
 
 from dataclasses import dataclass, field
+import os
 from typing import List, Optional, Sequence
 
 import numpy as np
 
 from ._lib import Context, ESFM_HAMMING, ESFM_L2_F32, default_context
 from .ba import BundleAdjustment
-from .cloud import CProceesing, write_ply, write_ply_mesh, write_ply_normals, write_ply_textured_mesh
+from .cloud import CProceesing, write_ply, write_ply_mesh, write_ply_normals, write_ply_textured_mesh, write_png_rgb
 from .matching import DescriptorBank, FeatureMatching, PairMatcher
 from .motion import MotionEstimator, _dehomogenise, find_essential_pairs, pixel2cam, recover_pose_pairs, triangulate_pairs
 from .mesh import (MeshCleanOptions, MeshOptions, auto_texels, default_atlas_width, mesh_arrays, mesh_clean, mesh_components, mesh_simplify,
                    mesh_texture_bake, mesh_texture_level, mesh_texture_views)
+from .render import mesh_render, mesh_render_error
 from .mvs import MergeOptions, default_mvs_options, dense_reconstruction, frame_arrays, merge_arrays
 from .types import DMatch, Frame, SparsePointCloud
 
@@ -164,7 +166,7 @@ def run_sfm(frames: List[Frame], output_file: Optional[str] = None, use_feature:
             ctx: Optional[Context] = None, verbose: bool = False, match_filter: str = "ratio", dense_output_file: Optional[str] = None,
             dense_merged_output_file: Optional[str] = None, dense_mesh_output_file: Optional[str] = None,
             dense_mesh_clean: Optional[MeshCleanOptions] = None, dense_mesh_simplify: Optional[float] = None,
-            dense_mesh_texture: Optional[int] = None, dense_mesh_texture_level: bool = False):
+            dense_mesh_texture: Optional[int] = None, dense_mesh_texture_level: bool = False, dense_mesh_render_dir: Optional[str] = None):
     """sfm.cpp:128-339.  Returns (sparse cloud before the final filter, filtered cloud, img_match_graph).
     dense_output_file: after the final BA and the sparse .ply, run dense_reconstruct on the registered frames and the cloud
     before the filter (it carries the track ids) and write the dense cloud there (esfm.h "Dense reconstruction").
@@ -184,7 +186,11 @@ def run_sfm(frames: List[Frame], output_file: Optional[str] = None, use_feature:
     frame order) and a texture atlas is baked from them (esfm.h "Mesh texturing", default options, a square atlas); the mesh is
     written with texture coordinates and the atlas beside it as a .png; prints one "Mesh texture:" line.  None: vertex colours only.
     dense_mesh_texture_level: with dense_mesh_texture, level the seams between triangles that chose different frames before the bake
-    (esfm.h "Mesh texturing", esfm_mesh_texture_level, default options); prints one "Mesh texture level:" line."""
+    (esfm.h "Mesh texturing", esfm_mesh_texture_level, default options); prints one "Mesh texture level:" line.
+    dense_mesh_render_dir: with dense_mesh_output_file, an existing directory (it is not created here, nor by the drivers): after the mesh is written it is drawn into every registered frame,
+    in frame order (esfm.h "Mesh rendering", default options; with the atlas if the mesh was textured, else with its vertex colours);
+    the pictures go there as render_%04d.png, numbered by frame index, and one "Mesh render:" line states the number of views, the
+    pixels the mesh covers in them and the mean absolute difference to the photographs over those pixels and three channels."""
     ctx = ctx or default_context()
     fm, ee = FeatureMatching(ctx), MotionEstimator(ctx)
     for f in frames:
@@ -284,5 +290,19 @@ def run_sfm(frames: List[Frame], output_file: Optional[str] = None, use_feature:
                       f"[{texels}] texels, atlas [{atlas.shape[1]}] x [{atlas.shape[0]}].")
                 write_ply_textured_mesh(dense_mesh_output_file, vertices, normals, triangles, uv, atlas)
             else:
+                uv = atlas = None
                 write_ply_mesh(dense_mesh_output_file, vertices, normals, rgb, triangles)
+            if dense_mesh_render_dir:
+                registered = np.nonzero(~np.asarray(todo, bool))[0]
+                total = covered = 0
+                for first in range(0, len(registered), 64):              # esfm_mesh_render takes 64 views per call
+                    sel = registered[first:first + 64]
+                    pictures, _, ids = mesh_render(vertices, triangles, K4[sel], poses[sel], imgs.shape[1], imgs.shape[2], None if uv is not None else rgb,
+                                                   uv, atlas, None, ctx, outputs=("rgb", "triangle_id"))
+                    err, cov = mesh_render_error(pictures, ids, imgs[sel])
+                    total += int(err.sum()); covered += int(cov.sum())
+                    for frame, picture in zip(sel, pictures):
+                        write_png_rgb(os.path.join(dense_mesh_render_dir, "render_%04d.png" % int(frame)), picture)
+                mean = float(total) / (3.0 * float(covered)) if covered else 0.0
+                print(f"Mesh render: [{len(registered)}] views, [{covered}] covered pixels, mean absolute error [{mean:.3f}]")
     return cloud, out, graph

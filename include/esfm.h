@@ -1196,6 +1196,61 @@ int esfm_mesh_texture_bake_ex(esfm_ctx *ctx, int n_vertices, int n_triangles, co
                               int max_atlas_rows, uint8_t *atlas /*max_atlas_rows x W x 3*/, float *uv /*T x 3 x 2*/,
                               int32_t *atlas_rows, const float *offsets /*T x 3 x 3, may be NULL*/);
 
+/* ---- Mesh rendering: watertight rasteriser, depth, triangle identity, colour ---------------------------------
+ * An indexed triangle mesh is drawn into n views: per pixel the triangle that owns it, its depth and its colour from the texture
+ * atlas, from vertex colours or plain grey.  The conventions are those of "Mesh texturing": poses, K4, pixel centres at integers,
+ * the projection and its `in front` test with the 2^20 bound, f32 with no mul + add contraction, correctly rounded division.  The
+ * only combination across threads is an integer maximum, so images, depths and identities do not depend on scheduling;
+ * tests/render_ref.py restates this text in numpy and the GPU reproduces it bit for bit.
+ *
+ * Input: V vertices and T triangles with the texturing section's ranges and checks; optional vertex_rgb [V, 3] u8; optional
+ * uv [T, 3, 2] f32 (finite; mesh_texture_bake's) together with atlas [H, W, 3] u8 RGB, H and W 2..16384 -- uv and atlas are both
+ * given or both NULL; n_views 1..64 of rows x cols pixels, both 2..16384, with K4 and poses.
+ *
+ * Screen vertex of a world point in view v: u, w, p2 by the texturing section's projection; sx = (int32)rintf(u * 256.0f),
+ * sy = (int32)rintf(w * 256.0f) (1/256-pixel fixed point, ties to even), z = 1.0f / p2.  A triangle takes part in a view only if
+ * all three vertices are in front (the texturing section's skip rule; there is no clipping).
+ *
+ * Coverage, all of it int64 and exact.  With vertices k = 0, 1, 2 in the triangle's own order,
+ *   area2 = (sx1 - sx0) (sy2 - sy0) - (sy1 - sy0) (sx2 - sx0);  area2 == 0: the triangle is skipped;  s = the sign of area2 (both
+ *   windings are drawn).  For edge k, from vertex k to k' = (k + 1) mod 3: dx = sx_k' - sx_k, dy = sy_k' - sy_k, and at pixel
+ *   (px, py)  e_k = dx (256 py - sy_k) - dy (256 px - sx_k).
+ *   The pixel is covered if for all three edges  s e_k > 0,  or  s e_k == 0 and the edge owns its boundary:  s dy > 0, or s dy == 0
+ *   and s dx < 0.  An edge and its reverse never both own and never both disown, so two triangles that share an edge cover each
+ *   pixel on it exactly once: no cracks, no double hits.  Candidate pixels are the integer pixels inside the fixed-point bounding
+ *   box, ceil(min / 256) .. floor(max / 256) by floor division, clipped to the image.
+ *
+ * Depth and identity.  b0 = (float)e_1 / (float)area2, b1 = (float)e_2 / (float)area2, b2 = (float)e_0 / (float)area2 (each int64
+ * rounded to f32 once, to nearest even; the signs cancel: the barycentrics of vertices 0, 1, 2);  q_k = b_k z_k;
+ * iz = (q0 + q1) + q2.  The pixel's key is (uint64)bits(iz) << 32 | (0xFFFFFFFF - t), skipped if bits(iz) == 0; the buffer keeps
+ * the largest key: the nearest surface wins, on equal depth the lowest triangle index.  Key 0 is background.
+ *
+ * Shading, one pass per pixel from the winning key, with the same b_k, q_k and iz recomputed:  triangle_id = t (-1 background),
+ * depth = 1.0f / iz (0 background).  An attribute a is perspective-correct:  ((q0 a0 + q1 a1) + q2 a2) / iz.
+ *   With uv: (uu, vv) from the triangle's three corner uvs;  a = uu * (float)W - 0.5f,  c = vv * (float)H - 0.5f;  the bake's
+ *   bilinear rule on the atlas as a one-view, three-channel image at (a, c) -- the same clamps, x0, y0, ax, ay and operation order,
+ *   channel by channel (the atlas is RGB already) --, the output (uint8)floorf(c + 0.5f).
+ *   Without uv but with vertex_rgb: the three vertex colours as f32 per channel, fminf(fmaxf(c, 0.0f), 255.0f), rounded the same way.
+ *   With neither: (128, 128, 128).  Background pixels get options.background (three u8, default 0, 0, 0).
+ *
+ * Outputs: rgb [n_views, rows, cols, 3] u8 RGB, depth [n_views, rows, cols] f32, triangle_id [n_views, rows, cols] int32; each may
+ * be NULL, not all three.
+ * Rejected with ESFM_ERR_INVALID_ARG, before the device is looked at and with nothing written: what the texturing section rejects
+ * of a mesh and of cameras, uv without atlas or atlas without uv, an atlas side outside 2..16384, a texture coordinate that is not
+ * finite, options that are NULL, all three outputs NULL.  Host pointers; without a usable device ESFM_ERR_NO_DEVICE (no CPU
+ * fallback). */
+typedef struct esfm_mesh_render_options {
+    uint8_t background[3];
+    uint8_t reserved;
+} esfm_mesh_render_options;
+void esfm_mesh_render_options_default(esfm_mesh_render_options *opt);
+int esfm_mesh_render(esfm_ctx *ctx, int n_vertices, int n_triangles, const float *vertices /*3 each*/,
+                     const int32_t *triangles /*3 each*/, const uint8_t *vertex_rgb /*3 each, may be NULL*/,
+                     const float *uv /*T x 3 x 2, NULL with atlas*/, int atlas_rows, int atlas_cols,
+                     const uint8_t *atlas /*atlas_rows x atlas_cols x 3, NULL with uv*/, int n_views, int rows, int cols,
+                     const float *K4 /*4 each*/, const float *poses /*12 each*/, const esfm_mesh_render_options *opt,
+                     uint8_t *rgb /*may be NULL*/, float *depth /*may be NULL*/, int32_t *triangle_id /*may be NULL*/);
+
 #ifdef __cplusplus
 }
 #endif
