@@ -15,7 +15,8 @@ from .ba import (BAProblem, BundleAdjustment, Comm, ba_solve, ba_solve_ex, ba_sw
 
 from .cloud import (CProceesing, read_ply_mesh, read_ply_normals, read_ply_textured_mesh, read_ply_vertices, sor_filter,  # noqa: F401
                     voxel_merge, write_ply, write_ply_mesh, write_ply_normals, write_ply_textured_mesh, write_png_rgb)
-from .motion import (MotionEstimator, find_essential_mat, find_essential_pairs, five_point_models, pixel2cam, ransac_sample_stream, recover_pose,  # noqa: F401
+from .motion import (MotionEstimator, find_essential_mat, find_essential_pairs, find_homography, find_homography_pairs, five_point_models,
+                     homography_models, homography_refit_host, homography_sample_stream, pixel2cam, ransac_sample_stream, recover_pose,  # noqa: F401
                      recover_pose_pairs, solve_pnp_ransac, triangulate_pairs, triangulate_points)
 
 from .features import (detectFeaturesORB, detectFeaturesSIFT, detectFeaturesSURF, import_distort, orb_detect_and_compute,  # noqa: F401

@@ -15,6 +15,9 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ESFM_LIB") or os.path.join(_HERE, "libesfm_hip.so")
 
 ESFM_OK = 0
+ESFM_ERR_INVALID_ARG = -1
+ESFM_ERR_UNSUPPORTED = -5
+ESFM_ERR_NUMERIC = -6
 ESFM_L2_F32 = 0
 ESFM_HAMMING = 1
 ESFM_REDUCE_SUM = 0
@@ -43,6 +46,8 @@ EXPORTED_SYMBOLS = [
     "esfm_ba_problem_fix_camera", "esfm_ba_solve_ex", "esfm_ba_line_search_next_step",
     "esfm_sor_filter", "esfm_sor_mean_distances_dev", "esfm_triangulate_points", "esfm_triangulate_pairs",
     "esfm_find_essential_mat", "esfm_find_essential_pairs", "esfm_recover_pose", "esfm_recover_pose_pairs", "esfm_ransac_sample_stream", "esfm_five_point_models", "esfm_five_point_models_host",
+    "esfm_find_homography", "esfm_find_homography_pairs", "esfm_homography_models", "esfm_homography_models_host", "esfm_homography_refit_host",
+    "esfm_homography_sample_stream",
     "esfm_solve_pnp_ransac", "esfm_surf_detect_and_compute", "esfm_orb_detect_and_compute", "esfm_sift_detect_and_compute", "esfm_undistort",
     "esfm_mvs_options_default", "esfm_mvs_plan", "esfm_mvs_depth_maps", "esfm_mvs_fuse",
     "esfm_mvs_normal_options_default", "esfm_mvs_normals", "esfm_mvs_fuse_ex", "esfm_cloud_voxel_merge",
@@ -244,6 +249,12 @@ def lib() -> C.CDLL:
     L.esfm_ransac_sample_stream.argtypes = [C.c_int, C.c_int, vp]
     L.esfm_five_point_models.argtypes = [vp, vp, vp, C.c_int, vp, vp, vp]
     L.esfm_five_point_models_host.argtypes = [vp, vp, C.c_int, vp, vp, vp]
+    L.esfm_find_homography.argtypes = [vp, vp, vp, C.c_int, C.c_double, C.c_double, vp, vp, i32p]
+    L.esfm_find_homography_pairs.argtypes = [vp, C.c_int, vp, vp, vp, C.c_double, C.c_double, vp, vp, vp, vp, vp]
+    L.esfm_homography_models.argtypes = [vp, vp, vp, C.c_int, vp, vp]
+    L.esfm_homography_models_host.argtypes = [vp, vp, C.c_int, vp, vp]
+    L.esfm_homography_refit_host.argtypes = [vp, vp, C.c_int, vp, vp]
+    L.esfm_homography_sample_stream.argtypes = [vp, vp, C.c_int, C.c_int, vp, i64p]
     L.esfm_surf_detect_and_compute.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, vp, vp, i32p]
     L.esfm_orb_detect_and_compute.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, i32p]
     L.esfm_sift_detect_and_compute.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, i32p]

@@ -247,11 +247,18 @@ public:
     // depth / baseline ratio exceeds the limit are out; the best score of at least min_track_num_init wins, the LATER pair on ties.
     // appro_depth[i][j] = img_match_graph[i][j].appro_depth.  Written over per-frame track lists: a frame's weights are laid out once
     // and every earlier frame sums over its own list -- O(frames x observations) where the reference walks frames^2 x tracks.
+    // max_h_inlier_ratio (not in the reference; < 0: off): with h_inlier_ratio[i][j] = the pair's homography inliers / essential-matrix
+    // inliers (esfm.h "Homography RANSAC"), a pair that passed the depth guard and exceeds the limit is skipped at the same place -- it
+    // is planar or rotation-only; *h_candidate_pairs / *h_skipped_pairs (or NULL) then receive the pairs that reached this test and those
+    // it skipped.
     bool findInitializeFramePair(std::vector<std::vector<bool>> &feature_track_matrix, std::vector<frame_t> &frames,
                                  const std::vector<std::vector<double>> &appro_depth, int &initialization_frame_1,
                                  int &initialization_frame_2, double &depth_init, int min_track_num_init = 100,
-                                 double max_depth_baseline_ratio_init = 50.0)
+                                 double max_depth_baseline_ratio_init = 50.0, double max_h_inlier_ratio = -1.0,
+                                 const std::vector<std::vector<double>> *h_inlier_ratio = nullptr, int *h_candidate_pairs = nullptr,
+                                 int *h_skipped_pairs = nullptr)
     {
+        int candidates = 0, skipped = 0;
         const size_t n_frames = frames.size(), n_tracks = feature_track_matrix.empty() ? 0 : feature_track_matrix[0].size();
         std::vector<int> weight(n_tracks, 0);
         std::vector<std::vector<int>> seen(n_frames);            // track ids per frame
@@ -269,12 +276,18 @@ public:
             for (size_t j = 0; j < i; ++j) {
                 const double ratio = appro_depth[i][j];
                 if (ratio > max_depth_baseline_ratio_init) continue;
+                if (max_h_inlier_ratio >= 0.0 && h_inlier_ratio) {
+                    ++candidates;
+                    if ((*h_inlier_ratio)[i][j] > max_h_inlier_ratio) { ++skipped; continue; }
+                }
                 long long score = 0;
                 for (int t : seen[j]) score += laid[size_t(t)];
                 if (score >= best) { best = score; best_ratio = ratio; first = int(i); second = int(j); }
             }
             for (int t : seen[i]) laid[size_t(t)] = 0;
         }
+        if (h_candidate_pairs) *h_candidate_pairs = candidates;
+        if (h_skipped_pairs) *h_skipped_pairs = skipped;
         if (first == second) {
             if (!quiet) std::cout << "Failed to find proper frame pair for initialization. Use default frame [1] and frame [0]" << std::endl;
             initialization_frame_1 = 1; initialization_frame_2 = 0;
@@ -682,6 +695,57 @@ public:
         T = Matrix4f::Identity();
         for (int r = 0; r < 3; ++r) { for (int c = 0; c < 3; ++c) T(r, c) = float(R[3 * r + c]); T(r, 3) = float(t[r]); }   // :76-85
         if (!quiet) std::cout << "Find [" << inlier_matches.size() << "] inlier matches from [" << matches.size() << "] total matches." << std::endl;
+        return true;
+    }
+
+    // The homography counterpart (not in the reference; esfm.h "Homography RANSAC"): 4-point RANSAC on the matched pixels, the matches
+    // of the RANSAC mask appended to inlier_matches, H (9 doubles, row-major, frame 1's pixels to frame 2's; or NULL).  *n_inliers (or
+    // NULL) = esfm_find_homography_pairs' count: the matches within the threshold of the RETURNED, re-fitted H -- the numerator of
+    // h_inlier_ratio, which is not the number of matches appended.  false: fewer than 4 matches or no model (*n_inliers = 0).
+    bool estimate2D2D_H4P_RANSAC(frame_t &cur_frame_1, frame_t &cur_frame_2, std::vector<DMatch> &matches, std::vector<DMatch> &inlier_matches,
+                                 double *H, double ransac_thre = 1.0, double ransac_prob = 0.995, int *n_inliers = nullptr)
+    {
+        std::vector<float> p1, p2;
+        gather(cur_frame_1, cur_frame_2, matches, 1, p1, p2);
+        const int n = int(matches.size());
+        if (p1.empty()) { p1.assign(2, 0.f); p2.assign(2, 0.f); }
+        std::vector<uint8_t> mask(size_t(std::max(n, 1)));
+        const int32_t off[2] = {0, n};
+        int32_t status = 0, count = 0;
+        double Hm[9];
+        if (n_inliers) *n_inliers = 0;
+        const int rc = esfm_find_homography_pairs(default_ctx(), 1, off, p1.data(), p2.data(), ransac_thre, ransac_prob, Hm, mask.data(), &status, nullptr, &count);
+        if (rc != ESFM_OK) { std::cerr << esfm_last_error() << std::endl; return false; }
+        if (!status) return false;
+        if (H) std::copy(Hm, Hm + 9, H);
+        if (n_inliers) *n_inliers = int(count);
+        for (int i = 0; i < n; ++i) if (mask[size_t(i)]) inlier_matches.push_back(matches[size_t(i)]);
+        return true;
+    }
+
+    // ... for MANY pairs in shared launches (esfm_find_homography_pairs): n_inliers[p] = job p's matches within the threshold of its
+    // returned, re-fitted H (what the per-pair member puts in *n_inliers), 0 without a model
+    bool estimate2D2D_H4P_RANSAC_pairs(std::vector<frame_t> &frames, const std::vector<std::pair<int, int>> &jobs, const std::vector<std::vector<DMatch>> &matches,
+                                       std::vector<int> &n_inliers, double ransac_thre = 1.0, double ransac_prob = 0.995)
+    {
+        const size_t nj = jobs.size();
+        n_inliers.assign(nj, 0);
+        if (nj == 0) return true;
+        std::vector<int32_t> off(nj + 1, 0);
+        for (size_t p = 0; p < nj; ++p) off[p + 1] = off[p] + int32_t(matches[p].size());
+        std::vector<float> p1(size_t(2) * size_t(std::max(off[nj], 1))), p2(p1.size());
+        for (size_t p = 0; p < nj; ++p) {
+            std::vector<float> a, b;
+            gather(frames[size_t(jobs[p].first)], frames[size_t(jobs[p].second)], matches[p], 1, a, b);
+            std::copy(a.begin(), a.end(), p1.begin() + 2 * off[p]); std::copy(b.begin(), b.end(), p2.begin() + 2 * off[p]);
+        }
+        std::vector<double> H(9 * nj);
+        std::vector<uint8_t> mask(size_t(std::max(off[nj], 1)));
+        std::vector<int32_t> status(nj, 0), count(nj, 0);
+        const int rc = esfm_find_homography_pairs(default_ctx(), int(nj), off.data(), p1.data(), p2.data(), ransac_thre, ransac_prob, H.data(), mask.data(),
+                                                  status.data(), nullptr, count.data());
+        if (rc != ESFM_OK) { std::cerr << esfm_last_error() << std::endl; return false; }
+        for (size_t p = 0; p < nj; ++p) n_inliers[p] = status[p] ? int(count[p]) : 0;
         return true;
     }
 

@@ -34,6 +34,9 @@ struct frame_pair_t {  // utility.h:57-78
     std::vector<DMatch> matches;
     Matrix4f T_21 = Matrix4f::Identity();
     double appro_depth = 1.0;
+    int h_inliers = 0;              // correspondences within the threshold of the returned, re-fitted homography (esfm_find_homography_pairs'
+                                    // n_inliers, not the RANSAC mask's count); find_init_frames = 2 only
+    double h_inlier_ratio = 0.0;    // ... divided by the essential matrix's RANSAC mask count
 };
 
 Matrix4f mul(const Matrix4f &a, const Matrix4f &b)
@@ -138,7 +141,7 @@ int main(int argc, char **argv)
     }
     if (argc < 14 || argc > 19 || (match_filter != "ratio" && match_filter != "cross" && match_filter != "ratio+cross") || level_alone || render_alone) {
         std::cerr << "usage: sfm_native image_folder image_list calib_K_file calib_distort_file output.ply feature_type(S | O | I) feature_parameter "
-                     "repro_dis_ransac find_init_frames ba_calib_change_tolerance ba_frequency launch_viewer view_sphere [match_filter: ratio | cross | ratio+cross | "
+                     "repro_dis_ransac find_init_frames(0 | 1 | 2: as 1, and no planar or rotation-only initial pair) ba_calib_change_tolerance ba_frequency launch_viewer view_sphere [match_filter: ratio | cross | ratio+cross | "
                      "ratio+guided | cross+guided | ratio+cross+guided [dense.ply | none [merged.ply | none [simplify:mesh.ply | "
                      "clean+simplify:mesh.ply | mesh.ply | clean:mesh.ply | none [render_dir | none]]]]] (the 17th's prefix also takes +texture: texture:, clean+texture:, "
                      "simplify+texture:, clean+simplify+texture:) (and +level behind +texture: texture+level:, clean+texture+level:, simplify+texture+level:, "
@@ -154,6 +157,8 @@ int main(int argc, char **argv)
     const int feature_extract_parameter = std::atoi(argv[7]);
     const double ransac_reproj_distance = std::atof(argv[8]);
     const bool use_track_frames_as_init = std::atoi(argv[9]) != 0;
+    const bool init_h_check = std::atoi(argv[9]) == 2;              // 2: the initial pair must not be planar or rotation-only
+    const double init_max_h_inlier_ratio = 0.8;
     const double fix_calib_tolerance_BA = std::atof(argv[10]);
     const int frequency_BA = std::max(1, std::atoi(argv[11]));
     if (using_feature != 'S' && using_feature != 'O' && using_feature != 'I') { std::cout << "Wrong feature input. Use SURF as default feature." << std::endl; using_feature = 'S'; }
@@ -261,6 +266,12 @@ int main(int argc, char **argv)
                         double E[9];
                         if (ee.estimate2D2D_E5P_RANSAC(frames[size_t(i)], frames[size_t(j)], temp_matches, inlier_matches, T, ransac_reproj_distance, 0.99, false, E)) {
                             g.T_21 = T;
+                            if (init_h_check) {  // the same correspondences under the homography model
+                                std::vector<DMatch> h_matches;
+                                int h_count = 0;
+                                if (ee.estimate2D2D_H4P_RANSAC(frames[size_t(i)], frames[size_t(j)], temp_matches, h_matches, nullptr, ransac_reproj_distance, 0.995, &h_count)) g.h_inliers = h_count;
+                                g.h_inlier_ratio = inlier_matches.empty() ? 0.0 : double(g.h_inliers) / double(inlier_matches.size());
+                            }
                             double depth = 1.0;
                             if (ee.getDepthFast(frames[size_t(i)], frames[size_t(j)], T, inlier_matches, depth)) g.appro_depth = depth;
                             if (guided) {        // second pass along the epipolar lines, same filter; T_21 and the depth stay the first pass's
@@ -309,6 +320,16 @@ int main(int argc, char **argv)
                     Ts[p] = T;
                     if (ee.getDepthFast(fi, fj, T, inliers[p], depth)) depths[p] = depth;
                     ok[p] = 1;
+                }
+            }
+            if (init_h_check) {  // ONE homography batch over the same correspondences; the ratio is taken against the essential matrix's RANSAC inliers
+                std::vector<int> h_inliers;
+                if (!ee.estimate2D2D_H4P_RANSAC_pairs(frames, jobs, job_matches, h_inliers, ransac_reproj_distance)) return 3;
+                for (size_t p = 0; p < jobs.size(); ++p) {
+                    if (!ok[p]) continue;
+                    frame_pair_t &g = graph[size_t(jobs[p].first)][size_t(jobs[p].second)];
+                    g.h_inliers = h_inliers[p];
+                    g.h_inlier_ratio = inliers[p].empty() ? 0.0 : double(h_inliers[p]) / double(inliers[p].size());
                 }
             }
             if (guided) {       // ONE guided call for every pair with a model, the first pass's filter; each keeps the union
@@ -375,7 +396,14 @@ int main(int argc, char **argv)
         if (use_track_frames_as_init) {
             std::vector<std::vector<double>> depth(nf, std::vector<double>(nf, 0.0));
             for (int i = 0; i < frame_number; ++i) for (int j = 0; j < i; ++j) depth[size_t(i)][size_t(j)] = graph[size_t(i)][size_t(j)].appro_depth;
-            fm.findInitializeFramePair(track, frames, depth, init_1, init_2, depth_init);
+            if (init_h_check) {
+                std::vector<std::vector<double>> h_ratio(nf, std::vector<double>(nf, 0.0));
+                for (int i = 0; i < frame_number; ++i) for (int j = 0; j < i; ++j) h_ratio[size_t(i)][size_t(j)] = graph[size_t(i)][size_t(j)].h_inlier_ratio;
+                int h_candidates = 0, h_skipped = 0;
+                fm.findInitializeFramePair(track, frames, depth, init_1, init_2, depth_init, 100, 50.0, init_max_h_inlier_ratio, &h_ratio, &h_candidates, &h_skipped);
+                std::cout << "Init pair: skipped " << h_skipped << " of " << h_candidates << " candidate pairs as planar or panoramic" << std::endl;
+            } else
+                fm.findInitializeFramePair(track, frames, depth, init_1, init_2, depth_init);
         }
         std::cout << "Initialization frames: [ " << init_1 << " ] and [ " << init_2 << " ]" << std::endl;
         pointcloud_sparse_t cloud;

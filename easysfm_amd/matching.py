@@ -236,12 +236,17 @@ class FeatureMatching:
 
     # ---- frame selection (feature_matching.cpp:160-268): integer logic on the track matrix, host side ----
     def findInitializeFramePair(self, feature_track_matrix, frames, img_match_graph, min_track_num_init: int = 100,
-                                max_depth_baseline_ratio_init: float = 50.0):
+                                max_depth_baseline_ratio_init: float = 50.0, max_h_inlier_ratio: Optional[float] = None,
+                                h_stats: Optional[dict] = None):
         """feature_matching.cpp:160-229 (defaults feature_matching.h:26).  feature_track_matrix: [n_frames, n_unique] bool (frame sees track);
         img_match_graph[i][j].appro_depth (or a 2-D array of depths): depth / baseline of pair (i, j < i).
         Returns (found, initialization_frame_1, initialization_frame_2, depth_init).  The pair maximising the sum, over
         the tracks both frames see, of the number of frames that see the track; ties go to the LATER pair in (i, j < i)
-        order (`>=` at :203); pairs whose depth / baseline exceeds the limit are skipped (:193-194)."""
+        order (`>=` at :203); pairs whose depth / baseline exceeds the limit are skipped (:193-194).
+        max_h_inlier_ratio (not in the reference): when given, a pair that passed the depth guard and whose
+        img_match_graph[i][j].h_inlier_ratio exceeds it is skipped at the same place -- a homography explains it nearly as well as
+        the essential matrix, so it is planar or rotation-only (esfm.h "Homography RANSAC"); an entry without the field counts as 0.
+        h_stats (a dict, or None) then receives "candidates", the pairs that reached this test, and "skipped", those it skipped."""
         T = np.asarray(feature_track_matrix, bool)
         n_frames = len(frames)
         T = T[:n_frames]
@@ -253,13 +258,21 @@ class FeatureMatching:
             return float(getattr(e, "appro_depth", e))
 
         best, f1, f2, d_init = int(min_track_num_init), 0, 0, None
+        candidates = skipped = 0
         for i in range(n_frames):
             for j in range(i):
                 d = depth(i, j)
                 if d > max_depth_baseline_ratio_init:
                     continue
+                if max_h_inlier_ratio is not None:
+                    candidates += 1
+                    if float(getattr(img_match_graph[i][j], "h_inlier_ratio", 0.0)) > max_h_inlier_ratio:
+                        skipped += 1
+                        continue
                 if score[i, j] >= best:
                     best, f1, f2, d_init = int(score[i, j]), i, j, d
+        if h_stats is not None:
+            h_stats["candidates"], h_stats["skipped"] = candidates, skipped
         if f1 == f2:
             print("Failed to find proper frame pair for initialization. Use default frame [1] and frame [0]")
             return False, 1, 0, None                                # depth_init is left unset by the reference (:217-223)

@@ -164,6 +164,85 @@ def five_point_models(q1, q2, ctx: Optional[Context] = None, host: bool = False,
     return (Es[:n], nm[:n], st[:n]) if stages else (Es[:n], nm[:n])
 
 
+def find_homography(pts1, pts2, threshold: float = 3.0, confidence: float = 0.995, ctx: Optional[Context] = None):
+    """esfm_find_homography: cv::findHomography(pts1, pts2, RANSAC, threshold, mask, 2000, confidence) without the final
+    Levenberg-Marquardt polish (esfm.h "Homography RANSAC") -> (H [3,3] float64 with H[2,2] = 1, mask [n] bool, iterations).
+    Raises EsfmError for n < 4 (ESFM_ERR_UNSUPPORTED) and when there is no model (ESFM_ERR_NUMERIC)."""
+    ctx = ctx or default_context()
+    a = np.ascontiguousarray(pts1, np.float32).reshape(-1, 2); b = np.ascontiguousarray(pts2, np.float32).reshape(-1, 2)
+    if a.shape != b.shape:
+        raise ValueError("point sets differ in size")
+    n = a.shape[0]
+    H = np.zeros(9, np.float64); mask = np.zeros(max(n, 1), np.uint8); it = C.c_int32(0)
+    check(lib().esfm_find_homography(ctx.handle, C.c_void_p(a.ctypes.data), C.c_void_p(b.ctypes.data), n, float(threshold), float(confidence),
+                                     C.c_void_p(H.ctypes.data), C.c_void_p(mask.ctypes.data), C.byref(it)))
+    return H.reshape(3, 3), mask[:n].astype(bool), it.value
+
+
+def find_homography_pairs(point_offset, pts1, pts2, threshold: float = 3.0, confidence: float = 0.995, ctx: Optional[Context] = None):
+    """esfm_find_homography_pairs: every pair's homography RANSAC in shared launches -> (H [p,3,3], mask [n_total] bool,
+    status [p] bool, iterations [p], n_inliers [p])."""
+    ctx = ctx or default_context()
+    off = np.ascontiguousarray(point_offset, np.int32)
+    n_pairs = len(off) - 1
+    a = np.ascontiguousarray(pts1, np.float32).reshape(-1, 2); b = np.ascontiguousarray(pts2, np.float32).reshape(-1, 2)
+    if a.shape != b.shape:
+        raise ValueError("point sets differ in size")
+    n = a.shape[0]
+    if n_pairs > 0 and int(off[-1]) != n:
+        raise ValueError("point_offset does not end at the number of points")
+    a = a if n else np.zeros((1, 2), np.float32); b = b if n else np.zeros((1, 2), np.float32)
+    H = np.zeros((max(n_pairs, 1), 9), np.float64); mask = np.zeros(max(n, 1), np.uint8)
+    status = np.zeros(max(n_pairs, 1), np.int32); iters = np.zeros(max(n_pairs, 1), np.int32); ninl = np.zeros(max(n_pairs, 1), np.int32)
+    check(lib().esfm_find_homography_pairs(ctx.handle, n_pairs, C.c_void_p(off.ctypes.data), C.c_void_p(a.ctypes.data), C.c_void_p(b.ctypes.data),
+                                           float(threshold), float(confidence), C.c_void_p(H.ctypes.data), C.c_void_p(mask.ctypes.data),
+                                           C.c_void_p(status.ctypes.data), C.c_void_p(iters.ctypes.data), C.c_void_p(ninl.ctypes.data)))
+    return H[:n_pairs].reshape(n_pairs, 3, 3), mask[:n].astype(bool), status[:n_pairs].astype(bool), iters[:n_pairs], ninl[:n_pairs]
+
+
+def homography_models(q1, q2, ctx: Optional[Context] = None, host: bool = False):
+    """esfm_homography_models / esfm_homography_models_host: the 4-point solve alone on [n, 4, 2] pixel correspondences ->
+    (H [n, 3, 3], has_model [n] bool).  host=True runs the host build of the kernel's routines (no GPU)."""
+    a = np.ascontiguousarray(q1, np.float64).reshape(-1, 4, 2); b = np.ascontiguousarray(q2, np.float64).reshape(-1, 4, 2)
+    if a.shape != b.shape:
+        raise ValueError("sample sets differ in size")
+    n = len(a)
+    Hs = np.zeros((max(n, 1), 9)); has = np.zeros(max(n, 1), np.int32)
+    if host:
+        check(lib().esfm_homography_models_host(C.c_void_p(a.ctypes.data), C.c_void_p(b.ctypes.data), n, C.c_void_p(Hs.ctypes.data), C.c_void_p(has.ctypes.data)))
+    else:
+        ctx = ctx or default_context()
+        check(lib().esfm_homography_models(ctx.handle, C.c_void_p(a.ctypes.data), C.c_void_p(b.ctypes.data), n, C.c_void_p(Hs.ctypes.data),
+                                           C.c_void_p(has.ctypes.data)))
+    return Hs[:n].reshape(n, 3, 3), has[:n].astype(bool)
+
+
+def homography_refit_host(pts1, pts2, mask=None) -> np.ndarray:
+    """Host-only: esfm_homography_refit_host, the re-fit solve on the masked points in the refit kernel's summation order -> H [3,3]."""
+    a = np.ascontiguousarray(pts1, np.float32).reshape(-1, 2); b = np.ascontiguousarray(pts2, np.float32).reshape(-1, 2)
+    if a.shape != b.shape:
+        raise ValueError("point sets differ in size")
+    m = None if mask is None else np.ascontiguousarray(np.asarray(mask).astype(np.uint8))
+    if m is not None and len(m) != len(a):
+        raise ValueError("mask size")
+    H = np.zeros(9)
+    check(lib().esfm_homography_refit_host(C.c_void_p(a.ctypes.data), C.c_void_p(b.ctypes.data), len(a), None if m is None else C.c_void_p(m.ctypes.data),
+                                           C.c_void_p(H.ctypes.data)))
+    return H.reshape(3, 3)
+
+
+def homography_sample_stream(pts1, pts2, n_samples: int):
+    """Host-only: the 4-index samples the homography RANSAC draws for these correspondences, subset check included
+    (esfm_homography_sample_stream) -> (idx [n_samples, 4], rejected subsets on the way)."""
+    a = np.ascontiguousarray(pts1, np.float32).reshape(-1, 2); b = np.ascontiguousarray(pts2, np.float32).reshape(-1, 2)
+    if a.shape != b.shape:
+        raise ValueError("point sets differ in size")
+    idx = np.zeros((max(n_samples, 1), 4), np.int32); redraws = C.c_int64(0)
+    check(lib().esfm_homography_sample_stream(C.c_void_p(a.ctypes.data), C.c_void_p(b.ctypes.data), len(a), int(n_samples), C.c_void_p(idx.ctypes.data),
+                                              C.byref(redraws)))
+    return idx[:n_samples], redraws.value
+
+
 def pixel2cam(p: np.ndarray, K: np.ndarray) -> np.ndarray:
     """estimate_motion.h:41-46, float arithmetic on the float K: ((u - cx) / fx, (v - cy) / fy)."""
     p = np.asarray(p, np.float32).reshape(-1, 2); K = np.asarray(K, np.float32)
@@ -195,6 +274,21 @@ class MotionEstimator:
         T[:3, :3] = R.astype(np.float32); T[:3, 3] = t.astype(np.float32)       # cv2eigen into Matrix3f / Vector3f (:76-79)
         print(f"Find [{int(mask.sum())}] inlier matches from [{len(matches)}] total matches.")
         return T
+
+    def estimate2D2D_H4P_RANSAC(self, cur_frame_1: Frame, cur_frame_2: Frame, matches: Sequence[DMatch], inlier_matches: list,
+                                ransac_thre: float = 1.0, ransac_prob: float = 0.995):
+        """The homography counterpart of estimate2D2D_E5P_RANSAC (no such member in the reference): 4-point RANSAC on the matched
+        pixels (esfm.h "Homography RANSAC"), the matches of the RANSAC mask appended to `inlier_matches`.  Returns (found, H [3,3]
+        float64 mapping frame 1's pixels to frame 2's, n_inliers): n_inliers is esfm_find_homography_pairs' count -- the matches
+        within the threshold of the returned, re-fitted H, the numerator of h_inlier_ratio -- which is NOT the number of matches
+        appended.  found is False, H zero and n_inliers 0 with fewer than 4 matches or without a model."""
+        k1 = np.asarray(cur_frame_1.keypoints, np.float32).reshape(-1, 2)[[m.queryIdx for m in matches]].reshape(-1, 2)
+        k2 = np.asarray(cur_frame_2.keypoints, np.float32).reshape(-1, 2)[[m.trainIdx for m in matches]].reshape(-1, 2)
+        H, mask, status, _, n_inl = find_homography_pairs([0, len(matches)], k1, k2, ransac_thre, ransac_prob, self._ctx)
+        if not status[0]:
+            return False, np.zeros((3, 3)), 0
+        inlier_matches.extend(m for m, keep in zip(matches, mask) if keep)
+        return True, H[0], int(n_inl[0])
 
     def doUnDistort(self, cur_frame: Frame, distort_coeff) -> bool:
         """estimate_motion.cpp:431-441: cur_frame.rgb_image = cv::undistort(rgb_image, K_cam, distort_coeff)."""

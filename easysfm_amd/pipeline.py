@@ -18,7 +18,7 @@ from ._lib import Context, ESFM_HAMMING, ESFM_L2_F32, default_context
 from .ba import BundleAdjustment
 from .cloud import CProceesing, write_ply, write_ply_mesh, write_ply_normals, write_ply_textured_mesh, write_png_rgb
 from .matching import DescriptorBank, FeatureMatching, PairMatcher
-from .motion import MotionEstimator, _dehomogenise, find_essential_pairs, pixel2cam, recover_pose_pairs, triangulate_pairs
+from .motion import MotionEstimator, _dehomogenise, find_essential_pairs, find_homography_pairs, pixel2cam, recover_pose_pairs, triangulate_pairs
 from .mesh import (MeshCleanOptions, MeshOptions, auto_texels, default_atlas_width, mesh_arrays, mesh_clean, mesh_components, mesh_simplify,
                    mesh_texture_bake, mesh_texture_level, mesh_texture_views)
 from .render import mesh_render, mesh_render_error
@@ -34,6 +34,9 @@ class FramePair:
     matches: List[DMatch] = field(default_factory=list)
     T_21: np.ndarray = field(default_factory=lambda: np.eye(4, dtype=np.float32))
     appro_depth: float = 1.0
+    h_inliers: int = 0            # correspondences within the threshold of the returned, re-fitted homography (esfm_find_homography_pairs'
+                                  # n_inliers: not the RANSAC mask's count); homography_check only
+    h_inlier_ratio: float = 0.0   # ... divided by the essential matrix's RANSAC mask count: near 1 for a planar or rotation-only pair
 
 
 MATCH_FILTERS = ("ratio", "cross", "ratio+cross", "ratio+guided", "cross+guided", "ratio+cross+guided")
@@ -52,7 +55,8 @@ def merge_guided(plain, guided):
 
 
 def match_and_verify_all_pairs(frames: Sequence[Frame], use_feature: str = "S", ransac_reproj_distance: float = 1.0,
-                               num_min_pair: int = 20, ctx: Optional[Context] = None, match_filter: str = "ratio") -> List[List[FramePair]]:
+                               num_min_pair: int = 20, ctx: Optional[Context] = None, match_filter: str = "ratio",
+                               homography_check: bool = False) -> List[List[FramePair]]:
     """sfm.cpp:140-167 for every (i, j < i): matchFeatures{SURF,ORB,SIFT}(frames[i], frames[j]) (use_feature S, O or I); if more than num_min_pair
     matches survive, estimate2D2D_E5P_RANSAC (threshold = ransac_reproj_distance, prob 0.99) and getDepthFast on the inliers;
     otherwise no inliers, identity transform, depth 1 (:147-148).  Returns img_match_graph[i][j].
@@ -60,7 +64,11 @@ def match_and_verify_all_pairs(frames: Sequence[Frame], use_feature: str = "S", 
     ratio test in both directions: esfm.h "Cross-check matching").  With "+guided" appended, every pair that got an essential
     matrix is matched a second time with the search restricted to the rows that matrix admits within ransac_reproj_distance (one
     esfm_match_guided_pairs_dev call, the same filter), and its matches become the union of the RANSAC inliers and that list;
-    T_21 and appro_depth stay those of the first pass."""
+    T_21 and appro_depth stay those of the first pass.
+    homography_check: one esfm_find_homography_pairs call (esfm.h "Homography RANSAC", confidence 0.995) over the same
+    correspondences and the same ransac_reproj_distance fills h_inliers and h_inlier_ratio = homography inliers / essential-matrix
+    RANSAC inliers (the mask of find_essential_pairs, before recoverPose) of every pair that got an essential matrix; matches, T_21
+    and appro_depth are untouched."""
     if match_filter not in MATCH_FILTERS:
         raise ValueError(f"match_filter must be one of {MATCH_FILTERS}, not {match_filter!r}")
     ctx = ctx or default_context()
@@ -91,6 +99,13 @@ def match_and_verify_all_pairs(frames: Sequence[Frame], use_feature: str = "S", 
         Es, mask, status, _ = find_essential_pairs(off, p1, p2, K4, 0.99, ransac_reproj_distance, ctx)
         good, Rs, ts, _ = recover_pose_pairs(off, p1, p2, K4, Es, mask, ctx)
         verified = [s for s in range(len(sel)) if status[s]]
+        if homography_check:
+            _, _, _, _, h_inl = find_homography_pairs(off, p1, p2, ransac_reproj_distance, 0.995, ctx)
+            for s in verified:
+                i, j = pairs[sel[s]]
+                e_inl = int(np.count_nonzero(mask[off[s]:off[s + 1]]))
+                graph[i][j].h_inliers = int(h_inl[s])
+                graph[i][j].h_inlier_ratio = float(h_inl[s]) / float(e_inl) if e_inl else 0.0
         extra = {}
         if guided and verified:
             lists = pm.match_guided([sel[s] for s in verified], Es[verified], K4[verified], ransac_reproj_distance,
@@ -166,7 +181,8 @@ def run_sfm(frames: List[Frame], output_file: Optional[str] = None, use_feature:
             ctx: Optional[Context] = None, verbose: bool = False, match_filter: str = "ratio", dense_output_file: Optional[str] = None,
             dense_merged_output_file: Optional[str] = None, dense_mesh_output_file: Optional[str] = None,
             dense_mesh_clean: Optional[MeshCleanOptions] = None, dense_mesh_simplify: Optional[float] = None,
-            dense_mesh_texture: Optional[int] = None, dense_mesh_texture_level: bool = False, dense_mesh_render_dir: Optional[str] = None):
+            dense_mesh_texture: Optional[int] = None, dense_mesh_texture_level: bool = False, dense_mesh_render_dir: Optional[str] = None,
+            init_max_h_inlier_ratio: Optional[float] = None):
     """sfm.cpp:128-339.  Returns (sparse cloud before the final filter, filtered cloud, img_match_graph).
     dense_output_file: after the final BA and the sparse .ply, run dense_reconstruct on the registered frames and the cloud
     before the filter (it carries the track ids) and write the dense cloud there (esfm.h "Dense reconstruction").
@@ -190,12 +206,17 @@ def run_sfm(frames: List[Frame], output_file: Optional[str] = None, use_feature:
     dense_mesh_render_dir: with dense_mesh_output_file, an existing directory (it is not created here, nor by the drivers): after the mesh is written it is drawn into every registered frame,
     in frame order (esfm.h "Mesh rendering", default options; with the atlas if the mesh was textured, else with its vertex colours);
     the pictures go there as render_%04d.png, numbered by frame index, and one "Mesh render:" line states the number of views, the
-    pixels the mesh covers in them and the mean absolute difference to the photographs over those pixels and three channels."""
+    pixels the mesh covers in them and the mean absolute difference to the photographs over those pixels and three channels.
+    init_max_h_inlier_ratio: when given, every verified pair also gets a homography RANSAC (match_and_verify_all_pairs'
+    homography_check) and findInitializeFramePair skips the pairs whose h_inlier_ratio exceeds this limit (0.8 separates planar and
+    rotation-only pairs from general ones by an order of magnitude: DESIGN 6.4); prints one "Init pair:" line.  None: no check, every
+    output as before."""
     ctx = ctx or default_context()
     fm, ee = FeatureMatching(ctx), MotionEstimator(ctx)
     for f in frames:
         f.init_pixel_ids()
-    graph = match_and_verify_all_pairs(frames, use_feature, ransac_reproj_distance, 20, ctx, match_filter)
+    graph = match_and_verify_all_pairs(frames, use_feature, ransac_reproj_distance, 20, ctx, match_filter,
+                                       homography_check=init_max_h_inlier_ratio is not None)
     track, n_unique = propagate_track_ids(frames, graph)
     if verbose:
         for i in range(len(frames)):
@@ -205,7 +226,12 @@ def run_sfm(frames: List[Frame], output_file: Optional[str] = None, use_feature:
         print(f"The total unique feature point number is {n_unique}")
     init_1, init_2, depth_init = 1, 0, 10.0
     if use_track_frames_as_init:
-        found, a, b, d = fm.findInitializeFramePair(track, frames, [[p.appro_depth for p in row] + [0.0] * (len(frames) - len(row)) for row in graph])
+        if init_max_h_inlier_ratio is None:
+            found, a, b, d = fm.findInitializeFramePair(track, frames, [[p.appro_depth for p in row] + [0.0] * (len(frames) - len(row)) for row in graph])
+        else:
+            h_stats = {}
+            found, a, b, d = fm.findInitializeFramePair(track, frames, graph, max_h_inlier_ratio=init_max_h_inlier_ratio, h_stats=h_stats)
+            print(f"Init pair: skipped {h_stats['skipped']} of {h_stats['candidates']} candidate pairs as planar or panoramic")
         init_1, init_2 = a, b
         if found:
             depth_init = d

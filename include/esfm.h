@@ -91,7 +91,7 @@ typedef enum esfm_kernel_id {
     ESFM_K_L2_RESCAN = 5,     /* l2_exact_scan_kernel                                           */
     ESFM_K_SOR_KNN = 6,       /* sor_knn_mean_kernel: k-NN mean distances of the outlier filter   */
     ESFM_K_TRIANGULATE = 7,   /* triangulate_dlt_kernel                                         */
-    ESFM_K_RANSAC = 8,        /* essential_setup + _roots + _score kernels (one chunk)         */
+    ESFM_K_RANSAC = 8,        /* essential_setup + _roots + _score kernels (one chunk); homography_solve + _score (one chunk) */
     ESFM_K_SURF_DET = 9,      /* surf_det_trace_kernel                                          */
     ESFM_K_SURF_DESC = 10,    /* the four descriptor launches: surf_orient / window / rowsum / vector */
     ESFM_K_UNDISTORT = 11,    /* undistort_remap_kernel                                         */
@@ -646,6 +646,59 @@ int esfm_five_point_models_host(const double *q1, const double *q2, int n_sample
                                 double *stages /*or NULL*/);
 /* Host-only (no GPU): the first n_samples 5-index samples RANSAC draws for `count` points (cv::RNG replay). */
 int esfm_ransac_sample_stream(int count, int n_samples, int32_t *idx /*5 per sample*/);
+
+/* ---- Homography RANSAC: the planar / panoramic check of two-view verification ------------------------
+ * A pair of views related by a pure rotation, or looking at a plane, still gets an essential matrix with many inliers, but its
+ * translation is noise.  Such a pair is also explained by a homography; a caller compares the two models' inlier counts
+ * (pipeline.match_and_verify_all_pairs(homography_check=True), FeatureMatching::findInitializeFramePair's max_h_inlier_ratio).
+ *
+ * esfm_find_homography follows cv::findHomography(pts1, pts2, cv::RANSAC, threshold, mask, 2000, confidence) WITHOUT its final
+ * Levenberg-Marquardt polish; where the two differ, the rule written here is the authority (parity with OpenCV is not pinned).
+ *   - pts1 / pts2: n matched pixel positions (2 floats each).  H[9] row-major maps image 1 to image 2, H[8] = 1.
+ *   - RANSAC with 4 model points, at most 2000 iterations, on the sample stream of cv::RNG((uint64)-1).  A sample is four
+ *     distinct indices (a repeat is redrawn) that pass the subset check: none of the triples (0,1,2), (1,2,3), (0,2,3), (0,1,3) is
+ *     collinear in either image (|cross| <= FLT_EPSILON * (|dx1| + |dy1| + |dx2| + |dy2|), in double), and the products of the two
+ *     images' signed triangle areas are negative for none or for all four triples.  A rejected sample is redrawn whole; after
+ *     1000 rejections in a row the loop ends where it stands (before its first iteration: no model).
+ *   - Minimal solve (f64): Hartley normalisation per image (centroid to the origin, mean distance sqrt 2), the 8 x 9 DLT system,
+ *     its null vector by a Householder QR of the transpose, de-normalisation, division by H[8]; no model when
+ *     |H[8]| <= DBL_EPSILON * max|H| or an entry is not finite.  Every order of operations: easysfm_amd/csrc/homography_core.hpp.
+ *   - Score: the forward transfer error in FLOAT on (float)H: ww = 1.f / (H6 x + H7 y + 1.f), dx = (H0 x + H1 y + H2) ww - x',
+ *     dy likewise, err = dx dx + dy dy; inlier iff err <= (float)(threshold * threshold).
+ *   - A model replaces the best iff it has more inliers and at least 4; the iteration count adapts (RANSACUpdateNumIters with 4
+ *     model points).  mask[n] = the inliers of the winning RANSAC model, *iterations = iterations the sequential loop runs.
+ *   - Then H is re-fitted on those inliers: the eigenvector of the smallest eigenvalue of the 9 x 9 normal matrix A'A of their
+ *     normalised DLT rows (cyclic Jacobi), summed in one fixed order (256 lanes, lane l the points l, l + 256, .. whose mask is
+ *     set, ascending; then a halving tree).  The mask stays the RANSAC mask.  A re-fit without a model leaves the RANSAC winner.
+ *   - n = 4: the minimal solve of the four points as given, no subset check, mask all ones, no re-fit, *iterations = 0.
+ *   - n < 4 is ESFM_ERR_UNSUPPORTED; no model (no sample passed the check, or no model with 4 inliers) is ESFM_ERR_NUMERIC.
+ * esfm_find_homography_pairs batches many pairs (pair p owns points [point_offset[p], point_offset[p+1])): one launch per chunk
+ * of iterations of all still-active pairs.  status[p] = 1 iff pair p has a model (a pair with fewer than 4 points has none: no
+ * error); H and mask of a pair without a model are zero.  Results are those of the per-pair calls, bit for bit.
+ * n_inliers[p] (or NULL) = the correspondences of pair p within the threshold of the RETURNED (re-fitted) H, under the same float
+ * error -- not the number of set mask entries.  The mask belongs to a model of four noisy points and RANSAC stops as soon as
+ * such a model makes further iterations unlikely to pay, so its count swings with the sample: on planar and rotation-only pairs
+ * with 0.3 px noise and a 1 px threshold it was 0.59 .. 0.88 of the correspondences, the returned model's 0.84 .. 0.92 (general
+ * pairs: below 0.08 either way).  This count is the planar / panoramic statistic's numerator. */
+int esfm_find_homography(esfm_ctx *ctx, const float *pts1, const float *pts2, int n, double threshold, double confidence,
+                         double *H /*9*/, uint8_t *mask /*n*/, int32_t *iterations /*or NULL*/);
+int esfm_find_homography_pairs(esfm_ctx *ctx, int n_pairs, const int32_t *point_offset /*n_pairs+1*/, const float *pts1,
+                               const float *pts2, double threshold, double confidence, double *H /*9 per pair*/,
+                               uint8_t *mask /*per point*/, int32_t *status /*per pair*/, int32_t *iterations /*per pair or NULL*/,
+                               int32_t *n_inliers /*per pair or NULL*/);
+/* The minimal solve alone: n_samples samples of four correspondences in pixels, q1, q2 [n_samples][4][2] doubles.  H_out
+ * [n_samples][9] (zeros without a model), has_model[n_samples] 1 / 0.  esfm_homography_models runs homography_solve_kernel's code
+ * on the GPU, esfm_homography_models_host the host build of the same header (no GPU): the two and the Python restatement
+ * (tests/homography_ref.py) agree to the bit. */
+int esfm_homography_models(esfm_ctx *ctx, const double *q1, const double *q2, int n_samples, double *H_out, int32_t *has_model);
+int esfm_homography_models_host(const double *q1, const double *q2, int n_samples, double *H_out, int32_t *has_model);
+/* Host-only (no GPU): the re-fit solve on the points whose mask is set (mask NULL: all), in the refit kernel's summation order.
+ * Fewer than 4 such points or no model: ESFM_ERR_NUMERIC, H zeros. */
+int esfm_homography_refit_host(const float *pts1, const float *pts2, int n, const uint8_t *mask /*or NULL*/, double *H /*9*/);
+/* Host-only (no GPU): the first n_samples 4-index samples the RANSAC above draws for these `count` correspondences, the subset
+ * check included; *redraws (or NULL) = rejected subsets on the way.  ESFM_ERR_NUMERIC when 1000 subsets in a row are rejected. */
+int esfm_homography_sample_stream(const float *pts1, const float *pts2, int count, int n_samples, int32_t *idx /*4 per sample*/,
+                                  int64_t *redraws /*or NULL*/);
 
 /* ---- SURF detection + description (SURF half) ----------------------------
  * FeatureMatching::detectFeaturesSURF (cpp_code/src/feature_matching.cpp:43-58): cv::xfeatures2d::SURF::create(minHessian)
