@@ -1024,16 +1024,18 @@ __device__ __forceinline__ void l2_finish_body(const int fb, const int nfb, FinS
     // ---- (2), (3): the pair's uncertified queries, chunks of 32, the whole train set by this workgroup's four waves
     const int cnt = min(ld_coh_i(unc_cnt + p), nq);
     constexpr int kSmall = 8;      // uncertified queries of a pair up to which the exact brute force beats the threshold filter's fixed ~100-us chain
-    if (cnt > 0 && cnt <= kSmall && audit != 1) {
+    if (cnt > 0 && cnt <= kSmall) {
         // a handful of queries: their exact 2-NN over the whole train set straight away (the threshold filter below is a chain of
-        // nt / 128 dependent MFMA steps per chunk of 32 whatever the chunk holds: ~100 us for ONE query; this: a few us per query)
+        // nt / 128 dependent MFMA steps per chunk of 32 whatever the chunk holds: ~100 us for ONE query; this: a few us per query).
+        // Audit mode 1 lists them like the product path does and leaves them the re-rank's answer (it used to send them through the
+        // threshold filter instead, and its flagged list came out shorter than the product path's count of re-scanned queries).
         if (tid < 32) s_qrows[tid] = tid < cnt ? ld_coh_i(unc_list + pd.out_off + tid) : 0;
         __syncthreads();
         if (tid < cnt) {
             const int sl2 = atomicAdd(&counters[0], 1);
             if (sl2 < flag_cap) { flagged[2 * sl2] = p; flagged[2 * sl2 + 1] = s_qrows[tid]; }
         }
-        finish_bruteforce_chunk(desc, pd, s_qrows, cnt, s_q, s_keys, knn_idx, knn_dist);
+        if (audit != 1) finish_bruteforce_chunk(desc, pd, s_qrows, cnt, s_q, s_keys, knn_idx, knn_dist);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
     } else if (cnt > 0) {

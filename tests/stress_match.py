@@ -1,5 +1,5 @@
 """Randomised stress of the batched matcher against the oracle: ragged set sizes (incl. 0, 1, tile edges), clustered / duplicated /
-scaled rows, random ratios, L2 (64 and 128 floats) and 256-bit Hamming; match lists and 2-NN tables, bit for bit.
+scaled / integer-valued rows, query sets of many times the train rows' norm, random ratios, L2 (64 and 128 floats) and 256-bit Hamming; match lists and 2-NN tables, bit for bit.
 usage: python tests/stress_match.py [--seconds S | --cases N] [--seed K]"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -25,18 +25,26 @@ bits = lambda a: np.ascontiguousarray(a, np.float32).view(np.uint32)
 EDGE = [0, 1, 2, 3, 31, 32, 33, 63, 64, 65, 127, 128, 129, 255, 256, 257, 511, 512, 513, 1023, 1024, 1025, 2047, 2049, 4095, 4096, 4097]
 
 def l2_sets(n_sets, dim):
-    style = rng.integers(0, 5)
+    style = rng.integers(0, 7)
     pool = rng.standard_normal((int(rng.integers(8, 3000)), dim))
     if style == 1: pool = pool[: max(2, len(pool) // 50)]                      # few distinct rows: many duplicates / near ties
+    if style == 5: pool = rng.integers(0, 256, (max(2, len(pool) // 20), dim)).astype(np.float64)   # integer rows 0..255 (SIFT-like): exactly equal distances
+    if style == 6: pool = np.abs(pool)                                         # non-negative rows: q.t > 0, see below
     sets = []
-    for _ in range(n_sets):
+    for k in range(n_sets):
         n = int(rng.choice(EDGE)) if rng.random() < 0.5 else int(rng.integers(0, 3000))
         ids = rng.integers(0, len(pool), n)
+        if style == 5:                                                            # a few entries changed by one, values stay integers
+            x = np.clip(pool[ids] + rng.integers(-1, 2, (n, dim)) * (rng.random((n, dim)) < 0.02), 0, 255)
+            sets.append(x.astype(np.float32))
+            continue
         noise = [0.0, 1e-7, 1e-3, 0.02, 0.3][int(rng.integers(0, 5))]
         x = pool[ids] + noise * rng.standard_normal((n, dim))
         if style != 2: x /= np.maximum(np.linalg.norm(x, axis=1, keepdims=True), 1e-12)
         if style == 3: x *= 10.0 ** rng.uniform(-3, 3)                            # un-normalised magnitudes
         if style == 4 and n: x[rng.integers(0, n, max(1, n // 20))] = 0.0         # zero rows
+        if style == 6 and k % 2: x *= rng.uniform(5.0, 50.0)                      # every other set well above the rest: as queries against
+                                                                                  # those, |t|^2 - 2 q.t (what the passes rank) is negative
         sets.append(x.astype(np.float32))
     return sets
 

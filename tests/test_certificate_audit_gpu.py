@@ -16,52 +16,22 @@ import pytest
 import easysfm_amd as E
 from easysfm_amd import synth
 
+import match_cases as MC
+
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
 
 
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+_bits = MC.bits
 
 
 def _audit(sets, pairs, ctx=None, label=""):
     """Returns (n_queries, n_flagged for the re-scan, n uncertified by the one-product pass); asserts the audit properties."""
     bank = E.DescriptorBank(sets, E.ESFM_L2_F32)
     pm = E.PairMatcher(bank, pairs, ctx) if ctx is not None else E.PairMatcher(bank, pairs)
-
-    def run():
-        i_, d_ = pm.knn2(); pm.ctx.synchronize()
-        return i_.cpu().numpy().copy(), d_.cpu().numpy().copy()
-
-    idx, dist = run()
-    n_q, n_rescan = pm.stats()
-    pm.set_l2_audit(1)
-    a_idx, a_dist = run()
-    flagged = pm.flagged()
-    pm.set_l2_audit(3)           # the one-product bf16 pass alone: its answers, its own list of failures
-    f_idx, f_dist = run()
-    front_flagged = pm.flagged()
-    pm.set_l2_audit(2)
-    e_idx, e_dist = run()
-    pm.set_l2_audit(0)
-    assert np.array_equal(e_idx, idx) and np.array_equal(_bits(e_dist), _bits(dist)), f"{label}: brute force != product path"
-    assert len(flagged) == n_rescan, (label, len(flagged), n_rescan)
-    off = np.asarray(pm.offset, np.int64)
-    wrong = np.nonzero(np.any(a_idx != e_idx, axis=1) | np.any(_bits(a_dist) != _bits(e_dist), axis=1))[0]
-    flagged_rows = set((off[flagged[:, 0]] + flagged[:, 1]).tolist()) if len(flagged) else set()
-    certified_but_wrong = [int(r) for r in wrong if int(r) not in flagged_rows]
-    print(f"\n{label}: {n_q} queries, {len(flagged)} flagged ({100.0 * len(flagged) / max(n_q, 1):.3f} %), {len(wrong)} pass-only answers differ "
-          f"from brute force, certified-but-wrong {len(certified_but_wrong)}")
-    assert certified_but_wrong == [], (label, certified_but_wrong[:10])
-    # the same for the front pass on its own (its certificate carries the bf16 rounding of the operands)
-    f_wrong = np.nonzero(np.any(f_idx != e_idx, axis=1) | np.any(_bits(f_dist) != _bits(e_dist), axis=1))[0]
-    f_rows = set((off[front_flagged[:, 0]] + front_flagged[:, 1]).tolist()) if len(front_flagged) else set()
-    f_cbw = [int(r) for r in f_wrong if int(r) not in f_rows]
-    print(f"{label}: one-product pass alone: {len(front_flagged)} uncertified ({100.0 * len(front_flagged) / max(n_q, 1):.3f} %), {len(f_wrong)} of its answers "
-          f"differ from brute force, certified-but-wrong {len(f_cbw)}")
-    assert f_cbw == [], (label, f_cbw[:10])
-    assert len(front_flagged) >= len(flagged)           # the second pass only sees what the first one left
-    return n_q, len(flagged), len(front_flagged)
+    info = {}
+    n_q, n_flagged, _ = MC.audit(pm, label, front=True, info=info)
+    return n_q, n_flagged, info["front_flagged"]
 
 
 def _audit_screen(sets, pairs, ctx=None, label="", ratios=(0.5, 0.8, 1.0)):
@@ -121,38 +91,7 @@ def test_audit_fountain_surf_descriptors(gpu_ctx):
 
 
 def _adversarial(case):
-    rng = np.random.default_rng({"cluster": 1, "dynamic_range": 2, "tiny": 3, "huge_norms": 4, "equal_rows": 5, "sparse": 6, "denormal": 8, "denormal_mixed": 9,
-                                 "segment_edges": 7}[case])
-    nq, nt = 300, 1500
-    q = rng.standard_normal((nq, 64)).astype(np.float32)
-    t = rng.standard_normal((nt, 64)).astype(np.float32)
-    if case == "cluster":
-        c = rng.standard_normal(64).astype(np.float32)
-        t = (c[None, :] * (1 + 1e-5 * rng.standard_normal((nt, 64)))).astype(np.float32)
-        q[:150] = (c[None, :] * (1 + 1e-5 * rng.standard_normal((150, 64)))).astype(np.float32)
-    elif case == "dynamic_range":
-        q = (q * np.exp(rng.uniform(-14, 14, q.shape))).astype(np.float32)
-        t = (t * np.exp(rng.uniform(-14, 14, t.shape))).astype(np.float32)
-    elif case == "tiny":
-        q = (q * 1e-18).astype(np.float32); t = (t * 1e-18).astype(np.float32)
-    elif case == "denormal":
-        q = (q * 1e-20).astype(np.float32); t = (t * 1e-20).astype(np.float32)
-    elif case == "denormal_mixed":
-        q = (q * np.float32(10.0) ** rng.integers(-23, -16, (nq, 1))).astype(np.float32)
-        t = (t * np.float32(10.0) ** rng.integers(-23, -16, (nt, 1))).astype(np.float32)
-    elif case == "huge_norms":
-        q = (q + 300.0).astype(np.float32); t = (t + 300.0).astype(np.float32)
-    elif case == "equal_rows":
-        t[100:400] = t[7]; t[900:] = t[13]; q[:50] = t[7]; q[50:100] = t[13]
-    elif case == "sparse":
-        q[rng.random(q.shape) < 0.9] = 0; t[rng.random(t.shape) < 0.9] = 0
-    elif case == "segment_edges":
-        nt = 2100
-        t = rng.standard_normal((nt, 64)).astype(np.float32)
-        for k, pos in enumerate([0, 31, 32, 127, 128, 511, 512, 1023, 1024, 2047, 2048, 2099]):
-            q[k] = t[pos] * np.float32(1 + 1e-4)
-            q[k + 20] = t[pos]; t[(pos + 1) % nt] = t[pos] * np.float32(1 + 3e-7)
-    return q, t
+    return MC.adversarial(case, 64)
 
 
 @pytest.mark.parametrize("case", ["cluster", "dynamic_range", "tiny", "denormal", "denormal_mixed", "huge_norms", "equal_rows", "sparse", "segment_edges"])

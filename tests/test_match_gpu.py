@@ -6,11 +6,12 @@ import pytest
 import easysfm_amd as E
 from easysfm_amd import synth
 
+import match_cases as MC
+
 pytestmark = pytest.mark.gpu
 
 
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+_bits = MC.bits
 
 
 def _check_knn_l2(ctx, oracle, q, t):
@@ -45,24 +46,15 @@ def test_l2_empty_and_tiny_train(gpu_ctx, oracle_lib):
 def test_l2_duplicates_and_ties(gpu_ctx, oracle_lib):
     """Exact duplicates in the train set (distance-0 ties and equal-distance ties): the lower train
     index must win; more duplicates than the kernel keeps candidates forces the exact re-scan."""
-    rng = np.random.default_rng(7)
-    base = rng.standard_normal((50, 64)).astype(np.float32)
-    base /= np.linalg.norm(base, axis=1, keepdims=True)
-    t = np.concatenate([base, base[:20], base[:20], base[:10], base[:10], base[:10], base[:10], base[:10]], axis=0)
-    perm = rng.permutation(len(t)); t = t[perm]
-    q = np.concatenate([base[:30], base[:30] + 1e-4 * rng.standard_normal((30, 64)).astype(np.float32)], axis=0)
+    q, t = MC.duplicates_and_ties(64)
     _check_knn_l2(gpu_ctx, oracle_lib, q, t)
 
 
 def test_l2_near_ties(gpu_ctx, oracle_lib):
     """Train rows that differ from each other by a few ulps: arg-min and the second neighbour must
     follow the oracle's summation order, not the GEMM's."""
-    rng = np.random.default_rng(9)
-    q = rng.standard_normal((200, 64)).astype(np.float32); q /= np.linalg.norm(q, axis=1, keepdims=True)
-    t = np.repeat(q[:100], 6, axis=0)
-    t = t * (1.0 + rng.integers(-3, 4, size=t.shape) * np.float32(6e-8))
-    t = np.concatenate([t, rng.standard_normal((300, 64)).astype(np.float32) * 0.1], axis=0).astype(np.float32)
-    _check_knn_l2(gpu_ctx, oracle_lib, q, t[rng.permutation(len(t))])
+    q, t = MC.near_ties(64)
+    _check_knn_l2(gpu_ctx, oracle_lib, q, t)
 
 
 def test_l2_unnormalised_and_dim128(gpu_ctx, oracle_lib):
@@ -83,37 +75,7 @@ def test_l2_split_bf16_pass_adversarial(gpu_ctx, oracle_lib, case):
     """64-float descriptors go through the split-bf16 distance pass, whose scores carry ~2^-16 relative error: inputs built to
     sit inside that error (near-equal distances, cancellation, extreme magnitudes) must still come out bit-identical to the
     oracle, through the certificate's rescan if need be."""
-    rng = np.random.default_rng({"cluster": 1, "dynamic_range": 2, "tiny": 3, "huge_norms": 4, "equal_rows": 5, "sparse": 6, "denormal": 8, "denormal_mixed": 9,
-                                 "segment_edges": 7}[case])
-    nq, nt = 300, 1500
-    q = rng.standard_normal((nq, 64)).astype(np.float32)
-    t = rng.standard_normal((nt, 64)).astype(np.float32)
-    if case == "cluster":                   # every train within 1e-5 relative of one centre: all distances nearly equal
-        c = rng.standard_normal(64).astype(np.float32)
-        t = (c[None, :] * (1 + 1e-5 * rng.standard_normal((nt, 64)))).astype(np.float32)
-        q[:150] = (c[None, :] * (1 + 1e-5 * rng.standard_normal((150, 64)))).astype(np.float32)
-    elif case == "dynamic_range":           # components spread over 12 decades inside a row
-        q = (q * np.exp(rng.uniform(-14, 14, q.shape))).astype(np.float32)
-        t = (t * np.exp(rng.uniform(-14, 14, t.shape))).astype(np.float32)
-    elif case == "tiny":                    # magnitudes near the bottom of the normal range
-        q = (q * 1e-18).astype(np.float32); t = (t * 1e-18).astype(np.float32)
-    elif case == "denormal":                # |row|^2 and the bf16 residuals' squares are denormal or zero in f32 (ADVICE r03)
-        q = (q * 1e-20).astype(np.float32); t = (t * 1e-20).astype(np.float32)
-    elif case == "denormal_mixed":          # rows from 1e-23 (squares flush to zero) to 1e-17 (normal) in one train set
-        q = (q * np.float32(10.0) ** rng.integers(-23, -16, (nq, 1))).astype(np.float32)
-        t = (t * np.float32(10.0) ** rng.integers(-23, -16, (nt, 1))).astype(np.float32)
-    elif case == "huge_norms":              # large common offset: d^2 << |q|^2 + |t|^2 (catastrophic cancellation in the GEMM form)
-        q = (q + 300.0).astype(np.float32); t = (t + 300.0).astype(np.float32)
-    elif case == "equal_rows":              # many identical trains and queries equal to trains
-        t[100:400] = t[7]; t[900:] = t[13]; q[:50] = t[7]; q[50:100] = t[13]
-    elif case == "sparse":
-        q[rng.random(q.shape) < 0.9] = 0; t[rng.random(t.shape) < 0.9] = 0
-    elif case == "segment_edges":           # the two nearest trains at the seams of the 32-row steps / 512-row segments / 128-row tiles
-        nt = 2100
-        t = rng.standard_normal((nt, 64)).astype(np.float32)
-        for k, pos in enumerate([0, 31, 32, 127, 128, 511, 512, 1023, 1024, 2047, 2048, 2099]):
-            q[k] = t[pos] * np.float32(1 + 1e-4)
-            q[k + 20] = t[pos]; t[(pos + 1) % nt] = t[pos] * np.float32(1 + 3e-7)
+    q, t = MC.adversarial(case, 64)     # (the cases are described where they are built)
     _check_knn_l2(gpu_ctx, oracle_lib, q, t)
     qi, ti, d = E.match_l2(q, t, 0.8, gpu_ctx)
     rq, rt, rd = oracle_lib.match_l2(q, t, 0.8)
@@ -141,9 +103,7 @@ def test_hamming_knn_bitexact(gpu_ctx, oracle_lib, nq, nt):
 def test_hamming_forced_ties(gpu_ctx, oracle_lib):
     """All-equal rows and few distinct distances: ties for first AND second place everywhere."""
     rng = np.random.default_rng(5)
-    t = np.zeros((300, 32), np.uint8)
-    t[::3, 0] = 1; t[1::3, 1] = 3
-    q = np.zeros((100, 32), np.uint8); q[50:, 5] = 0xFF
+    q, t = MC.forced_ties(32)
     idx, dist = E.knn_match_hamming(q, t, gpu_ctx)
     ridx, rdist = oracle_lib.knn2_hamming(q, t)
     assert np.array_equal(idx, ridx) and np.array_equal(dist, rdist)
@@ -163,13 +123,9 @@ def test_hamming_fp4_adversarial(gpu_ctx, oracle_lib, case):
     the tail looks at -- ties for first and second place spread over more fold groups than a lane keeps keys, duplicates whose
     lowest indices sit late in the set, all-ones rows (the largest scores), neighbours one bit apart, and a ragged pair list
     (train sets of 1, 7, 300, 513 and 2300 rows: fewer rows than a ring tile, partial last tiles)."""
-    rng = np.random.default_rng(21)
     ratios = (0.5, 0.8, 1.0)
     if case == "ragged_batch":
-        sizes = [1, 7, 300, 513, 2300, 40]
-        sets = [rng.integers(0, 256, (n, 32), dtype=np.uint8) for n in sizes]
-        sets[4][:200] = sets[2][:200]; sets[4][200:260, 3] ^= 1          # exact copies and one-bit neighbours across sets
-        pairs = synth.all_pairs(len(sizes))
+        sets, pairs = MC.hamming_ragged_batch(32)
         pm = E.PairMatcher(E.DescriptorBank(sets, E.ESFM_HAMMING), pairs)
         for ratio in ratios:
             res = pm.match(ratio).to_host()
@@ -177,19 +133,7 @@ def test_hamming_fp4_adversarial(gpu_ctx, oracle_lib, case):
                 rq, rt, rd = oracle_lib.match_hamming(sets[i], sets[j], ratio)
                 assert np.array_equal(qi, rq) and np.array_equal(ti, rt) and np.array_equal(d, rd), (i, j, ratio)
         return
-    nt = 3000
-    t = rng.integers(0, 256, (nt, 32), dtype=np.uint8)
-    base = rng.integers(0, 256, (1, 32), dtype=np.uint8)
-    if case == "dups_everywhere":
-        t[rng.choice(nt, 400, replace=False)] = base                    # 400 copies: ties for both places in dozens of groups
-    elif case == "dups_late":
-        t[[2990, 2995, 1501, 2047, 2048]] = base
-    elif case == "all_ones":
-        t[::7] = 0xFF
-    elif case == "one_bit_apart":
-        for k in range(0, nt, 5):
-            t[k] = base; t[k, (k // 5) % 32] ^= np.uint8(1 << (k % 8))
-    q = np.concatenate([base, base ^ np.uint8(1), rng.integers(0, 256, (600, 32), dtype=np.uint8), np.full((3, 32), 0xFF, np.uint8), np.zeros((2, 32), np.uint8)])
+    q, t = MC.hamming_case(case, 32, 3000)
     idx, dist = E.knn_match_hamming(q, t, gpu_ctx)
     ridx, rdist = oracle_lib.knn2_hamming(q, t)
     assert np.array_equal(idx, ridx) and np.array_equal(dist, rdist)
@@ -488,14 +432,8 @@ def test_l2_overflowing_and_nan_rows(gpu_ctx, oracle_lib):
     """Rows whose distance overflows f32 (+inf) or is NaN are never neighbours (the oracle's strict `d < d1` against FLT_MAX):
     a few such train rows, a NaN query row, and a train set made of nothing else (no neighbours at all: indices -1)."""
     rng = np.random.default_rng(21)
-    q = rng.standard_normal((300, 64)).astype(np.float32); t = rng.standard_normal((700, 64)).astype(np.float32)
-    q /= np.linalg.norm(q, axis=1, keepdims=True); t /= np.linalg.norm(t, axis=1, keepdims=True)
-    t[[3, 77, 500]] *= np.float32(1e25)
-    t[123, 5] = np.nan
-    q[17, 40] = np.nan
+    q, t, huge = MC.nonfinite(64, rng)
     _check_knn_l2(gpu_ctx, oracle_lib, q, t)
-    with np.errstate(over="ignore", invalid="ignore"):
-        huge = (t[:50] * np.float32(1e25)).astype(np.float32)         # some entries overflow to inf themselves
     _check_knn_l2(gpu_ctx, oracle_lib, q, huge)
     # the same on 128-float descriptors (f32-input MFMA pass: a NaN key would corrupt its med3 network)
     q2 = rng.standard_normal((200, 128)).astype(np.float32); t2 = rng.standard_normal((500, 128)).astype(np.float32)
@@ -608,9 +546,10 @@ print("ok")
 
 @pytest.mark.parametrize("switch,value,metric", [("ESFM_L2_PASS", "bf16x3", "l2"), ("ESFM_L2_PASS", "f32", "l2"), ("ESFM_HM_PASS", "i8", "hamming")])
 def test_fallback_kernel_families_at_small_shapes(gpu_ctx, switch, value, metric):
-    """The kernel families behind the default paths, which otherwise run only at very large train sets: ESFM_L2_PASS=bf16x3 (the
-    three-product bf16 kernel + the per-pair re-scan), ESFM_L2_PASS=f32 (the 64-wide f32 MFMA kernel + l2_rescan64_kernel) and
-    ESFM_HM_PASS=i8 (the byte-per-bit kernel and its expander).  The switches are read once per process, so each runs in a child:
+    """The kernel families behind the default 64-float and 256-bit paths: ESFM_L2_PASS=bf16x3 (the three-product bf16 kernel + the
+    per-pair re-scan, otherwise the path of train sets above 65 536 rows), ESFM_L2_PASS=f32 (the 64-wide form of the f32 MFMA kernel,
+    whose 128-wide form is the default path of every 128-float descriptor, + l2_rescan64_kernel) and ESFM_HM_PASS=i8 (the
+    byte-per-bit kernel and its expander, otherwise the path of train sets above 262 144 rows).  The switches are read once per process, so each runs in a child:
     all ordered pairs of sets of 1500, 700, 513, 40 and 1 rows -- rows beyond a 512- and a 256-row block boundary, a set smaller
     than one 64-row tile, a train set without a second neighbour -- at ratios 0.6 and 1.0, indices and distance bit patterns
     against the oracle."""
