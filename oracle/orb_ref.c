@@ -6,7 +6,10 @@
  * TEST INFRASTRUCTURE ONLY.  Nothing in the product path may include, link, call or execute this file
  * (see oracle/match_ref.c header).
  *
- * PARITY UNPINNED: OpenCV is absent here and the reference holds no fixture.  Restated from memory of OpenCV 3.4
+ * PINNED TO THE RULE LIST BELOW, NOT TO OPENCV: tests/orb_ref.py states the same rules independently in numpy (exact integers,
+ * float64 elsewhere) and tests/test_orb_ref_cpu.py checks this file's output against it claim by claim; tests/test_feature_ref_gpu.py
+ * does the same for the kernels.  OpenCV itself is still absent and the reference holds no fixture, so the rule list remains a
+ * restatement from memory of OpenCV 3.4
  * [upstream modules/features2d/src/orb.cpp, fast.cpp, fast_score.cpp, keypoint.cpp; modules/imgproc resize / smooth],
  * cv::ORB::create(nfeatures) defaults: scaleFactor 1.2, nlevels 8, edgeThreshold 31, firstLevel 0, WTA_K 2, HARRIS_SCORE,
  * patchSize 31, fastThreshold 20.
@@ -16,6 +19,7 @@
  *   quota       n_l = cvRound(N (1 - f) / (1 - f^8) f^l), f = 1 / 1.2, the last level takes the remainder
  *   FAST        9 of 16, threshold 20, score = (largest t for which the pixel is still a corner) = max over the 16 arcs of 9 of
  *               min |difference| - 1, strict 3 x 3 non-maximum suppression, keypoints within 31 px of the border dropped,
+ *               (a level is searched at 31 <= x < cols - 31, 31 <= y < rows - 31: a 63 x 63 level has exactly one such position),
  *               the best 2 n_l by FAST score kept (all ties with the last kept one stay, as KeyPointsFilter::retainBest does)
  *   Harris      7 x 7 block of Sobel-like 3 x 3 gradients, ((float)a b - (float)c c - 0.04 ((float)a + b)^2) / (4 * 7 * 255)^4;
  *               the best n_l kept (ties as above)

@@ -6,23 +6,34 @@
  * TEST INFRASTRUCTURE ONLY.  Nothing in the product path may include, link, call or execute this file
  * (see oracle/match_ref.c header).
  *
- * PARITY UNPINNED: opencv_contrib's xfeatures2d (non-free SURF) is absent here and the reference holds no fixture.  Restated
+ * PINNED TO THE RULE LIST BELOW, NOT TO OPENCV: tests/surf_ref.py states the same rules independently in numpy (exact integers,
+ * float64 elsewhere) and tests/test_surf_ref_cpu.py checks this file's output against it claim by claim; tests/test_feature_ref_gpu.py
+ * does the same for the kernels.  opencv_contrib's xfeatures2d (non-free SURF) is still absent and the reference holds no fixture,
+ * so the rule list remains a restatement
  * from memory of OpenCV 3.4 [upstream opencv_contrib/modules/xfeatures2d/src/surf.cpp, modules/imgproc color / resize /
  * smooth, modules/core mathfuncs], defaults nOctaves = 4, nOctaveLayers = 3, extended = false, upright = false:
  *   gray        (B*1868 + G*9617 + R*4899 + 8192) >> 14   (cvtColor BGR2GRAY, 14-bit fixed point)
  *   integral    32-bit sums, one row and column larger than the image
  *   layers      size = (9 + 6 layer) << octave, sample step = 1 << octave, 5 layers per octave; box filters dx, dy (3 boxes,
  *               weights 1 -2 1) and dxy (4 boxes, 1 -1 -1 1) of the 9 x 9 template scaled by cvRound(size / 9 * coord), each box
- *               normalised by its area; det = dx dy - 0.81 dxy^2, trace = dx + dy (float)
- *   maxima      middle layers only; det > threshold and strictly greater than its 26 neighbours; 3-D quadratic refinement
- *               (A x = b by LU with partial pivoting in float), kept iff x != 0 and |x_i| <= 1; pt += x * step,
+ *               normalised by its area; det = dx dy - 0.81 dxy^2, trace = dx + dy (float).  A layer is a grid of (rows / step) x
+ *               (cols / step) samples; the filter whose top-left corner is (i step, j step) writes sample (i + m, j + m), m = (size / 2) / step
+ *   maxima      middle layers only, samples at least (size of the layer above / 2) / step + 1 from the grid's edge;
+ *               det > threshold and strictly greater than its 26 neighbours; 3-D quadratic refinement
+ *               (A x = b by LU with partial pivoting in float), kept iff x != 0 and |x_i| <= 1; pt = the filter's centre (corner +
+ *               (size - 1) / 2) + x * step,
  *               size = cvRound(size + x_s * (size - size of the layer below)); response = det, class_id = sign(trace);
  *               keypoints sorted by (response, size, octave, y) descending, then x ascending
- *   orientation s = size * 1.2 / 9; Haar responses of side 2 cvRound(2 s) at the 109 grid points of a radius-6 disc scaled by
- *               s, Gaussian weights (sigma 2.5); angles by cv::fastAtan2 (the 7th-order polynomial, degrees); a 60 degree
- *               window slid in 5 degree steps over the rounded angles, the window with the largest summed vector wins;
- *               angle = fastAtan2(-sum_y, sum_x)
- *   descriptor  a (int)(21 s) square window rotated by the angle, sampled bilinearly (cvRound to uchar; border: nearest
+ *   orientation s = size * 1.2 / 9; Haar responses of side g = 2 cvRound(2 s) at the 113 grid points (i, j), i^2 + j^2 <= 36, of a
+ *               radius-6 disc scaled by s (the paper's "circular neighbourhood of radius 6s"; the 13 x 13 grid's 169 points less 14
+ *               per corner), wavelet corner at cvRound(pt + (i, j) s - (g - 1) / 2), a
+ *               point takes part iff its wavelet lies inside the image; X = right half - left half, Y = upper half - lower half;
+ *               Gaussian weights (sigma 2.5); angles by cv::fastAtan2 (the 7th-order polynomial, degrees); a 60 degree
+ *               window slid in 5 degree steps over the rounded angles, the window with the largest summed vector wins (the first
+ *               of equals); angle = fastAtan2(-sum_y, sum_x)
+ *   descriptor  a (int)(21 s) square window rotated by the angle (column axis along (cos, sin) of it, y down; cos, sin, the
+ *               first row's start and every further row start -- the previous one plus the step -- are floats, positions along a row
+ *               double), sampled bilinearly (cvRound to uchar; border: nearest
  *               clamped pixel), shrunk to 21 x 21 by area averaging (INTER_AREA, general weighted form), 20 x 20 gradients
  *               (2 x 2 differences) weighted by a Gaussian (sigma 3.3), 4 x 4 cells of 5 x 5 samples with sum dx, sum dy,
  *               sum |dx|, sum |dy|, normalised to unit length.  Keypoints whose orientation cannot be sampled are dropped.

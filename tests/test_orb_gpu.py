@@ -1,6 +1,6 @@
 """Parity of the HIP ORB detector + descriptor (ORB half; reference
 FeatureMatching::detectFeaturesORB, cpp_code/src/feature_matching.cpp:14-41) through the C ABI against the CPU oracle
-(oracle/orb_ref.c, parity unpinned: OpenCV absent, own test point pairs): keypoints and descriptors bit for bit -- the image
+(oracle/orb_ref.c, pinned to its rule list by tests/orb_ref.py; OpenCV absent, own test point pairs): keypoints and descriptors bit for bit -- the image
 arithmetic is integer, the few float expressions keep their operation order, cos / sin come from the host's libm on both sides.
 Then the properties an ORB implementation must have and the hand-off to the Hamming matcher."""
 import os

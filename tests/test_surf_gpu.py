@@ -1,5 +1,5 @@
 """Parity of the HIP SURF detector + descriptor (reference FeatureMatching::detectFeaturesSURF,
-cpp_code/src/feature_matching.cpp:43-58) through the C ABI against the CPU oracle: keypoints and descriptors bit for bit (both
+cpp_code/src/feature_matching.cpp:43-58) through the C ABI against the CPU oracle (pinned to its rule list by tests/surf_ref.py): keypoints and descriptors bit for bit (both
 sides keep OpenCV's float operation order; the Gaussian tables come from the host's exp() on both), on real texture (the
 reference's first two test images at half resolution) and on synthetic images; then the properties a SURF implementation
 must have (rotation invariance, repeatability under a shift) and the hand-off to the matcher."""
