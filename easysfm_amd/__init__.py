@@ -31,6 +31,7 @@ from .mesh import (MeshCleanOptions, MeshOptions, MeshSimplifyOptions, MeshTextu
                    dense_mesh, masked_depth, mesh_arrays, mesh_clean, mesh_components, mesh_grid, mesh_simplify, mesh_texture,
                    mesh_texture_bake, mesh_texture_level, mesh_texture_views, mvs_mesh, tsdf_extract, tsdf_grid, tsdf_integrate)
 from .render import MeshRenderOptions, default_mesh_render_options, mesh_render, mesh_render_error, orbit_poses  # noqa: F401
+from .tracks import TrackOptions, TrackResult, refine_tracks, track_evaluate, track_observations, track_triangulate  # noqa: F401
 from .pipeline import MATCH_FILTERS, FramePair, match_and_verify_all_pairs, propagate_track_ids, run_sfm  # noqa: F401
 
 __version__ = "0.1.0"

@@ -57,6 +57,7 @@ EXPORTED_SYMBOLS = [
     "esfm_mesh_texture_options_default", "esfm_mesh_texture_views", "esfm_mesh_texture_bake",
     "esfm_mesh_texture_level_options_default", "esfm_mesh_texture_level", "esfm_mesh_texture_bake_ex",
     "esfm_mesh_render_options_default", "esfm_mesh_render",
+    "esfm_track_options_default", "esfm_track_triangulate", "esfm_track_evaluate", "esfm_track_triangulate_host", "esfm_track_evaluate_host",
 ]
 
 
@@ -151,6 +152,12 @@ class MeshTextureLevelStats(C.Structure):
 class MeshRenderOptions(C.Structure):
     """esfm_mesh_render_options (include/esfm.h, "Mesh rendering")."""
     _fields_ = [("background", C.c_uint8 * 3), ("reserved", C.c_uint8)]
+
+
+class TrackOptionsStruct(C.Structure):
+    """esfm_track_options (include/esfm.h, "Track triangulation")."""
+    _fields_ = [("max_reproj_error_px", C.c_double), ("min_angle_deg", C.c_double), ("cos_min_angle", C.c_double),
+                ("min_views", C.c_int32), ("max_hypotheses", C.c_int32), ("refine_iterations", C.c_int32), ("reserved", C.c_int32)]
 
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p)
@@ -297,6 +304,14 @@ def lib() -> C.CDLL:
     L.esfm_mesh_render_options_default.restype = None
     L.esfm_mesh_render.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp,
                                    C.POINTER(MeshRenderOptions), vp, vp, vp]
+    L.esfm_track_options_default.argtypes = [C.POINTER(TrackOptionsStruct)]
+    L.esfm_track_options_default.restype = None
+    track_in = [C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, C.POINTER(TrackOptionsStruct)]   # n_cam .. xyz_in, options
+    track_out = [vp, vp, vp, vp, vp, vp]                                                            # obs_inlier .. pt_mse
+    L.esfm_track_triangulate.argtypes = [vp] + track_in + [vp] + track_out
+    L.esfm_track_evaluate.argtypes = [vp] + track_in + track_out
+    L.esfm_track_triangulate_host.argtypes = track_in + [vp] + track_out
+    L.esfm_track_evaluate_host.argtypes = track_in + track_out
     L.esfm_solve_pnp_ransac.argtypes = [vp, vp, vp, C.c_int, vp, C.c_int, C.c_double, C.c_double, vp, vp, vp, vp, i32p, i32p]
     L.esfm_ba_problem_set_params.argtypes = [vp, vp, vp]
     L.esfm_ba_problem_solve.argtypes = [vp, C.POINTER(BAOptions), ALLREDUCE_FN, vp, C.POINTER(BASummary)]

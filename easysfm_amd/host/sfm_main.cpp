@@ -96,7 +96,9 @@ int main(int argc, char **argv)
 {
     if (argc == 4 && std::string(argv[1]) == "--dump-image") return dump_image(argv[2], argv[3]);
     // optional 14th argument: the match filter -- ratio (the reference's, default), cross (mutual nearest neighbours) or ratio+cross,
-    // or one of these with +guided appended (a second, epipolar-guided pass over the verified pairs; the union is kept);
+    // or one of these with +guided appended (a second, epipolar-guided pass over the verified pairs; the union is kept); +tracks behind
+    // any of them (ratio+tracks, ratio+guided+tracks) re-triangulates the cloud's tracks before every bundle adjustment and filters
+    // them after the last (esfm.h "Track triangulation", default options; one "Track refine:" line per call);
     // optional 15th (needs the 14th): a dense .ply path, or none; optional 16th (needs the 15th): a .ply path for the merged dense cloud
     // (one oriented point per voxel), or none; optional 17th (needs the 16th): a .ply path for the surface mesh, or none; clean:mesh.ply
     // cleans the mesh with the defaults of esfm.h "Mesh clean-up" before it is written to mesh.ply, simplify:mesh.ply merges the
@@ -107,7 +109,10 @@ int main(int argc, char **argv)
     // optional 18th (needs a mesh as the 17th): an existing directory, or none: the mesh is drawn into every registered frame (esfm.h "Mesh
     // rendering"; with the atlas if it was textured, else with its vertex colours), the pictures go there as render_%04d.png and one
     // "Mesh render:" line states their mean absolute error against the photographs
-    const std::string filter_arg = argc >= 15 ? argv[14] : "ratio";
+    std::string filter_arg = argc >= 15 ? argv[14] : "ratio";
+    const std::string tracks_suffix = "+tracks";
+    const bool refine_tracks = filter_arg.size() > tracks_suffix.size() && filter_arg.compare(filter_arg.size() - tracks_suffix.size(), tracks_suffix.size(), tracks_suffix) == 0;
+    if (refine_tracks) filter_arg.erase(filter_arg.size() - tracks_suffix.size());
     const std::string guided_suffix = "+guided";
     const bool guided = filter_arg.size() > guided_suffix.size() && filter_arg.compare(filter_arg.size() - guided_suffix.size(), guided_suffix.size(), guided_suffix) == 0;
     const std::string match_filter = guided ? filter_arg.substr(0, filter_arg.size() - guided_suffix.size()) : filter_arg;      // the first pass's filter
@@ -142,7 +147,7 @@ int main(int argc, char **argv)
     if (argc < 14 || argc > 19 || (match_filter != "ratio" && match_filter != "cross" && match_filter != "ratio+cross") || level_alone || render_alone) {
         std::cerr << "usage: sfm_native image_folder image_list calib_K_file calib_distort_file output.ply feature_type(S | O | I) feature_parameter "
                      "repro_dis_ransac find_init_frames(0 | 1 | 2: as 1, and no planar or rotation-only initial pair) ba_calib_change_tolerance ba_frequency launch_viewer view_sphere [match_filter: ratio | cross | ratio+cross | "
-                     "ratio+guided | cross+guided | ratio+cross+guided [dense.ply | none [merged.ply | none [simplify:mesh.ply | "
+                     "ratio+guided | cross+guided | ratio+cross+guided, each also with +tracks appended [dense.ply | none [merged.ply | none [simplify:mesh.ply | "
                      "clean+simplify:mesh.ply | mesh.ply | clean:mesh.ply | none [render_dir | none]]]]] (the 17th's prefix also takes +texture: texture:, clean+texture:, "
                      "simplify+texture:, clean+simplify+texture:) (and +level behind +texture: texture+level:, clean+texture+level:, simplify+texture+level:, "
                      "clean+simplify+texture+level:) (render_dir, the 18th: an existing directory for render_%04d.png, one re-render of the mesh per "
@@ -413,6 +418,9 @@ int main(int argc, char **argv)
         std::vector<bool> todo(nf, true);
         todo[size_t(init_1)] = todo[size_t(init_2)] = false;
         BundleAdjustment ba;
+        esfm_track_options track_options;
+        esfm_track_options_default(&track_options);
+        if (refine_tracks && !ee.refineTracks(frames, todo, cloud, track_options)) return 3;
         t_register += clk.lap();
         ba.doSFMBA(frames, todo, cloud, fix_calib_tolerance_BA);
         t_ba += clk.lap(); ++n_ba;
@@ -440,15 +448,18 @@ int main(int argc, char **argv)
             t_register += clk.lap();
             if (remaining % frequency_BA == 0) {
                 ba.initBA();
+                if (refine_tracks) { if (!ee.refineTracks(frames, todo, cloud, track_options)) return 3; t_register += clk.lap(); }
                 ba.doSFMBA(frames, todo, cloud, fix_calib_tolerance_BA);
                 reproj = ransac_reproj_distance;
                 t_ba += clk.lap(); ++n_ba;
             }
             std::cout << "Progress: [ " << frame_number - remaining << " / " << frame_number << " ]" << std::endl;
         }
+        if (refine_tracks && !ee.refineTracks(frames, todo, cloud, track_options)) return 3;
         clk.lap();
         ba.doSFMBA(frames, todo, cloud);
         t_ba += clk.lap(); ++n_ba;
+        if (refine_tracks && !ee.refineTracks(frames, todo, cloud, track_options, true)) return 3;
 
         // ---- final cloud: SOR filter, .ply (sfm.cpp:329-337)
         std::vector<PointXYZRGB> filtered;

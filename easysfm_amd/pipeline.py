@@ -23,6 +23,7 @@ from .mesh import (MeshCleanOptions, MeshOptions, auto_texels, default_atlas_wid
                    mesh_texture_bake, mesh_texture_level, mesh_texture_views)
 from .render import mesh_render, mesh_render_error
 from .mvs import MergeOptions, default_mvs_options, dense_reconstruction, frame_arrays, merge_arrays
+from .tracks import TrackOptions, refine_tracks
 from .types import DMatch, Frame, SparsePointCloud
 
 
@@ -182,7 +183,7 @@ def run_sfm(frames: List[Frame], output_file: Optional[str] = None, use_feature:
             dense_merged_output_file: Optional[str] = None, dense_mesh_output_file: Optional[str] = None,
             dense_mesh_clean: Optional[MeshCleanOptions] = None, dense_mesh_simplify: Optional[float] = None,
             dense_mesh_texture: Optional[int] = None, dense_mesh_texture_level: bool = False, dense_mesh_render_dir: Optional[str] = None,
-            init_max_h_inlier_ratio: Optional[float] = None):
+            init_max_h_inlier_ratio: Optional[float] = None, track_refine: Optional[TrackOptions] = None):
     """sfm.cpp:128-339.  Returns (sparse cloud before the final filter, filtered cloud, img_match_graph).
     dense_output_file: after the final BA and the sparse .ply, run dense_reconstruct on the registered frames and the cloud
     before the filter (it carries the track ids) and write the dense cloud there (esfm.h "Dense reconstruction").
@@ -210,7 +211,12 @@ def run_sfm(frames: List[Frame], output_file: Optional[str] = None, use_feature:
     init_max_h_inlier_ratio: when given, every verified pair also gets a homography RANSAC (match_and_verify_all_pairs'
     homography_check) and findInitializeFramePair skips the pairs whose h_inlier_ratio exceeds this limit (0.8 separates planar and
     rotation-only pairs from general ones by an order of magnitude: DESIGN 6.4); prints one "Init pair:" line.  None: no check, every
-    output as before."""
+    output as before.
+    track_refine: when given, tracks.refine_tracks runs immediately before every doSFMBA call (every cloud point is re-triangulated
+    from all its observations in the registered frames; points that fail the reprojection / depth / angle verdict and the outlier
+    observations of the others leave bundle adjustment) and once more after the final doSFMBA, before SORFilter, as a filter alone
+    (evaluate_only); each call prints one "Track refine:" line (esfm.h "Track triangulation").  A point dropped by one call may be
+    added again by a later doTriangulation and is then judged again.  None: every output as before, to the bit."""
     ctx = ctx or default_context()
     fm, ee = FeatureMatching(ctx), MotionEstimator(ctx)
     for f in frames:
@@ -244,6 +250,8 @@ def run_sfm(frames: List[Frame], output_file: Optional[str] = None, use_feature:
     todo = [True] * len(frames)
     todo[init_1] = todo[init_2] = False
     ba = BundleAdjustment(ctx)
+    if track_refine is not None:
+        refine_tracks(frames, todo, cloud, track_refine, ctx)
     ba.doSFMBA(frames, todo, cloud, fix_calib_tolerance_BA)
     remaining = len(frames) - 2
     reproj = ransac_reproj_distance
@@ -265,11 +273,17 @@ def run_sfm(frames: List[Frame], output_file: Optional[str] = None, use_feature:
         remaining -= 1
         if remaining % frequency_BA == 0:
             ba.initBA()
+            if track_refine is not None:
+                refine_tracks(frames, todo, cloud, track_refine, ctx)
             ba.doSFMBA(frames, todo, cloud, fix_calib_tolerance_BA)
             reproj = ransac_reproj_distance
         if verbose:
             print(f"Progress: [ {len(frames) - remaining} / {len(frames)} ]")
+    if track_refine is not None:
+        refine_tracks(frames, todo, cloud, track_refine, ctx)
     ba.doSFMBA(frames, todo, cloud)
+    if track_refine is not None:
+        refine_tracks(frames, todo, cloud, track_refine, ctx, evaluate_only=True)
     out = CProceesing(ctx).SORFilter(cloud)
     if output_file:
         write_ply(output_file, out)

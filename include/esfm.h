@@ -1304,6 +1304,87 @@ int esfm_mesh_render(esfm_ctx *ctx, int n_vertices, int n_triangles, const float
                      const float *K4 /*4 each*/, const float *poses /*12 each*/, const esfm_mesh_render_options *opt,
                      uint8_t *rgb /*may be NULL*/, float *depth /*may be NULL*/, int32_t *triangle_id /*may be NULL*/);
 
+/* ---- Track triangulation: robust multi-view points and a reprojection filter ------------------------------------
+ * Re-estimates every sparse-cloud point from ALL the observations of its track and judges it by reprojection error, depth sign
+ * and triangulation angle.  Opt-in: nothing else in the library calls it.  One arithmetic (csrc/track_core.hpp: f64, only
+ * + - * / sqrt and comparisons, every sum in a fixed order) serves the kernels, the host build (the *_host entry points, no GPU)
+ * and the restatement in tests/track_ref.py; the three agree to the bit.
+ *
+ * Inputs: bundle adjustment's three observation arrays unchanged (cam_idx, pt_idx, obs_uv float32 pixels), K4 = fx, cx, fy, cy
+ * floats per camera, and a world -> camera [R | t] per camera as 12 doubles, row-major (Rt[4 r + c]; column 3 is t).  A track is
+ * the observations of one point in INPUT order; the arrays need not be grouped.
+ *
+ * Per observation k:  x = (u - cx) / fx, y = (v - cy) / fy;  centre C_j = -((R0j t0 + R1j t1) + R2j t2);
+ *   direction d_j = (R0j x + R1j y) + R2j.  Dot products are (a0 b0 + a1 b1) + a2 b2 throughout.
+ * Projection of X:  p_r = ((Rr0 X0 + Rr1 X1) + Rr2 X2) + t_r;  iz = 1 / p_2;  xn = p_0 iz, yn = p_1 iz;
+ *   ru = (fx xn + cx) - u, rv = (fy yn + cy) - v, err2 = ru ru + rv rv.  Inlier iff p_2 > 0 and err2 <= thr2 (thr2 =
+ *   max_reproj_error_px squared); the cost term is err2 for an inlier and thr2 otherwise (= min(err2, thr2), NaN-free).
+ * Hypotheses: the observation pairs (a, b), a < b, in lexicographic order, P = n (n - 1) / 2 of them.  P <= max_hypotheses: all;
+ *   else hypothesis h (0 <= h < max_hypotheses) is pair number floor(h P / max_hypotheses) in 64-bit integers.  The point is the
+ *   midpoint of the two rays: w = C_a - C_b, aa = d_a.d_a, bb = d_b.d_b, ab = d_a.d_b, dw = d_a.w, ew = d_b.w,
+ *   det = aa bb - ab ab, s = (ab ew - bb dw) / det, t = (aa ew - ab dw) / det, X_j = 0.5 ((C_a,j + s d_a,j) + (C_b,j + t d_b,j)).
+ *   Void unless det > 1e-12 (aa bb) and s > 0 and t > 0.
+ * Rank: (inliers, cost = sum of the cost terms in observation order, hypothesis index) compared as one key: more inliers, then the
+ *   lower cost, then the lower index -- a total order, so the reduction over hypotheses does not depend on its shape.
+ * Refit: refine_iterations Gauss-Newton steps on the best hypothesis's inliers.  Per inlier in observation order, with a = fx iz,
+ *   b = fy iz: Ju_j = a (R0j - xn R2j), Jv_j = b (R1j - yn R2j); A_ij += Ju_i Ju_j + Jv_i Jv_j (i <= j); g_i += Ju_i ru + Jv_i rv.
+ *   LDL' in the order 0, 1, 2 without pivoting: d0 = A00; l10 = A01 / d0; l20 = A02 / d0; d1 = A11 - l10 A01; m = A12 - l20 A01;
+ *   l21 = m / d1; d2 = (A22 - l20 A02) - l21 m;  y0 = -g0; y1 = -g1 - l10 y0; y2 = (-g2 - l20 y0) - l21 y1;  z_i = y_i / d_i;
+ *   e2 = z2; e1 = z1 - l21 e2; e0 = (z0 - l10 e1) - l20 e2;  X += e.  A pivot that is not > 0 or a non-finite new X ends the refit
+ *   with the X before that step.  Inliers are then recomputed once; if the refitted point has fewer than the hypothesis had, the
+ *   hypothesis point and its inliers stand.
+ * Statistics: n_inliers; mse = (sum of the inliers' err2 in observation order) / n_inliers (0 without inliers); min_cos = the
+ *   minimum over inlier pairs of e_i.e_j with e_i = (C_i - X) / sqrt((C_i - X).(C_i - X)) componentwise (1 with fewer than two
+ *   inliers) -- an exact f64 minimum.
+ * Verdict (pt_status): 0 kept; 1 fewer than two observations; 2 no valid hypothesis; 3 n_inliers < min_views; 4 min_cos >
+ *   cos_min_angle; 5 a non-finite uv, K4 or Rt value in the track (or, for evaluate, a non-finite point).  The first that applies
+ *   in the order 1, 5, 2, 3, 4.  Statuses 0, 3, 4 report the estimated point's inliers and statistics; 1, 2, 5 report obs_inlier 0,
+ *   obs_err2 +inf, n_inliers 0, min_cos 1, mse 0.  xyz_out of a point that is not kept is xyz_in's (zeros without xyz_in).
+ *
+ * Options (esfm_track_options_default): max_reproj_error_px 4.0, min_angle_deg 1.5, min_views 2, max_hypotheses 64,
+ * refine_iterations 5.  4 px and 1.5 degrees are the common conventions of incremental SfM; they have NOT been measured on this
+ * project's data.  cos_min_angle is what the verdict compares against; _default sets it to cos(min_angle_deg) and a caller who
+ * changes the angle sets both (the Python and C++ wrappers do).  Rejected with ESFM_ERR_INVALID_ARG, nothing written: options
+ * NULL, a threshold that is not finite and > 0, cos_min_angle NaN, min_views < 2, max_hypotheses outside 1 .. 4096,
+ * refine_iterations outside 0 .. 100, an index out of range, a NULL required array.  A track longer than 65 535 observations is
+ * ESFM_ERR_UNSUPPORTED.
+ *
+ * esfm_track_triangulate / esfm_track_evaluate run on the GPU (host pointers; without a usable device no context exists and
+ * creating one fails with ESFM_ERR_NO_DEVICE: no CPU fallback).  The tracks are grouped on the device: 64-bit keys
+ * (pt_idx << 32 | input index), the radix sort, run heads by the block scan; one wave per track, observations staged in LDS up to
+ * ESFM_TRACK_STAGE_CAP (256) per track, longer tracks read the same records from global memory.  esfm_track_evaluate runs no
+ * hypotheses and no refit: inliers, statistics and verdict of the given points (status 2 cannot occur) -- the filter after BA.
+ * The *_host forms run the same header on the CPU. */
+#define ESFM_TRACK_STAGE_CAP 256
+#define ESFM_TRACK_MAX_OBS 65535
+typedef struct esfm_track_options {
+    double max_reproj_error_px;
+    double min_angle_deg;
+    double cos_min_angle;
+    int32_t min_views;
+    int32_t max_hypotheses;
+    int32_t refine_iterations;
+    int32_t reserved;
+} esfm_track_options;
+void esfm_track_options_default(esfm_track_options *opt);
+int esfm_track_triangulate(esfm_ctx *ctx, int n_cam, int n_pt, int n_obs, const int32_t *cam_idx, const int32_t *pt_idx,
+                           const float *obs_uv /*2 each*/, const float *K4_per_cam, const double *Rt12_per_cam,
+                           const double *xyz_in /*3 n_pt or NULL*/, const esfm_track_options *opt, double *xyz_out /*3 n_pt*/,
+                           uint8_t *obs_inlier /*n_obs*/, float *obs_err2 /*n_obs or NULL*/, int32_t *pt_status /*n_pt*/,
+                           int32_t *pt_n_inliers /*n_pt*/, double *pt_min_cos /*n_pt or NULL*/, double *pt_mse /*n_pt or NULL*/);
+int esfm_track_evaluate(esfm_ctx *ctx, int n_cam, int n_pt, int n_obs, const int32_t *cam_idx, const int32_t *pt_idx,
+                        const float *obs_uv, const float *K4_per_cam, const double *Rt12_per_cam, const double *xyz_in /*3 n_pt*/,
+                        const esfm_track_options *opt, uint8_t *obs_inlier, float *obs_err2 /*or NULL*/, int32_t *pt_status,
+                        int32_t *pt_n_inliers, double *pt_min_cos /*or NULL*/, double *pt_mse /*or NULL*/);
+int esfm_track_triangulate_host(int n_cam, int n_pt, int n_obs, const int32_t *cam_idx, const int32_t *pt_idx, const float *obs_uv,
+                                const float *K4_per_cam, const double *Rt12_per_cam, const double *xyz_in /*or NULL*/,
+                                const esfm_track_options *opt, double *xyz_out, uint8_t *obs_inlier, float *obs_err2 /*or NULL*/,
+                                int32_t *pt_status, int32_t *pt_n_inliers, double *pt_min_cos /*or NULL*/, double *pt_mse /*or NULL*/);
+int esfm_track_evaluate_host(int n_cam, int n_pt, int n_obs, const int32_t *cam_idx, const int32_t *pt_idx, const float *obs_uv,
+                             const float *K4_per_cam, const double *Rt12_per_cam, const double *xyz_in,
+                             const esfm_track_options *opt, uint8_t *obs_inlier, float *obs_err2 /*or NULL*/, int32_t *pt_status,
+                             int32_t *pt_n_inliers, double *pt_min_cos /*or NULL*/, double *pt_mse /*or NULL*/);
+
 #ifdef __cplusplus
 }
 #endif
