@@ -1,6 +1,6 @@
-"""Input images shared by the ORB / SURF reference tests (tests/test_orb_ref_cpu.py, tests/test_surf_ref_cpu.py,
-tests/test_feature_ref_gpu.py): one crop of a committed fixture and seeded synthetic images, the smallest that reach every rule
-of the two detectors.  Every case is (name, BGR image, parameter); the gray form of a case is the 14-bit BGR2GRAY of its BGR
+"""Input images shared by the ORB / SURF / SIFT reference tests (tests/test_orb_ref_cpu.py, tests/test_surf_ref_cpu.py,
+tests/test_sift_ref_cpu.py, tests/test_feature_ref_gpu.py): one crop of a committed fixture and seeded synthetic images, the
+smallest that reach every rule of the detectors.  Every case is (name, BGR image, parameter); the gray form of a case is the 14-bit BGR2GRAY of its BGR
 form, taken by the reference under test, so both forms of a case describe the same picture."""
 import functools
 import os
@@ -80,4 +80,35 @@ SURF_CASES = [  # (name, BGR image, hessian threshold)
     ("blobs240x320", lambda: blobs(240, 320, 0, 260), 60.0),
     ("blobs33x40", lambda: blobs(33, 40, 3, 10, 1.5, 3.0), 10.0),
     ("border150x203", lambda: blobs(150, 203, 5, 48, border=True), 60.0),
+]
+
+
+def single_blob(side, ground, sigma, cx, cy):
+    """One Gaussian blob of height 150 on a flat ground, rounded to uint8."""
+    y, x = np.mgrid[0:side, 0:side].astype(np.float64)
+    return np.rint(ground + 150 * np.exp(-((x - cx) ** 2 + (y - cy) ** 2) / (2 * sigma * sigma))).astype(np.uint8)
+
+
+def blob11_symmetric():
+    """11 x 11, centred exactly on pixel (5, 5): its keypoint lies in the octave of side 11, whose only searchable position is
+    (5, 5).  The picture equals its own transpose, so whole diagonals of orientation samples have |dx| = |dy| exactly, where
+    cv::fastAtan2 jumps from 44.990 to 45.010 degrees across a bin edge: which peaks exist turns on float32 round-off alone."""
+    return single_blob(11, 100, 2.5, 5.0, 5.0)
+
+
+def _gray3(gray):
+    return np.repeat(gray[:, :, None], 3, axis=2)             # 1868 + 9617 + 4899 = 2^14: the gray of (g, g, g) is g
+
+
+SIFT_CASES = [  # (name, BGR image, keypoints the CPU restatement returns)
+    ("fountain256x320", fountain_crop, 299),                                          # octaves -1..4
+    ("blobs240x320", lambda: blobs(240, 320, 0, 260), 197),                           # five octaves
+    ("blobs33x40", lambda: blobs(33, 40, 3, 10, 1.5, 3.0), 7),                        # smallest general picture
+    # orientation discs and descriptor windows that leave the image.  Seed 9, not SURF's 5: with seed 5 three of 61 keypoints
+    # (4.9 %) turn on a decision within the float32 bound, above the cap of the reference tests
+    ("border150x203", lambda: blobs(150, 203, 9, 48, border=True), 72),
+    ("checker168", lambda: _gray3(checker()), 537),                                   # massive ties: 488 share a response
+    # an octave with one searchable position.  blob11_symmetric moved off its axes of symmetry (see there): 2 orientations
+    ("blob11", lambda: _gray3(single_blob(11, 100, 2.5, 5.1, 4.95)), 2),
+    ("blob24", lambda: _gray3(single_blob(24, 60, 4.0, 11.8, 12.3)), 5),              # descriptor radius 36 clipped to the diagonal 33
 ]

@@ -1,8 +1,9 @@
-"""The HIP ORB and SURF detectors against the independent statements tests/orb_ref.py and tests/surf_ref.py -- the same `verify`
-and the same caps that pin the CPU oracle in tests/test_orb_ref_cpu.py / tests/test_surf_ref_cpu.py, run on the library's output
-directly, in gray and in BGR form -- and the host-side selection paths the bit-parity tests leave out, bit for bit against the
-CPU oracle: small and zero quotas, max_keypoints, massive ties, minimum image sizes, SURF's candidate read-back past its first
-chunk and keypoints whose window and orientation disc leave the image."""
+"""The HIP ORB, SURF and SIFT detectors against the independent statements tests/orb_ref.py, tests/surf_ref.py and
+tests/sift_np.py -- the same `verify` and the same caps that pin the CPU oracle in tests/test_orb_ref_cpu.py /
+tests/test_surf_ref_cpu.py / tests/test_sift_ref_cpu.py, run on the library's output directly, in gray and in BGR form -- and
+the host-side selection paths the bit-parity tests leave out, bit for bit against the CPU oracle: small and zero quotas,
+max_keypoints, massive ties, minimum image sizes, SURF's candidate read-back past its first chunk, keypoints whose window and
+orientation disc leave the image, and for SIFT the smallest octaves, empty results and both cuts."""
 import functools
 import os
 import re
@@ -13,7 +14,9 @@ import pytest
 import easysfm_amd as E
 import feature_cases as F
 import orb_ref as O
+import sift_np as N
 import surf_ref as R
+from sift_ref import SiftRef
 
 pytestmark = pytest.mark.gpu
 UNDECIDED_CAP = 0.02
@@ -182,3 +185,92 @@ def test_surf_border_keypoints(gpu_ctx, oracle_lib):
     edge = np.minimum(np.minimum(kp[:, 0], gray.shape[1] - 1 - kp[:, 0]), np.minimum(kp[:, 1], gray.shape[0] - 1 - kp[:, 1]))
     half_window = np.array([R.window_size(s) for s in kp[:, 2]]) / 2
     assert (edge < half_window).sum() >= 10 and (edge < 6 * kp[:, 2] * 1.2 / 9).sum() >= 10
+
+
+# ---- SIFT: the same verifier on the library's output ------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def sref(tmp_path_factory):
+    return SiftRef(tmp_path_factory.mktemp("sift_ref"))
+
+
+@functools.lru_cache(maxsize=None)
+def _sift_stages(name):
+    _, make, n = next(c for c in F.SIFT_CASES if c[0] == name)
+    return make(), n, N.Stages(make())
+
+
+@pytest.mark.parametrize("form", ["gray", "bgr"])
+@pytest.mark.parametrize("name", [c[0] for c in F.SIFT_CASES])
+def test_sift_library_passes_verifier(gpu_ctx, name, form):
+    img, n, st = _sift_stages(name)
+    kp, d = E.sift_detect_and_compute(img if form == "bgr" else N.as_gray(img), 0, None, gpu_ctx)
+    rep = N.verify(img, {"nfeatures": 0}, kp, d, st)
+    print(name, form, rep, "undecided share %.4f" % rep.undecided_share())
+    assert rep.ok, rep.errors[:10]
+    assert rep.n_reported == n and rep.undecided_share() <= UNDECIDED_CAP
+    assert rep.n_described >= min(len(kp), 150) - len(rep.undecided) and rep.max_desc_distance <= N.DESC_TOL
+    if name in ("fountain256x320", "blobs240x320"):
+        assert rep.n_reported > 100
+    if name == "blob24":
+        assert rep.n_clipped_radius >= 1
+    if name == "border150x203":
+        assert rep.n_partial_disc >= 10
+
+
+# ---- SIFT bit for bit on the pictures tests/test_sift_gpu.py leaves out ----------------------------------------------------
+def _sift_same(got, want):
+    (kg, dg), (kw, dw) = got, want
+    assert kg.shape == kw.shape, (kg.shape, kw.shape)
+    assert np.array_equal(_bits(kg), _bits(kw)) and np.array_equal(_bits(dg), _bits(dw))
+
+
+def test_sift_smallest_octaves_and_ties(gpu_ctx, sref):
+    """11 x 11: the keypoint lies in the octave of side 11, whose only searchable position is (5, 5), and its orientation disc and
+    descriptor window cover the whole octave (the symmetric blob, whose peaks turn on float32 round-off alone, and the one moved
+    off its axes).  24 x 24: descriptor radius 36 clipped to the octave's diagonal 33.  checker: 537 keypoints, 488 of which
+    repeat an earlier response.  White noise: 479 keypoints of the finest layers."""
+    for img, n in ((F.blob11_symmetric(), 1), (F.single_blob(11, 100, 2.5, 5.1, 4.95), 2), (F.single_blob(24, 60, 4.0, 11.8, 12.3), 5),
+                   (F.checker(), 537), (F.white_noise(296, 390, 7), 479)):
+        want = sref.detect(img)
+        assert len(want[0]) == n
+        _sift_same(E.sift_detect_and_compute(img, 0, None, gpu_ctx), want)
+    kp = sref.detect(F.single_blob(24, 60, 4.0, 11.8, 12.3))[0]
+    assert len(np.unique(kp[:, :3], axis=0)) == 1 and len(np.unique(kp[:, 3])) == 5           # five orientations of one point
+
+
+@pytest.mark.parametrize("shape", [(1, 1), (2, 2), (3, 3), (5, 5), (6, 200), (200, 6), (1, 200), (200, 1), (40, 40)])
+def test_sift_empty_results(gpu_ctx, sref, shape):
+    """No octave at all (one row or column), octaves narrower than the border of 5, taps wider than the image, and a constant
+    picture: every kernel runs on a degenerate pyramid and both sides return nothing, without an error."""
+    img = np.full(shape, 77, np.uint8) if shape == (40, 40) else (np.arange(shape[0] * shape[1]) * 37 % 256).astype(np.uint8).reshape(shape)
+    for im in (img, np.repeat(img[:, :, None], 3, axis=2)):
+        kp, d = E.sift_detect_and_compute(im, 0, None, gpu_ctx)
+        assert kp.shape == (0, 7) and d.shape == (0, 128)
+    kw, dw = sref.detect(img)
+    assert len(kw) == 0 and len(dw) == 0
+
+
+def test_sift_selection_edges(gpu_ctx, sref):
+    """nfeatures 1; a cut inside one candidate's orientations (the tie is kept); n - 1; n and beyond; 0 (all).  max_keypoints 0, 1
+    and n are prefixes of the full result.  All bit-equal to the CPU restatement, and the cut lists pass the verifier."""
+    img, n, st = _sift_stages("fountain256x320")
+    gray = N.as_gray(img)
+    full = E.sift_detect_and_compute(gray, 0, None, gpu_ctx)
+    _sift_same(full, sref.detect(gray))
+    assert len(full[0]) == n
+    resp = np.sort(full[0][:, 4])[::-1]
+    tied = next(i + 1 for i in range(1, n - 1) if resp[i] == resp[i + 1])
+    for nf in (1, tied, n - 1, n, n + 7):
+        got = E.sift_detect_and_compute(gray, nf, None, gpu_ctx)
+        _sift_same(got, sref.detect(gray, nf))
+        sel = full[0][:, 4] >= resp[min(nf, n) - 1]
+        _sift_same(got, (full[0][sel], full[1][sel]))
+        assert len(got[0]) >= min(nf, n) and N.verify(gray, {"nfeatures": nf}, *got, st).ok
+    assert len(E.sift_detect_and_compute(gray, tied, None, gpu_ctx)[0]) > tied
+    for cap in (0, 1, n):
+        got = E.sift_detect_and_compute(gray, 0, cap, gpu_ctx)
+        _sift_same(got, (full[0][:cap], full[1][:cap]))
+        _sift_same(got, sref.detect(gray, 0, cap))
+        assert N.verify(gray, {"nfeatures": 0, "max_keypoints": cap}, *got, st).ok
+    got = E.sift_detect_and_compute(gray, tied, 5, gpu_ctx)                                  # both cuts: the prefix of the nfeatures list
+    _sift_same(got, sref.detect(gray, tied, 5))
