@@ -43,7 +43,9 @@ __device__ __forceinline__ double l2x1_e1(double qn, double rq, double sqrt_tmax
 //    result stays bit-identical to the oracle whatever the data;
 //  * 512 queries per item (four sets of 32 per wave), a ring of two 32-KiB tiles of bf16(t) rows fed by LDS-DMA, 12-bit position
 //    codes in the group keys: l2x1_segment_gfx950.inc (gen_l2x1_segment_asm.py) is the whole main loop.  Train sets the code cannot
-//    number skip this pass (l2_x1_supported).
+//    number skip this pass (l2_x1_supported).  Since round 10 the loop itself runs on v_mfma_f32_16x16x32_bf16 -- eight K = 32
+//    instructions per 32 x 32 x 64 tile, a wave's sets split into eight of 16 queries (ESFM_L2X1_QSETS), a fold group per lane
+//    quarter, the quarters of a lane half merged at the end of the block -- and leaves the keys of the 32-query sets as before.
 constexpr int l2x1_query_block_c = 128 * ESFM_L2X1_SETS;
 // Cross-lane moves without an address register (__shfl_xor goes through ds_bpermute_b32, whose lane addresses the compiler hoists out
 // of l2_knn_bf16x1_kernel's item loop and then has to keep in scratch memory across the main loop's asm block).
@@ -146,10 +148,12 @@ __device__ __forceinline__ void l2_knn_bf16x1_body(const int bid, const int G, c
     };
 
     // what the set-up of an item leaves in registers until its round trip is over
-    u32x4 bq[NS][4];                     // B operands: bf16(-2 q), this lane's 8 features of every K-step
+    constexpr int QS = ESFM_L2X1_QSETS;  // sets of 16 queries per wave: set 2 s + b = queries 16 b .. 16 b + 15 of the 32-query set s
+    static_assert(QS == 2 * NS, "the main loop's 16-query sets halve the tail's 32-query sets");
+    u32x4 bq[QS][2];                     // B operands: bf16(-2 q), this lane's 8 features of both 32-feature K-steps
     float st_norm[2], st_qn[2], st_rq[2], st_m, st_r;
     // set-up, part 1: every load of the item goes out (and the ring's first tiles: LDS-DMA, wave w rows [TT/4 w, TT/4 (w + 1)) of a
-    // tile, 8 rows = 1 KiB per instruction, lane l -> row l >> 3, physical slot l & 7 = logical slot (l & 7) ^ ((row >> 1) & 7))
+    // tile, 8 rows = 1 KiB per instruction, lane l -> row l >> 3, physical slot l & 7 = logical slot (l & 7) ^ (((row >> 1) & 3) | ((row >> 2) & 4)): the generator's lds_phys_slot)
     auto stage_issue = [&](const X1Item &it) {
         const int nt = it.nt, nq = it.nq;
         const int ntiles = (nt + TT - 1) / TT;
@@ -166,17 +170,17 @@ __device__ __forceinline__ void l2_knn_bf16x1_body(const int bid, const int G, c
 #pragma unroll
             for (int i = 0; i < TT / 32; ++i) {
                 const int row = wave_s * (TT / 4) + 8 * i + (lane >> 3);
-                const int voff = row * (HS * 16) + (((lane & 7) ^ ((row >> 1) & 7)) * 16);
+                const int voff = row * (HS * 16) + (((lane & 7) ^ (((row >> 1) & 3) | ((row >> 2) & 4))) * 16);
                 lds_dma_b128(lds_tile_addr + (uint32_t)(b * TILE_BYTES + (wave_s * (TT / 4) + 8 * i) * (HS * 16)), voff, trsrc, b * TILE_BYTES);
             }
         }
         const int qbase = it.qblk * QB + wave * 32 * NS;
         const __amdgpu_buffer_rsrc_t qrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<u32x4 *>(hi_q + (size_t)it.q_row0 * HS), 0, nq * (HS * 16), 0x00020000);   // rows past nq read as zeros
 #pragma unroll
-        for (int s = 0; s < NS; ++s) {
-            const int voff = (qbase + 32 * s + j) * (HS * 16) + h * 16;
+        for (int s = 0; s < QS; ++s) {        // lane (n = lane & 15, c = lane >> 4): query n of the set, slot 4 ks + c of its row
+            const int voff = (qbase + 16 * s + (lane & 15)) * (HS * 16) + (lane >> 4) * 16;
 #pragma unroll
-            for (int ks = 0; ks < 4; ++ks) bq[s][ks] = __builtin_amdgcn_raw_buffer_load_b128(qrsrc, voff + 32 * ks, 0, 0);
+            for (int ks = 0; ks < 2; ++ks) bq[s][ks] = __builtin_amdgcn_raw_buffer_load_b128(qrsrc, voff + 64 * ks, 0, 0);
         }
         const float *__restrict__ tn = norms + it.t_row0;
         const float *__restrict__ tr = rho_t + it.t_row0;
@@ -233,8 +237,8 @@ __device__ __forceinline__ void l2_knn_bf16x1_body(const int bid, const int G, c
             const u32x4 nrsrc = raw_buffer_rsrc(norms + cur.t_row0, (uint32_t)nt * 4u);
             asm volatile(ESFM_L2X1_SEGMENT_ASM
                          :
-                         : "v"(bq[0][0]), "v"(bq[0][1]), "v"(bq[0][2]), "v"(bq[0][3]), "v"(bq[1][0]), "v"(bq[1][1]), "v"(bq[1][2]), "v"(bq[1][3]),
-                           "v"(bq[2][0]), "v"(bq[2][1]), "v"(bq[2][2]), "v"(bq[2][3]), "v"(bq[3][0]), "v"(bq[3][1]), "v"(bq[3][2]), "v"(bq[3][3]),
+                         : "v"(bq[0][0]), "v"(bq[0][1]), "v"(bq[1][0]), "v"(bq[1][1]), "v"(bq[2][0]), "v"(bq[2][1]), "v"(bq[3][0]), "v"(bq[3][1]),
+                           "v"(bq[4][0]), "v"(bq[4][1]), "v"(bq[5][0]), "v"(bq[5][1]), "v"(bq[6][0]), "v"(bq[6][1]), "v"(bq[7][0]), "v"(bq[7][1]),
                            "s"(ntiles), "s"(nt), "s"(trsrc), "s"(nrsrc), "s"(lds_tile_addr), "s"(wave_s)
                          : ESFM_L2X1_SEGMENT_CLOBBERS);
         }
