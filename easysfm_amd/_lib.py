@@ -58,6 +58,8 @@ EXPORTED_SYMBOLS = [
     "esfm_mesh_texture_level_options_default", "esfm_mesh_texture_level", "esfm_mesh_texture_bake_ex",
     "esfm_mesh_render_options_default", "esfm_mesh_render",
     "esfm_track_options_default", "esfm_track_triangulate", "esfm_track_evaluate", "esfm_track_triangulate_host", "esfm_track_evaluate_host",
+    "esfm_retrieval_options_default", "esfm_retrieval_train", "esfm_retrieval_vlad", "esfm_retrieval_rank", "esfm_retrieval_pair_list",
+    "esfm_retrieval_pairs", "esfm_retrieval_pairs_dev", "esfm_retrieval_last_stage_ms",
 ]
 
 
@@ -158,6 +160,12 @@ class TrackOptionsStruct(C.Structure):
     """esfm_track_options (include/esfm.h, "Track triangulation")."""
     _fields_ = [("max_reproj_error_px", C.c_double), ("min_angle_deg", C.c_double), ("cos_min_angle", C.c_double),
                 ("min_views", C.c_int32), ("max_hypotheses", C.c_int32), ("refine_iterations", C.c_int32), ("reserved", C.c_int32)]
+
+
+class RetrievalOptionsStruct(C.Structure):
+    """esfm_retrieval_options (include/esfm.h, "Image retrieval")."""
+    _fields_ = [("n_centres", C.c_int32), ("kmeans_iterations", C.c_int32), ("max_train", C.c_int32), ("top_k", C.c_int32),
+                ("window", C.c_int32), ("reserved", C.c_int32)]
 
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p)
@@ -312,6 +320,16 @@ def lib() -> C.CDLL:
     L.esfm_track_evaluate.argtypes = [vp] + track_in + track_out
     L.esfm_track_triangulate_host.argtypes = track_in + [vp] + track_out
     L.esfm_track_evaluate_host.argtypes = track_in + track_out
+    L.esfm_retrieval_options_default.argtypes = [C.POINTER(RetrievalOptionsStruct)]
+    L.esfm_retrieval_options_default.restype = None
+    rows_in = [vp, C.c_int, vp, vp, C.c_int, C.c_int]                                               # ctx, metric, rows, set_row_offset, n_sets, width
+    L.esfm_retrieval_train.argtypes = rows_in + [C.POINTER(RetrievalOptionsStruct), vp]
+    L.esfm_retrieval_vlad.argtypes = rows_in + [C.c_int, vp, vp, vp, vp, vp]
+    L.esfm_retrieval_rank.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp]
+    L.esfm_retrieval_pair_list.argtypes = [C.c_int, C.c_int, vp, C.c_int, vp, i32p]
+    L.esfm_retrieval_pairs.argtypes = rows_in + [C.POINTER(RetrievalOptionsStruct), vp, i32p]
+    L.esfm_retrieval_pairs_dev.argtypes = L.esfm_retrieval_pairs.argtypes
+    L.esfm_retrieval_last_stage_ms.argtypes = [vp, f64p]
     L.esfm_solve_pnp_ransac.argtypes = [vp, vp, vp, C.c_int, vp, C.c_int, C.c_double, C.c_double, vp, vp, vp, vp, i32p, i32p]
     L.esfm_ba_problem_set_params.argtypes = [vp, vp, vp]
     L.esfm_ba_problem_solve.argtypes = [vp, C.POINTER(BAOptions), ALLREDUCE_FN, vp, C.POINTER(BASummary)]

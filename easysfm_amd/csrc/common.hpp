@@ -121,6 +121,10 @@ struct esfm_ctx {
     // the guided matcher's own scratch (guided_api.cpp alone touches it; nothing of `match` is shared with it): pair + geometry tables,
     // both directions' 2-NN tables, and the host-pointer forms' uploaded descriptor rows and keypoints
     esfm::DevBuf guided_tab, guided_idx, guided_dist, guided_bank, guided_kp;
+    // image retrieval's own scratch (retrieval_api.cpp alone touches it): every intermediate of the chain in one carved buffer, and
+    // the host-pointer forms' uploaded descriptor rows
+    esfm::DevBuf retrieval, retrieval_bank;
+    double retrieval_stage_ms[4] = {0, 0, 0, 0};   // under esfm_ctx_set_kernel_timing: the last esfm_retrieval_pairs[_dev] call's train, assign + accumulate, finalise, rank
     // pinned host staging for small tables / counters
     void *pinned = nullptr;
     size_t pinned_cap = 0;

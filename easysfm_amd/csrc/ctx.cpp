@@ -171,7 +171,7 @@ int esfm_ctx_destroy(esfm_ctx *ctx)
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
     for (esfm::DevBuf *b : {&ctx->knn_dist, &ctx->stage_a, &ctx->stage_b, &ctx->stage_c, &ctx->stage_d, &ctx->stage_e, &ctx->guided_tab, &ctx->guided_idx,
-                            &ctx->guided_dist, &ctx->guided_bank, &ctx->guided_kp}) b->release();
+                            &ctx->guided_dist, &ctx->guided_bank, &ctx->guided_kp, &ctx->retrieval, &ctx->retrieval_bank}) b->release();
     ctx->match.release();
     if (ctx->pinned) (void)hipHostFree(ctx->pinned);
     if (ctx->pinned_rounds) (void)hipHostFree(ctx->pinned_rounds);

@@ -367,6 +367,37 @@ public:
         return true;
     }
 
+    // Pair selection in front of the pair loop (esfm.h "Image retrieval", esfm_retrieval_pairs; not in the reference, whose to-do
+    // "add sequential mode" is the options' window): `pairs` becomes the (i, j < i) pairs that retrieval selects among `frames`, in
+    // the loop's order, for matchFeaturesAllPairs or the pair-by-pair loop.  Prints one "Pair selection:" line.
+    bool selectPairs(std::vector<frame_t> &frames, bool hamming, const esfm_retrieval_options &options, std::vector<std::pair<int, int>> &pairs)
+    {
+        pairs.clear();
+        const int n = int(frames.size());
+        int width = 0;
+        for (const frame_t &f : frames) if (f.descriptors.rows > 0) { width = f.descriptors.cols; break; }
+        if (width == 0) { std::cerr << "pair selection: no frame has a descriptor\n"; return false; }
+        const size_t row_bytes = hamming ? size_t(width) : size_t(width) * 4;
+        std::vector<int32_t> off(frames.size() + 1, 0);
+        for (size_t i = 0; i < frames.size(); ++i) {
+            const DescMat &d = frames[i].descriptors;
+            if (d.rows > 0 && (d.cols != width || d.type != (hamming ? DescMat::U8 : DescMat::F32))) { std::cerr << "descriptor shapes differ\n"; return false; }
+            off[i + 1] = off[i] + d.rows;
+        }
+        std::vector<uint8_t> bank(size_t(off.back()) * row_bytes + 16);
+        for (size_t i = 0; i < frames.size(); ++i)
+            if (frames[i].descriptors.rows > 0) std::memcpy(bank.data() + size_t(off[i]) * row_bytes, frames[i].descriptors.bytes.data(), size_t(frames[i].descriptors.rows) * row_bytes);
+        const size_t reach = size_t(std::min(std::max(options.window, 0), std::max(n - 1, 0)));
+        std::vector<int32_t> list(2 * std::max<size_t>(size_t(n) * (size_t(std::max(options.top_k, 0)) + reach), 1));
+        int32_t count = 0;
+        const int rc = esfm_retrieval_pairs(default_ctx(), hamming ? ESFM_HAMMING : ESFM_L2_F32, bank.data(), off.data(), n, width, &options, list.data(), &count);
+        if (rc != ESFM_OK) { std::cerr << esfm_last_error() << std::endl; return false; }
+        for (int32_t p = 0; p < count; ++p) pairs.emplace_back(int(list[2 * size_t(p)]), int(list[2 * size_t(p) + 1]));
+        std::cout << "Pair selection: [" << count << "] of [" << n * (n - 1) / 2 << "] pairs, [" << options.top_k << "] nearest of [" << n << "] images, window ["
+                  << options.window << "], codebook [" << options.n_centres << "] x [" << (hamming ? 8 * width : width) << "]" << std::endl;
+        return true;
+    }
+
     // Epipolar-guided second pass (esfm.h "Epipolar-guided matching", esfm_match_guided_pairs) for pairs that have an essential
     // matrix: E holds 9 doubles per listed pair (what estimate2D2D_E5P_RANSAC[_pairs] returned), K is frame pairs[p].first's for both
     // images as there, max_epipolar_px the RANSAC's threshold, ratio_thre / cross_check the first pass's filter (ratio_thre == 0:

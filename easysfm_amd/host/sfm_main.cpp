@@ -110,6 +110,20 @@ int main(int argc, char **argv)
     // rendering"; with the atlas if it was textured, else with its vertex colours), the pictures go there as render_%04d.png and one
     // "Mesh render:" line states their mean absolute error against the photographs
     std::string filter_arg = argc >= 15 ? argv[14] : "ratio";
+    // +retrieval or +retrievalK (K decimal, 1 .. 999) at the very end, behind everything else (ratio+retrieval, ratio+guided+tracks+retrieval4):
+    // only the pairs that image retrieval selects are matched (esfm.h "Image retrieval", default options, K = top_k; one "Pair selection:" line)
+    bool retrieval = false;
+    int retrieval_top_k = 0;                                 // 0: the default
+    {
+        const std::string token = "+retrieval";
+        const size_t at = filter_arg.rfind(token);
+        if (at != std::string::npos && at > 0) {
+            const std::string k = filter_arg.substr(at + token.size());
+            bool well_formed = k.size() <= 3 && (k.empty() || k[0] != '0');
+            for (char c : k) well_formed = well_formed && c >= '0' && c <= '9';
+            if (well_formed) { retrieval = true; retrieval_top_k = k.empty() ? 0 : std::atoi(k.c_str()); filter_arg.erase(at); }
+        }
+    }
     const std::string tracks_suffix = "+tracks";
     const bool refine_tracks = filter_arg.size() > tracks_suffix.size() && filter_arg.compare(filter_arg.size() - tracks_suffix.size(), tracks_suffix.size(), tracks_suffix) == 0;
     if (refine_tracks) filter_arg.erase(filter_arg.size() - tracks_suffix.size());
@@ -147,7 +161,7 @@ int main(int argc, char **argv)
     if (argc < 14 || argc > 19 || (match_filter != "ratio" && match_filter != "cross" && match_filter != "ratio+cross") || level_alone || render_alone) {
         std::cerr << "usage: sfm_native image_folder image_list calib_K_file calib_distort_file output.ply feature_type(S | O | I) feature_parameter "
                      "repro_dis_ransac find_init_frames(0 | 1 | 2: as 1, and no planar or rotation-only initial pair) ba_calib_change_tolerance ba_frequency launch_viewer view_sphere [match_filter: ratio | cross | ratio+cross | "
-                     "ratio+guided | cross+guided | ratio+cross+guided, each also with +tracks appended [dense.ply | none [merged.ply | none [simplify:mesh.ply | "
+                     "ratio+guided | cross+guided | ratio+cross+guided, each also with +tracks appended, and +retrieval or +retrievalK (K = 1 .. 999 nearest images) at the very end [dense.ply | none [merged.ply | none [simplify:mesh.ply | "
                      "clean+simplify:mesh.ply | mesh.ply | clean:mesh.ply | none [render_dir | none]]]]] (the 17th's prefix also takes +texture: texture:, clean+texture:, "
                      "simplify+texture:, clean+simplify+texture:) (and +level behind +texture: texture+level:, clean+texture+level:, simplify+texture+level:, "
                      "clean+simplify+texture+level:) (render_dir, the 18th: an existing directory for render_%04d.png, one re-render of the mesh per "
@@ -256,9 +270,21 @@ int main(int argc, char **argv)
         std::vector<std::vector<frame_pair_t>> graph(nf, std::vector<frame_pair_t>(nf));
         const double guided_ratio = match_filter == "cross" ? 0.0 : using_feature == 'O' ? 0.8 : using_feature == 'I' ? 0.7 : 0.5;
         const bool pair_by_pair = std::getenv("ESFM_PAIR_BY_PAIR") != nullptr && std::atoi(std::getenv("ESFM_PAIR_BY_PAIR")) != 0;
+        // the pairs to match: every (i, j < i), or those image retrieval selects, in the same order
+        std::vector<std::pair<int, int>> pairs;
+        if (retrieval) {
+            esfm_retrieval_options ro;
+            esfm_retrieval_options_default(&ro);
+            if (retrieval_top_k > 0) ro.top_k = retrieval_top_k;
+            StageClock sc;
+            if (!fm.selectPairs(frames, using_feature == 'O', ro, pairs)) return 3;
+            t_match += sc.lap();
+        } else
+            for (int i = 0; i < frame_number; ++i) for (int j = 0; j < i; ++j) pairs.emplace_back(i, j);
         if (pair_by_pair) {
-            for (int i = 0; i < frame_number; ++i)
-                for (int j = 0; j < i; ++j) {
+            for (const std::pair<int, int> &chosen : pairs) {
+                {
+                    const int i = chosen.first, j = chosen.second;
                     frame_pair_t &g = graph[size_t(i)][size_t(j)];
                     std::vector<DMatch> temp_matches, inlier_matches;
                     StageClock pc;
@@ -291,12 +317,11 @@ int main(int argc, char **argv)
                     }
                     t_verify += pc.lap();
                 }
+            }
         } else {
             // the same loop, batched: one match call for the whole (i, j < i) list, one RANSAC + pose + depth batch for the pairs with
             // more than num_min_pair matches (none of them depends on another pair's result)
             StageClock pc;
-            std::vector<std::pair<int, int>> pairs;
-            for (int i = 0; i < frame_number; ++i) for (int j = 0; j < i; ++j) pairs.emplace_back(i, j);
             std::vector<std::vector<DMatch>> temp_matches;
             const double ratio_thre = match_filter == "cross" ? 0.0 : using_feature == 'I' ? 0.7 : -1.0;        // -1: the S / O members' defaults
             if (!fm.matchFeaturesAllPairs(frames, pairs, using_feature == 'O', temp_matches, ratio_thre, cross_check)) return 3;

@@ -23,6 +23,7 @@ from .mesh import (MeshCleanOptions, MeshOptions, auto_texels, default_atlas_wid
                    mesh_texture_bake, mesh_texture_level, mesh_texture_views)
 from .render import mesh_render, mesh_render_error
 from .mvs import MergeOptions, default_mvs_options, dense_reconstruction, frame_arrays, merge_arrays
+from .retrieval import RetrievalOptions, select_pairs, working_dim
 from .tracks import TrackOptions, refine_tracks
 from .types import DMatch, Frame, SparsePointCloud
 
@@ -55,9 +56,19 @@ def merge_guided(plain, guided):
     return q[order], t[order], d[order]
 
 
+def _checked_pairs(pairs, n_frames: int) -> np.ndarray:
+    """A pair list as match_and_verify_all_pairs takes it: int32 [P, 2], every pair (i, j) with 0 <= j < i < n_frames, none twice."""
+    pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+    if len(pairs) and not (np.all(pairs[:, 1] >= 0) and np.all(pairs[:, 0] > pairs[:, 1]) and np.all(pairs[:, 0] < n_frames)):
+        raise ValueError("pairs must be (i, j) with 0 <= j < i < the number of frames")
+    if len(np.unique(pairs, axis=0)) != len(pairs):
+        raise ValueError("pairs lists a pair twice")
+    return pairs
+
+
 def match_and_verify_all_pairs(frames: Sequence[Frame], use_feature: str = "S", ransac_reproj_distance: float = 1.0,
                                num_min_pair: int = 20, ctx: Optional[Context] = None, match_filter: str = "ratio",
-                               homography_check: bool = False) -> List[List[FramePair]]:
+                               homography_check: bool = False, pairs=None) -> List[List[FramePair]]:
     """sfm.cpp:140-167 for every (i, j < i): matchFeatures{SURF,ORB,SIFT}(frames[i], frames[j]) (use_feature S, O or I); if more than num_min_pair
     matches survive, estimate2D2D_E5P_RANSAC (threshold = ransac_reproj_distance, prob 0.99) and getDepthFast on the inliers;
     otherwise no inliers, identity transform, depth 1 (:147-148).  Returns img_match_graph[i][j].
@@ -69,21 +80,33 @@ def match_and_verify_all_pairs(frames: Sequence[Frame], use_feature: str = "S", 
     homography_check: one esfm_find_homography_pairs call (esfm.h "Homography RANSAC", confidence 0.995) over the same
     correspondences and the same ransac_reproj_distance fills h_inliers and h_inlier_ratio = homography inliers / essential-matrix
     RANSAC inliers (the mask of find_essential_pairs, before recoverPose) of every pair that got an essential matrix; matches, T_21
-    and appro_depth are untouched."""
+    and appro_depth are untouched.
+    pairs: None for every (i, j < i); else an int32 [P, 2] list of (i, j < i) pairs (retrieval.select_pairs' output), or a callable
+    that is given the DescriptorBank built here and returns such a list (so that a selection runs on the rows already uploaded).
+    Only the listed pairs are matched and verified; every other graph[i][j] stays the default FramePair."""
     if match_filter not in MATCH_FILTERS:
         raise ValueError(f"match_filter must be one of {MATCH_FILTERS}, not {match_filter!r}")
     ctx = ctx or default_context()
     n = len(frames)
     metric = ESFM_HAMMING if use_feature == "O" else ESFM_L2_F32
     ratio = {"O": 0.8, "I": 0.7}.get(use_feature, 0.5)                   # I (SIFT): the prototype's nn_ratio
+    selection = pairs
     pairs = np.array([(i, j) for i in range(n) for j in range(i)], np.int32).reshape(-1, 2)
     graph: List[List[FramePair]] = [[FramePair(i, j) for j in range(i)] for i in range(n)]
     if len(pairs) == 0:
         return graph
+    if selection is not None and not callable(selection):
+        pairs = _checked_pairs(selection, n)
+        if len(pairs) == 0:
+            return graph
     guided = match_filter.endswith("+guided")
     first_filter = match_filter[:-len("+guided")] if guided else match_filter
     kps = [np.asarray(f.keypoints, np.float32).reshape(-1, 2) for f in frames] if guided else None
     bank = DescriptorBank([f.descriptors for f in frames], metric, device=f"cuda:{ctx.device}", keypoints=kps)
+    if callable(selection):
+        pairs = _checked_pairs(selection(bank), n)
+        if len(pairs) == 0:
+            return graph
     pm = PairMatcher(bank, pairs, ctx)                                  # drains torch's upload stream before its first launch
     if first_filter == "ratio":
         res = pm.match(ratio).to_host()
@@ -183,7 +206,8 @@ def run_sfm(frames: List[Frame], output_file: Optional[str] = None, use_feature:
             dense_merged_output_file: Optional[str] = None, dense_mesh_output_file: Optional[str] = None,
             dense_mesh_clean: Optional[MeshCleanOptions] = None, dense_mesh_simplify: Optional[float] = None,
             dense_mesh_texture: Optional[int] = None, dense_mesh_texture_level: bool = False, dense_mesh_render_dir: Optional[str] = None,
-            init_max_h_inlier_ratio: Optional[float] = None, track_refine: Optional[TrackOptions] = None):
+            init_max_h_inlier_ratio: Optional[float] = None, track_refine: Optional[TrackOptions] = None,
+            pair_selection: Optional[RetrievalOptions] = None):
     """sfm.cpp:128-339.  Returns (sparse cloud before the final filter, filtered cloud, img_match_graph).
     dense_output_file: after the final BA and the sparse .ply, run dense_reconstruct on the registered frames and the cloud
     before the filter (it carries the track ids) and write the dense cloud there (esfm.h "Dense reconstruction").
@@ -216,13 +240,26 @@ def run_sfm(frames: List[Frame], output_file: Optional[str] = None, use_feature:
     from all its observations in the registered frames; points that fail the reprojection / depth / angle verdict and the outlier
     observations of the others leave bundle adjustment) and once more after the final doSFMBA, before SORFilter, as a filter alone
     (evaluate_only); each call prints one "Track refine:" line (esfm.h "Track triangulation").  A point dropped by one call may be
-    added again by a later doTriangulation and is then judged again.  None: every output as before, to the bit."""
+    added again by a later doTriangulation and is then judged again.  None: every output as before, to the bit.
+    pair_selection: when given, retrieval.select_pairs chooses the pairs to match (esfm.h "Image retrieval": the top_k most similar
+    images of every image by int8 VLAD, plus the `window` preceding ones) on the descriptor rows the matcher has uploaded, and only
+    those pairs are matched and verified; prints one "Pair selection:" line.  None: every output as before, to the bit."""
     ctx = ctx or default_context()
     fm, ee = FeatureMatching(ctx), MotionEstimator(ctx)
     for f in frames:
         f.init_pixel_ids()
-    graph = match_and_verify_all_pairs(frames, use_feature, ransac_reproj_distance, 20, ctx, match_filter,
-                                       homography_check=init_max_h_inlier_ratio is not None)
+    if pair_selection is None:
+        graph = match_and_verify_all_pairs(frames, use_feature, ransac_reproj_distance, 20, ctx, match_filter,
+                                           homography_check=init_max_h_inlier_ratio is not None)
+    else:
+        def choose(bank):
+            chosen = select_pairs(bank, bank.metric, pair_selection, ctx)
+            n = len(frames)
+            print(f"Pair selection: [{len(chosen)}] of [{n * (n - 1) // 2}] pairs, [{pair_selection.top_k}] nearest of [{n}] images, "
+                  f"window [{pair_selection.window}], codebook [{pair_selection.n_centres}] x [{working_dim(bank.metric, bank.width)}]")
+            return chosen
+        graph = match_and_verify_all_pairs(frames, use_feature, ransac_reproj_distance, 20, ctx, match_filter,
+                                           homography_check=init_max_h_inlier_ratio is not None, pairs=choose)
     track, n_unique = propagate_track_ids(frames, graph)
     if verbose:
         for i in range(len(frames)):

@@ -1385,6 +1385,85 @@ int esfm_track_evaluate_host(int n_cam, int n_pt, int n_obs, const int32_t *cam_
                              const esfm_track_options *opt, uint8_t *obs_inlier, float *obs_err2 /*or NULL*/, int32_t *pt_status,
                              int32_t *pt_n_inliers, double *pt_min_cos /*or NULL*/, double *pt_mse /*or NULL*/);
 
+/* ---- Image retrieval: VLAD global descriptors and a k-nearest pair list ------------------------------------------
+ * Which images look alike, as an opt-in stage in front of the matcher: one global descriptor per image (VLAD over a k-means
+ * codebook trained on the run's own local descriptors, quantised to int8), an all-images similarity table on the i8 matrix cores,
+ * the top_k nearest images of each image, and from that table (and an optional window of preceding images) the pair list the
+ * match entry points already take.  The reference has no counterpart (its to-do list's "add sequential mode" is the window part).
+ * Nothing else in the library calls it.  Every sum across descriptors is an integer sum, so it does not depend on order; the
+ * only float arithmetic is per element, in the order stated here.  The kernels and tests/retrieval_ref.py follow this list line
+ * by line and agree to the bit.
+ *
+ * Inputs as esfm_match_pairs: metric, the rows of all sets back to back, set_row_offset[n_sets + 1], width.
+ *   Working dimension d: L2: d = width (1 .. 256).  Hamming: d = 8 width (width 1 .. 64 bytes), component
+ *   t = (byte[t >> 3] >> (t & 7)) & 1 as 0.0f / 1.0f (numpy: unpackbits(bitorder="little")).
+ *   Output dimension D = n_centres d, at most ESFM_RETRIEVAL_MAX_DIM (32768); n_sets at most ESFM_RETRIEVAL_MAX_SETS (8192);
+ *   beyond either: ESFM_ERR_UNSUPPORTED.  A non-finite L2 value, or |x| > 16384, is ESFM_ERR_INVALID_ARG (the bound keeps every
+ *   int64 sum below 2^62).
+ * Distance and assignment: dist(x, m) = acc after acc = 0f; for t ascending: df = x_t - m_t; acc = acc + df df -- all in f32,
+ *   multiply and add rounded separately.  assign(x) = the lowest centre index with the smallest dist (centres scanned in ascending
+ *   order with a strict <).
+ * Fixed point: q(x) = llrint((double)x * 65536.0).
+ * Training sample: total = all rows; stride = ceil(total / max_train); the sample is rows 0, stride, 2 stride, ... of the
+ *   concatenation; nt their number.  total == 0 is ESFM_ERR_INVALID_ARG.
+ * Codebook: centre c starts as sample row floor(c nt / n_centres) (64-bit integers; n_centres > nt gives duplicates, and the tie
+ *   rule sends everything to the lower index).  kmeans_iterations times: assign every sample row; count_c and
+ *   sum_ct = sum of q(x_t) in int64; a centre with count_c > 0 becomes m_ct = (float)(((double)sum_ct / (double)count_c) / 65536.0),
+ *   an empty centre keeps its value.  kmeans_iterations == 0 returns the initialisation.
+ * VLAD: per image i, centre c, component t: S = (sum over x in image i with assign(x) = c of q(x_t)) - n_ic q(m_ct) in int64
+ *   (n_ic the count); maxS = max |S| over the image's D entries; maxS == 0: b = 0; else
+ *   b = sign(S) rint((127.0 * sqrt((double)|S|)) / sqrt((double)maxS)) in f64, rint half-to-even: an int8 in -127 .. 127
+ *   (signed-square-root VLAD scaled to its largest entry).  norm2_i = sum of b^2 (at most 32768 * 127^2: an int32).
+ * Similarity: dot_ij = sum of b_i b_j in int32 (exact);
+ *   score_ij = (double)dot_ij / (sqrt((double)norm2_i) * sqrt((double)norm2_j)), 0 when either norm is 0.
+ * Nearest table: nearest[i][0 .. top_k) = the images j != i with norm2_j > 0, ranked by (score_ij descending, j ascending) -- a
+ *   total order -- padded with -1; a row with norm2_i == 0 is all -1.
+ * Pair list (host): the union of (max(i, j), min(i, j)) over the table's entries >= 0 and of (i, i - w), 1 <= w <= window,
+ *   i - w >= 0; ascending by (first, second), without duplicates: the order of the (i, j < i) loop, restricted to the chosen pairs.
+ *
+ * Options (esfm_retrieval_options_default): n_centres 64 (1 .. 256), kmeans_iterations 10 (0 .. 100), max_train 65536
+ * (1 .. 2^24), top_k 10 (0 .. 1024), window 0 (>= 0).  64 centres and 10 nearest images are conventions of VLAD retrieval; they
+ * have NOT been tuned on this project's data.  Rejected with ESFM_ERR_INVALID_ARG, nothing written: options NULL or out of range,
+ * a NULL required pointer, negative or decreasing offsets, a width outside the ranges above.
+ *
+ * esfm_retrieval_train writes the codebook (n_centres x d floats).  esfm_retrieval_vlad takes a codebook and writes vlad
+ * (n_sets x D int8), norm2 and, for tests, assign (the centre of every row) and sums (S, n_sets x D int64).  esfm_retrieval_rank
+ * takes int8 descriptors and writes nearest (n_sets x top_k) and, for tests, dots and scores (n_sets^2 each).
+ * esfm_retrieval_pair_list is host code and needs no context; a table entry outside -1 .. n_sets - 1 or equal to its row is
+ * ESFM_ERR_INVALID_ARG.  esfm_retrieval_pairs runs the whole chain with the intermediates kept on the device and one read-back
+ * of the table; esfm_retrieval_pairs_dev is the same over a resident descriptor buffer and, unlike the other _dev entry points,
+ * synchronises (the pair list is built on the host).  With top_k == 0 the list is the window's alone and no device work is done.
+ * All pointers but desc_dev are host pointers.  No CPU fallback: without a
+ * usable device no context exists. */
+#define ESFM_RETRIEVAL_MAX_DIM 32768
+#define ESFM_RETRIEVAL_MAX_SETS 8192
+typedef struct esfm_retrieval_options {
+    int32_t n_centres;
+    int32_t kmeans_iterations;
+    int32_t max_train;
+    int32_t top_k;
+    int32_t window;
+    int32_t reserved;
+} esfm_retrieval_options;
+void esfm_retrieval_options_default(esfm_retrieval_options *opt);
+int esfm_retrieval_train(esfm_ctx *ctx, esfm_metric metric, const void *desc_host, const int32_t *set_row_offset, int n_sets,
+                         int width, const esfm_retrieval_options *opt, float *centres /*n_centres x d*/);
+int esfm_retrieval_vlad(esfm_ctx *ctx, esfm_metric metric, const void *desc_host, const int32_t *set_row_offset, int n_sets,
+                        int width, int n_centres, const float *centres, int8_t *vlad /*n_sets x D*/, int32_t *norm2 /*n_sets*/,
+                        int32_t *assign /*total rows, or NULL*/, int64_t *sums /*n_sets x D, or NULL*/);
+int esfm_retrieval_rank(esfm_ctx *ctx, int n_sets, int D, const int8_t *vlad, int top_k, int32_t *nearest /*n_sets x top_k*/,
+                        int32_t *dots /*n_sets^2, or NULL*/, double *scores /*n_sets^2, or NULL*/);
+int esfm_retrieval_pair_list(int n_sets, int top_k, const int32_t *nearest /*may be NULL when top_k == 0*/, int window,
+                             int32_t *pairs /*capacity n_sets (top_k + window), 2 each*/, int32_t *n_pairs);
+int esfm_retrieval_pairs(esfm_ctx *ctx, esfm_metric metric, const void *desc_host, const int32_t *set_row_offset, int n_sets,
+                         int width, const esfm_retrieval_options *opt, int32_t *pairs /*as esfm_retrieval_pair_list*/,
+                         int32_t *n_pairs);
+int esfm_retrieval_pairs_dev(esfm_ctx *ctx, esfm_metric metric, const void *desc_dev, const int32_t *set_row_offset, int n_sets,
+                             int width, const esfm_retrieval_options *opt, int32_t *pairs, int32_t *n_pairs);
+/* Measurement only: with esfm_ctx_set_kernel_timing on, the last esfm_retrieval_pairs / _pairs_dev call's device time per stage in
+ * ms[4] (hipEvents on the context's stream): codebook training, assignment + accumulation of all rows, finalise, similarity + ranking. */
+int esfm_retrieval_last_stage_ms(esfm_ctx *ctx, double *ms /*4*/);
+
 #ifdef __cplusplus
 }
 #endif
