@@ -1,6 +1,6 @@
 // C-ABI entry points for bundle adjustment (include/esfm.h, rows a-4..a-8 of SURVEY.md section 8) except the solve itself
 // (ba_solve.cpp): argument checks, problem set-up and tear-down, parameter access, the one-shot wrappers, and the host-only helpers.
-// A problem's index tables come from ba_layout.cpp, the forms of its size-dependent kernels from ba_forms (ba_kernels.hip); this file
+// A problem's index tables come from ba_layout.cpp, the forms of its size-dependent kernels from ba_forms (ba_forms.cpp); this file
 // allocates and uploads.
 #include <climits>
 #include <cmath>
@@ -164,7 +164,7 @@ int create_impl(esfm_ctx *ctx, int n_real, int n_pt, int n_obs, const int32_t *c
     A(&d.EtE, (size_t)6 * n_pt); A(&d.Etr, np3); A(&d.Minv, (size_t)6 * n_pt); A(&d.Aig, np3);
     A(&d.camacc, esfm::ba_camacc_doubles(n_cam)); A(&d.red, esfm::ba_red_doubles(n_cam));
     A(&d.y_c, nc6); A(&d.scal, (size_t)esfm::SC_COUNT);
-    // (the tiled solve's work space; the in-LDS solves take none, the packed matrix is what ba_chol_solve_kernel's global form would use)
+    // (the tiled solve's work space; the in-LDS solves take none, the packed matrix is not read on those paths)
     A(&d.chol, forms.solve == esfm::BaForms::SOLVE_TILED ? esfm::ba_chol_large_doubles(n_cam) : (nc6 + 1) * (nc6 + 2) / 2 + 2);
     if (forms.schur == esfm::BaForms::SCHUR_LDS_SLABS) d.slab_cap = esfm::ba_schur_slab_doubles(n_cam) * (size_t)ctx->num_cu;
     if (d.slab_cap) A(&d.slabs, d.slab_cap);

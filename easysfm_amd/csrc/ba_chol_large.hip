@@ -352,7 +352,7 @@ __global__ __launch_bounds__(256) void chol2_back_kernel(BADev d, const double *
 // LDS-fed steps per block column, 1.45 us.)
 // Round 1's kernel (ba_chol_solve_kernel: 8-column panels, dot products from packed rows, 19 panels x 3 barriers): 127 us.
 constexpr int kSmallThreads = 1024;
-constexpr int kSmallMaxNb = 11;
+static_assert(SB == kSmallTile, "ba_chol_small_fits (ba_forms.hpp) counts block rows of this kernel's tile edge; kSmallMaxNb is there too");
 __device__ __forceinline__ int blk_off(int i, int j) { return (i * (i + 1) / 2 + j) * (SB * VLD); }
 
 __global__ __launch_bounds__(kSmallThreads) void ba_chol_small_kernel(BADev d, double radius, double min_diag, double max_diag)
@@ -491,8 +491,6 @@ __global__ __launch_bounds__(kSmallThreads) void ba_chol_small_kernel(BADev d, d
     __syncthreads();
     ba_camera_step_body(d, rd, z);       // candidate cameras from y (z: reduction scratch from here on)
 }
-
-bool ba_chol_small_fits(int n_cam) { return (6 * n_cam + SB - 1) / SB <= kSmallMaxNb; }
 
 int ba_solve_reduced_small(hipStream_t st, const BADev &d, double radius, double min_diag, double max_diag)
 {

@@ -1,7 +1,8 @@
-// Launch interface between ba_solve.cpp (LM control loop on the host), ba_api.cpp (problem set-up) and ba_kernels.hip.
+// Launch interface between ba_solve.cpp (LM control loop on the host), ba_api.cpp (problem set-up) and ba_linearize.hip / ba_schur.hip / ba_step.hip.
 #pragma once
 
 #include "common.hpp"
+#include "ba_forms.hpp"
 #include "ba_layout.hpp"
 
 namespace esfm {
@@ -21,23 +22,6 @@ enum BAScalar {
     SC_DMAX = 17,     // max |delta| over this rank's points and all camera-side unknowns
     SC_MAX_COUNT = 2, SC_COUNT = 24
 };
-
-// Which form of the size-dependent kernels a problem takes.  A function of the problem's sizes alone (ba_forms, next to the
-// launchers): evaluated once at creation, sizes the buffers each form needs and is what every launcher reads (BADev::parts->forms);
-// conditions of the running solve (one rank or several, bounds, the structure-aware plan) combine with it at the launch sites.
-// DESIGN.md section 5 has the table.
-struct BaForms {
-    enum Schur { SCHUR_LDS_SLABS,   // all camera blocks of S in every workgroup's LDS, summed over per-workgroup slabs (ba_schur_lds_kernel)
-                 SCHUR_TABLES };    // matrix-core / windowed / wide tables of BaLayout
-    enum Solve { SOLVE_SMALL_ONE_WG,   // one-workgroup MFMA solve, the camera step included (ba_chol_small_kernel)
-                 SOLVE_LDS,            // one workgroup, packed factor in LDS (ba_chol_solve_kernel)
-                 SOLVE_TILED };        // multi-workgroup tiled solve, dense or structure-aware (ba_chol_large.hip, ba_chol_sparse.hip)
-    Schur schur = SCHUR_LDS_SLABS;
-    Solve solve = SOLVE_SMALL_ONE_WG;
-    bool sweep_sums_in_lds = false;    // the Jacobian sweep keeps the per-camera sums in LDS (else: camera chunks, BaLayout::cchunk_*)
-    bool large = false;                // >= 2^20 observations: 512-thread sweep, chunked per-point blocks, candidate cost in a pass of its own
-};
-BaForms ba_forms(int n_real_cam, bool has_calib, int n_obs);
 
 // Device-resident bundle-adjustment problem.  Observations are sorted by point (CSR), so a
 // point's observations are contiguous: obs k in [pt_start[p], pt_start[p+1]) belongs to point p.
@@ -174,8 +158,7 @@ int ba_solve_reduced(hipStream_t st, const BADev &d, double radius, double min_d
 // ba_chol_large_doubles(n_cam) doubles
 int ba_solve_reduced_large(hipStream_t st, const BADev &d, double radius, double min_diag, double max_diag);
 size_t ba_chol_large_doubles(int n_cam);
-// one-workgroup MFMA solve for n = 6 n_cam <= 176 (ba_chol_large.hip); ba_forms is the one caller of the predicate
-bool ba_chol_small_fits(int n_cam);
+// one-workgroup MFMA solve for n = 6 n_cam <= 176 (ba_chol_large.hip; ba_chol_small_fits, ba_forms.hpp)
 int ba_solve_reduced_small(hipStream_t st, const BADev &d, double radius, double min_diag, double max_diag);
 // intrinsics row/column block of the reduced system (has_calib): runs after ba_schur, adds into d.red
 int ba_schur_calib(hipStream_t st, const BADev &d, double rhs_bound);

@@ -1,6 +1,6 @@
 // Index tables of one bundle-adjustment problem (host side, no GPU): the observations sorted by point, the per-camera chunks of the
 // atomic-free camera sums, the three families of Schur tables (matrix-core, windowed, wide) and the point chunks.  Pure arithmetic on
-// the caller's (camera, point) index lists; ba_api.cpp uploads the vectors as they stand and ba_kernels.hip reads them (BADev names
+// the caller's (camera, point) index lists; ba_api.cpp uploads the vectors as they stand and the BA kernel files read them (BADev names
 // the consumers).  The solver is bit-reproducible BECAUSE the order inside these tables is fixed: tests/cpp/ba_layout_check.cpp states
 // what the kernels rely on.
 #pragma once
@@ -38,7 +38,7 @@ struct BaLayout : BaPointSort {
 };
 
 // cam_idx in [0, n_real), pt_idx in [0, n_pt) (the caller has checked).  schur_tables: the LDS-slab Schur does not apply to this
-// problem (BaForms::schur, ba_kernels.hpp); num_cu sizes the Schur chunks (about two per compute unit).
+// problem (BaForms::schur, ba_forms.hpp); num_cu sizes the Schur chunks (about two per compute unit).
 BaLayout make_ba_layout(int n_real, int n_pt, int n_obs, const int32_t *cam_idx, const int32_t *pt_idx, int num_cu, bool schur_tables);
 
 }  // namespace esfm

@@ -2,7 +2,7 @@
 // The control flow restates Ceres' TrustRegionMinimizer + LevenbergMarquardtStrategy
 // with DENSE_SCHUR, which is what BundleAdjustment::solveBA configures (reference
 // cpp_code/src/ba.cpp:146-151, :201-206); the oracle (oracle/ba_ref.c) documents the upstream rules.
-// All arithmetic on the observations runs in ba_kernels.hip; this file only sequences kernels, reads
+// All arithmetic on the observations runs in ba_linearize.hip, ba_schur.hip and ba_step.hip; this file only sequences kernels, reads
 // back a handful of scalars per iteration and takes the accept/reject decision.
 #include <chrono>
 #include <thread>
