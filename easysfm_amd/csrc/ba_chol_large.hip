@@ -396,16 +396,22 @@ __global__ __launch_bounds__(kSmallThreads) void ba_chol_small_kernel(BADev d, d
             }
         }
     }
-    double ftf = 0.0;
-    if (tid < 36 * d.n_cam) ftf = FtF[tid];                 // (n_cam <= 29: one entry per thread)
+    // (36 n_cam entries: one per thread up to 28 cameras, and 20 more at 29 -- the 1 044 entries of kSmallMaxNb block rows)
+    constexpr int kFtfPerThread = (36 * (kSmallMaxNb * kSmallTile / 6) + kSmallThreads - 1) / kSmallThreads;
+    double ftf[kFtfPerThread];
+#pragma unroll
+    for (int u = 0; u < kFtfPerThread; ++u) { const int e = tid + u * kSmallThreads; ftf[u] = e < 36 * d.n_cam ? FtF[e] : 0.0; }
     const double zr = tid < n ? Ftr[tid] + rc[tid] : 0.0;
     __syncthreads();
-    if (tid < 36 * d.n_cam) {
-        const int cam = tid / 36, a = (tid % 36) / 6, b2 = tid % 6;
+#pragma unroll
+    for (int u = 0; u < kFtfPerThread; ++u) {
+        const int e = tid + u * kSmallThreads;
+        if (e >= 36 * d.n_cam) break;
+        const int cam = e / 36, a = (e % 36) / 6, b2 = e % 6;
         if (b2 <= a) {
             const int i = 6 * cam + a, k = 6 * cam + b2;
-            double add = ftf;
-            if (a == b2) add += fmin(fmax(ftf, min_diag), max_diag) / radius;
+            double add = ftf[u];
+            if (a == b2) add += fmin(fmax(ftf[u], min_diag), max_diag) / radius;
             double *B = A + blk_off(i / SB, k / SB);
             B[(i % SB) * VLD + (k % SB)] += add;
             if (i / SB == k / SB && i != k) B[(k % SB) * VLD + (i % SB)] += add;

@@ -92,6 +92,35 @@ __device__ __forceinline__ void scal_commit(const BADev &d, const ScalBase &base
     }
 }
 
+// scal_commit with the per-wave partials staged in the CALLER's LDS (`stage`, N * WAVES doubles; a workgroup of at most WAVES waves)
+// instead of a static array: for a kernel whose dynamic LDS is sized to the last byte a workgroup may take (the Jacobian sweep:
+// lin_lds_bytes, ba_forms.hpp), where 128 N static bytes beside it make the launch illegal.  The same shuffle tree and wave order, hence
+// the same bits.
+template <int N, int WAVES>
+__device__ __forceinline__ void scal_commit_staged(const BADev &d, const ScalBase &base, const int (&slots)[N], const double (&vals)[N], double *stage)
+{
+    double t[N];
+#pragma unroll
+    for (int q = 0; q < N; ++q) {
+        t[q] = vals[q];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) t[q] += __shfl_xor(t[q], o);
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
+    __syncthreads();
+    if (lane == 0) {
+#pragma unroll
+        for (int q = 0; q < N; ++q) stage[q * WAVES + wave] = t[q];
+    }
+    __syncthreads();
+    if (threadIdx.x < N) {
+        const int q = threadIdx.x;
+        double sum = 0.0;
+        for (int w = 0; w < nw; ++w) sum += stage[q * WAVES + w];
+        d.scal_part[(size_t)slots[q] * d.scal_cap + base.b[q] + blockIdx.x] = sum;
+    }
+}
+
 // 1024 threads: wave w adds the pending partials of slot w (SC_SUM_COUNT <= 16) -- lane l takes entries l, l + 64, ... in order,
 // 32 loads in flight, then the fixed shuffle tree -- so all slots cost one memory round trip together.
 __device__ __forceinline__ void scal_reduce_pending(const double *scal_part, int scal_cap, double *scal, const ScalCounts &c)

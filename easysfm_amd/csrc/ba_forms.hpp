@@ -25,6 +25,7 @@ BaForms ba_forms(int n_real_cam, bool has_calib, int n_obs);
 
 // dynamic LDS of the three kernels that have an in-LDS form
 constexpr int kLinLdsPerCam = 27 * 8 + 7 * 8 + 4 + 7 * 4;   // ba_linearize_kernel: acc, maxima, count, exponents
+// (ALL of the sweep's LDS: at 538 cameras 144 bytes short of a compute unit's 160 KiB, so the kernel keeps no static __shared__ object)
 constexpr size_t lin_lds_bytes(int n_real_cam) { return 18 * sizeof(double) + (size_t)n_real_cam * kLinLdsPerCam; }
 // LDS pitch of a 6 x 6 block: 37 doubles, not 36.  The lanes of a wave add the same entry of DIFFERENT blocks; at pitch 36 (288 B)
 // those addresses fall on 8 of the 64 banks (SQ_LDS_BANK_CONFLICT was two thirds of SQ_LDS_IDX_ACTIVE), at 37 on all of them.
@@ -38,6 +39,11 @@ constexpr size_t chol_lds_bytes(int n_cam)      // ba_chol_solve_kernel: packed 
     const size_t n = 6 * (size_t)n_cam;
     return sizeof(double) * ((n + 1) * (n + 2) / 2 + n + 2);
 }
+// ba_schur_calib_kernel (free intrinsics): 8 doubles of reduction scratch, then -- while it fits the 64 KiB a workgroup may always take --
+// an LDS copy of the intrinsics block row, 4 x 6 n_real_cam; beyond (n_real_cam >= 342) the row's addends go to d.red directly
+constexpr size_t kCalibRowLdsBudget = 64 * 1024;
+constexpr size_t calib_row_lds_bytes(int n_real_cam) { return sizeof(double) * (8 + (size_t)4 * 6 * n_real_cam); }
+constexpr bool ba_calib_row_in_lds(int n_real_cam) { return calib_row_lds_bytes(n_real_cam) <= kCalibRowLdsBudget; }
 // the one-workgroup MFMA solve (ba_chol_small_kernel) holds at most kSmallMaxNb block rows of kSmallTile (= SB, ba_chol_tile.hpp)
 // unknowns: n = 6 n_cam <= 176
 constexpr int kSmallTile = 16, kSmallMaxNb = 11;

@@ -242,7 +242,10 @@ __global__ __launch_bounds__(kLinThreads, 1) void ba_linearize_kernel(BADev d, d
     {
         const int slots[2] = {SC_COST, SC_LIN_BAD};
         const double vals[2] = {cost, bad};
-        scal_commit<2>(d, sbase, slots, vals, red);
+        // staged in red[0 .. 2 waves): no static LDS beside lin_lds_bytes, which takes a compute unit's LDS to within 144 bytes at 538
+        // cameras (red[8 .. 16] are written further down, red[17] is the guard's verdict)
+        static_assert(2 * (kLinThreads / 64) <= 17, "the sweep's 18 doubles of scratch hold the staged partials in front of the verdict");
+        scal_commit_staged<2, kLinThreads / 64>(d, sbase, slots, vals, red);
     }
     if (!PRIV) return;
     if (CALIB) {

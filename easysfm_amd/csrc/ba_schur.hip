@@ -744,9 +744,8 @@ int ba_schur(hipStream_t st, const BADev &d, int num_cu, double rhs_bound)
 int ba_schur_calib(hipStream_t st, const BADev &d, double rhs_bound)
 {
     if (!d.has_calib || d.n_pt <= 0 || d.n_obs <= 0) return ESFM_OK;
-    const size_t row_bytes = sizeof(double) * (8 + (size_t)4 * 6 * d.n_real_cam);
-    const bool use_lds = row_bytes <= 64 * 1024;
-    const size_t lds = use_lds ? row_bytes : sizeof(double) * 8;
+    const bool use_lds = ba_calib_row_in_lds(d.n_real_cam);
+    const size_t lds = use_lds ? calib_row_lds_bytes(d.n_real_cam) : calib_row_lds_bytes(0);
     const int rhs_exp = bound_exponent(rhs_bound);
     hipLaunchKernelGGL(ba_schur_calib_kernel, dim3(div_up(d.n_pt, 256)), dim3(256), lds, st, d, use_lds ? 1 : 0, rhs_exp);
     LAUNCH_CHECK();

@@ -21,6 +21,7 @@ namespace esfm {
         if (e__ != hipSuccess) {                                                                \
             ::esfm::set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e__), __FILE__, \
                               __LINE__);                                                        \
+            (void)hipGetLastError();   /* reported here: not left for the next call's launch check */ \
             return e__ == hipErrorOutOfMemory ? ESFM_ERR_OOM : ESFM_ERR_HIP;                    \
         }                                                                                       \
     } while (0)

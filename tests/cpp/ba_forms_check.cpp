@@ -21,6 +21,8 @@ int g_failed = 0;
 static_assert(schur_lds_bytes(32) == 158592 && schur_lds_bytes(32) <= 156 * 1024 && schur_lds_bytes(33) > 156 * 1024, "LDS-slab Schur: n_cam <= 32");
 static_assert(lin_lds_bytes(0) == 144 && kLinLdsPerCam == 304 && lin_lds_bytes(538) <= 160 * 1024 && lin_lds_bytes(539) > 160 * 1024, "sweep sums: n_real <= 538");
 static_assert(chol_lds_bytes(32) == 151320 && chol_lds_bytes(32) <= 150 * 1024 && chol_lds_bytes(33) == 160800, "packed factor in LDS: n_cam <= 32");
+static_assert(calib_row_lds_bytes(0) == 64 && calib_row_lds_bytes(341) == 65536 && calib_row_lds_bytes(341) <= 64 * 1024 && calib_row_lds_bytes(342) == 65728,
+              "intrinsics block row in LDS: n_real <= 341");
 static_assert(ba_chol_small_fits(29) && !ba_chol_small_fits(30) && kSmallTile * kSmallMaxNb == 176, "one-workgroup solve: 6 n_cam <= 176");
 
 constexpr int kObs = 1000;              // any count below 2^20
@@ -46,6 +48,16 @@ void boundaries()
         }
         CHECK(!at_cam(32).large && !ba_forms(6, calib != 0, 0).large, "calib %d", calib);
     }
+    // ba_schur_calib's LDS copy of the intrinsics block row: per REAL camera, and independent of every BaForms value
+    CHECK(ba_calib_row_in_lds(1) && ba_calib_row_in_lds(341) && !ba_calib_row_in_lds(342) && !ba_calib_row_in_lds(kMaxCam - 1), "calib row");
+    int row_switches = 0;
+    for (int n_real = 1; n_real < kMaxCam; ++n_real) {
+        CHECK(ba_calib_row_in_lds(n_real + 1) <= ba_calib_row_in_lds(n_real), "n_real %d", n_real);
+        row_switches += ba_calib_row_in_lds(n_real + 1) != ba_calib_row_in_lds(n_real);
+        // the launch never asks for more than the budget, whichever branch it takes
+        CHECK((ba_calib_row_in_lds(n_real) ? calib_row_lds_bytes(n_real) : calib_row_lds_bytes(0)) <= kCalibRowLdsBudget, "n_real %d", n_real);
+    }
+    CHECK(row_switches == 1, "%d", row_switches);
 }
 
 void sweep()

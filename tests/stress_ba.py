@@ -1,5 +1,6 @@
-"""Randomised stress of the BA path against the oracle's LM trace: camera counts across every kernel-path threshold (LDS slab Schur +
-one-workgroup solve, small / tiled Cholesky, matrix-core / window / plain Schur kernels, structure-aware solve), random track
+"""Randomised stress of the BA path against the oracle's LM trace: camera counts on both sides of every threshold of ba_forms (LDS-slab
+Schur + one-workgroup solves | Schur tables -- matrix-core / window / plain kernels -- + tiled or structure-aware solve; the
+intrinsics block row in LDS or not; per-camera sums in the sweep's LDS or by camera chunks), random track
 structure (consecutive windows, random subsets, far pairs, single observations, unobserved cameras / points), observation order
 camera-major or shuffled, with and without free intrinsics.
 usage: python tests/stress_ba.py [--seconds S | --cases N] [--seed K]"""
@@ -24,6 +25,12 @@ oracle.build()
 oracle.set_num_threads(min(16, os.cpu_count() or 1))
 ctx = E.Context(0)
 K = np.array(synth.FOUNTAIN_K4, np.float64)
+# Camera counts: both sides of every boundary of ba_forms -- n_cam 29 | 30 (one-workgroup MFMA solve | packed factor in
+# LDS) and 32 | 33 (LDS-slab Schur + LDS solve | Schur tables + tiled solves), which free intrinsics move to 28 | 29 and 31 | 32 real
+# cameras -- among sizes well inside each form; 342 (ba_schur_calib without its LDS block row) and 539 (per-camera sums by camera
+# chunks) at a twentieth of the others' weight: the oracle takes seconds there.
+CAMS = [3, 5, 8, 16, 25, 28, 29, 30, 31, 32, 33, 43, 64, 90, 107, 150, 220, 342, 539]
+CAM_P = np.array([1.0] * (len(CAMS) - 2) + [0.05, 0.05]); CAM_P /= CAM_P.sum()
 
 def trace_equal(summ, rs, constrained):
     a_log, b_log = summ.log(), oracle.iterations(rs)
@@ -71,7 +78,7 @@ def explained_by_conditioning(ss, solve_oracle, base_rs, cams0, pts0):
 t_end = time.time() + budget
 n_cases = n_artefacts = 0
 while time.time() < t_end and n_cases < max_cases:
-    n_cam = int(rng.choice([3, 5, 8, 16, 25, 26, 27, 30, 42, 43, 44, 64, 90, 107, 150, 220]))
+    n_cam = int(rng.choice(CAMS, p=CAM_P))
     n_pt = int(rng.integers(max(40, 4 * n_cam), 60 * n_cam + 200))
     base = synth.ba_scene(n_cam, n_pt, 3, radius=10.0 + 0.1 * n_cam, extent=2.0 + 0.01 * n_cam, seed=int(rng.integers(1, 1 << 30)))
     style = int(rng.integers(0, 4))

@@ -1,7 +1,10 @@
 """Run-to-run reproducibility of the HIP bundle adjustment.
 
 No reduction of the solver depends on the order in which workgroups or waves arrive:
-  * per-camera sums F'F / F'r: gathered per camera in observation order (ba_camacc_chunk_kernel), chunk sums added in order;
+  * per-camera sums F'F / F'r: up to 538 cameras the Jacobian sweep adds them in LDS as 64-bit fixed-point integers (exact in any
+    order), one slab per workgroup, the slabs summed in index order (ba_camacc_reduce_kernel); from 539 cameras they are gathered
+    per camera in observation order, 256 observations a chunk (ba_camacc_chunk_kernel: a fixed shuffle tree), and a camera's chunk
+    sums added in chunk order (ba_camacc_final_kernel);
   * scalar sums (cost, model cost change, norms): per-workgroup partials added in block order by the last workgroup;
   * the Schur complement: accumulated as 64-bit fixed-point integers, entry (r, c) scaled by 2^(60 - qexp[r] - qexp[c]), so the
     LDS / global integer atomics and the slab sums are exact whatever their order; converted to f64 once, before the solve
@@ -39,12 +42,15 @@ def _twice(sc, ctx, runs=3, **kw):
 
 @pytest.mark.parametrize("n_cam,n_pt,k,seed,iters", [
     (4, 50, 3, 1, 50),          # the scene whose long run used to stop an iteration apart about one run in twenty
-    (25, 7776, 8, 3, 25),       # BA-25, the metric configuration: Schur complement in LDS slabs, one-workgroup Cholesky
-    (40, 4000, 6, 5, 10),       # LDS Schur slabs, LDS Cholesky of the round-1 kernel
-    (96, 9000, 6, 7, 8),        # windowed Schur (LDS window + global f64 atomics), tiled large Cholesky
+    (25, 7776, 8, 3, 25),       # BA-25, the metric configuration: Schur complement in LDS slabs, one-workgroup MFMA solve (ba_chol_small_kernel)
+    (32, 1500, 5, 9, 10),       # the largest LDS Schur slabs, packed factor in LDS (ba_chol_solve_kernel)
+    (40, 4000, 6, 5, 10),       # Schur tables (n_cam >= 33: matrix-core / windowed kernels), the shortest tiled solves
+    (96, 9000, 6, 7, 8),        # Schur tables, tiled large Cholesky
+    (539, 6000, 6, 15, 6),      # per-camera sums by camera chunks (ba_camacc_chunk_kernel + ba_camacc_final_kernel), not in the sweep's LDS
 ])
 def test_two_solves_are_bit_identical(gpu_ctx, n_cam, n_pt, k, seed, iters):
-    _twice(synth.ba_scene(n_cam, n_pt, k, seed=seed), gpu_ctx, max_num_iterations=iters)
+    big = n_cam > 100
+    _twice(synth.ba_scene(n_cam, n_pt, k, radius=40.0 if big else 10.0, extent=8.0 if big else 2.0, seed=seed), gpu_ctx, max_num_iterations=iters)
 
 
 def test_squared_loss_and_no_jacobi_scaling_bit_identical(gpu_ctx):

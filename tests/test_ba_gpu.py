@@ -297,9 +297,12 @@ def test_ba_medium_large_camera_count_paths(gpu_ctx, oracle_lib):
 
 @pytest.mark.parametrize("n_cam,n_pt,k,seed", [(30, 2500, 5, 31), (43, 4000, 6, 32), (107, 9000, 6, 33)])
 def test_ba_tiled_cholesky_sizes(gpu_ctx, oracle_lib, n_cam, n_pt, k, seed):
-    """Reduced systems of 180, 258 and 642 unknowns: 3, 5 and 11 block columns of the dataflow Cholesky (chol3_kernel), with 12, 62
-    and 62 identity-padded rows in the last tile -- the chain workgroup's hand-over (early rows of the tile inverse on a second flag,
-    the inverse formed beside the pivot chains) at the shortest chains there are; the trace must follow the oracle's."""
+    """Reduced systems of 180, 258 and 642 unknowns.  30 cameras take the one-workgroup solve with its packed factor in LDS
+    (ba_chol_solve_kernel, n_cam 30 - 32) behind the LDS-slab Schur kernel; 43 and 107 the Schur tables and 5 and 11 block columns of
+    the dataflow Cholesky (chol3_kernel), with 62 identity-padded rows in the last tile -- the chain workgroup's hand-over (early rows
+    of the tile inverse on a second flag, the inverse formed beside the pivot chains) at short chains; the trace must follow the
+    oracle's.  The sizes at which a form begins or ends (29, 30, 32, 33 cameras, ...) are in tests/test_ba_forms_gpu.py, each tied to
+    the host rule that picks the form."""
     sc = synth.ba_scene(n_cam, n_pt, k, radius=15.0, extent=3.0, seed=seed)
     opt, ropt = _solve_both(oracle_lib, sc, 3)
     cams, pts, summ = E.ba_solve(sc.cam_idx, sc.pt_idx, sc.uv, sc.K4, sc.cams0, sc.pts0, opt, gpu_ctx)

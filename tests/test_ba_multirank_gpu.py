@@ -23,7 +23,8 @@ def _free_port():
 CALIB0 = [703.67, 376.37, 677.22, 254.22]     # shared intrinsics start, ~2 % off the scene's
 
 
-SCENES = {"small": (8, 600, 5, 21, 10.0, 2.0), "loop200": (200, 12000, 8, 34, 15.0, 3.0)}     # n_cam, n_pt, obs per point, seed, radius, extent
+SCENES = {"small": (8, 600, 5, 21, 10.0, 2.0), "loop200": (200, 12000, 8, 34, 15.0, 3.0),     # n_cam, n_pt, obs per point, seed, radius, extent
+          "cams32": (32, 1500, 5, 35, 10.0, 2.0), "cams539": (539, 6000, 6, 36, 40.0, 8.0)}
 
 
 def _scene(name):
@@ -106,6 +107,26 @@ def test_sharded_ba_two_ranks_matches_single(gpu_ctx):
         assert np.allclose(p, pts, rtol=1e-6, atol=1e-6)              # and, after the final merge, ALL points
         assert 0 < n_active < sc.n_pt                                  # but owns only its shard
     assert np.array_equal(res[0][2], res[1][2])                       # camera blocks bit-identical across ranks
+    assert res[0][5] + res[1][5] == sc.n_pt
+
+
+@pytest.mark.parametrize("scene", ["cams32", "cams539"])
+def test_sharded_ba_two_ranks_matches_single_at_form_limits(gpu_ctx, scene):
+    """Two ranks on forms no other sharded test takes.  32 cameras: the LDS-slab Schur kernel, whose reduce kernel
+    converts `red` to doubles for the exchange, beside the one-workgroup LDS solve (ba_chol_solve_kernel).  539 cameras: each rank's
+    per-camera sums by camera chunks (ba_camacc_chunk_kernel + ba_camacc_final_kernel) over its own observations, summed over the
+    ranks.  Off one rank the camera gradient is ba_camera_gradient_kernel's, after the exchange, at both sizes.  Same assertions as
+    test_sharded_ba_two_ranks_matches_single."""
+    sc, (cams, pts, summ) = _single(scene)
+    res = _run(2, "gloo", scene=scene)
+    ref_cost = [it.cost for it in summ.log()]
+    for rank, _, c, p, costs, n_active, _cal, _ls in res:
+        assert len(costs) == len(ref_cost)
+        assert np.allclose(costs, ref_cost, rtol=1e-9)
+        assert np.allclose(c, cams, rtol=1e-6, atol=1e-6)
+        assert np.allclose(p, pts, rtol=1e-6, atol=1e-6)
+        assert 0 < n_active < sc.n_pt
+    assert np.array_equal(res[0][2], res[1][2])
     assert res[0][5] + res[1][5] == sc.n_pt
 
 
