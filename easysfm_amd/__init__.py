@@ -10,7 +10,7 @@ from .types import DMatch, Frame, SparsePointCloud  # noqa: F401
 from .matching import (DescriptorBank, FeatureMatching, PairMatcher, knn_match_hamming, knn_match_l2,  # noqa: F401
                        match_cross_hamming, match_cross_l2, match_cross_pairs_host, match_guided_hamming, match_guided_l2,
                        match_guided_pairs_host, match_hamming, match_l2, match_pairs_host, shard_pair_list)
-from .ba import (BAProblem, BundleAdjustment, Comm, ba_solve, ba_solve_ex, ba_sweep_bytes_per_obs, default_options, line_search_next_step, reduced_plan, shard_points,  # noqa: F401
+from .ba import (BAProblem, BundleAdjustment, Comm, ba_solve, ba_solve_ex, ba_solve_groups, ba_sweep_bytes_per_obs, default_options, line_search_next_step, reduced_plan, shard_points,  # noqa: F401
                  torch_allreduce_callback)
 
 from .cloud import (CProceesing, read_ply_mesh, read_ply_normals, read_ply_textured_mesh, read_ply_vertices, sor_filter,  # noqa: F401
@@ -37,3 +37,5 @@ from .retrieval import (RetrievalOptions, retrieval_pair_list, retrieval_rank, r
 from .pipeline import MATCH_FILTERS, FramePair, match_and_verify_all_pairs, propagate_track_ids, run_sfm  # noqa: F401
 
 __version__ = "0.1.0"
+from .cameras import (canonical_camera, cameras_line, check_one_image_size, pair_stage_view, parse_camera_distort, parse_camera_file,  # noqa: F401
+                      remap_keypoints, split_cameras_token)

@@ -116,10 +116,13 @@ class BAProblem:
 
     ``calib`` (fx, cx, fy, cy) switches to the free shared intrinsics of ReprojectErrorTerm_updatecalib (ba.h:170-222),
     bounded to ``calib +- calib_tol`` (ba.cpp:190-194); ``K4`` is then ignored.  ``ref_cam >= 0`` bounds that camera's
-    six parameters to ``+-ref_threshold`` (ba.cpp:155-162)."""
+    six parameters to ``+-ref_threshold`` (ba.cpp:155-162).
+
+    ``calib_groups = (group_of_cam[n_cam], calib4[G, 4], tol[G])`` is the multiple-camera mode: one free block per camera
+    group, block g bounded to ``calib4[g] +- tol[g]`` (esfm_ba_problem_create_calib_groups); ``K4`` and ``calib`` are ignored."""
 
     def __init__(self, cam_idx, pt_idx, uv, K4, cams, pts, ctx: Optional[Context] = None, calib=None, calib_tol: float = 0.0,
-                 ref_cam: int = -1, ref_threshold: float = 1e-10):
+                 ref_cam: int = -1, ref_threshold: float = 1e-10, calib_groups=None):
         self.ctx = ctx or default_context()
         self.cam_idx = np.ascontiguousarray(cam_idx, np.int32).reshape(-1)
         self.pt_idx = np.ascontiguousarray(pt_idx, np.int32).reshape(-1)
@@ -127,11 +130,23 @@ class BAProblem:
         cams = np.ascontiguousarray(cams, np.float64).reshape(-1, 6)
         pts = np.ascontiguousarray(pts, np.float64).reshape(-1, 3)
         self.n_cam, self.n_pt, self.n_obs = cams.shape[0], pts.shape[0], self.cam_idx.shape[0]
-        self.free_calib = calib is not None
+        self.free_calib = calib is not None or calib_groups is not None
+        self.n_groups = 0 if not self.free_calib else 1
         if self.pt_idx.shape[0] != self.n_obs or self.uv.shape[0] != self.n_obs:
             raise ValueError("inconsistent BA array sizes")
         self._h = C.c_void_p()
-        if self.free_calib:
+        if calib_groups is not None:
+            group_of_cam, cal4, tol = calib_groups
+            grp = np.ascontiguousarray(group_of_cam, np.int32).reshape(-1)
+            cal4 = np.ascontiguousarray(cal4, np.float64).reshape(-1, 4)
+            tol = np.ascontiguousarray(np.broadcast_to(np.asarray(tol, np.float64), (cal4.shape[0],)))
+            if grp.shape[0] != self.n_cam:
+                raise ValueError("inconsistent BA array sizes")
+            self.n_groups = cal4.shape[0]
+            check(lib().esfm_ba_problem_create_calib_groups(self.ctx.handle, self.n_cam, self.n_pt, self.n_obs, _p(self.cam_idx),
+                                                            _p(self.pt_idx), _p(self.uv), self.n_groups, _p(grp), _p(cal4), _p(tol),
+                                                            _p(cams), _p(pts), C.byref(self._h)))
+        elif self.free_calib:
             cal = np.ascontiguousarray(calib, np.float64).reshape(4)
             check(lib().esfm_ba_problem_create_free_calib(self.ctx.handle, self.n_cam, self.n_pt, self.n_obs, _p(self.cam_idx),
                                                           _p(self.pt_idx), _p(self.uv), _p(cal), float(calib_tol), _p(cams), _p(pts),
@@ -157,6 +172,16 @@ class BAProblem:
         cal = np.empty(4, np.float64)
         check(lib().esfm_ba_problem_get_calib(self._h, _p(cal)))
         return cal
+
+    def set_calib_groups(self, calib4, tol) -> None:
+        cal4 = np.ascontiguousarray(calib4, np.float64).reshape(self.n_groups, 4)
+        tol = np.ascontiguousarray(np.broadcast_to(np.asarray(tol, np.float64), (self.n_groups,)))
+        check(lib().esfm_ba_problem_set_calib_groups(self._h, _p(cal4), _p(tol)))
+
+    def get_calib_groups(self) -> np.ndarray:
+        cal4 = np.empty((self.n_groups, 4), np.float64)
+        check(lib().esfm_ba_problem_get_calib_groups(self._h, _p(cal4)))
+        return cal4
 
     def set_params(self, cams, pts) -> None:
         cams = np.ascontiguousarray(cams, np.float64).reshape(-1, 6); pts = np.ascontiguousarray(pts, np.float64).reshape(-1, 3)
@@ -219,6 +244,32 @@ def ba_solve_ex(cam_idx, pt_idx, uv, K4, cams, pts, calib=None, calib_tol: float
         k = prob.get_calib() if prob.free_calib else None
     finally:
         prob.close()
+    return c, p, k, summ
+
+
+def ba_solve_groups(cam_idx, pt_idx, uv, cams, pts, group_of_cam, calib4, calib_tol, ref_cam: int = -1, ref_threshold: float = 1e-10,
+                    options: Optional[BAOptions] = None, ctx: Optional[Context] = None, allreduce=None):
+    """solveBA in multiple-camera mode (esfm_ba_solve_groups): one free intrinsics block fx, cx, fy, cy per camera group,
+    ``calib4[g] +- calib_tol[g]``.  Returns (cams, pts, calib[G, 4], summary); the inputs are not modified."""
+    ctx = ctx or default_context()
+    cam_idx = np.ascontiguousarray(cam_idx, np.int32).reshape(-1); pt_idx = np.ascontiguousarray(pt_idx, np.int32).reshape(-1)
+    uv = np.ascontiguousarray(uv, np.float32).reshape(-1, 2)
+    c = np.array(cams, np.float64).reshape(-1, 6); p = np.array(pts, np.float64).reshape(-1, 3)      # copies: in/out in the C call
+    grp = np.ascontiguousarray(group_of_cam, np.int32).reshape(-1)
+    k = np.array(calib4, np.float64).reshape(-1, 4)
+    tol = np.ascontiguousarray(np.broadcast_to(np.asarray(calib_tol, np.float64), (k.shape[0],)))
+    if pt_idx.shape[0] != cam_idx.shape[0] or uv.shape[0] != cam_idx.shape[0] or grp.shape[0] != c.shape[0]:
+        raise ValueError("inconsistent BA array sizes")
+    summ = BASummary()
+    opt = options if options is not None else default_options()
+    user = None
+    if isinstance(allreduce, Comm):
+        cb, user = C.cast(lib().esfm_comm_allreduce, ALLREDUCE_FN), allreduce.handle
+    else:
+        cb = allreduce if allreduce is not None else _NULL_ALLREDUCE
+    check(lib().esfm_ba_solve_groups(ctx.handle, c.shape[0], p.shape[0], cam_idx.shape[0], _p(cam_idx), _p(pt_idx), _p(uv), _p(c), _p(p),
+                                     k.shape[0], _p(grp), _p(k), _p(tol), int(ref_cam), float(ref_threshold), C.byref(opt), cb, user,
+                                     C.byref(summ)))
     return c, p, k, summ
 
 
@@ -304,6 +355,10 @@ class BundleAdjustment:
         self.num_parameters_ = 0
         self.num_observations_ = 0
         self.ref_process_camera_id_ = -1
+        # multiple-camera mode (free intrinsics over frames of more than one camera_id): group of every processed camera, and the
+        # camera_id of every group in order of first appearance; one distinct id leaves both empty and the shared block in charge
+        self.camera_group_ = np.zeros(0, np.int32)
+        self.group_camera_ids_: List[int] = []
         self.parameters_ = np.zeros(0, np.float64)
         self.summary: Optional[BASummary] = None
         return True
@@ -345,7 +400,12 @@ class BundleAdjustment:
         self.point_index_ = np.concatenate(pts_i) if pts_i else np.zeros(0, np.int32)
         self.points_2d_ = np.concatenate(uv) if uv else np.zeros((0, 2), np.float32)
         self.num_observations_ = len(self.camera_index_)
-        self.num_parameters_ = 6 * self.num_cameras_ + 3 * self.num_points_ + (4 if fix_calib_tolerance_BA != 0 else 0)
+        ids = [int(fr.camera_id) for i, fr in enumerate(frames) if not process_frame_id[i]]
+        if fix_calib_tolerance_BA != 0 and len(set(ids)) > 1:
+            self.group_camera_ids_ = list(dict.fromkeys(ids))                     # distinct ids, first appearance first
+            self.camera_group_ = np.array([self.group_camera_ids_.index(c) for c in ids], np.int32)
+        n_blocks = len(self.group_camera_ids_) if self.group_camera_ids_ else 1
+        self.num_parameters_ = 6 * self.num_cameras_ + 3 * self.num_points_ + (4 * n_blocks if fix_calib_tolerance_BA != 0 else 0)
         par = np.zeros(self.num_parameters_, np.float64)
         k = 0
         for i, fr in enumerate(frames):
@@ -358,7 +418,12 @@ class BundleAdjustment:
             k += 1
         xyz = np.asarray(sfm_sparse_points.xyz, np.float32).reshape(-1, 3)
         par[6 * self.num_cameras_:6 * self.num_cameras_ + 3 * self.num_points_] = xyz.astype(np.float64).reshape(-1)
-        if fix_calib_tolerance_BA != 0 and self.calibs_:
+        if fix_calib_tolerance_BA != 0 and self.calibs_ and self.group_camera_ids_:
+            # the reference's calibs_[0] rule, per group: a group starts from the K_cam of its first processed frame
+            for g in range(n_blocks):
+                Kg = self.calibs_[int(np.nonzero(self.camera_group_ == g)[0][0])]
+                par[len(par) - 4 * (n_blocks - g):len(par) - 4 * (n_blocks - g) + 4] = [Kg[0, 0], Kg[0, 2], Kg[1, 1], Kg[1, 2]]
+        elif fix_calib_tolerance_BA != 0 and self.calibs_:
             K0 = self.calibs_[0]
             par[-4:] = [K0[0, 0], K0[0, 2], K0[1, 1], K0[1, 2]]
         self.parameters_ = par
@@ -372,6 +437,17 @@ class BundleAdjustment:
         K4 = np.array([[K[0, 0], K[0, 2], K[1, 1], K[1, 2]] for K in self.calibs_], np.float32).reshape(-1, 4)
         cams = self.parameters_[:6 * nc].reshape(nc, 6)
         pts = self.parameters_[6 * nc:6 * nc + 3 * npt].reshape(npt, 3)
+        if fix_calib_tolerance_BA != 0 and self.group_camera_ids_:
+            G = len(self.group_camera_ids_)
+            c, p, k, summ = ba_solve_groups(self.camera_index_, self.point_index_, self.points_2d_, cams, pts, self.camera_group_,
+                                            self.parameters_[-4 * G:].reshape(G, 4), np.full(G, float(fix_calib_tolerance_BA)),
+                                            ref_cam=self.ref_process_camera_id_, ref_threshold=fixed_threshold, options=self.options,
+                                            ctx=self._ctx or default_context())
+            self.parameters_[:6 * nc] = c.reshape(-1)
+            self.parameters_[6 * nc:6 * nc + 3 * npt] = p.reshape(-1)
+            self.parameters_[-4 * G:] = k.reshape(-1)
+            self.summary = summ
+            return True
         calib = self.parameters_[-4:].copy() if fix_calib_tolerance_BA != 0 else None
         c, p, k, summ = ba_solve_ex(self.camera_index_, self.point_index_, self.points_2d_, K4, cams, pts, calib=calib,
                                     calib_tol=float(fix_calib_tolerance_BA), ref_cam=self.ref_process_camera_id_,
@@ -401,7 +477,12 @@ class BundleAdjustment:
             k += 1
             if fix_calib_tolerance_BA != 0:                                            # :250-256 (float K_cam)
                 K = np.array(fr.K_cam, np.float32, copy=True)
-                K[0, 0], K[0, 2], K[1, 1], K[1, 2] = self.parameters_[-4:].astype(np.float32)
+                if self.group_camera_ids_:          # each group's result goes to that group's frames only
+                    G = len(self.group_camera_ids_)
+                    g = int(self.camera_group_[k - 1])
+                    K[0, 0], K[0, 2], K[1, 1], K[1, 2] = self.parameters_[len(self.parameters_) - 4 * (G - g):][:4].astype(np.float32)
+                else:
+                    K[0, 0], K[0, 2], K[1, 1], K[1, 2] = self.parameters_[-4:].astype(np.float32)
                 fr.K_cam = K
         nc, npt = self.num_cameras_, self.num_points_
         sfm_sparse_points.xyz = self.parameters_[6 * nc:6 * nc + 3 * npt].reshape(npt, 3).astype(np.float32)  # :277-279

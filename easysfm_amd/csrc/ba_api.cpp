@@ -70,20 +70,34 @@ void ba_options_default(esfm_ba_options *o)
 
 namespace {
 
+// The free intrinsics blocks of a problem: n == 0 fixed intrinsics; else n blocks fx, cx, fy, cy (calib4: 4 n doubles), block g boxed
+// to calib4 +- tol[g] and used by the cameras with group_of_cam[c] == g (NULL: every camera uses block 0).
+struct CalibGroups {
+    int n = 0;
+    const int32_t *group_of_cam = nullptr;
+    const double *calib4 = nullptr;
+    const double *tol = nullptr;
+    bool checked = false;      // the grouped entry points validate these arrays before anything else (checked_groups)
+};
+
 int check_create_args(esfm_ctx *ctx, int n_real, int n_pt, int n_obs, const int32_t *cam_idx, const int32_t *pt_idx, const float *obs_uv,
-                      const float *K4_per_cam, const double *calib, double calib_tol, const double *cams, const double *pts, esfm_ba_problem **out)
+                      const float *K4_per_cam, const CalibGroups &cg, const double *cams, const double *pts, esfm_ba_problem **out)
 {
     if (!ctx || !out) { esfm::set_error("ctx/out is NULL"); return ESFM_ERR_INVALID_ARG; }
     *out = nullptr;
     ESFM_REQUIRE(n_real >= 0 && n_pt >= 0 && n_obs >= 0, "negative size");
     ESFM_REQUIRE(n_obs == 0 || (cam_idx && pt_idx && obs_uv), "observation arrays are NULL");
-    ESFM_REQUIRE(n_real == 0 || ((K4_per_cam || calib) && cams), "camera arrays are NULL");
+    ESFM_REQUIRE(n_real == 0 || ((K4_per_cam || cg.n) && cams), "camera arrays are NULL");
     ESFM_REQUIRE(n_pt == 0 || pts, "pts is NULL");
     // Ceres rejects a variable block whose lower bound is not below its upper bound (Program::IsFeasible)
-    ESFM_REQUIRE(!calib || calib_tol > 0.0, "intrinsics tolerance must be positive");
-    if (calib) for (int i = 0; i < 4; ++i) if (!std::isfinite(calib[i])) { esfm::set_error("non-finite intrinsics"); return ESFM_ERR_NUMERIC; }
-    const int n_cam = n_real + (calib ? 1 : 0);   // 6-wide blocks of the reduced system
-    ESFM_REQUIRE((int64_t)6 * n_cam < 46000, "reduced system too large for this build (6 n_cam < 46000)");
+    // (the one shared block of the older entry points: its place among their checks, and their codes -- a NaN tolerance is "not
+    // positive" there; the grouped entry points have validated theirs already)
+    if (!cg.checked) {
+        ESFM_REQUIRE(cg.n == 0 || cg.tol[0] > 0.0, "intrinsics tolerance must be positive");
+        for (int i = 0; i < 4 * cg.n; ++i) if (!std::isfinite(cg.calib4[i])) { esfm::set_error("non-finite intrinsics"); return ESFM_ERR_NUMERIC; }
+    }
+    const int64_t n_cam = (int64_t)n_real + cg.n;   // 6-wide blocks of the reduced system
+    ESFM_REQUIRE(6 * n_cam < 46000, "reduced system too large for this build (6 n_cam < 46000)");
     for (int k = 0; k < n_obs; ++k)
         ESFM_REQUIRE(cam_idx[k] >= 0 && cam_idx[k] < n_real && pt_idx[k] >= 0 && pt_idx[k] < n_pt, "observation index out of range");
     for (size_t i = 0; i < (size_t)6 * n_real; ++i) if (!std::isfinite(cams[i])) { esfm::set_error("non-finite camera parameter"); return ESFM_ERR_NUMERIC; }
@@ -91,16 +105,17 @@ int check_create_args(esfm_ctx *ctx, int n_real, int n_pt, int n_obs, const int3
     return ESFM_OK;
 }
 
-// calib == NULL: fixed per-camera intrinsics K4_per_cam; else the shared free block fx, cx, fy, cy, carried as one more
-// 6-wide camera-side block behind the n_real cameras (ba_kernels.hpp).
+// cg.n == 0: fixed per-camera intrinsics K4_per_cam; else the free blocks fx, cx, fy, cy -- the one shared block or one per camera
+// group -- carried as cg.n more 6-wide camera-side blocks behind the n_real cameras (ba_kernels.hpp).
 int create_impl(esfm_ctx *ctx, int n_real, int n_pt, int n_obs, const int32_t *cam_idx, const int32_t *pt_idx,
-                const float *obs_uv, const float *K4_per_cam, const double *calib, double calib_tol, const double *cams,
+                const float *obs_uv, const float *K4_per_cam, const CalibGroups &cg, const double *cams,
                 const double *pts, esfm_ba_problem **out)
 {
-    if (int rc = check_create_args(ctx, n_real, n_pt, n_obs, cam_idx, pt_idx, obs_uv, K4_per_cam, calib, calib_tol, cams, pts, out)) return rc;
+    if (int rc = check_create_args(ctx, n_real, n_pt, n_obs, cam_idx, pt_idx, obs_uv, K4_per_cam, cg, cams, pts, out)) return rc;
     if (int rc = esfm::set_device(ctx)) return rc;
-    const int n_cam = n_real + (calib ? 1 : 0);   // 6-wide blocks of the reduced system
-    const esfm::BaForms forms = esfm::ba_forms(n_real, calib != nullptr, n_obs);
+    const bool calib = cg.n > 0;
+    const int n_cam = n_real + cg.n;   // 6-wide blocks of the reduced system
+    const esfm::BaForms forms = esfm::ba_forms(n_real, calib, n_obs, calib ? cg.n : 1);
     const esfm::BaLayout L = esfm::make_ba_layout(n_real, n_pt, n_obs, cam_idx, pt_idx, ctx->num_cu, forms.schur == esfm::BaForms::SCHUR_TABLES);
     std::vector<float> s_uv((size_t)2 * n_obs);
     for (size_t t = 0; t < (size_t)n_obs; ++t) {
@@ -114,14 +129,16 @@ int create_impl(esfm_ctx *ctx, int n_real, int n_pt, int n_obs, const int32_t *c
     P->cam_nobs_local.assign((size_t)n_cam, 0.0);
     for (int c = 0; c < n_real; ++c) P->cam_nobs_local[(size_t)c] = (double)L.cam_nobs[(size_t)c];
     if (calib) {
-        P->cam_nobs_local[(size_t)n_real] = (double)n_obs;   // every observation involves the intrinsics block
-        for (int i = 0; i < 4; ++i) P->calib_center[i] = calib[i];
-        P->calib_tol = calib_tol;
+        // every observation involves the intrinsics block of its camera's group
+        if (cg.n == 1) P->cam_nobs_local[(size_t)n_real] = (double)n_obs;
+        else for (int c = 0; c < n_real; ++c) P->cam_nobs_local[(size_t)n_real + cg.group_of_cam[c]] += (double)L.cam_nobs[(size_t)c];
+        P->calib_center.assign(cg.calib4, cg.calib4 + 4 * (size_t)cg.n);
+        P->calib_tol.assign(cg.tol, cg.tol + cg.n);
     }
     if (!calib && forms.solve == esfm::BaForms::SOLVE_TILED) { P->h_pt_start = L.pt_start; P->h_obs_cam = L.cam; }   // (for the reduced system's structure)
     BADev &d = P->d;
     d.n_cam = n_cam; d.n_pt = n_pt; d.n_obs = n_obs;
-    d.n_real_cam = n_real; d.has_calib = calib ? 1 : 0;
+    d.n_real_cam = n_real; d.has_calib = cg.n;
     d.parts = &P->parts;
     d.n_cchunks = (int)L.cchunk_cam.size();
     for (int tb = 0; tb < 2; ++tb) d.n_mchunks[tb] = (int)L.mchunk_cam0[tb].size();
@@ -149,6 +166,7 @@ int create_impl(esfm_ctx *ctx, int n_real, int n_pt, int n_obs, const int32_t *c
     index_table(&d.wide_obs, L.wide_obs);
     index_table(&d.pchunk_pt0, L.pchunk_pt0);
     table(&d.pchunk_info, L.pchunk_info.data(), L.pchunk_info.size());
+    if (cg.n > 1) table(&d.cam_group, cg.group_of_cam, (size_t)n_real);
 
     // the tables first, then the work arrays (an empty table takes one padded slot of the arena like any other array)
     const size_t no = (size_t)n_obs, nc6 = (size_t)6 * n_cam, np3 = (size_t)3 * n_pt;
@@ -187,14 +205,40 @@ int create_impl(esfm_ctx *ctx, int n_real, int n_pt, int n_obs, const int32_t *c
         }
     };
     for (const Table &t : tables) up(*t.dev, t.src, t.bytes);
-    const double calib_block[6] = {calib ? calib[0] : 0.0, calib ? calib[1] : 0.0, calib ? calib[2] : 0.0, calib ? calib[3] : 0.0, 0.0, 0.0};
-    if (calib) up(d.x_c + 6 * (size_t)n_real, calib_block, sizeof(calib_block));
+    std::vector<double> calib_blocks(6 * (size_t)cg.n, 0.0);      // four unknowns and two padding unknowns per block
+    for (int g = 0; g < cg.n; ++g) for (int i = 0; i < 4; ++i) calib_blocks[6 * (size_t)g + i] = cg.calib4[4 * (size_t)g + i];
+    if (calib) up(d.x_c + 6 * (size_t)n_real, calib_blocks.data(), sizeof(double) * calib_blocks.size());
     up(d.x_c, cams, sizeof(double) * 6 * (size_t)n_real); up(d.x_p, pts, sizeof(double) * np3);
     // red: the entries no kernel ever writes (blocks above the diagonal) must read as zero
     if (rc == ESFM_OK && hipMemsetAsync(d.red, 0, sizeof(double) * esfm::ba_red_doubles(n_cam), st) != hipSuccess) { esfm::set_error("memset failed"); rc = ESFM_ERR_HIP; }
     if (rc == ESFM_OK && hipStreamSynchronize(st) != hipSuccess) { esfm::set_error("stream sync failed"); rc = ESFM_ERR_HIP; }
     if (rc != ESFM_OK) { esfm_ba_problem_destroy(P); return rc; }
     *out = P;
+    return ESFM_OK;
+}
+
+CalibGroups one_block(const double *calib4, const double *tol)
+{
+    CalibGroups cg;
+    cg.n = 1; cg.calib4 = calib4; cg.tol = tol;
+    return cg;
+}
+
+// the group arguments of the grouped entry points, checked before anything else is looked at (nothing is written on failure)
+int checked_groups(int n_real, int n_groups, const int32_t *group_of_cam, const double *calib4, const double *tol, esfm_ba_problem **out, CalibGroups &cg)
+{
+    if (out) *out = nullptr;
+    ESFM_REQUIRE(n_groups >= 1, "n_groups must be at least 1");
+    ESFM_REQUIRE(calib4 && tol, "calib4 / calib_tolerance is NULL");
+    ESFM_REQUIRE(n_real <= 0 || group_of_cam, "group_of_cam is NULL");
+    ESFM_REQUIRE((int64_t)6 * ((int64_t)std::max(n_real, 0) + n_groups) < 46000, "reduced system too large for this build (6 (n_cam + n_groups) < 46000)");
+    for (int g = 0; g < n_groups; ++g) {
+        if (tol[g] != tol[g] || std::isinf(tol[g])) { esfm::set_error("non-finite intrinsics tolerance"); return ESFM_ERR_NUMERIC; }
+        ESFM_REQUIRE(tol[g] > 0.0, "intrinsics tolerance must be positive");
+    }
+    for (int i = 0; i < 4 * n_groups; ++i) if (!std::isfinite(calib4[i])) { esfm::set_error("non-finite intrinsics"); return ESFM_ERR_NUMERIC; }
+    for (int c = 0; c < n_real; ++c) ESFM_REQUIRE(group_of_cam[c] >= 0 && group_of_cam[c] < n_groups, "camera group index out of range");
+    cg.n = n_groups; cg.group_of_cam = group_of_cam; cg.calib4 = calib4; cg.tol = tol; cg.checked = true;
     return ESFM_OK;
 }
 
@@ -209,7 +253,7 @@ int esfm_ba_problem_create(esfm_ctx *ctx, int n_cam, int n_pt, int n_obs, const 
                            esfm_ba_problem **out)
 {
     if (n_cam > 0 && !K4_per_cam) { esfm::set_error("K4_per_cam is NULL"); return ESFM_ERR_INVALID_ARG; }
-    return create_impl(ctx, n_cam, n_pt, n_obs, cam_idx, pt_idx, obs_uv, K4_per_cam, nullptr, 0.0, cams, pts, out);
+    return create_impl(ctx, n_cam, n_pt, n_obs, cam_idx, pt_idx, obs_uv, K4_per_cam, CalibGroups(), cams, pts, out);
 }
 
 int esfm_ba_problem_create_free_calib(esfm_ctx *ctx, int n_cam, int n_pt, int n_obs, const int32_t *cam_idx, const int32_t *pt_idx,
@@ -217,18 +261,60 @@ int esfm_ba_problem_create_free_calib(esfm_ctx *ctx, int n_cam, int n_pt, int n_
                                       const double *pts, esfm_ba_problem **out)
 {
     if (!calib4) { esfm::set_error("calib4 is NULL"); return ESFM_ERR_INVALID_ARG; }
-    return create_impl(ctx, n_cam, n_pt, n_obs, cam_idx, pt_idx, obs_uv, nullptr, calib4, calib_tolerance, cams, pts, out);
+    return create_impl(ctx, n_cam, n_pt, n_obs, cam_idx, pt_idx, obs_uv, nullptr, one_block(calib4, &calib_tolerance), cams, pts, out);
+}
+
+int esfm_ba_problem_create_calib_groups(esfm_ctx *ctx, int n_cam, int n_pt, int n_obs, const int32_t *cam_idx, const int32_t *pt_idx,
+                                        const float *obs_uv, int n_groups, const int32_t *group_of_cam, const double *calib4,
+                                        const double *calib_tolerance, const double *cams, const double *pts, esfm_ba_problem **out)
+{
+    CalibGroups cg;
+    if (int rc = checked_groups(n_cam, n_groups, group_of_cam, calib4, calib_tolerance, out, cg)) return rc;
+    return create_impl(ctx, n_cam, n_pt, n_obs, cam_idx, pt_idx, obs_uv, nullptr, cg, cams, pts, out);
+}
+
+int esfm_ba_problem_calib_groups(const esfm_ba_problem *P) { return P ? P->d.has_calib : 0; }
+
+int esfm_ba_problem_set_calib_groups(esfm_ba_problem *P, const double *calib4, const double *calib_tolerance)
+{
+    if (!P || !calib4 || !calib_tolerance) { esfm::set_error("NULL argument"); return ESFM_ERR_INVALID_ARG; }
+    ESFM_REQUIRE(P->d.has_calib, "problem was created with fixed intrinsics");
+    const int G = P->d.has_calib;
+    for (int g = 0; g < G; ++g) ESFM_REQUIRE(calib_tolerance[g] > 0.0 && std::isfinite(calib_tolerance[g]), "intrinsics tolerance must be positive and finite");
+    for (int i = 0; i < 4 * G; ++i) if (!std::isfinite(calib4[i])) { esfm::set_error("non-finite intrinsics"); return ESFM_ERR_NUMERIC; }
+    if (int rc = esfm::set_device(P->ctx)) return rc;
+    P->calib_center.assign(calib4, calib4 + 4 * (size_t)G);
+    P->calib_tol.assign(calib_tolerance, calib_tolerance + G);
+    std::vector<double> blocks(6 * (size_t)G, 0.0);
+    for (int g = 0; g < G; ++g) for (int i = 0; i < 4; ++i) blocks[6 * (size_t)g + i] = calib4[4 * (size_t)g + i];
+    ESFM_HIP_TRY(esfm::copy_h2d(P->d.x_c + 6 * (size_t)P->d.n_real_cam, blocks.data(), sizeof(double) * blocks.size(), P->ctx->stream));
+    ESFM_HIP_TRY(hipStreamSynchronize(P->ctx->stream));
+    return ESFM_OK;
+}
+
+int esfm_ba_problem_get_calib_groups(esfm_ba_problem *P, double *calib4)
+{
+    if (!P || !calib4) { esfm::set_error("NULL argument"); return ESFM_ERR_INVALID_ARG; }
+    ESFM_REQUIRE(P->d.has_calib, "problem was created with fixed intrinsics");
+    if (int rc = esfm::set_device(P->ctx)) return rc;
+    const int G = P->d.has_calib;
+    std::vector<double> blocks(6 * (size_t)G);
+    ESFM_HIP_TRY(esfm::copy_d2h(blocks.data(), P->d.x_c + 6 * (size_t)P->d.n_real_cam, sizeof(double) * blocks.size(), P->ctx->stream));
+    ESFM_HIP_TRY(hipStreamSynchronize(P->ctx->stream));
+    for (int g = 0; g < G; ++g) for (int i = 0; i < 4; ++i) calib4[4 * (size_t)g + i] = blocks[6 * (size_t)g + i];
+    return ESFM_OK;
 }
 
 int esfm_ba_problem_set_calib(esfm_ba_problem *P, const double *calib4, double calib_tolerance)
 {
     if (!P || !calib4) { esfm::set_error("NULL argument"); return ESFM_ERR_INVALID_ARG; }
     ESFM_REQUIRE(P->d.has_calib, "problem was created with fixed intrinsics");
+    ESFM_REQUIRE(P->d.has_calib == 1, "problem has several intrinsics blocks: use esfm_ba_problem_set_calib_groups");
     ESFM_REQUIRE(calib_tolerance > 0.0, "intrinsics tolerance must be positive");
     for (int i = 0; i < 4; ++i) if (!std::isfinite(calib4[i])) { esfm::set_error("non-finite intrinsics"); return ESFM_ERR_NUMERIC; }
     if (int rc = esfm::set_device(P->ctx)) return rc;
-    for (int i = 0; i < 4; ++i) P->calib_center[i] = calib4[i];
-    P->calib_tol = calib_tolerance;
+    P->calib_center.assign(calib4, calib4 + 4);
+    P->calib_tol.assign(1, calib_tolerance);
     ESFM_HIP_TRY(esfm::copy_h2d(P->d.x_c + 6 * (size_t)P->d.n_real_cam, calib4, sizeof(double) * 4, P->ctx->stream));
     ESFM_HIP_TRY(hipStreamSynchronize(P->ctx->stream));
     return ESFM_OK;
@@ -238,6 +324,7 @@ int esfm_ba_problem_get_calib(esfm_ba_problem *P, double *calib4)
 {
     if (!P || !calib4) { esfm::set_error("NULL argument"); return ESFM_ERR_INVALID_ARG; }
     ESFM_REQUIRE(P->d.has_calib, "problem was created with fixed intrinsics");
+    ESFM_REQUIRE(P->d.has_calib == 1, "problem has several intrinsics blocks: use esfm_ba_problem_get_calib_groups");
     if (int rc = esfm::set_device(P->ctx)) return rc;
     ESFM_HIP_TRY(esfm::copy_d2h(calib4, P->d.x_c + 6 * (size_t)P->d.n_real_cam, sizeof(double) * 4, P->ctx->stream));
     ESFM_HIP_TRY(hipStreamSynchronize(P->ctx->stream));
@@ -343,12 +430,32 @@ int esfm_ba_solve_ex(esfm_ctx *ctx, int n_cam, int n_pt, int n_obs, const int32_
                      esfm_ba_summary *summary)
 {
     esfm_ba_problem *P = nullptr;
-    if (int rc = create_impl(ctx, n_cam, n_pt, n_obs, cam_idx, pt_idx, obs_uv, K4_per_cam, calib4, calib_tolerance, cams, pts, &P)) return rc;
+    if (int rc = create_impl(ctx, n_cam, n_pt, n_obs, cam_idx, pt_idx, obs_uv, K4_per_cam, calib4 ? one_block(calib4, &calib_tolerance) : CalibGroups(), cams, pts,
+                             &P)) return rc;
     int rc = esfm_ba_problem_fix_camera(P, ref_cam, ref_threshold);
     if (rc == ESFM_OK) rc = esfm_ba_problem_solve(P, options, allreduce, allreduce_user, summary);
     if (rc == ESFM_OK || rc == ESFM_ERR_NUMERIC) {
         int rc2 = esfm_ba_problem_get_params(P, cams, pts);
         if (rc2 == ESFM_OK && calib4) rc2 = esfm_ba_problem_get_calib(P, calib4);
+        if (rc == ESFM_OK) rc = rc2;
+    }
+    esfm_ba_problem_destroy(P);
+    return rc;
+}
+
+int esfm_ba_solve_groups(esfm_ctx *ctx, int n_cam, int n_pt, int n_obs, const int32_t *cam_idx, const int32_t *pt_idx, const float *obs_uv,
+                         double *cams, double *pts, int n_groups, const int32_t *group_of_cam, double *calib4, const double *calib_tolerance,
+                         int ref_cam, double ref_threshold, const esfm_ba_options *options, esfm_allreduce_fn allreduce, void *allreduce_user,
+                         esfm_ba_summary *summary)
+{
+    esfm_ba_problem *P = nullptr;
+    if (int rc = esfm_ba_problem_create_calib_groups(ctx, n_cam, n_pt, n_obs, cam_idx, pt_idx, obs_uv, n_groups, group_of_cam, calib4, calib_tolerance,
+                                                     cams, pts, &P)) return rc;
+    int rc = esfm_ba_problem_fix_camera(P, ref_cam, ref_threshold);
+    if (rc == ESFM_OK) rc = esfm_ba_problem_solve(P, options, allreduce, allreduce_user, summary);
+    if (rc == ESFM_OK || rc == ESFM_ERR_NUMERIC) {
+        int rc2 = esfm_ba_problem_get_params(P, cams, pts);
+        if (rc2 == ESFM_OK) rc2 = esfm_ba_problem_get_calib_groups(P, calib4);
         if (rc == ESFM_OK) rc = rc2;
     }
     esfm_ba_problem_destroy(P);

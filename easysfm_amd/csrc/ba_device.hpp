@@ -243,11 +243,16 @@ __device__ __forceinline__ void transform_point(const double *__restrict__ cam, 
 }
 
 // fx, cx, fy, cy of camera c: the camera's float calibration (ba.h:142-143), or the shared free block, which is
-// stored behind the real cameras of the camera-side parameter vector `cams` (ba.h:199-202).
+// stored behind the real cameras of the camera-side parameter vector `cams` (ba.h:199-202).  GROUPS (several free blocks, one per
+// camera group): the block of the camera's group, n_real_cam + cam_group[c].
+template <bool GROUPS = false>
+__device__ __forceinline__ int calib_block_of(const BADev &d, int c) { return GROUPS ? d.n_real_cam + d.cam_group[c] : d.n_real_cam; }
+
+template <bool GROUPS = false>
 __device__ __forceinline__ void load_intrinsics(const BADev &d, const double *__restrict__ cams, int c, double in4[4])
 {
     if (d.has_calib) {
-        const double *kp = cams + 6 * (size_t)d.n_real_cam;
+        const double *kp = cams + 6 * (size_t)calib_block_of<GROUPS>(d, c);
         in4[0] = kp[0]; in4[1] = kp[1]; in4[2] = kp[2]; in4[3] = kp[3];
     } else {
         const float4 K = d.K4[c];

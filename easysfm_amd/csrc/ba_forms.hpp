@@ -21,7 +21,10 @@ struct BaForms {
     bool sweep_sums_in_lds = false;    // the Jacobian sweep keeps the per-camera sums in LDS (else: camera chunks, BaLayout::cchunk_*)
     bool large = false;                // >= 2^20 observations: 512-thread sweep, chunked per-point blocks, candidate cost in a pass of its own
 };
-BaForms ba_forms(int n_real_cam, bool has_calib, int n_obs);
+// n_groups: the free intrinsics blocks (one per camera group; read only with has_calib).  The rule is the one of a single block with
+// n_cam = n_real_cam + n_groups, except that with several groups the sweep never keeps the per-camera sums in LDS: a group's ten
+// sums G'G / G'r are its cameras' chunk sums added in chunk order (ba_camacc_groups_kernel), so every size takes the camera chunks.
+BaForms ba_forms(int n_real_cam, bool has_calib, int n_obs, int n_groups = 1);
 
 // dynamic LDS of the three kernels that have an in-LDS form
 constexpr int kLinLdsPerCam = 27 * 8 + 7 * 8 + 4 + 7 * 4;   // ba_linearize_kernel: acc, maxima, count, exponents
@@ -44,6 +47,14 @@ constexpr size_t chol_lds_bytes(int n_cam)      // ba_chol_solve_kernel: packed 
 constexpr size_t kCalibRowLdsBudget = 64 * 1024;
 constexpr size_t calib_row_lds_bytes(int n_real_cam) { return sizeof(double) * (8 + (size_t)4 * 6 * n_real_cam); }
 constexpr bool ba_calib_row_in_lds(int n_real_cam) { return calib_row_lds_bytes(n_real_cam) <= kCalibRowLdsBudget; }
+// ba_schur_groups_kernel (several free intrinsics blocks): the block rows of ALL groups, 4 n_groups rows of 6 (n_real_cam + n_groups)
+// fixed-point entries -- the camera columns and the group-by-group cross blocks -- under the same budget (two groups: up to 168
+// cameras); beyond, every addend goes to d.red directly
+constexpr size_t calib_groups_lds_bytes(int n_real_cam, int n_groups)
+{
+    return sizeof(double) * ((size_t)4 * n_groups * 6 * ((size_t)n_real_cam + n_groups));
+}
+constexpr bool ba_calib_groups_in_lds(int n_real_cam, int n_groups) { return calib_groups_lds_bytes(n_real_cam, n_groups) <= kCalibRowLdsBudget; }
 // the one-workgroup MFMA solve (ba_chol_small_kernel) holds at most kSmallMaxNb block rows of kSmallTile (= SB, ba_chol_tile.hpp)
 // unknowns: n = 6 n_cam <= 176
 constexpr int kSmallTile = 16, kSmallMaxNb = 11;

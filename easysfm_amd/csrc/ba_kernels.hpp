@@ -48,8 +48,8 @@ struct ScalBase { int b[6]; };                // kernel argument: first partial 
 
 struct BADev {
     int n_cam = 0, n_pt = 0, n_obs = 0;
-    int n_real_cam = 0, has_calib = 0;
-    int constrained = 0;          // any box bound on a camera-side unknown (lo_c / up_c hold +-inf elsewhere)
+    int n_real_cam = 0, has_calib = 0;   // has_calib: the number of free intrinsics blocks G (0: fixed intrinsics); n_cam = n_real_cam + G
+    int constrained = 0;         // any box bound on a camera-side unknown (lo_c / up_c hold +-inf elsewhere)
     // structure (static per problem)
     int32_t *obs_cam = nullptr;   // [n_obs] camera of sorted observation k
     int32_t *obs_pt = nullptr;    // [n_obs] point of sorted observation k
@@ -131,6 +131,8 @@ struct BADev {
     int32_t *pchunk_pt0 = nullptr;      // [n_pchunks + 1]
     int4 *pchunk_info = nullptr;        // [n_pchunks] {first point, end point, first observation, end observation}: what a chunk's workgroup needs before it can request anything else, in ONE load
     int n_pchunks = 0;
+    // several free intrinsics blocks (has_calib = G > 1): camera c uses block n_real_cam + cam_group[c].  One block: not read.
+    int32_t *cam_group = nullptr;       // [n_real_cam]
 };
 
 inline size_t ba_camacc_doubles(int n_cam) { return (size_t)42 * (size_t)n_cam; }

@@ -44,7 +44,9 @@ namespace esfm {
 // layout (SoA of doubles as here, double2, tiles of 64: profiles/r05_soa_stream_ubench.txt), so the layout is not what holds the sweep back.
 constexpr int kLinThreadsLarge = 512, kLinThreadsSmall = 256;
 
-template <bool PRIV, bool CALIB, int kLinThreads>
+// GROUPS (several free intrinsics blocks, has_calib = G > 1; always !PRIV): the intrinsics and their column scales are those of the
+// observation's camera's group, gathered with the camera's parameters; the per-group sums come from the camera chunks.
+template <bool PRIV, bool CALIB, int kLinThreads, bool GROUPS = false>
 __global__ __launch_bounds__(kLinThreads, 1) void ba_linearize_kernel(BADev d, double cauchy_a, int use_scaling, ScalBase sbase, double *__restrict__ slabs,
                                                                    int prov_rexp)
 {
@@ -55,6 +57,7 @@ __global__ __launch_bounds__(kLinThreads, 1) void ba_linearize_kernel(BADev d, d
     // and column: if one fails (a first linearisation, a problem that changed under the solver) the workgroup clears its sums and
     // runs the two-pass form below.  Either way the integers are exact sums on the grid the slab is converted with.  (Round 3: the
     // re-read of pass 2 was 336 MB of BA-512's sweep.)
+    static_assert(!GROUPS || (CALIB && !PRIV), "the grouped sweep is a free-intrinsics sweep without LDS sums");
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     double *red = reinterpret_cast<double *>(lds_raw);                                  // [8] reduction scratch, [10] intrinsics-block sums
     unsigned long long *acc = reinterpret_cast<unsigned long long *>(lds_raw) + 18;     // PRIV: [n_real_cam * 27]
@@ -111,12 +114,17 @@ __global__ __launch_bounds__(kLinThreads, 1) void ba_linearize_kernel(BADev d, d
     // register copy that has to wait for the load -- in front of the stores.  The camera's float calibration is converted where it
     // is used, for the same reason.)
     struct LinIdx { int c, p; float2 uv; };
-    struct LinPar { float4 K; double kd[4], cam[6], X[3], sc[6], sp[3]; };
+    struct LinPar { float4 K; double kd[4], cam[6], X[3], sc[6], sp[3], ksc[4]; };
     auto load_idx = [&](int k, LinIdx &o) { o.c = d.obs_cam[k]; o.p = d.obs_pt[k]; o.uv = d.obs_uv[k]; };
     auto load_par = [&](const LinIdx &ix, LinPar &o) {
         if (CALIB) {         // (== d.has_calib: the free block rides behind the real cameras, load_intrinsics)
-            const double *kp = d.x_c + 6 * (size_t)d.n_real_cam;
+            const size_t kb = 6 * (size_t)calib_block_of<GROUPS>(d, ix.c);
+            const double *kp = d.x_c + kb;
             o.kd[0] = kp[0]; o.kd[1] = kp[1]; o.kd[2] = kp[2]; o.kd[3] = kp[3];
+            if (GROUPS) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) o.ksc[i] = use_scaling ? d.scale_c[kb + i] : 1.0;
+            }
         } else {
             o.K = d.K4[ix.c];
         }
@@ -132,7 +140,7 @@ __global__ __launch_bounds__(kLinThreads, 1) void ba_linearize_kernel(BADev d, d
         }
     };
     double kscale[4] = {1.0, 1.0, 1.0, 1.0};      // the free intrinsics' column scales: the same for every observation, read once
-    if (CALIB && use_scaling) {
+    if (CALIB && !GROUPS && use_scaling) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) kscale[i] = d.scale_c[6 * (size_t)d.n_real_cam + i];
     }
@@ -202,7 +210,7 @@ __global__ __launch_bounds__(kLinThreads, 1) void ba_linearize_kernel(BADev d, d
             }
             if (CALIB) {
 #pragma unroll
-                for (int i = 0; i < 4; ++i) Jk[i] *= sq * kscale[i];
+                for (int i = 0; i < 4; ++i) Jk[i] *= sq * (GROUPS ? par_cur.ksc[i] : kscale[i]);
             }
         }
         if (CALIB) {
@@ -454,7 +462,7 @@ __global__ __launch_bounds__(256) void ba_camacc_final_kernel(BADev d)
         return;
     }
     const int q = e - nr * 27;
-    if (!d.has_calib || q >= 42) return;
+    if (d.has_calib != 1 || q >= 42) return;     // (several blocks: ba_camacc_groups_kernel)
     // the shared intrinsics block rides as camera-side block nr: 6 x 6 with the 4 x 4 part G'G (fx, cx | fy, cy never mix), then G'r
     const int kc = nr;
     if (q < 36) {
@@ -472,6 +480,48 @@ __global__ __launch_bounds__(256) void ba_camacc_final_kernel(BADev d)
         double v = 0.0;
         if (a < 4) for (int b = 0; b < d.n_cchunks; ++b) v += d.cam_part[(size_t)b * kCamPart + 33 + a];
         d.camacc[36 * (size_t)d.n_cam + 6 * (size_t)kc + a] = v;
+    }
+}
+
+// Several free intrinsics blocks: block g rides as camera-side block n_real_cam + g, and its sums G'G / G'r are the sums 27..36 of the
+// chunks of ITS cameras (a chunk belongs to one camera, hence to one group).  One WAVE per entry of the block's 6 x 6 and of its
+// right-hand side: lane l takes chunks l, l + 64, ... in that order -- a chunk of another group adds 0.0 -- then the wave shuffle
+// tree: a fixed association whatever the launch timing.  (One thread per entry walking all chunks was a chain of three dependent
+// loads per chunk: 2 ms per sweep at 938 chunks.)  A group without observations gets zeros.
+__global__ __launch_bounds__(64) void ba_camacc_groups_kernel(BADev d)
+{
+    const int g = blockIdx.x / 42, q = blockIdx.x % 42, lane = threadIdx.x;
+    const int kc = d.n_real_cam + g;
+    int src = -1;
+    if (q < 36) {
+        const int a = q / 6, b2 = q % 6;
+        const int lo = a < b2 ? a : b2, hi = a < b2 ? b2 : a;
+        if (lo == 0 && hi == 0) src = 27; else if (lo == 0 && hi == 1) src = 28; else if (lo == 1 && hi == 1) src = 29;
+        else if (lo == 2 && hi == 2) src = 30; else if (lo == 2 && hi == 3) src = 31; else if (lo == 3 && hi == 3) src = 32;
+    } else if (q - 36 < 4) src = 33 + (q - 36);
+    double v = 0.0;
+    if (src >= 0) {
+        constexpr int U = 4;
+        for (int b0 = lane; b0 < d.n_cchunks; b0 += 64 * U) {
+            double t[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int b = b0 + 64 * u;
+                const bool mine = b < d.n_cchunks && d.cam_group[d.cchunk_cam[b < d.n_cchunks ? b : 0]] == g;
+                t[u] = mine ? d.cam_part[(size_t)b * kCamPart + src] : 0.0;
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) v += t[u];
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    }
+    if (lane != 0) return;
+    if (q < 36) {
+        d.camacc[36 * (size_t)kc + q] = v;
+        if (q / 6 == q % 6) d.qexp[6 * kc + q / 6] = qexp_of(v);
+    } else {
+        d.camacc[36 * (size_t)d.n_cam + 6 * (size_t)kc + (q - 36)] = v;
     }
 }
 
@@ -718,6 +768,7 @@ int ba_linearize(hipStream_t st, const BADev &d, int num_cu, double cauchy_a, bo
     // after the first, paying the 9-us prologue (LDS clear, exponents) and the 8-us epilogue (guard, slab) again: one per CU)
     const int grid = std::min(div_up(d.n_obs, kLinThreads), std::max(1, num_cu) * (small ? 2 : 1));
     const bool priv = forms.sweep_sums_in_lds;
+    if (priv && d.has_calib > 1) { set_error("BA sweep: several intrinsics blocks take the camera-chunk sums"); return ESFM_ERR_INVALID_ARG; }
     if (priv && (size_t)grid * ba_lin_slab_doubles(d.n_cam) > d.lin_slab_cap) { set_error("BA sweep: %d slabs do not fit lin_slabs", grid); return ESFM_ERR_INVALID_ARG; }
     ScalBase sbase;
     { const int slots[2] = {SC_COST, SC_LIN_BAD}; if (int rc = scal_reserve<2>(st, d, slots, grid, sbase)) return rc; }
@@ -741,6 +792,7 @@ int ba_linearize(hipStream_t st, const BADev &d, int num_cu, double cauchy_a, bo
         KernelTimer tm(timing_ctx, ESFM_K_BA_LINEARIZE);   // the Jacobian sweep alone
         auto kern = small ? (d.has_calib ? &ba_linearize_kernel<false, true, kLinThreadsSmall> : &ba_linearize_kernel<false, false, kLinThreadsSmall>)
                           : (d.has_calib ? &ba_linearize_kernel<false, true, kLinThreadsLarge> : &ba_linearize_kernel<false, false, kLinThreadsLarge>);
+        if (d.has_calib > 1) kern = small ? &ba_linearize_kernel<false, true, kLinThreadsSmall, true> : &ba_linearize_kernel<false, true, kLinThreadsLarge, true>;
         hipLaunchKernelGGL(kern, dim3(grid), dim3(kLinThreads), 18 * sizeof(double), st, d, cauchy_a, use_scaling ? 1 : 0, sbase, (double *)nullptr, INT_MIN);
     }
     LAUNCH_CHECK();
@@ -748,6 +800,10 @@ int ba_linearize(hipStream_t st, const BADev &d, int num_cu, double cauchy_a, bo
     else hipLaunchKernelGGL(ba_camacc_chunk_kernel<false>, dim3(d.n_cchunks), dim3(64), 0, st, d);
     hipLaunchKernelGGL(ba_camacc_final_kernel, dim3(div_up(d.n_real_cam * 27 + 42, 256)), dim3(256), 0, st, d);
     LAUNCH_CHECK();
+    if (d.has_calib > 1) {
+        hipLaunchKernelGGL(ba_camacc_groups_kernel, dim3(d.has_calib * 42), dim3(64), 0, st, d);
+        LAUNCH_CHECK();
+    }
     return ESFM_OK;
 }
 

@@ -564,6 +564,125 @@ __global__ __launch_bounds__(256) void ba_schur_calib_kernel(BADev d, int use_ld
     }
 }
 
+// Several free intrinsics blocks (has_calib = G > 1): block g rides as camera-side block n_real_cam + g and takes the observations of
+// the cameras with cam_group[c] == g.  One thread per point p; for every group g that occurs in the track (found at its first
+// observation), with Wk_g = sum_{i in p, group(i) = g} G_i'E_i (4 x 3) and Yk_g = Wk_g M^-1:
+//   rhs[g]     -= Wk_g M^-1 E'r
+//   S[g][c_j]  -= Yk_g W_j'  for every observation j of p,  += G_j'F_j  where group(c_j) == g
+//   S[g][g2]   -= Yk_g Wk_g2'  for every group g2 <= g of the track (g2 == g: the lower triangle, as the one block's kernel writes it)
+// Every addend is rounded to its entry's fixed-point grid and added as an integer -- through an LDS copy of all 4 G block rows while
+// that fits (ba_calib_groups_in_lds), else into d.red directly -- so the sums do not depend on the order of arrival.  A track of T
+// observations over L groups walks its rows L (L + 1) T / 2 + 2 L T times: the tracks are short.  Runs after ba_schur.
+__global__ __launch_bounds__(256) void ba_schur_groups_kernel(BADev d, int use_lds, int rhs_exp)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned long long rowq[];   // use_lds: [4 G][6 n_cam]
+    const int tid = threadIdx.x;
+    const int nr = d.n_real_cam, G = d.has_calib, n = 6 * d.n_cam;
+    unsigned long long *redq = reinterpret_cast<unsigned long long *>(d.red);
+    if (use_lds) {
+        for (int e = tid; e < 4 * G * n; e += 256) rowq[e] = 0ull;
+        __syncthreads();
+    }
+    auto add = [&](int g, int a, int col, double v, int sh) {
+        const unsigned long long q = fx64(v, sh);
+        if (q == 0ull) return;
+        if (use_lds) atomicAdd(&rowq[(size_t)(4 * g + a) * n + col], q);
+        else atomicAdd(&redq[(size_t)(6 * (nr + g) + a) * n + col], q);
+    };
+    const size_t no = d.n_obs;
+    // Wk of group g over the track [b, e)
+    auto group_W = [&](int b, int e, int g, double (&Wk)[4][3]) {
+#pragma unroll
+        for (int a = 0; a < 4; ++a) Wk[a][0] = Wk[a][1] = Wk[a][2] = 0.0;
+        for (int k = b; k < e; ++k) {
+            if (d.cam_group[d.obs_cam[k]] != g) continue;
+            const double k0 = d.Jk[k], k1 = d.Jk[no + k], k2 = d.Jk[2 * no + k], k3 = d.Jk[3 * no + k];
+#pragma unroll
+            for (int m = 0; m < 3; ++m) {
+                const double e0 = d.Jp[m * no + k], e1 = d.Jp[(3 + m) * no + k];
+                Wk[0][m] += k0 * e0; Wk[1][m] += k1 * e0; Wk[2][m] += k2 * e1; Wk[3][m] += k3 * e1;
+            }
+        }
+    };
+    auto first_of_group = [&](int b, int k, int g) {
+        for (int j = b; j < k; ++j) if (d.cam_group[d.obs_cam[j]] == g) return false;
+        return true;
+    };
+    const int p = blockIdx.x * 256 + tid;
+    const int b = p < d.n_pt ? d.pt_start[p] : 0, e = p < d.n_pt ? d.pt_start[p + 1] : 0;
+    if (e > b) {
+        const double *Mi = d.Minv + 6 * (size_t)p;
+        const double M[9] = {Mi[0], Mi[1], Mi[2], Mi[1], Mi[3], Mi[4], Mi[2], Mi[4], Mi[5]};
+        const double ag[3] = {d.Aig[3 * (size_t)p], d.Aig[3 * (size_t)p + 1], d.Aig[3 * (size_t)p + 2]};
+        for (int kl = b; kl < e; ++kl) {
+            const int g = d.cam_group[d.obs_cam[kl]];
+            if (!first_of_group(b, kl, g)) continue;
+            const int kap = 6 * (nr + g);
+            double Wk[4][3], Yk[4][3];
+            group_W(kl, e, g, Wk);
+            int qe[4];
+#pragma unroll
+            for (int a = 0; a < 4; ++a) {
+                qe[a] = d.qexp[kap + a];
+#pragma unroll
+                for (int m = 0; m < 3; ++m) Yk[a][m] = Wk[a][0] * M[m] + Wk[a][1] * M[3 + m] + Wk[a][2] * M[6 + m];
+                const double v = -(Wk[a][0] * ag[0] + Wk[a][1] * ag[1] + Wk[a][2] * ag[2]);
+                if (v != 0.0) fx_add(&d.red[(size_t)n * n + kap + a], v, kFxBits - qe[a] - rhs_exp);
+            }
+            // the camera columns of block row g
+            for (int k = b; k < e; ++k) {
+                const int c = d.obs_cam[k];
+                const bool same = d.cam_group[c] == g;
+                double kk[4] = {0.0, 0.0, 0.0, 0.0};
+                if (same) { kk[0] = d.Jk[k]; kk[1] = d.Jk[no + k]; kk[2] = d.Jk[2 * no + k]; kk[3] = d.Jk[3 * no + k]; }
+                double Ej[6];
+#pragma unroll
+                for (int m = 0; m < 6; ++m) Ej[m] = d.Jp[m * no + k];
+#pragma unroll
+                for (int c2 = 0; c2 < 6; ++c2) {
+                    const double f0 = d.Jc[c2 * no + k], f1 = d.Jc[(6 + c2) * no + k];
+                    const double w0 = f0 * Ej[0] + f1 * Ej[3], w1 = f0 * Ej[1] + f1 * Ej[4], w2 = f0 * Ej[2] + f1 * Ej[5];
+                    const int ej = d.qexp[6 * c + c2];
+#pragma unroll
+                    for (int a = 0; a < 4; ++a) {
+                        const double v = (a < 2 ? kk[a] * f0 : kk[a] * f1) - (Yk[a][0] * w0 + Yk[a][1] * w1 + Yk[a][2] * w2);
+                        add(g, a, 6 * c + c2, v, kFxBits - qe[a] - ej);
+                    }
+                }
+            }
+            // the group-by-group blocks of block row g: the groups g2 <= g of the track
+            for (int k2 = b; k2 < e; ++k2) {
+                const int g2 = d.cam_group[d.obs_cam[k2]];
+                if (g2 > g || !first_of_group(b, k2, g2)) continue;
+                double W2[4][3];
+                if (g2 == g) {
+#pragma unroll
+                    for (int a = 0; a < 4; ++a) { W2[a][0] = Wk[a][0]; W2[a][1] = Wk[a][1]; W2[a][2] = Wk[a][2]; }
+                } else {
+                    group_W(k2, e, g2, W2);
+                }
+                const int kap2 = 6 * (nr + g2);
+#pragma unroll
+                for (int a = 0; a < 4; ++a)
+#pragma unroll
+                    for (int b2 = 0; b2 < 4; ++b2) {
+                        if (g2 == g && b2 > a) continue;
+                        const double v = -(Yk[a][0] * W2[b2][0] + Yk[a][1] * W2[b2][1] + Yk[a][2] * W2[b2][2]);
+                        add(g, a, kap2 + b2, v, kFxBits - qe[a] - d.qexp[kap2 + b2]);
+                    }
+            }
+        }
+    }
+    if (use_lds) {
+        __syncthreads();
+        for (int e2 = tid; e2 < 4 * G * n; e2 += 256) {
+            const unsigned long long v = rowq[e2];
+            const int row = e2 / n, col = e2 % n;
+            if (v != 0ull) atomicAdd(&redq[(size_t)(6 * (nr + row / 4) + row % 4) * n + col], v);
+        }
+    }
+}
+
 // Sum the per-workgroup slabs (fixed-point integers: exact in any order) and scatter into red = S_schur (n x n) | rhs_corr (n);
 // TO_DOUBLE: converted to f64 on the way (no free intrinsics), else left in fixed point for ba_schur_calib_kernel to add to.
 template <bool TO_DOUBLE>
@@ -744,6 +863,14 @@ int ba_schur(hipStream_t st, const BADev &d, int num_cu, double rhs_bound)
 int ba_schur_calib(hipStream_t st, const BADev &d, double rhs_bound)
 {
     if (!d.has_calib || d.n_pt <= 0 || d.n_obs <= 0) return ESFM_OK;
+    if (d.has_calib > 1) {
+        const bool rows_in_lds = ba_calib_groups_in_lds(d.n_real_cam, d.has_calib);
+        const size_t bytes = rows_in_lds ? calib_groups_lds_bytes(d.n_real_cam, d.has_calib) : 0;
+        const int exp = bound_exponent(rhs_bound);
+        hipLaunchKernelGGL(ba_schur_groups_kernel, dim3(div_up(d.n_pt, 256)), dim3(256), bytes, st, d, rows_in_lds ? 1 : 0, exp);
+        LAUNCH_CHECK();
+        return schur_to_double(st, d, exp);
+    }
     const bool use_lds = ba_calib_row_in_lds(d.n_real_cam);
     const size_t lds = use_lds ? calib_row_lds_bytes(d.n_real_cam) : calib_row_lds_bytes(0);
     const int rhs_exp = bound_exponent(rhs_bound);

@@ -174,10 +174,13 @@ struct Solver {
             for (int i = 0; i < 6; ++i) { lo[6 * (size_t)P->ref_cam + i] = -P->ref_threshold; up[6 * (size_t)P->ref_cam + i] = P->ref_threshold; }
             d.constrained = 1;
         }
-        if (d.has_calib && cn[(size_t)d.n_real_cam] > 0.0) {
+        // (a block's count is its group's, summed over all ranks: a rank that holds none of a group's observations still boxes it)
+        for (int g = 0; g < d.has_calib; ++g) {
+            const size_t blk = (size_t)d.n_real_cam + g;
+            if (!(cn[blk] > 0.0)) continue;
             for (int i = 0; i < 4; ++i) {
-                lo[6 * (size_t)d.n_real_cam + i] = P->calib_center[i] - P->calib_tol;
-                up[6 * (size_t)d.n_real_cam + i] = P->calib_center[i] + P->calib_tol;
+                lo[6 * blk + i] = P->calib_center[4 * (size_t)g + i] - P->calib_tol[(size_t)g];
+                up[6 * blk + i] = P->calib_center[4 * (size_t)g + i] + P->calib_tol[(size_t)g];
             }
             d.constrained = 1;
         }

@@ -218,12 +218,13 @@ __global__ __launch_bounds__(256) void ba_camera_step_kernel(BADev d)
 
 // 1/2 rho(|r|^2) of observation k at the candidate (d.cand_c, point X): what ba_cost_kernel<false> evaluates, here inside the
 // back-substitution that has just produced X (WITH_COST: unbounded problems, where no slope along the step is needed)
+template <bool GROUPS>
 __device__ __forceinline__ void candidate_cost(const BADev &d, int k, const double (&X)[3], double cauchy_a, double &cost, double &bad)
 {
     const int c = d.obs_cam[k];
     const float2 uv = d.obs_uv[k];
     double in4[4];
-    load_intrinsics(d, d.cand_c, c, in4);
+    load_intrinsics<GROUPS>(d, d.cand_c, c, in4);
     double cam[6], pt[3];
 #pragma unroll
     for (int q = 0; q < 6; ++q) cam[q] = d.cand_c[6 * (size_t)c + q];
@@ -240,7 +241,9 @@ __device__ __forceinline__ void candidate_cost(const BADev &d, int k, const doub
 // (register budget: four workgroups per CU.  The WITH_COST form had been compiled to 198 registers -- two waves per SIMD for a kernel
 // that streams; at 128 BA-25's iteration went 0.136 -> 0.133 ms.  The same audit found nothing else: the sweep at three / four
 // workgroups per CU spills, 25.7 / 36 us against 22.5; the f64-MFMA Schur kernel at one / three: 462 / 640 us against 294.)
-template <bool WITH_COST>
+// GROUPS (several free intrinsics blocks): the intrinsics part of the step is that of the observation's camera's group, read per
+// observation where the one block's is read once per workgroup.
+template <bool WITH_COST, bool GROUPS = false>
 __global__ __launch_bounds__(kPtChunkObs, 4) void ba_backsub_chunk_kernel(BADev d, ScalBase sbase, double cauchy_a)
 {
     __shared__ double red[8];
@@ -254,10 +257,16 @@ __global__ __launch_bounds__(kPtChunkObs, 4) void ba_backsub_chunk_kernel(BADev 
     const size_t n = d.n_obs;
     double mc = 0.0, ssq = 0.0, csq = 0.0, gd = 0.0, dmax = 0.0, ccost = 0.0, cbad = 0.0;
     double yk[4] = {0.0, 0.0, 0.0, 0.0};
-    if (d.has_calib) {
+    if (d.has_calib && !GROUPS) {
 #pragma unroll
         for (int a = 0; a < 4; ++a) yk[a] = d.y_c[6 * d.n_real_cam + a];
     }
+    auto group_step = [&](int c) {
+        if (GROUPS) {
+#pragma unroll
+            for (int a = 0; a < 4; ++a) yk[a] = d.y_c[6 * calib_block_of<true>(d, c) + a];
+        }
+    };
     auto point_step_pre = [&](int p, const double g[3], const double (&Mi)[6], const double (&xq)[3], const double (&scq)[3]) {   // the same from operands already in registers
         double sp[3] = {-(Mi[0] * g[0] + Mi[1] * g[1] + Mi[2] * g[2]), -(Mi[1] * g[0] + Mi[3] * g[1] + Mi[4] * g[2]),
                         -(Mi[2] * g[0] + Mi[4] * g[1] + Mi[5] * g[2])};
@@ -318,6 +327,7 @@ __global__ __launch_bounds__(kPtChunkObs, 4) void ba_backsub_chunk_kernel(BADev 
 #pragma unroll
             for (int a = 0; a < 6; ++a) { f0 += Jc[a] * yc[a]; f1 += Jc[6 + a] * yc[a]; }
             if (d.has_calib) {
+                group_step(c);
                 f0 += d.Jk[k] * yk[0] + d.Jk[n + k] * yk[1];
                 f1 += d.Jk[2 * n + k] * yk[2] + d.Jk[3 * n + k] * yk[3];
             }
@@ -354,7 +364,7 @@ __global__ __launch_bounds__(kPtChunkObs, 4) void ba_backsub_chunk_kernel(BADev 
             gd = m0 * r0 + m1 * r1;
             if (WITH_COST) {
                 const double X[3] = {cnd[pl][0], cnd[pl][1], cnd[pl][2]};
-                candidate_cost(d, k, X, cauchy_a, ccost, cbad);
+                candidate_cost<GROUPS>(d, k, X, cauchy_a, ccost, cbad);
             }
         }
     } else {
@@ -367,6 +377,7 @@ __global__ __launch_bounds__(kPtChunkObs, 4) void ba_backsub_chunk_kernel(BADev 
 #pragma unroll
             for (int a = 0; a < 6; ++a) { const double yc = d.y_c[6 * c + a]; f0 += d.Jc[a * n + k] * yc; f1 += d.Jc[(6 + a) * n + k] * yc; }
             if (d.has_calib) {
+                group_step(c);
                 f0 += d.Jk[k] * yk[0] + d.Jk[n + k] * yk[1];
                 f1 += d.Jk[2 * n + k] * yk[2] + d.Jk[3 * n + k] * yk[3];
             }
@@ -389,6 +400,7 @@ __global__ __launch_bounds__(kPtChunkObs, 4) void ba_backsub_chunk_kernel(BADev 
 #pragma unroll
             for (int a = 0; a < 6; ++a) { const double sc = -d.y_c[6 * c + a]; m0 += d.Jc[a * n + k] * sc; m1 += d.Jc[(6 + a) * n + k] * sc; }
             if (d.has_calib) {
+                group_step(c);
                 m0 -= d.Jk[k] * yk[0] + d.Jk[n + k] * yk[1];
                 m1 -= d.Jk[2 * n + k] * yk[2] + d.Jk[3 * n + k] * yk[3];
             }
@@ -399,7 +411,7 @@ __global__ __launch_bounds__(kPtChunkObs, 4) void ba_backsub_chunk_kernel(BADev 
             gd += m0 * r0 + m1 * r1;
             if (WITH_COST) {
                 const double X[3] = {cnd[0][0], cnd[0][1], cnd[0][2]};
-                candidate_cost(d, k, X, cauchy_a, ccost, cbad);
+                candidate_cost<GROUPS>(d, k, X, cauchy_a, ccost, cbad);
             }
         }
     }
@@ -422,7 +434,7 @@ __global__ __launch_bounds__(kPtChunkObs, 4) void ba_backsub_chunk_kernel(BADev 
 // Robustified cost 1/2 sum rho(|r|^2) of (cams, pts) over this rank's observations.
 // SLOPE: also d/dt cost(Plus(x, t delta)) at this point = gradient . delta = sum rho' r.(J delta), the derivative
 // the Armijo search's cubic interpolation uses [upstream line_search.cc LineSearchFunction::Evaluate].
-template <bool SLOPE>
+template <bool SLOPE, bool GROUPS = false>
 __global__ __launch_bounds__(256) void ba_cost_kernel(BADev d, const double *__restrict__ cams, const double *__restrict__ pts,
                                                       double cauchy_a, int slot, int bad_slot, ScalBase sbase)
 {
@@ -432,7 +444,7 @@ __global__ __launch_bounds__(256) void ba_cost_kernel(BADev d, const double *__r
         const int c = d.obs_cam[k], p = d.obs_pt[k];
         const float2 uv = d.obs_uv[k];
         double in4[4];
-        load_intrinsics(d, cams, c, in4);
+        load_intrinsics<GROUPS>(d, cams, c, in4);
         double cam[6], X[3];
 #pragma unroll
         for (int i = 0; i < 6; ++i) cam[i] = cams[6 * (size_t)c + i];
@@ -447,7 +459,7 @@ __global__ __launch_bounds__(256) void ba_cost_kernel(BADev d, const double *__r
 #pragma unroll
             for (int a = 0; a < 3; ++a) { const double dl = d.delta_p[3 * (size_t)p + a]; m0 += Jp[a] * dl; m1 += Jp[3 + a] * dl; }
             if (d.has_calib) {
-                const double *dk = d.delta_c + 6 * (size_t)d.n_real_cam;
+                const double *dk = d.delta_c + 6 * (size_t)calib_block_of<GROUPS>(d, c);
                 m0 -= xn * dk[0] + dk[1];
                 m1 -= yn * dk[2] + dk[3];
             }
@@ -638,11 +650,15 @@ int ba_backsub(hipStream_t st, const BADev &d, bool with_cost, double cauchy_a)
         // the candidate's cost comes out of the same launch (SC_CAND_COST / SC_CAND_BAD): no ba_cost pass over the observations
         const int slots[6] = {SC_MODEL_CHANGE, SC_STEP_SQ_PT, SC_CAND_SQ_PT, SC_GDOTD, SC_CAND_COST, SC_CAND_BAD};
         if (int rc = scal_reserve<6>(st, d, slots, d.n_pchunks, sbase)) return rc;
-        hipLaunchKernelGGL(ba_backsub_chunk_kernel<true>, dim3(d.n_pchunks), dim3(kPtChunkObs), 0, st, d, sbase, cauchy_a);
+        auto kern = d.has_calib > 1 ? &ba_backsub_chunk_kernel<true, true> : &ba_backsub_chunk_kernel<true>;
+        hipLaunchKernelGGL(kern, dim3(d.n_pchunks), dim3(kPtChunkObs), 0, st, d,
+                           sbase, cauchy_a);
     } else {
         const int slots[4] = {SC_MODEL_CHANGE, SC_STEP_SQ_PT, SC_CAND_SQ_PT, SC_GDOTD};
         if (int rc = scal_reserve<4>(st, d, slots, d.n_pchunks, sbase)) return rc;
-        hipLaunchKernelGGL(ba_backsub_chunk_kernel<false>, dim3(d.n_pchunks), dim3(kPtChunkObs), 0, st, d, sbase, cauchy_a);
+        auto kern = d.has_calib > 1 ? &ba_backsub_chunk_kernel<false, true> : &ba_backsub_chunk_kernel<false>;
+        hipLaunchKernelGGL(kern, dim3(d.n_pchunks), dim3(kPtChunkObs), 0, st, d,
+                           sbase, cauchy_a);
     }
     LAUNCH_CHECK();
     return ESFM_OK;
@@ -657,11 +673,15 @@ int ba_cost(hipStream_t st, const BADev &d, int num_cu, const double *cams, cons
     if (with_slope) {
         const int slots[3] = {slot, bad_slot, SC_LS_GRAD};
         if (int rc = scal_reserve<3>(st, d, slots, grid, sbase)) return rc;
-        hipLaunchKernelGGL(ba_cost_kernel<true>, dim3(grid), dim3(256), 0, st, d, cams, pts, cauchy_a, slot, bad_slot, sbase);
+        auto kern = d.has_calib > 1 ? &ba_cost_kernel<true, true> : &ba_cost_kernel<true>;
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, st, d, cams, pts, cauchy_a, slot, bad_slot,
+                           sbase);
     } else {
         const int slots[2] = {slot, bad_slot};
         if (int rc = scal_reserve<2>(st, d, slots, grid, sbase)) return rc;
-        hipLaunchKernelGGL(ba_cost_kernel<false>, dim3(grid), dim3(256), 0, st, d, cams, pts, cauchy_a, slot, bad_slot, sbase);
+        auto kern = d.has_calib > 1 ? &ba_cost_kernel<false, true> : &ba_cost_kernel<false>;
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, st, d, cams, pts, cauchy_a, slot, bad_slot,
+                           sbase);
     }
     LAUNCH_CHECK();
     return ESFM_OK;

@@ -86,6 +86,7 @@ struct frame_t {  // utility.h:21-55
     std::vector<bool> unique_pixel_has_match;
     Matrix4f pose_cam = Matrix4f::Identity();
     Matrix3f K_cam = Matrix3f::Identity();
+    int camera_id = 0;  // multiple-camera mode: which physical camera (intrinsics model) took the frame; not in the reference's frame_t
     frame_t() = default;
     frame_t(unsigned int id, const std::string &path) : frame_id(id), image_file_path(path) {}
     bool init_pixel_ids()
@@ -683,6 +684,63 @@ public:
     // DataIO::importDistort (data_io.cpp:97-125): up to three groups of k1 k2 p1 p2 are extracted as floats, then stored with
     // at<float>(0, i) into the CV_64FC1 matrix -- i.e. into its first 16 bytes.  Reproduced: cv::undistort
     // sees v[0] = the double made of the bits of (k1, k2), v[1] = that of (p1, p2), v[2] = v[3] = 0.
+    // Multiple-camera mode (the drivers' +cameras token): the calibration file holds 9 G numbers (G row-major matrices) followed by
+    // one camera index per image -- exactly 9 G + n_images numbers, every index in [0, G).  false with `error` set otherwise.
+    static bool importCameras(const std::string &fileName, int n_images, std::vector<Matrix3f> &K_all, std::vector<int> &camera_of_image, std::string &error)
+    {
+        std::ifstream in(fileName, std::ios::in);
+        if (!in) { error = "cannot read the camera file " + fileName; return false; }
+        std::vector<double> vals;
+        std::string tok;
+        while (in >> tok) {
+            char *end = nullptr;
+            const double v = std::strtod(tok.c_str(), &end);
+            if (end == tok.c_str() || *end != 0) { error = "camera file: not a number: " + tok; return false; }
+            vals.push_back(v);
+        }
+        const long n_k = long(vals.size()) - n_images;
+        if (n_k < 9 || n_k % 9 != 0) {
+            error = "camera file: " + std::to_string(vals.size()) + " numbers for " + std::to_string(n_images) + " images; expected 9 G + " +
+                    std::to_string(n_images) + " (G matrices, then one camera index per image)";
+            return false;
+        }
+        const int G = int(n_k / 9);
+        K_all.assign(size_t(G), Matrix3f::Identity());
+        for (int g = 0; g < G; ++g) for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) K_all[size_t(g)](r, c) = float(vals[size_t(9 * g + 3 * r + c)]);
+        camera_of_image.clear();
+        for (int i = 0; i < n_images; ++i) {
+            const double v = vals[size_t(n_k + i)];
+            if (v != double(long(v)) || v < 0 || v >= G) { error = "camera file: a camera index is not an integer in [0, " + std::to_string(G) + ")"; return false; }
+            camera_of_image.push_back(int(v));
+        }
+        return true;
+    }
+
+    // ... and its distortion file: unreadable (none: zeros), 4 numbers (all cameras) or 4 G (per camera), each group stored as
+    // importDistort stores its four floats.  *imported tells whether a file was read.
+    static bool importCameraDistort(const std::string &fileName, int n_cameras, std::vector<DistortMat> &distort_all, bool &imported, std::string &error)
+    {
+        distort_all.assign(size_t(n_cameras), DistortMat());
+        imported = false;
+        std::ifstream in(fileName, std::ios::in);
+        if (!in) return true;
+        std::vector<float> vals;
+        std::string tok;
+        while (in >> tok) {
+            char *end = nullptr;
+            const double v = std::strtod(tok.c_str(), &end);
+            if (end == tok.c_str() || *end != 0) { error = "distortion file: not a number: " + tok; return false; }
+            vals.push_back(float(v));
+        }
+        if (vals.size() != 4 && vals.size() != size_t(4 * n_cameras)) {
+            error = "distortion file: " + std::to_string(vals.size()) + " numbers; expected 4 (all cameras) or " + std::to_string(4 * n_cameras) + " (4 per camera)";
+            return false;
+        }
+        for (int g = 0; g < n_cameras; ++g) std::memcpy(distort_all[size_t(g)].v, vals.data() + (vals.size() == 4 ? 0 : 4 * g), 4 * sizeof(float));
+        imported = true;
+        return true;
+    }
+
     bool importDistort(const std::string &fileName, DistortMat &distort_coeff)
     {
         std::ifstream in(fileName, std::ios::in);
@@ -702,6 +760,60 @@ public:
 };
 
 inline void angle_axis_to_rotation(const double aa[3], double R[9]);
+
+// Multiple-camera mode, the pair stage: its kernels take one K per pair and stay as they are.  While an object of this class lives,
+// every frame carries its keypoints remapped into the pixels of the canonical camera -- K_ref, the K_cam of the first frame with
+// camera_id 0 -- and K_ref itself: u' = (u - cx) fx_ref / fx + cx_ref, likewise v, in double, rounded to float once.  The pair
+// stage's thresholds are then in canonical pixels.  Its destructor puts the frames' own pixels and K_cam back.  Frames whose K_cam
+// equals K_ref bit for bit are not touched, and nothing is when all frames share one K_cam.
+class CanonicalPairView {
+public:
+    explicit CanonicalPairView(std::vector<frame_t> &frames) : frames_(frames)
+    {
+        if (frames.empty()) return;
+        const frame_t *ref = &frames[0];
+        for (const frame_t &f : frames) if (f.camera_id == 0) { ref = &f; break; }
+        const Matrix3f K_ref = ref->K_cam;
+        for (const frame_t &f : frames) active_ = active_ || !same(f.K_cam, K_ref);
+        if (!active_) return;
+        for (frame_t &f : frames) {
+            saved_K_.push_back(f.K_cam);
+            std::vector<Point2f> pts;
+            for (const KeyPoint &kp : f.keypoints) pts.push_back(kp.pt);
+            saved_pts_.push_back(pts);
+            if (!same(f.K_cam, K_ref)) {
+                const double fx = f.K_cam(0, 0), cx = f.K_cam(0, 2), fy = f.K_cam(1, 1), cy = f.K_cam(1, 2);
+                for (KeyPoint &kp : f.keypoints) {
+                    kp.pt.x = float((double(kp.pt.x) - cx) * double(K_ref(0, 0)) / fx + double(K_ref(0, 2)));
+                    kp.pt.y = float((double(kp.pt.y) - cy) * double(K_ref(1, 1)) / fy + double(K_ref(1, 2)));
+                }
+            }
+            f.K_cam = K_ref;
+        }
+    }
+    ~CanonicalPairView()
+    {
+        if (!active_) return;
+        for (size_t i = 0; i < frames_.size(); ++i) {
+            frames_[i].K_cam = saved_K_[i];
+            for (size_t k = 0; k < frames_[i].keypoints.size(); ++k) frames_[i].keypoints[k].pt = saved_pts_[i][k];
+        }
+    }
+    CanonicalPairView(const CanonicalPairView &) = delete;
+    CanonicalPairView &operator=(const CanonicalPairView &) = delete;
+    bool active() const { return active_; }
+
+private:
+    static bool same(const Matrix3f &a, const Matrix3f &b)
+    {
+        for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) { const float x = a(r, c), y = b(r, c); if (std::memcmp(&x, &y, sizeof(float)) != 0) return false; }
+        return true;
+    }
+    std::vector<frame_t> &frames_;
+    std::vector<Matrix3f> saved_K_;
+    std::vector<std::vector<Point2f>> saved_pts_;
+    bool active_ = false;
+};
 
 // ---- two-view / 3-D/2-D geometry (estimate_motion.h) ------------------------------------------------------
 class MotionEstimator {
@@ -858,7 +970,7 @@ public:
         std::vector<float> a, b;
         gather(cur_frame_1, cur_frame_2, matches, random_rate, a, b);
         const int n = int(a.size() / 2);
-        pixel2cam(a, cur_frame_1.K_cam); pixel2cam(b, cur_frame_1.K_cam);   // frame 1's K for both (:245)
+        pixel2cam(a, cur_frame_1.K_cam); pixel2cam(b, cur_frame_2.K_cam);   // the reference: frame 1's K for both (:245); the same when the K's are equal
         float P1[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0}, P2[12];
         for (int r = 0; r < 3; ++r) for (int c = 0; c < 4; ++c) P2[4 * r + c] = T_21(r, c);
         std::vector<float> h(size_t(4) * size_t(std::max(n, 1)));
@@ -890,7 +1002,7 @@ public:
             b.push_back(cur_frame_2.keypoints[size_t(m.trainIdx)].pt.x); b.push_back(cur_frame_2.keypoints[size_t(m.trainIdx)].pt.y);
             ++count_new;
         }
-        pixel2cam(a, cur_frame_1.K_cam); pixel2cam(b, cur_frame_1.K_cam);
+        pixel2cam(a, cur_frame_1.K_cam); pixel2cam(b, cur_frame_2.K_cam);
         float P1[12], P2[12];
         for (int r = 0; r < 3; ++r) for (int c = 0; c < 4; ++c) { P1[4 * r + c] = cur_frame_1.pose_cam(r, c); P2[4 * r + c] = cur_frame_2.pose_cam(r, c); }
         std::vector<float> h(size_t(4) * size_t(std::max(count_new, 1)));
@@ -1126,10 +1238,12 @@ public:
     int num_observations() const { return num_observations_; }
     double *mutable_cameras() { return parameters_.data(); }
     double *mutable_points() { return parameters_.data() + 6 * num_cameras_; }
+    double *mutable_calib() { return parameters_.data() + 6 * num_cameras_ + 3 * num_points_; }   // ba.h:45; several blocks: 4 doubles each
 
     bool initBA()  // ba.h:59-75
     {
         point_index_.clear(); camera_index_.clear(); points_2d_.clear(); calibs_.clear(); parameters_.clear();
+        camera_group_.clear(); group_camera_ids_.clear();
         num_cameras_ = num_points_ = num_parameters_ = num_observations_ = 0;
         ref_process_camera_id_ = -1;
         if (verbose) std::cout << "Bundle Ajustment parameters initialization done." << std::endl;
@@ -1162,7 +1276,22 @@ public:
             if (int(i) == reference_frame_id) ref_process_camera_id_ = num_cameras_;
             ++num_cameras_;
         }
-        num_parameters_ = 6 * num_cameras_ + 3 * num_points_ + (fix_calib_tolerance_BA != 0 ? 4 : 0);
+        // multiple-camera mode: free intrinsics over processed frames of more than one camera_id open one block per distinct id, in
+        // order of first appearance; one distinct id leaves the shared block of calibs_[0] in charge
+        if (fix_calib_tolerance_BA != 0) {
+            std::vector<int> ids, order;
+            for (size_t i = 0; i < frames.size(); ++i) {
+                if (process_frame_id[i]) continue;
+                ids.push_back(frames[i].camera_id);
+                if (std::find(order.begin(), order.end(), frames[i].camera_id) == order.end()) order.push_back(frames[i].camera_id);
+            }
+            if (order.size() > 1) {
+                group_camera_ids_ = order;
+                for (int id : ids) camera_group_.push_back(int(std::find(order.begin(), order.end(), id) - order.begin()));
+            }
+        }
+        const int n_blocks = group_camera_ids_.empty() ? 1 : int(group_camera_ids_.size());
+        num_parameters_ = 6 * num_cameras_ + 3 * num_points_ + (fix_calib_tolerance_BA != 0 ? 4 * n_blocks : 0);
         parameters_.assign(size_t(num_parameters_), 0.0);
         int k = 0;
         for (size_t i = 0; i < frames.size(); ++i) {
@@ -1182,7 +1311,14 @@ public:
             parameters_[size_t(6 * num_cameras_ + 3 * i + 1)] = p.y;
             parameters_[size_t(6 * num_cameras_ + 3 * i + 2)] = p.z;
         }
-        if (fix_calib_tolerance_BA != 0 && !calibs_.empty()) {
+        if (fix_calib_tolerance_BA != 0 && !group_camera_ids_.empty()) {
+            // the reference's calibs_[0] rule, per group: a group starts from the K_cam of its first processed frame
+            for (int g = 0; g < n_blocks; ++g) {
+                const size_t first = size_t(std::find(camera_group_.begin(), camera_group_.end(), g) - camera_group_.begin());
+                double *k4 = mutable_calib() + 4 * g;
+                k4[0] = calibs_[first](0, 0); k4[1] = calibs_[first](0, 2); k4[2] = calibs_[first](1, 1); k4[3] = calibs_[first](1, 2);
+            }
+        } else if (fix_calib_tolerance_BA != 0 && !calibs_.empty()) {
             parameters_[size_t(num_parameters_ - 4)] = calibs_[0](0, 0); parameters_[size_t(num_parameters_ - 3)] = calibs_[0](0, 2);
             parameters_[size_t(num_parameters_ - 2)] = calibs_[0](1, 1); parameters_[size_t(num_parameters_ - 1)] = calibs_[0](1, 2);
         }
@@ -1192,8 +1328,6 @@ public:
         }
         return 2 * num_observations_ > num_parameters_;  // "Ready to solve" (:120-129)
     }
-
-    double *mutable_calib() { return parameters_.data() + 6 * num_cameras_ + 3 * num_points_; }   // ba.h:45
 
     // ba.cpp:132-212: ceres::Solve -> esfm_ba_solve_ex.  Fixed intrinsics (:142-164) or the shared free block bounded to
     // +- tolerance (:167-196); a reference frame named in setBAProblem is bounded to +-1e-10 (:134, :155-162).
@@ -1206,6 +1340,15 @@ public:
             K4[size_t(4 * c + 2)] = calibs_[size_t(c)](1, 1); K4[size_t(4 * c + 3)] = calibs_[size_t(c)](1, 2);
         }
         options_.verbose = verbose ? 1 : 0;  // minimizer_progress_to_stdout (:204)
+        if (fix_calib_tolerance_BA != 0 && !group_camera_ids_.empty()) {   // one free block per camera group, each within +- tolerance
+            const std::vector<double> tol(group_camera_ids_.size(), fix_calib_tolerance_BA);
+            int rcg = esfm_ba_solve_groups(default_ctx(), num_cameras_, num_points_, num_observations_, camera_index_.data(), point_index_.data(),
+                                           reinterpret_cast<const float *>(points_2d_.data()), mutable_cameras(), mutable_points(),
+                                           int(group_camera_ids_.size()), camera_group_.data(), mutable_calib(), tol.data(),
+                                           ref_process_camera_id_, fixed_threshold, &options_, nullptr, nullptr, &summary_);
+            if (rcg != ESFM_OK) { std::cerr << esfm_last_error() << std::endl; return false; }
+            return true;
+        }
         int rc = esfm_ba_solve_ex(default_ctx(), num_cameras_, num_points_, num_observations_, camera_index_.data(), point_index_.data(),
                                   reinterpret_cast<const float *>(points_2d_.data()), K4.data(), mutable_cameras(), mutable_points(),
                                   fix_calib_tolerance_BA != 0 ? mutable_calib() : nullptr, fix_calib_tolerance_BA,
@@ -1234,14 +1377,25 @@ public:
                 frames[i].pose_cam(r, 3) = float(parameters_[size_t(6 * k + 3 + r)]);
             }
             ++k;
-            if (fix_calib_tolerance_BA != 0) {  // :250-256
+            if (fix_calib_tolerance_BA != 0 && !group_camera_ids_.empty()) {   // each group's result goes to that group's frames only
+                const double *k4 = mutable_calib() + 4 * camera_group_[size_t(k - 1)];
+                frames[i].K_cam(0, 0) = float(k4[0]); frames[i].K_cam(0, 2) = float(k4[1]);
+                frames[i].K_cam(1, 1) = float(k4[2]); frames[i].K_cam(1, 2) = float(k4[3]);
+            } else if (fix_calib_tolerance_BA != 0) {  // :250-256
                 frames[i].K_cam(0, 0) = float(parameters_[size_t(num_parameters_ - 4)]);
                 frames[i].K_cam(0, 2) = float(parameters_[size_t(num_parameters_ - 3)]);
                 frames[i].K_cam(1, 1) = float(parameters_[size_t(num_parameters_ - 2)]);
                 frames[i].K_cam(1, 2) = float(parameters_[size_t(num_parameters_ - 1)]);
             }
         }
-        if (verbose && fix_calib_tolerance_BA != 0)
+        if (verbose && fix_calib_tolerance_BA != 0 && !group_camera_ids_.empty()) {
+            std::cout << "Calib intrinsic parameters after BA:" << std::endl;
+            for (size_t g = 0; g < group_camera_ids_.size(); ++g) {
+                const double *k4 = mutable_calib() + 4 * g;
+                std::cout << "camera " << group_camera_ids_[g] << " [fx:" << k4[0] << " ,cx:" << k4[1] << " ,fy:" << k4[2] << " ,cy:" << k4[3] << " ]" << std::endl;
+            }
+        }
+        if (verbose && fix_calib_tolerance_BA != 0 && group_camera_ids_.empty())
             std::cout << "Calib intrinsic parameters after BA:" << std::endl
                       << "[fx:" << parameters_[size_t(num_parameters_ - 4)] << " ,cx:" << parameters_[size_t(num_parameters_ - 3)]
                       << " ,fy:" << parameters_[size_t(num_parameters_ - 2)] << " ,cy:" << parameters_[size_t(num_parameters_ - 1)] << " ]"
@@ -1268,6 +1422,9 @@ public:
     std::vector<Point2f> points_2d_;
     std::vector<Matrix3f> calibs_;
     int ref_process_camera_id_ = -1;
+    // multiple-camera mode: group of every processed camera and the camera_id of every group (first appearance first); both empty
+    // unless the intrinsics are free and the processed frames carry more than one camera_id
+    std::vector<int> camera_group_, group_camera_ids_;
 };
 
 // ---- dense reconstruction (esfm.h "Dense reconstruction"; the reference README's TODO "add multi-view stereo dense

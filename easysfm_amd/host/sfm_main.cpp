@@ -20,6 +20,7 @@
 #include <atomic>
 #include <string>
 #include <condition_variable>
+#include <memory>
 #include <mutex>
 #include <thread>
 #include <vector>
@@ -110,6 +111,18 @@ int main(int argc, char **argv)
     // rendering"; with the atlas if it was textured, else with its vertex colours), the pictures go there as render_%04d.png and one
     // "Mesh render:" line states their mean absolute error against the photographs
     std::string filter_arg = argc >= 15 ? argv[14] : "ratio";
+    // +cameras as the final token, behind everything else (ratio+cameras, ratio+guided+tracks+retrieval4+cameras): multiple-camera mode.
+    // calib_K_file then holds 9 G numbers (G row-major matrices) and one camera index per image, calib_distort_file none, 4 or 4 G
+    // numbers; one "Cameras:" line; the pair stage runs in camera 0's pixels (CanonicalPairView: repro_dis_ransac is then in those
+    // canonical pixels), free intrinsics free one block per camera; dense outputs need images of one size.  Stripped first.
+    bool multi_camera = false;
+    {
+        const std::string token = "+cameras";
+        if (filter_arg.size() > token.size() && filter_arg.compare(filter_arg.size() - token.size(), token.size(), token) == 0) {
+            multi_camera = true;
+            filter_arg.erase(filter_arg.size() - token.size());
+        }
+    }
     // +retrieval or +retrievalK (K decimal, 1 .. 999) at the very end, behind everything else (ratio+retrieval, ratio+guided+tracks+retrieval4):
     // only the pairs that image retrieval selects are matched (esfm.h "Image retrieval", default options, K = top_k; one "Pair selection:" line)
     bool retrieval = false;
@@ -193,9 +206,25 @@ int main(int argc, char **argv)
         if (!io.importImageFilenames(image_list_path, image_data_path, frames) || frames.size() < 2) { std::cerr << "need at least two images" << std::endl; return 3; }
         const int frame_number = int(frames.size());
         Matrix3f K_mat = Matrix3f::Identity();
-        if (!io.importCalib(calib_file_path, K_mat)) { std::cerr << "cannot read the calibration file " << calib_file_path << std::endl; return 3; }
         DistortMat distort_coeff;
-        if (!io.importDistort(distort_file_path, distort_coeff)) std::cout << "No distortion coefficients imported. Use defualt one (0)." << std::endl;
+        std::vector<Matrix3f> K_all;
+        std::vector<DistortMat> distort_all;
+        std::vector<int> camera_of_image;
+        if (multi_camera) {
+            std::string error;
+            bool imported = false;
+            if (!DataIO::importCameras(calib_file_path, frame_number, K_all, camera_of_image, error) ||
+                !DataIO::importCameraDistort(distort_file_path, int(K_all.size()), distort_all, imported, error)) { std::cerr << error << std::endl; return 3; }
+            std::vector<int> counts(K_all.size(), 0);
+            for (int c : camera_of_image) ++counts[size_t(c)];
+            std::cout << "Cameras: " << K_all.size() << " models, ";
+            for (size_t g = 0; g < counts.size(); ++g) std::cout << (g ? " / " : "") << counts[g];
+            std::cout << " images" << std::endl;
+            std::cout << (imported ? "Import camera distortion coefficients file done." : "No distortion coefficients imported. Use defualt one (0).") << std::endl;
+        } else {
+            if (!io.importCalib(calib_file_path, K_mat)) { std::cerr << "cannot read the calibration file " << calib_file_path << std::endl; return 3; }
+            if (!io.importDistort(distort_file_path, distort_coeff)) std::cout << "No distortion coefficients imported. Use defualt one (0)." << std::endl;
+        }
 
         // The image files are decoded by a few host threads running ahead of the loop below (a 768 x 512 PNG is ~10 ms of inflate; the
         // first frame's import otherwise also waits for the GPU's first-touch initialisation): frame i is taken when its decode is done,
@@ -241,6 +270,17 @@ int main(int argc, char **argv)
             return true;
         };
 
+        // dense outputs take one image size for all views: checked on the decoded images before any other work
+        if (!dense_file.empty() || !merged_file.empty() || !mesh_file.empty())
+            for (int i = 0; i < frame_number; ++i) {
+                if (!import_decoded(i)) return 3;
+                const ImageMat &a = frames[0].rgb_image, &b = frames[size_t(i)].rgb_image;
+                if (a.rows != b.rows || a.cols != b.cols) {
+                    std::cerr << "dense outputs need images of one size; this run has " << a.rows << " x " << a.cols << " and " << b.rows << " x " << b.cols << std::endl;
+                    return 3;
+                }
+            }
+
         // ---- per frame: import, undistort, SURF (sfm.cpp:84-126)
         std::cout << "Begin feature extraction" << std::endl;
         const bool frame_trace = std::getenv("ESFM_FRAME_TRACE") != nullptr;       // per-frame milliseconds on stderr (diagnosis of first-touch costs)
@@ -248,6 +288,11 @@ int main(int argc, char **argv)
             clk.lap();
             if (!import_decoded(i)) return 3;
             const double t_wait = clk.lap();
+            if (multi_camera) {
+                frames[size_t(i)].camera_id = camera_of_image[size_t(i)];
+                K_mat = K_all[size_t(camera_of_image[size_t(i)])];
+                distort_coeff = distort_all[size_t(camera_of_image[size_t(i)])];
+            }
             frames[size_t(i)].K_cam = K_mat;
             if (!ee.doUnDistort(frames[size_t(i)], distort_coeff)) return 3;
             const double t_und = clk.lap();
@@ -265,6 +310,8 @@ int main(int argc, char **argv)
         std::cout << "Feature extraction done" << std::endl;
 
         // ---- all pairs (i, j < i): match, verify, relative depth (sfm.cpp:140-167)
+        // (frames that do not all share one K_cam: in the canonical camera's pixels and with its K until the pair stage is done)
+        auto pair_view = std::make_unique<CanonicalPairView>(frames);
         const int num_min_pair = 20;
         const size_t nf = size_t(frame_number);
         std::vector<std::vector<frame_pair_t>> graph(nf, std::vector<frame_pair_t>(nf));
@@ -382,6 +429,7 @@ int main(int argc, char **argv)
             }
             t_verify += pc.lap();
         }
+        pair_view.reset();          // back to every frame's own pixels and K_cam
 
         // ---- track ids (sfm.cpp:173-216): a keypoint takes the id of its verified match in an earlier frame unless the frame
         // already uses that id; the rest get fresh ids

@@ -357,7 +357,7 @@ class MotionEstimator:
             return float("nan")
         k1 = np.asarray(cur_frame_1.keypoints, np.float32).reshape(-1, 2)[[m.queryIdx for m in sel]]
         k2 = np.asarray(cur_frame_2.keypoints, np.float32).reshape(-1, 2)[[m.trainIdx for m in sel]]
-        h = triangulate_points(T1, T2, pixel2cam(k1, cur_frame_1.K_cam), pixel2cam(k2, cur_frame_1.K_cam), self._ctx)   # K of frame 1 for both (:245)
+        h = triangulate_points(T1, T2, pixel2cam(k1, cur_frame_1.K_cam), pixel2cam(k2, cur_frame_2.K_cam), self._ctx)   # the reference: K of frame 1 for both (:245); the same when the K's are equal
         p = _dehomogenise(h)
         depth_sum = 0.0
         for v in p:                                                     # Eigen::Vector3f::norm(), accumulated in double (:279)
@@ -384,7 +384,7 @@ class MotionEstimator:
         if new_ids:
             k1 = np.asarray(cur_frame_1.keypoints, np.float32).reshape(-1, 2)
             k2 = np.asarray(cur_frame_2.keypoints, np.float32).reshape(-1, 2)
-            h = triangulate_points(T1, T2, pixel2cam(k1[new_q], cur_frame_1.K_cam), pixel2cam(k2[new_t], cur_frame_1.K_cam), self._ctx)
+            h = triangulate_points(T1, T2, pixel2cam(k1[new_q], cur_frame_1.K_cam), pixel2cam(k2[new_t], cur_frame_2.K_cam), self._ctx)
             xyz = _dehomogenise(h)
             rgb = np.zeros((len(new_ids), 3), np.uint8)
             if rgb_image is not None:

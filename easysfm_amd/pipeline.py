@@ -26,6 +26,7 @@ from .mvs import MergeOptions, default_mvs_options, dense_reconstruction, frame_
 from .retrieval import RetrievalOptions, select_pairs, working_dim
 from .tracks import TrackOptions, refine_tracks
 from .types import DMatch, Frame, SparsePointCloud
+from .cameras import check_one_image_size, pair_stage_view
 
 
 @dataclass
@@ -248,6 +249,20 @@ def run_sfm(frames: List[Frame], output_file: Optional[str] = None, use_feature:
     fm, ee = FeatureMatching(ctx), MotionEstimator(ctx)
     for f in frames:
         f.init_pixel_ids()
+    if dense_output_file or dense_merged_output_file or dense_mesh_output_file:
+        check_one_image_size(frames)                    # before any work: the dense stages take one image size
+    # Multiple-camera mode (cameras.py): frames that do not all share one K_cam go through the pair stage with their keypoints remapped
+    # into the canonical camera's pixels and its K -- ransac_reproj_distance is then in canonical pixels; everything behind the pair
+    # stage sees the original pixels and each frame's own K_cam.  One K_cam: nothing is touched.
+    with pair_stage_view(frames):
+        graph = _pair_stage(frames, use_feature, ransac_reproj_distance, ctx, match_filter, init_max_h_inlier_ratio, pair_selection)
+    return _run_sfm_after_pairs(frames, graph, fm, ee, output_file, ransac_reproj_distance, use_track_frames_as_init, fix_calib_tolerance_BA,
+                                frequency_BA, ctx, verbose, dense_output_file, dense_merged_output_file, dense_mesh_output_file, dense_mesh_clean,
+                                dense_mesh_simplify, dense_mesh_texture, dense_mesh_texture_level, dense_mesh_render_dir, init_max_h_inlier_ratio,
+                                track_refine)
+
+
+def _pair_stage(frames, use_feature, ransac_reproj_distance, ctx, match_filter, init_max_h_inlier_ratio, pair_selection):
     if pair_selection is None:
         graph = match_and_verify_all_pairs(frames, use_feature, ransac_reproj_distance, 20, ctx, match_filter,
                                            homography_check=init_max_h_inlier_ratio is not None)
@@ -260,6 +275,12 @@ def run_sfm(frames: List[Frame], output_file: Optional[str] = None, use_feature:
             return chosen
         graph = match_and_verify_all_pairs(frames, use_feature, ransac_reproj_distance, 20, ctx, match_filter,
                                            homography_check=init_max_h_inlier_ratio is not None, pairs=choose)
+    return graph
+
+
+def _run_sfm_after_pairs(frames, graph, fm, ee, output_file, ransac_reproj_distance, use_track_frames_as_init, fix_calib_tolerance_BA, frequency_BA,
+                         ctx, verbose, dense_output_file, dense_merged_output_file, dense_mesh_output_file, dense_mesh_clean, dense_mesh_simplify,
+                         dense_mesh_texture, dense_mesh_texture_level, dense_mesh_render_dir, init_max_h_inlier_ratio, track_refine):
     track, n_unique = propagate_track_ids(frames, graph)
     if verbose:
         for i in range(len(frames)):

@@ -149,10 +149,12 @@ class BAScene:
 def ba_scene(n_cam: int, n_pt: int, obs_per_pt: int, radius: float = 10.0, extent: float = 2.0,
              seed: int = 4000, uv_noise: float = 0.5, outlier_frac: float = 0.02,
              start_noise: Tuple[float, float, float] = (0.01, 0.05, 0.05),
-             camera_major: bool = True) -> BAScene:
+             camera_major: bool = True, K4_per_cam=None) -> BAScene:
     """Ring of cameras looking at the origin; each point seen by `obs_per_pt`
     consecutive ring cameras.  Observation order is camera-major, point-minor,
-    as setBAProblem emits it (ba.cpp:22-48) unless camera_major=False."""
+    as setBAProblem emits it (ba.cpp:22-48) unless camera_major=False.
+    K4_per_cam [n_cam, 4] (fx, cx, fy, cy): every camera projects with its own intrinsics (multiple-camera mode) instead
+    of the one FOUNTAIN_K4; the random draws, and with None every bit of the scene, are the same."""
     rng = np.random.default_rng(np.random.PCG64(seed))
     obs_per_pt = min(obs_per_pt, n_cam)
     cams = np.zeros((n_cam, 6))
@@ -174,10 +176,15 @@ def ba_scene(n_cam: int, n_pt: int, obs_per_pt: int, radius: float = 10.0, exten
         order = np.lexsort((pt_idx, cam_idx))
         cam_idx, pt_idx = cam_idx[order], pt_idx[order]
     K4 = np.tile(np.array(FOUNTAIN_K4, np.float32), (n_cam, 1))
+    if K4_per_cam is not None:
+        K4 = np.ascontiguousarray(K4_per_cam, np.float32).reshape(n_cam, 4)
     # project
     Rs = np.stack([aa_to_R(cams[c, :3]) for c in range(n_cam)])
     P = np.einsum("nij,nj->ni", Rs[cam_idx], pts[pt_idx]) + cams[cam_idx, 3:]
     uv = np.stack([P[:, 0] / P[:, 2] * K4[0, 0] + K4[0, 1], P[:, 1] / P[:, 2] * K4[0, 2] + K4[0, 3]], axis=1)
+    if K4_per_cam is not None:
+        Ko = K4[cam_idx].astype(np.float64)
+        uv = np.stack([P[:, 0] / P[:, 2] * Ko[:, 0] + Ko[:, 1], P[:, 1] / P[:, 2] * Ko[:, 2] + Ko[:, 3]], axis=1)
     uv += uv_noise * rng.standard_normal(uv.shape)
     n_out = int(outlier_frac * len(uv))
     if n_out > 0:
@@ -211,12 +218,16 @@ def in_reference_frame(sc: BAScene, ref: int) -> BAScene:
                    cams_gt=cams_gt, pts_gt=pts_gt)
 
 
-def sfm_scene(n_cam: int = 8, n_pt: int = 900, seed: int = 7000, pix_noise: float = 0.3, n_clutter: int = 150, desc_noise: float = 0.03):
+def sfm_scene(n_cam: int = 8, n_pt: int = 900, seed: int = 7000, pix_noise: float = 0.3, n_clutter: int = 150, desc_noise: float = 0.03,
+              K_per_cam=None):
     """A synthetic reconstruction problem for the whole pipeline (cpp_code/test/sfm.cpp:128-339): cameras on an arc looking at
     a point cloud with depth relief; every camera sees the points in front of it inside the 768 x 512 image; a keypoint's
     descriptor is its point's random unit 64-vector plus noise (SURF-like, L2-normalised); clutter keypoints carry fresh
     random descriptors.  Returns (frames as dicts of numpy arrays: keypoints, descriptors, point_id per keypoint; K [3,3];
-    camera poses world->camera [n_cam,4,4]; points [n_pt,3])."""
+    camera poses world->camera [n_cam,4,4]; points [n_pt,3]).
+    K_per_cam [n_cam, 3, 3]: camera c projects with its own matrix (multiple-camera mode) and its frame dict also carries it as "K";
+    the points, descriptors and poses are the same (what is in view, hence the later draws, differs), and with None every bit of the
+    scene is what it was; the returned K is then K_per_cam[0]."""
     rng = np.random.default_rng(np.random.PCG64(seed))
     K = np.array([[FOUNTAIN_K4[0], 0, FOUNTAIN_K4[1]], [0, FOUNTAIN_K4[2], FOUNTAIN_K4[3]], [0, 0, 1]], np.float32)
     pts = np.stack([rng.uniform(-3, 3, n_pt), rng.uniform(-2, 2, n_pt), rng.uniform(-1.5, 1.5, n_pt)], 1)
@@ -232,6 +243,8 @@ def sfm_scene(n_cam: int = 8, n_pt: int = 900, seed: int = 7000, pix_noise: floa
         T = np.eye(4); T[:3, :3] = R; T[:3, 3] = -R @ C
         poses.append(T)
         Xc = pts @ R.T + T[:3, 3]
+        if K_per_cam is not None:
+            K = np.asarray(K_per_cam[c], np.float32)
         uv = np.stack([Xc[:, 0] / Xc[:, 2] * K[0, 0] + K[0, 2], Xc[:, 1] / Xc[:, 2] * K[1, 1] + K[1, 2]], 1)
         vis = (Xc[:, 2] > 1) & (uv[:, 0] > 5) & (uv[:, 0] < 763) & (uv[:, 1] > 5) & (uv[:, 1] < 507)
         ids = np.nonzero(vis)[0]
@@ -244,4 +257,8 @@ def sfm_scene(n_cam: int = 8, n_pt: int = 900, seed: int = 7000, pix_noise: floa
         d /= np.linalg.norm(d, axis=1, keepdims=True)
         order = rng.permutation(len(kp))
         frames.append(dict(keypoints=kp[order].astype(np.float32), descriptors=np.ascontiguousarray(d[order], np.float32), point_id=pid[order]))
+        if K_per_cam is not None:
+            frames[-1]["K"] = K.copy()
+    if K_per_cam is not None:
+        K = np.asarray(K_per_cam[0], np.float32)
     return frames, K, np.stack(poses), pts

@@ -522,6 +522,43 @@ int esfm_ba_solve_ex(esfm_ctx *ctx, int n_cam, int n_pt, int n_obs,
                      const esfm_ba_options *options, esfm_allreduce_fn allreduce, void *allreduce_user,
                      esfm_ba_summary *summary);
 
+/* ---- multiple-camera mode: one free intrinsics block per camera group ---------------------------
+ * The reference's open to-do "multiple-camera mode (different intrinsic elements)".  Camera c belongs to group
+ * group_of_cam[c] in [0, n_groups); group g owns a parameter block fx, cx, fy, cy (calib4 + 4 g, doubles), bounded
+ * to its start value +- calib_tolerance[g] (each > 0).  The functor is ReprojectErrorTerm_updatecalib with the block
+ * of the observation's camera's group.  A group that no observation uses keeps its four values bit for bit.  With
+ * n_groups == 1 this is esfm_ba_problem_create_free_calib: the same kernels, launches and summation orders, hence
+ * the same bits.  Two solves of the same problem agree in every bit for any n_groups.
+ * Errors, reported before anything is written: n_groups < 1, a group index outside [0, n_groups), a tolerance <= 0
+ * (ESFM_ERR_INVALID_ARG), a non-finite intrinsic or tolerance (ESFM_ERR_NUMERIC), 6 (n_cam + n_groups) >= 46000.
+ * Multi-GPU: every rank passes the same group arrays; a rank need not hold observations of every group; the
+ * exchanged sizes are the documented ones with n_cam + n_groups camera-side blocks.
+ * Not provided: a mix of fixed and free cameras in one problem (give the cameras to hold a group with a narrow box),
+ * and intrinsics models other than fx, cx, fy, cy.
+ * In front of the solver the two-view entry points (esfm_find_essential_*, esfm_recover_pose_*, esfm_find_homography_*,
+ * esfm_match_guided_*) keep taking ONE K per pair: the host mirrors hand them the keypoints of both images remapped into the
+ * pixels of one canonical camera (camera 0), so their pixel thresholds are in canonical pixels in a multi-camera run; the dense
+ * stages take K4 per view but one image size for all views. */
+int esfm_ba_problem_create_calib_groups(esfm_ctx *ctx, int n_cam, int n_pt, int n_obs,
+                                        const int32_t *cam_idx, const int32_t *pt_idx, const float *obs_uv,
+                                        int n_groups, const int32_t *group_of_cam /*n_cam*/, const double *calib4 /*4 n_groups*/,
+                                        const double *calib_tolerance /*n_groups, each > 0*/,
+                                        const double *cams, const double *pts, esfm_ba_problem **out);
+/* new start values and box centres / half widths of every block (problems with free intrinsics, any group count) */
+int esfm_ba_problem_set_calib_groups(esfm_ba_problem *p, const double *calib4, const double *calib_tolerance);
+int esfm_ba_problem_get_calib_groups(esfm_ba_problem *p, double *calib4 /*4 n_groups*/);
+/* 0: fixed intrinsics, else the number of free blocks.  esfm_ba_problem_set_calib / _get_calib serve one-block problems only and
+ * return ESFM_ERR_INVALID_ARG on more. */
+int esfm_ba_problem_calib_groups(const esfm_ba_problem *p);
+/* One-shot, as esfm_ba_solve_ex with the group arrays (calib4 in/out) */
+int esfm_ba_solve_groups(esfm_ctx *ctx, int n_cam, int n_pt, int n_obs,
+                         const int32_t *cam_idx, const int32_t *pt_idx, const float *obs_uv,
+                         double *cams, double *pts,
+                         int n_groups, const int32_t *group_of_cam, double *calib4, const double *calib_tolerance,
+                         int ref_cam, double ref_threshold,
+                         const esfm_ba_options *options, esfm_allreduce_fn allreduce, void *allreduce_user,
+                         esfm_ba_summary *summary);
+
 /* The step-length rule of that line search alone (host arithmetic, no GPU): next trial step after the trial
  * (x_cur, f_cur, g_cur) failed the sufficient-decrease test, given the start point (0, f0, g0) and optionally
  * the trial before; *_valid = 0 marks a sample whose evaluation failed.  [upstream line_search.cc
