@@ -1,10 +1,10 @@
 // C-ABI entry points of the homography model of two-view verification (include/esfm.h "Homography RANSAC"): RANSAC with the semantics
 // of cv::findHomography(pts1, pts2, RANSAC, threshold, mask, 2000, confidence) without its final Levenberg-Marquardt polish.
 //
-// Host side: the cv::RNG sample stream with getSubset's subset check (ransac_host.hpp) and the best-model / adaptive-iteration-count
-// bookkeeping, replayed over the inlier counts the GPU produced for a chunk of iterations of every pair at once -- the layout of
-// ransac_api.cpp's essential-matrix loop.  Everything that touches the correspondences -- the 4-point solve, the float transfer
-// error, masks, the re-fit's sums and its eigenvector -- runs in homography_kernels.hip.
+// Host side: the cv::RNG sample stream with getSubset's subset check and the registrator's replay over the inlier counts the GPU produced
+// for a chunk of iterations of every pair at once, both ransac_host.hpp's (fill_round / replay_round).  Everything that touches the
+// correspondences -- the 4-point solve, the float transfer error, masks, the re-fit's sums and its eigenvector -- runs in
+// homography_kernels.hip.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -13,17 +13,30 @@
 #include "homography_core.hpp"
 #include "homography_kernels.hpp"
 #include "ransac_host.hpp"
+#include "ransac_kernels.hpp"   // check_pair_args, launch_ransac_take_best
+#include "scratch_layout.hpp"
 
 using esfm::HomogPair;
-using esfm::ransac::CvRng;
-using esfm::ransac::draw_subset;
-using esfm::ransac::kHomogMaxIters;
-using esfm::ransac::kHomogPoints;
-using esfm::ransac::update_num_iters;
+using namespace esfm::ransac;   // CvRng, draw_subset, Registrator, fill_round, replay_round, RoundTables, the constants
 
 namespace {
 
 constexpr int kChunk = 64;            // iterations of every active pair evaluated per round
+
+// Scratch of esfm_find_homography_pairs.  t: the rounds' int32 tables (one model per slot, n_models = the kernels' has_model), element
+// offsets into stage_d and into its pinned mirror alike; `ok` (the re-fit's flags) follows them on the device only.  The rest: byte
+// offsets into stage_e on 256-byte boundaries; best | refit is one array because one memset clears both.
+struct HomogLayout {
+    RoundTables t;
+    size_t ok, ints;
+    size_t models, best_refit, mask, bytes_e;
+    HomogLayout(int n_pairs, int chunk, int n_total) : t(n_pairs, chunk, kFourPoints, 1), ok(t.end), ints(t.end + (size_t)n_pairs)
+    {
+        esfm::ScratchCarver c;
+        models = c.take(sizeof(double) * 9 * t.n_slots); best_refit = c.take(sizeof(double) * 18 * (size_t)n_pairs);
+        mask = c.take((size_t)std::max(n_total, 1)); bytes_e = c.at;
+    }
+};
 
 }  // namespace
 
@@ -32,21 +45,17 @@ extern "C" {
 int esfm_find_homography_pairs(esfm_ctx *ctx, int n_pairs, const int32_t *point_offset, const float *pts1, const float *pts2, double threshold,
                                double confidence, double *H_out, uint8_t *mask, int32_t *status, int32_t *iterations, int32_t *n_inliers)
 {
-    if (!ctx) { esfm::set_error("ctx is NULL"); return ESFM_ERR_INVALID_ARG; }
-    ESFM_REQUIRE(n_pairs >= 0, "negative pair count");
+    if (int rc = esfm::check_pair_args(ctx, n_pairs, point_offset, pts1, pts2)) return rc;
     if (n_pairs == 0) return ESFM_OK;
-    ESFM_REQUIRE(point_offset && H_out && status, "NULL argument");
-    ESFM_REQUIRE(point_offset[0] == 0, "point_offset[0] must be 0");
-    for (int p = 0; p < n_pairs; ++p) ESFM_REQUIRE(point_offset[p + 1] >= point_offset[p], "point_offset must be non-decreasing");
+    ESFM_REQUIRE(H_out && status, "NULL argument");
     const int n_total = point_offset[n_pairs];
-    ESFM_REQUIRE(n_total == 0 || (pts1 && pts2 && mask), "NULL point or mask arrays");
+    ESFM_REQUIRE(n_total == 0 || mask, "mask is NULL");
     ESFM_REQUIRE(confidence > 0.0 && confidence < 1.0, "confidence must be in (0, 1)");
     ESFM_REQUIRE(threshold >= 0.0 && std::isfinite(threshold), "threshold must be finite and not negative");
-    if (int rc = esfm::set_device(ctx)) return rc;
     hipStream_t st = ctx->stream;
 
-    struct State { CvRng rng; int niters = kHomogMaxIters, max_good = 0, iter = 0, valid = kChunk; bool done = false, exact4 = false, failed = false /* getSubset gave up */; };
-    std::vector<State> S((size_t)n_pairs);
+    std::vector<Registrator> S;
+    S.reserve((size_t)n_pairs);
     std::vector<HomogPair> tab((size_t)n_pairs);
     for (int p = 0; p < n_pairs; ++p) {
         HomogPair &r = tab[(size_t)p];
@@ -56,85 +65,48 @@ int esfm_find_homography_pairs(esfm_ctx *ctx, int n_pairs, const int32_t *point_
         if (iterations) iterations[p] = 0;
         if (n_inliers) n_inliers[p] = 0;
         for (int k = 0; k < 9; ++k) H_out[9 * (size_t)p + k] = 0.0;
-        if (r.count < kHomogPoints) { S[(size_t)p].done = true; r.active = 0; }
-        if (r.count == kHomogPoints) S[(size_t)p].exact4 = true;
+        S.emplace_back(kFourPoints, kHomogMaxIters, r.count);
     }
     if (n_total > 0) memset(mask, 0, (size_t)n_total);
 
-    const size_t n_slots = (size_t)n_pairs * kChunk, nt = (size_t)std::max(n_total, 1);
+    const HomogLayout L(n_pairs, kChunk, n_total);
+    const size_t np = (size_t)n_pairs, nt = (size_t)std::max(n_total, 1);
     if (int rc = ctx->stage_a.reserve(sizeof(float) * 2 * nt)) return rc;
     if (int rc = ctx->stage_b.reserve(sizeof(float) * 2 * nt)) return rc;
-    if (int rc = ctx->stage_c.reserve(sizeof(HomogPair) * (size_t)n_pairs)) return rc;
-    if (int rc = ctx->stage_d.reserve(sizeof(int32_t) * (6 * n_slots + 3 * (size_t)n_pairs))) return rc;   // samples | has_model | counts | take | refit ok
-    if (int rc = ctx->stage_e.reserve(sizeof(double) * 9 * (n_slots + 2 * (size_t)n_pairs) + nt)) return rc;  // models | best | refit | mask
+    if (int rc = ctx->stage_c.reserve(sizeof(HomogPair) * np)) return rc;
+    if (int rc = ctx->stage_d.reserve(sizeof(int32_t) * L.ints)) return rc;
+    if (int rc = ctx->stage_e.reserve(L.bytes_e)) return rc;
+    if (int rc = ctx->pin_rounds(sizeof(int32_t) * L.t.end)) return rc;
     float *d_p1 = ctx->stage_a.as<float>(), *d_p2 = ctx->stage_b.as<float>();
     HomogPair *d_tab = ctx->stage_c.as<HomogPair>();
-    int32_t *d_samples = ctx->stage_d.as<int32_t>();
-    int32_t *d_has = d_samples + 4 * n_slots, *d_counts = d_has + n_slots, *d_take = d_counts + n_slots, *d_ok = d_take + 2 * (size_t)n_pairs;
-    double *d_models = ctx->stage_e.as<double>();
-    double *d_best = d_models + 9 * n_slots, *d_refit = d_best + 9 * (size_t)n_pairs;
-    uint8_t *d_mask = reinterpret_cast<uint8_t *>(d_refit + 9 * (size_t)n_pairs);
+    int32_t *d_t = ctx->stage_d.as<int32_t>(), *h_t = static_cast<int32_t *>(ctx->pinned_rounds);   // the same offsets L.t on both sides
+    int32_t *d_counts = d_t + L.t.counts, *d_ok = d_t + L.ok;
+    uint8_t *d_e = ctx->stage_e.as<uint8_t>();
+    double *d_models = reinterpret_cast<double *>(d_e + L.models), *d_best = reinterpret_cast<double *>(d_e + L.best_refit), *d_refit = d_best + 9 * np;
+    uint8_t *d_mask = d_e + L.mask;
     if (n_total > 0) {
         ESFM_HIP_TRY(esfm::copy_h2d(d_p1, pts1, sizeof(float) * 2 * (size_t)n_total, st));
         ESFM_HIP_TRY(esfm::copy_h2d(d_p2, pts2, sizeof(float) * 2 * (size_t)n_total, st));
     }
-    ESFM_HIP_TRY(hipMemsetAsync(d_best, 0, sizeof(double) * 18 * (size_t)n_pairs, st));
-    ESFM_HIP_TRY(hipMemsetAsync(d_ok, 0, sizeof(int32_t) * (size_t)n_pairs, st));
+    ESFM_HIP_TRY(hipMemsetAsync(d_best, 0, sizeof(double) * 18 * np, st));   // best | refit
+    ESFM_HIP_TRY(hipMemsetAsync(d_ok, 0, sizeof(int32_t) * np, st));
 
-    if (int rc = ctx->pin_rounds(sizeof(int32_t) * (6 * n_slots + 2 * (size_t)n_pairs))) return rc;
-    int32_t *samples = static_cast<int32_t *>(ctx->pinned_rounds), *has = samples + 4 * n_slots, *counts = has + n_slots, *take = counts + n_slots;
-    for (;;) {
-        bool any = false;
-        for (int p = 0; p < n_pairs; ++p) {
-            State &s = S[(size_t)p];
-            tab[(size_t)p].active = s.done ? 0 : 1;
-            int32_t *dst = &samples[4 * (size_t)p * kChunk];
-            if (s.done) { for (int k = 0; k < kChunk; ++k) dst[4 * k] = -1; continue; }
-            any = true;
-            const int n = tab[(size_t)p].count;
-            const float *a = pts1 + 2 * (size_t)tab[(size_t)p].first, *b = pts2 + 2 * (size_t)tab[(size_t)p].first;
-            s.valid = std::min(kChunk, s.niters - s.iter);   // the loop cannot use more: iterations beyond niters are never replayed, so their draws are not made
-            for (int k = 0; k < kChunk; ++k) {
-                if (s.exact4) { if (k == 0) for (int j = 0; j < 4; ++j) dst[j] = j; else dst[4 * k] = -1; }
-                else if (k >= s.valid) dst[4 * k] = -1;
-                else if (!draw_subset(s.rng, n, a, b, dst + 4 * k)) { s.valid = k; s.failed = true; dst[4 * k] = -1; }   // getSubset failed: the loop ends before this iteration
-            }
-        }
-        if (!any) break;
-        ESFM_HIP_TRY(esfm::copy_h2d(d_tab, tab.data(), sizeof(HomogPair) * (size_t)n_pairs, st));
-        ESFM_HIP_TRY(esfm::copy_h2d(d_samples, samples, sizeof(int32_t) * 4 * n_slots, st));
-        if (int rc = esfm::launch_homography_chunk(st, d_tab, n_pairs, d_p1, d_p2, d_samples, kChunk, d_models, d_has, d_counts, ctx)) return rc;
-        ESFM_HIP_TRY(esfm::copy_d2h(has, d_has, sizeof(int32_t) * 2 * n_slots, st));   // has_model | counts
+    const auto draw = [&](int p) {   // (the subset check needs the points, which the host has anyway)
+        const int n = tab[(size_t)p].count;
+        const float *a = pts1 + 2 * (size_t)tab[(size_t)p].first, *b = pts2 + 2 * (size_t)tab[(size_t)p].first;
+        return [=](CvRng &rng, int32_t *idx) { return draw_subset(rng, n, a, b, idx); };
+    };
+    while (fill_round(S.data(), n_pairs, kChunk, h_t + L.t.samples, draw)) {
+        for (int p = 0; p < n_pairs; ++p) tab[(size_t)p].active = S[(size_t)p].done ? 0 : 1;
+        ESFM_HIP_TRY(esfm::copy_h2d(d_tab, tab.data(), sizeof(HomogPair) * np, st));
+        ESFM_HIP_TRY(esfm::copy_h2d(d_t + L.t.samples, h_t + L.t.samples, sizeof(int32_t) * kFourPoints * L.t.n_slots, st));
+        if (int rc = esfm::launch_homography_chunk(st, d_tab, n_pairs, d_p1, d_p2, d_t + L.t.samples, kChunk, d_models, d_t + L.t.n_models, d_counts, ctx)) return rc;
+        ESFM_HIP_TRY(esfm::copy_d2h(h_t + L.t.down, d_t + L.t.down, sizeof(int32_t) * L.t.down_len, st));
         ESFM_HIP_TRY(hipStreamSynchronize(st));
-        // replay RANSACPointSetRegistrator::run over this chunk
-        int n_take = 0;
-        for (int p = 0; p < n_pairs; ++p) {
-            State &s = S[(size_t)p];
-            if (s.done) continue;
-            const int n = tab[(size_t)p].count;
-            long best_slot = -1;
-            if (s.exact4) {
-                const size_t g = (size_t)p * kChunk;
-                if (has[g] > 0) { best_slot = (long)g; s.max_good = n; }
-                s.done = true; s.iter = 0;
-            } else {
-                int k = 0;
-                for (; k < s.valid && s.iter < s.niters; ++k, ++s.iter) {
-                    const size_t g = (size_t)p * kChunk + (size_t)k;
-                    if (has[g] <= 0) continue;
-                    const int good = counts[g];
-                    if (good > std::max(s.max_good, kHomogPoints - 1)) {
-                        best_slot = (long)g; s.max_good = good;
-                        s.niters = update_num_iters(confidence, (double)(n - good) / n, kHomogPoints, s.niters);
-                    }
-                }
-                if (s.iter >= s.niters || s.failed) s.done = true;
-            }
-            if (best_slot >= 0) { take[2 * n_take] = p; take[2 * n_take + 1] = (int32_t)best_slot; ++n_take; }
-        }
+        const int n_take = replay_round(S.data(), n_pairs, point_offset, kChunk, h_t + L.t.n_models, h_t + L.t.counts, 1, confidence, h_t + L.t.take);
         if (n_take > 0) {
-            ESFM_HIP_TRY(esfm::copy_h2d(d_take, take, sizeof(int32_t) * 2 * (size_t)n_take, st));
-            if (int rc = esfm::launch_homography_take_best(st, d_take, n_take, d_models, d_best)) return rc;
+            ESFM_HIP_TRY(esfm::copy_h2d(d_t + L.t.take, h_t + L.t.take, sizeof(int32_t) * 3 * (size_t)n_take, st));
+            if (int rc = esfm::launch_ransac_take_best(st, d_t + L.t.take, n_take, d_models, 9, d_best)) return rc;
         }
     }
     // masks of the winners, then the re-fit on them (pairs with a model and more than four points)
@@ -149,7 +121,7 @@ int esfm_find_homography_pairs(esfm_ctx *ctx, int n_pairs, const int32_t *point_
     if (n_total > 0) {
         if (int rc = esfm::launch_homography_mask(st, d_tab, n_pairs, d_p1, d_p2, d_best, d_mask)) return rc;
         ESFM_HIP_TRY(esfm::copy_d2h(mask, d_mask, (size_t)n_total, st));
-        for (int p = 0; p < n_pairs; ++p) tab[(size_t)p].active = (status[p] && !S[(size_t)p].exact4) ? 1 : 0;
+        for (int p = 0; p < n_pairs; ++p) tab[(size_t)p].active = (status[p] && !S[(size_t)p].exact) ? 1 : 0;
         ESFM_HIP_TRY(esfm::copy_h2d(d_tab, tab.data(), sizeof(HomogPair) * (size_t)n_pairs, st));   // (stream-ordered behind the mask kernel's read)
         if (int rc = esfm::launch_homography_refit(st, d_tab, n_pairs, d_p1, d_p2, d_mask, d_refit, d_ok)) return rc;
         ESFM_HIP_TRY(esfm::copy_d2h(refit.data(), d_refit, sizeof(double) * 9 * (size_t)n_pairs, st));
@@ -165,7 +137,7 @@ int esfm_find_homography_pairs(esfm_ctx *ctx, int n_pairs, const int32_t *point_
             for (int k = 0; k < 9; ++k) H_out[9 * (size_t)p + k] = 0.0;
             continue;
         }
-        if (S[(size_t)p].exact4) memset(m, 1, (size_t)n);   // bestMask.setTo(1)
+        if (S[(size_t)p].exact) memset(m, 1, (size_t)n);   // bestMask.setTo(1)
         else if (ok[(size_t)p]) for (int k = 0; k < 9; ++k) H_out[9 * (size_t)p + k] = refit[9 * (size_t)p + k];   // (else: the RANSAC winner stays)
     }
     if (n_inliers && n_total > 0) {
@@ -185,7 +157,7 @@ int esfm_find_homography(esfm_ctx *ctx, const float *pts1, const float *pts2, in
                          int32_t *iterations)
 {
     if (n < 0) { esfm::set_error("negative point count"); return ESFM_ERR_INVALID_ARG; }
-    if (n < kHomogPoints) { esfm::set_error("a homography needs at least 4 correspondences"); return ESFM_ERR_UNSUPPORTED; }
+    if (n < kFourPoints) { esfm::set_error("a homography needs at least 4 correspondences"); return ESFM_ERR_UNSUPPORTED; }
     const int32_t off[2] = {0, n};
     int32_t status = 0;
     if (int rc = esfm_find_homography_pairs(ctx, 1, off, pts1, pts2, threshold, confidence, H, mask, &status, iterations, nullptr)) return rc;
@@ -236,7 +208,7 @@ int esfm_homography_refit_host(const float *pts1, const float *pts2, int n, cons
 // Host-only: the first n_samples 4-subsets getSubset emits for these correspondences, the subset check included.
 int esfm_homography_sample_stream(const float *pts1, const float *pts2, int count, int n_samples, int32_t *idx, int64_t *redraws)
 {
-    if (count < kHomogPoints || n_samples < 0 || !pts1 || !pts2 || (n_samples && !idx)) { esfm::set_error("esfm_homography_sample_stream: bad arguments"); return ESFM_ERR_INVALID_ARG; }
+    if (count < kFourPoints || n_samples < 0 || !pts1 || !pts2 || (n_samples && !idx)) { esfm::set_error("esfm_homography_sample_stream: bad arguments"); return ESFM_ERR_INVALID_ARG; }
     CvRng rng;
     if (redraws) *redraws = 0;
     for (int s = 0; s < n_samples; ++s)

@@ -182,15 +182,6 @@ __global__ __launch_bounds__(kRefitLanes) void homography_refit_kernel(const Hom
     }
 }
 
-__global__ __launch_bounds__(256) void homography_take_best_kernel(const int32_t *__restrict__ take, int n_take, const double *__restrict__ models,
-                                                                   double *__restrict__ best)
-{
-    const int t = blockIdx.x * 256 + threadIdx.x;
-    if (t >= 9 * n_take) return;
-    const int e = t / 9, a = t % 9;
-    best[9 * (size_t)take[2 * e] + a] = models[9 * (size_t)take[2 * e + 1] + a];
-}
-
 // ---- launchers ---------------------------------------------------------------------------------------------------------
 int launch_homography_chunk(hipStream_t st, const HomogPair *pairs, int n_pairs, const float *p1, const float *p2, const int32_t *samples, int chunk,
                             double *models, int32_t *has_model, int32_t *counts, esfm_ctx *timing_ctx)
@@ -222,14 +213,6 @@ int launch_homography_solve_samples(hipStream_t st, const double *q, int n, doub
 {
     if (n <= 0) return ESFM_OK;
     hipLaunchKernelGGL(homography_solve_samples_kernel, dim3((n + kSolveLanes - 1) / kSolveLanes), dim3(kSolveLanes), 0, st, q, n, models, has_model);
-    ESFM_HIP_TRY(hipGetLastError());
-    return ESFM_OK;
-}
-
-int launch_homography_take_best(hipStream_t st, const int32_t *take, int n_take, const double *models, double *best)
-{
-    if (n_take <= 0) return ESFM_OK;
-    hipLaunchKernelGGL(homography_take_best_kernel, dim3((9 * n_take + 255) / 256), dim3(256), 0, st, take, n_take, models, best);
     ESFM_HIP_TRY(hipGetLastError());
     return ESFM_OK;
 }

@@ -20,8 +20,6 @@ int launch_homography_score(hipStream_t st, const HomogPair *pairs, int n_pairs,
                             const int32_t *has_model, int32_t *counts);
 // the minimal solver alone on samples given as pixel coordinates (q[16 g ..] = q1[8], q2[8])
 int launch_homography_solve_samples(hipStream_t st, const double *q, int n, double *models, int32_t *has_model);
-// best[9 take[2 e]] = models[9 take[2 e + 1]] (9 doubles) for e < n_take
-int launch_homography_take_best(hipStream_t st, const int32_t *take, int n_take, const double *models, double *best);
 int launch_homography_mask(hipStream_t st, const HomogPair *pairs, int n_pairs, const float *p1, const float *p2, const double *best, uint8_t *mask);
 // per pair with `active` set: the re-fit on the points whose mask is set -> refit[9 p ..], ok[p] (0: fewer than 4 inliers or no model)
 int launch_homography_refit(hipStream_t st, const HomogPair *pairs, int n_pairs, const float *p1, const float *p2, const uint8_t *mask, double *refit,

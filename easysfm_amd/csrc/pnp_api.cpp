@@ -61,7 +61,7 @@ int esfm_solve_pnp_ransac(esfm_ctx *ctx, const float *pts3d, const float *pts2d,
     ESFM_REQUIRE(confidence > 0.0 && confidence < 1.0, "confidence must be in (0, 1)");
     if (n_inliers) *n_inliers = 0;
     if (iterations) *iterations = 0;
-    if (n < rs::kModelPoints) {   // OpenCV falls back to P3P at n == 4 and asserts below; neither is built
+    if (n < rs::kFivePoints) {   // OpenCV falls back to P3P at n == 4 and asserts below; neither is built
         esfm::set_error("solvePnPRansac (EPnP) needs at least 5 correspondences (got %d)", n);
         return ESFM_ERR_UNSUPPORTED;
     }
@@ -88,11 +88,10 @@ int esfm_solve_pnp_ransac(esfm_ctx *ctx, const float *pts3d, const float *pts2d,
     ESFM_HIP_TRY(esfm::copy_h2d(d_p2, pts2d, sizeof(float) * 2 * nn, st));
 
     // ---- RANSAC over EPnP hypotheses
-    rs::CvRng rng;
-    int niters = std::max(iterations_count, 1), max_good = 0, iter = 0;
+    rs::Registrator reg(rs::kFivePoints, std::max(iterations_count, 1), n);   // (its own rounds: variable sizes, deferred hypotheses)
     bool have_best = false;
     std::vector<int32_t> samples(5 * (size_t)kPnpChunk), counts((size_t)kPnpChunk);
-    if (n == rs::kModelPoints) {
+    if (reg.exact) {
         // count == modelPoints: the kernel runs once on all points and every point is an inlier
         for (int j = 0; j < 5; ++j) samples[(size_t)j] = j;
         ESFM_HIP_TRY(esfm::copy_h2d(d_samples, samples.data(), sizeof(int32_t) * 5, st));
@@ -100,17 +99,17 @@ int esfm_solve_pnp_ransac(esfm_ctx *ctx, const float *pts3d, const float *pts2d,
         int32_t ok = 0;
         ESFM_HIP_TRY(esfm::copy_d2h(&ok, d_valid, sizeof(int32_t), st));
         ESFM_HIP_TRY(hipStreamSynchronize(st));
-        if (ok) { ESFM_HIP_TRY(hipMemcpyAsync(d_small, d_poses, sizeof(double) * 12, hipMemcpyDeviceToDevice, st)); have_best = true; max_good = n; }
+        if (ok) { ESFM_HIP_TRY(hipMemcpyAsync(d_small, d_poses, sizeof(double) * 12, hipMemcpyDeviceToDevice, st)); have_best = true; reg.max_good = n; }
         ESFM_HIP_TRY(hipMemsetAsync(d_mask, 1, nn, st));
     } else {
-        while (iter < niters) {
+        while (reg.iter < reg.niters) {
             // The first rounds are small: with the usual inlier ratios the adaptive count falls below 64 after the first good hypothesis,
             // and a launch lasts as long as its SLOWEST hypothesis (a degenerate sample runs the 12 x 12 Jacobi into its 30-sweep cap:
             // ~2 ms) -- one of 64 samples is rarely that, one of 1024 nearly always.  Which hypotheses count is decided by `iter <
             // niters` below, in the sample stream's order: the chunking changes no result.
-            const int chunk = iter == 0 ? 64 : (iter < 320 ? 256 : kPnpChunk);
-            const int n_hyp = std::min(chunk, niters - iter);
-            for (int k = 0; k < n_hyp; ++k) rs::draw_subset(rng, n, &samples[5 * (size_t)k]);
+            const int chunk = reg.iter == 0 ? 64 : (reg.iter < 320 ? 256 : kPnpChunk);
+            const int n_hyp = std::min(chunk, reg.niters - reg.iter);
+            for (int k = 0; k < n_hyp; ++k) rs::draw_subset(reg.rng, n, &samples[5 * (size_t)k]);
             ESFM_HIP_TRY(esfm::copy_h2d(d_samples, samples.data(), sizeof(int32_t) * 5 * (size_t)n_hyp, st));
             // first pass with a short sweep budget: the one hypothesis in a hundred whose diagonalisation stalls (all 30 sweeps: ~2 ms against
             // 0.5) comes back unfinished (count -1) instead of holding the launch, and is solved in full below only if the replay reaches it
@@ -120,21 +119,17 @@ int esfm_solve_pnp_ransac(esfm_ctx *ctx, const float *pts3d, const float *pts2d,
             ESFM_HIP_TRY(esfm::copy_d2h(counts.data(), d_counts, sizeof(int32_t) * (size_t)n_hyp, st));
             ESFM_HIP_TRY(hipStreamSynchronize(st));
             int best_k = -1;
-            for (int k = 0; k < n_hyp && iter < niters; ++k, ++iter) {
+            for (int k = 0; k < n_hyp && reg.iter < reg.niters; ++k, ++reg.iter) {
                 if (counts[(size_t)k] < 0) {
                     // every unfinished hypothesis the replay can still reach -- niters only ever shrinks -- in ONE launch (side by side, as
                     // they ran before they were deferred; one after the other they would cost 2 ms each)
-                    const int reach = std::min(n_hyp - k, niters - iter);
+                    const int reach = std::min(n_hyp - k, reg.niters - reg.iter);
                     if (int rc = esfm::launch_pnp_chunk(st, pb, d_p3, d_p2, d_samples + 5 * (size_t)k, reach, d_poses + 12 * (size_t)k, d_valid + k, d_counts + k,
                                                         esfm::kPnpFullSweeps, true, ctx)) return rc;
                     ESFM_HIP_TRY(esfm::copy_d2h(&counts[(size_t)k], d_counts + k, sizeof(int32_t) * (size_t)reach, st));
                     ESFM_HIP_TRY(hipStreamSynchronize(st));
                 }
-                const int good = counts[(size_t)k];   // 0 for a sample whose pose is not finite (runKernel returned no model)
-                if (good > std::max(max_good, rs::kModelPoints - 1)) {
-                    best_k = k; max_good = good;
-                    niters = rs::update_num_iters(confidence, (double)(n - good) / n, rs::kModelPoints, niters);
-                }
+                if (reg.offer(counts[(size_t)k], n, confidence)) best_k = k;   // (count 0: a sample whose pose is not finite -- runKernel returned no model)
             }
             if (best_k >= 0) {
                 ESFM_HIP_TRY(hipMemcpyAsync(d_small, d_poses + 12 * (size_t)best_k, sizeof(double) * 12, hipMemcpyDeviceToDevice, st));
@@ -143,8 +138,8 @@ int esfm_solve_pnp_ransac(esfm_ctx *ctx, const float *pts3d, const float *pts2d,
         }
         if (have_best) { if (int rc = esfm::launch_pnp_mask(st, pb, d_p3, d_p2, d_small, d_mask)) return rc; }
     }
-    if (iterations) *iterations = iter;
-    if (!have_best || max_good <= 0) {
+    if (iterations) *iterations = reg.iter;
+    if (!have_best || reg.max_good <= 0) {
         esfm::set_error("solvePnPRansac: no pose with at least 5 inliers");
         return ESFM_ERR_NUMERIC;   // OpenCV returns false and releases `inliers`
     }
@@ -163,7 +158,7 @@ int esfm_solve_pnp_ransac(esfm_ctx *ctx, const float *pts3d, const float *pts2d,
         // (ESFM_PNP_HOST_REFIT=0: every re-fit through the device reductions below, whatever its size -- tests; read on each call)
         const char *env_refit = getenv("ESFM_PNP_HOST_REFIT");
         const int host_refit = env_refit ? std::max(0, atoi(env_refit)) : kPnpHostRefit;
-        if (m_host >= rs::kModelPoints && m_host <= host_refit) {
+        if (m_host >= rs::kFivePoints && m_host <= host_refit) {
             std::vector<double> w(3 * (size_t)m_host), px(2 * (size_t)m_host), al(4 * (size_t)m_host), pc(3 * (size_t)m_host);
             for (size_t i = 0, k = 0; i < nn; ++i)
                 if (mask[i]) { for (int c = 0; c < 3; ++c) w[3 * k + c] = (double)pts3d[3 * i + c]; px[2 * k] = (double)pts2d[2 * i]; px[2 * k + 1] = (double)pts2d[2 * i + 1]; ++k; }

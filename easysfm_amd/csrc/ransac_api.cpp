@@ -16,17 +16,15 @@
 #include "five_point_core.hpp"
 #include "ransac_host.hpp"
 #include "ransac_kernels.hpp"
+#include "scratch_layout.hpp"
 
 using esfm::RansacPair;
-using esfm::ransac::CvRng;
-using esfm::ransac::draw_subset;
-using esfm::ransac::kMaxIters;
-using esfm::ransac::kModelPoints;
-using esfm::ransac::update_num_iters;
+using namespace esfm::ransac;   // CvRng, draw_subset, Registrator, fill_round, replay_round, RoundTables, the constants
 
 namespace {
 
 constexpr int kChunk = 64;            // iterations of every active pair evaluated per round
+constexpr int kModelsPerSlot = 10;    // the 5-point kernel returns up to ten essential matrices per sample
 
 int fill_pairs(int n_pairs, const int32_t *off, const float *K4, double threshold, std::vector<RansacPair> &tab)
 {
@@ -103,17 +101,19 @@ void decompose_essential(const double *E, double *R1, double *R2, double *t)
     t[0] = U[2]; t[1] = U[5]; t[2] = U[8];
 }
 
-int check_pair_args(esfm_ctx *ctx, int n_pairs, const int32_t *off, const float *pts1, const float *pts2, const float *K4)
-{
-    if (!ctx) { esfm::set_error("ctx is NULL"); return ESFM_ERR_INVALID_ARG; }
-    ESFM_REQUIRE(n_pairs >= 0, "negative pair count");
-    if (n_pairs == 0) return ESFM_OK;
-    ESFM_REQUIRE(off && K4, "NULL argument");
-    ESFM_REQUIRE(off[0] == 0, "point_offset[0] must be 0");
-    for (int p = 0; p < n_pairs; ++p) ESFM_REQUIRE(off[p + 1] >= off[p], "point_offset must be non-decreasing");
-    ESFM_REQUIRE(off[n_pairs] == 0 || (pts1 && pts2), "NULL point arrays");
-    return esfm::set_device(ctx);
-}
+// Scratch of esfm_find_essential_pairs.  t: the rounds' int32 tables, element offsets into stage_d and into its pinned mirror alike;
+// the rest: byte offsets into stage_e, each on a 256-byte boundary (npts holds double4 records).
+struct EssentialLayout {
+    RoundTables t;
+    size_t models, best, npts, mask, bytes_e;
+    EssentialLayout(int n_pairs, int chunk, int n_total) : t(n_pairs, chunk, kFivePoints, kModelsPerSlot)
+    {
+        const size_t nt = (size_t)std::max(n_total, 1);
+        esfm::ScratchCarver c;
+        models = c.take(sizeof(double) * 9 * kModelsPerSlot * t.n_slots); best = c.take(sizeof(double) * 9 * (size_t)n_pairs);
+        npts = c.take(sizeof(double) * 4 * nt); mask = c.take(nt); bytes_e = c.at;
+    }
+};
 
 }  // namespace
 
@@ -123,9 +123,9 @@ int esfm_find_essential_pairs(esfm_ctx *ctx, int n_pairs, const int32_t *point_o
                               const float *K4_per_pair, double prob, double threshold, double *E_out, uint8_t *mask, int32_t *status,
                               int32_t *iterations)
 {
-    if (int rc = check_pair_args(ctx, n_pairs, point_offset, pts1, pts2, K4_per_pair)) return rc;
+    if (int rc = esfm::check_pair_args(ctx, n_pairs, point_offset, pts1, pts2)) return rc;
     if (n_pairs == 0) return ESFM_OK;
-    ESFM_REQUIRE(E_out && status, "NULL output");
+    ESFM_REQUIRE(K4_per_pair && E_out && status, "NULL argument");
     ESFM_REQUIRE(prob > 0.0 && prob < 1.0, "confidence must be in (0, 1)");   // CV_Assert( confidence > 0 && confidence < 1 )
     const int n_total = point_offset[n_pairs];
     ESFM_REQUIRE(n_total == 0 || mask, "mask is NULL");
@@ -133,35 +133,31 @@ int esfm_find_essential_pairs(esfm_ctx *ctx, int n_pairs, const int32_t *point_o
     if (int rc = fill_pairs(n_pairs, point_offset, K4_per_pair, threshold, tab)) return rc;
     hipStream_t st = ctx->stream;
 
-    struct State { CvRng rng; int niters = kMaxIters, max_good = 0, iter = 0; bool done = false, exact5 = false; };
-    std::vector<State> S((size_t)n_pairs);
+    std::vector<Registrator> S;
+    S.reserve((size_t)n_pairs);
     for (int p = 0; p < n_pairs; ++p) {
         status[p] = 0;
         if (iterations) iterations[p] = 0;
         for (int k = 0; k < 9; ++k) E_out[9 * (size_t)p + k] = 0.0;
-        const int n = tab[(size_t)p].count;
-        if (n < kModelPoints) { S[(size_t)p].done = true; tab[(size_t)p].active = 0; }   // registrator returns false: no model, no mask
-        if (n == kModelPoints) S[(size_t)p].exact5 = true;
+        S.emplace_back(kFivePoints, kEssentialMaxIters, tab[(size_t)p].count);   // (fewer than five points: done -- no model, no mask)
     }
     if (n_total > 0) memset(mask, 0, (size_t)n_total);
 
-    const size_t n_slots = (size_t)n_pairs * kChunk;
+    const EssentialLayout L(n_pairs, kChunk, n_total);
     if (int rc = ctx->stage_a.reserve(sizeof(float) * 2 * (size_t)std::max(n_total, 1))) return rc;
     if (int rc = ctx->stage_b.reserve(sizeof(float) * 2 * (size_t)std::max(n_total, 1))) return rc;
     if (int rc = ctx->stage_c.reserve(sizeof(RansacPair) * (size_t)n_pairs)) return rc;
-    if (int rc = ctx->stage_d.reserve(sizeof(int32_t) * (16 * n_slots + 3 * (size_t)n_pairs))) return rc;   // samples | n_models | counts | take
-    if (int rc = ctx->stage_e.reserve(sizeof(double) * 90 * n_slots + sizeof(double) * 9 * (size_t)n_pairs + sizeof(double) * 4 * (size_t)std::max(n_total, 1) + 32 +
-                                      (size_t)std::max(n_total, 1))) return rc;
+    if (int rc = ctx->stage_d.reserve(sizeof(int32_t) * L.t.end)) return rc;
+    if (int rc = ctx->stage_e.reserve(L.bytes_e)) return rc;
+    // the per-round tables in pinned memory (pageable copies of 0.4 MB up and 0.85 MB down per round were staged by the runtime)
+    if (int rc = ctx->pin_rounds(sizeof(int32_t) * L.t.end)) return rc;
     float *d_p1 = ctx->stage_a.as<float>(), *d_p2 = ctx->stage_b.as<float>();
     RansacPair *d_tab = ctx->stage_c.as<RansacPair>();
-    int32_t *d_samples = ctx->stage_d.as<int32_t>();
-    int32_t *d_nmodels = d_samples + 5 * n_slots;
-    int32_t *d_counts = d_nmodels + n_slots;
-    int32_t *d_take = d_counts + 10 * n_slots;
-    double *d_models = ctx->stage_e.as<double>();
-    double *d_best = d_models + 90 * n_slots;
-    double *d_npts = reinterpret_cast<double *>((reinterpret_cast<uintptr_t>(d_best + 9 * (size_t)n_pairs) + 31) & ~(uintptr_t)31);   // (double4 records)
-    uint8_t *d_mask = reinterpret_cast<uint8_t *>(d_npts + 4 * (size_t)std::max(n_total, 1));
+    int32_t *d_t = ctx->stage_d.as<int32_t>(), *h_t = static_cast<int32_t *>(ctx->pinned_rounds);   // the same offsets L.t on both sides
+    uint8_t *d_e = ctx->stage_e.as<uint8_t>();
+    double *d_models = reinterpret_cast<double *>(d_e + L.models), *d_best = reinterpret_cast<double *>(d_e + L.best),
+           *d_npts = reinterpret_cast<double *>(d_e + L.npts);
+    uint8_t *d_mask = d_e + L.mask;
     if (n_total > 0) {
         ESFM_HIP_TRY(esfm::copy_h2d(d_p1, pts1, sizeof(float) * 2 * (size_t)n_total, st));
         ESFM_HIP_TRY(esfm::copy_h2d(d_p2, pts2, sizeof(float) * 2 * (size_t)n_total, st));
@@ -171,62 +167,22 @@ int esfm_find_essential_pairs(esfm_ctx *ctx, int n_pairs, const int32_t *point_o
     ESFM_HIP_TRY(esfm::copy_h2d(d_tab, tab.data(), sizeof(RansacPair) * (size_t)n_pairs, st));
     if (int rc = esfm::launch_essential_normalise(st, d_tab, n_pairs, d_p1, d_p2, d_npts)) return rc;
 
-    // the per-round tables in pinned memory (pageable copies of 0.4 MB up and 0.85 MB down per round were staged by the runtime)
-    if (int rc = ctx->pin_rounds(sizeof(int32_t) * (16 * n_slots + 3 * (size_t)n_pairs))) return rc;
-    int32_t *samples = static_cast<int32_t *>(ctx->pinned_rounds), *nmodels = samples + 5 * n_slots, *counts = nmodels + n_slots,
-            *take = counts + 10 * n_slots;
-    for (;;) {
-        bool any = false;
-        for (int p = 0; p < n_pairs; ++p) {
-            State &s = S[(size_t)p];
-            tab[(size_t)p].active = s.done ? 0 : 1;
-            int32_t *dst = &samples[5 * (size_t)p * kChunk];
-            if (s.done) { for (int k = 0; k < kChunk; ++k) dst[5 * k] = -1; continue; }
-            any = true;
-            const int n = tab[(size_t)p].count;
-            for (int k = 0; k < kChunk; ++k) {
-                if (s.exact5) { if (k == 0) for (int j = 0; j < 5; ++j) dst[j] = j; else dst[5 * k] = -1; }
-                else draw_subset(s.rng, n, dst + 5 * k);
-            }
-        }
-        if (!any) break;
+    const auto draw = [&](int p) { return [n = tab[(size_t)p].count](CvRng &rng, int32_t *idx) { draw_subset(rng, n, idx); return true; }; };
+    while (fill_round(S.data(), n_pairs, kChunk, h_t + L.t.samples, draw)) {
+        for (int p = 0; p < n_pairs; ++p) tab[(size_t)p].active = S[(size_t)p].done ? 0 : 1;
         ESFM_HIP_TRY(esfm::copy_h2d(d_tab, tab.data(), sizeof(RansacPair) * (size_t)n_pairs, st));
-        ESFM_HIP_TRY(esfm::copy_h2d(d_samples, samples, sizeof(int32_t) * 5 * n_slots, st));
-        ESFM_HIP_TRY(hipMemsetAsync(d_counts, 0, sizeof(int32_t) * 10 * n_slots, st));
-        if (int rc = esfm::launch_essential_chunk(st, d_tab, n_pairs, d_p1, d_p2, d_npts, d_samples, kChunk, d_models, d_nmodels, d_counts, ctx)) return rc;
-        ESFM_HIP_TRY(esfm::copy_d2h(nmodels, d_nmodels, sizeof(int32_t) * 11 * n_slots, st));   // n_models | counts
+        ESFM_HIP_TRY(esfm::copy_h2d(d_t + L.t.samples, h_t + L.t.samples, sizeof(int32_t) * kFivePoints * L.t.n_slots, st));
+        ESFM_HIP_TRY(hipMemsetAsync(d_t + L.t.counts, 0, sizeof(int32_t) * kModelsPerSlot * L.t.n_slots, st));
+        if (int rc = esfm::launch_essential_chunk(st, d_tab, n_pairs, d_p1, d_p2, d_npts, d_t + L.t.samples, kChunk, d_models, d_t + L.t.n_models,
+                                                  d_t + L.t.counts, ctx)) return rc;
+        ESFM_HIP_TRY(esfm::copy_d2h(h_t + L.t.down, d_t + L.t.down, sizeof(int32_t) * L.t.down_len, st));
         ESFM_HIP_TRY(hipStreamSynchronize(st));
-        // replay RANSACPointSetRegistrator::run over this chunk
-        int n_take = 0;
-        for (int p = 0; p < n_pairs; ++p) {
-            State &s = S[(size_t)p];
-            if (s.done) continue;
-            const int n = tab[(size_t)p].count;
-            long best_slot = -1; int best_m = -1;
-            if (s.exact5) {
-                const size_t g = (size_t)p * kChunk;
-                if (nmodels[g] > 0) { best_slot = (long)g; best_m = 0; s.max_good = n; }
-                s.done = true; s.iter = 0;
-            } else {
-                for (int k = 0; k < kChunk && s.iter < s.niters; ++k, ++s.iter) {
-                    const size_t g = (size_t)p * kChunk + (size_t)k;
-                    for (int m = 0; m < nmodels[g]; ++m) {
-                        const int good = counts[10 * g + (size_t)m];
-                        if (good > std::max(s.max_good, kModelPoints - 1)) {
-                            best_slot = (long)g; best_m = m; s.max_good = good;
-                            s.niters = update_num_iters(prob, (double)(n - good) / n, kModelPoints, s.niters);
-                        }
-                    }
-                }
-                if (s.iter >= s.niters) s.done = true;
-            }
-            if (best_slot >= 0) { take[3 * n_take] = p; take[3 * n_take + 1] = (int32_t)best_slot; take[3 * n_take + 2] = best_m; ++n_take; }
-        }
+        const int n_take = replay_round(S.data(), n_pairs, point_offset, kChunk, h_t + L.t.n_models, h_t + L.t.counts, kModelsPerSlot, prob, h_t + L.t.take);
         // the pairs' new best models in ONE launch (a 72-byte device-to-device copy per pair was 300 API calls per round: most of the
         // batch's host time once the solver stopped being it)
         if (n_take > 0) {
-            ESFM_HIP_TRY(esfm::copy_h2d(d_take, take, sizeof(int32_t) * 3 * (size_t)n_take, st));
-            if (int rc = esfm::launch_essential_take_best(st, d_take, n_take, d_models, d_best)) return rc;
+            ESFM_HIP_TRY(esfm::copy_h2d(d_t + L.t.take, h_t + L.t.take, sizeof(int32_t) * 3 * (size_t)n_take, st));
+            if (int rc = esfm::launch_ransac_take_best(st, d_t + L.t.take, n_take, d_models, 9 * kModelsPerSlot, d_best)) return rc;
         }
     }
     for (int p = 0; p < n_pairs; ++p) {
@@ -243,7 +199,7 @@ int esfm_find_essential_pairs(esfm_ctx *ctx, int n_pairs, const int32_t *point_o
     ESFM_HIP_TRY(hipStreamSynchronize(st));
     for (int p = 0; p < n_pairs; ++p) {
         if (status[p]) {
-            if (S[(size_t)p].exact5) memset(mask + point_offset[p], 1, (size_t)tab[(size_t)p].count);   // bestMask.setTo(1)
+            if (S[(size_t)p].exact) memset(mask + point_offset[p], 1, (size_t)tab[(size_t)p].count);   // bestMask.setTo(1)
         } else if (tab[(size_t)p].count > 0) {
             memset(mask + point_offset[p], 0, (size_t)tab[(size_t)p].count);
         }
@@ -265,9 +221,9 @@ int esfm_find_essential_mat(esfm_ctx *ctx, const float *pts1, const float *pts2,
 int esfm_recover_pose_pairs(esfm_ctx *ctx, int n_pairs, const int32_t *point_offset, const float *pts1, const float *pts2,
                             const float *K4_per_pair, const double *E, uint8_t *mask, double *R, double *t, int32_t *good)
 {
-    if (int rc = check_pair_args(ctx, n_pairs, point_offset, pts1, pts2, K4_per_pair)) return rc;
+    if (int rc = esfm::check_pair_args(ctx, n_pairs, point_offset, pts1, pts2)) return rc;
     if (n_pairs == 0) return ESFM_OK;
-    ESFM_REQUIRE(E && R && t, "NULL argument");
+    ESFM_REQUIRE(K4_per_pair && E && R && t, "NULL argument");
     const int n_total = point_offset[n_pairs];
     std::vector<RansacPair> tab;
     if (int rc = fill_pairs(n_pairs, point_offset, K4_per_pair, 1.0, tab)) return rc;
@@ -392,7 +348,7 @@ int esfm_five_point_models_host(const double *q1, const double *q2, int n_sample
 // The index stream alone (host arithmetic, no GPU): the first n_samples 5-subsets getSubset draws for `count` points.
 int esfm_ransac_sample_stream(int count, int n_samples, int32_t *idx)
 {
-    if (count < kModelPoints || n_samples < 0 || (n_samples && !idx)) { esfm::set_error("esfm_ransac_sample_stream: bad arguments"); return ESFM_ERR_INVALID_ARG; }
+    if (count < kFivePoints || n_samples < 0 || (n_samples && !idx)) { esfm::set_error("esfm_ransac_sample_stream: bad arguments"); return ESFM_ERR_INVALID_ARG; }
     CvRng rng;
     for (int s = 0; s < n_samples; ++s) draw_subset(rng, count, idx + 5 * (size_t)s);
     return ESFM_OK;

@@ -380,19 +380,20 @@ int launch_five_point_roots(hipStream_t st, int n, double *models, int32_t *n_mo
     return ESFM_OK;
 }
 
-__global__ __launch_bounds__(256) void essential_take_best_kernel(const int32_t *__restrict__ take, int n_take, const double *__restrict__ models,
-                                                                  double *__restrict__ best)
+// the rounds' winners, shared by the essential-matrix (slot_stride 90: ten models per slot) and the homography (9) entry points
+__global__ __launch_bounds__(256) void ransac_take_best_kernel(const int32_t *__restrict__ take, int n_take, const double *__restrict__ models,
+                                                               int slot_stride, double *__restrict__ best)
 {
     const int t = blockIdx.x * 256 + threadIdx.x;
     if (t >= 9 * n_take) return;
     const int e = t / 9, a = t % 9;
-    best[9 * (size_t)take[3 * e] + a] = models[90 * (size_t)take[3 * e + 1] + 9 * (size_t)take[3 * e + 2] + a];
+    best[9 * (size_t)take[3 * e] + a] = models[(size_t)slot_stride * (size_t)take[3 * e + 1] + 9 * (size_t)take[3 * e + 2] + a];
 }
 
-int launch_essential_take_best(hipStream_t st, const int32_t *take, int n_take, const double *models, double *best)
+int launch_ransac_take_best(hipStream_t st, const int32_t *take, int n_take, const double *models, int slot_stride, double *best)
 {
     if (n_take <= 0) return ESFM_OK;
-    hipLaunchKernelGGL(essential_take_best_kernel, dim3((9 * n_take + 255) / 256), dim3(256), 0, st, take, n_take, models, best);
+    hipLaunchKernelGGL(ransac_take_best_kernel, dim3((9 * n_take + 255) / 256), dim3(256), 0, st, take, n_take, models, slot_stride, best);
     ESFM_HIP_TRY(hipGetLastError());
     return ESFM_OK;
 }
