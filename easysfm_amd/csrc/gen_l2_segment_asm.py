@@ -37,10 +37,10 @@ Operands: %0-%5 out: segment keys k0 k1 k2 of set 0, then set 1;  %6-%13 in: Bhi
 import os
 import sys
 
-# timing-only experiment knobs (the shipped file is generated with the defaults): products per K-step, keys kept by the fold
-PRODUCTS = int(os.environ.get("ESFM_GEN_PRODUCTS", "3"))
-KEEP = int(os.environ.get("ESFM_GEN_KEEP", "3"))
-DMA_SPREAD = int(os.environ.get("ESFM_GEN_DMA_SPREAD", "1"))   # 0: all eight pieces back to back after the barrier (measured 2 % slower)
+if os.path.dirname(os.path.abspath(__file__)) not in sys.path:      # (asm_inc sits beside this file, however it was loaded)
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from asm_inc import Emit, render_inc  # noqa: E402
+
 KBIG = 0x7F61B1E6          # 3.0e38f
 NKBIG = 0xFF61B1E6
 TT, SLOT_BYTES = 128, 256  # rows per tile, bytes per row image
@@ -61,14 +61,6 @@ def vr(base, n=16):
 def fr(ks, lo):
     b = 64 + 8 * ks + (4 if lo else 0)
     return f"v[{b}:{b + 3}]"
-
-
-class Emit:
-    def __init__(self):
-        self.lines = []
-
-    def __call__(self, s):
-        self.lines.append(s)
 
 
 def gen():
@@ -136,10 +128,9 @@ def gen():
     def fold(s, ks, p):
         b = p[s] + 4 * ks
         t, key = 130 + 2 * s, 131 + 2 * s
-        extra = [f"v_med3_f32 v{136 + 4 * s + i}, v{136 + 4 * s + i}, {OP_K(s, 2)}, v{key}" for i in range(KEEP - 3)]   # timing only
         return [f"v_min3_f32 v{t}, v{b}, s46, v{b + 1}",
                 f"v_min3_f32 v{t}, v{t}, v{b + 2}, v{b + 3}",
-                f"v_and_or_b32 v{key}, v{t}, v134, s44"] + extra + [
+                f"v_and_or_b32 v{key}, v{t}, v134, s44",
                 f"v_med3_f32 {OP_K(s, 2)}, {OP_K(s, 1)}, {OP_K(s, 2)}, v{key}",
                 f"v_med3_f32 {OP_K(s, 1)}, {OP_K(s, 0)}, {OP_K(s, 1)}, v{key}",
                 f"v_med3_f32 {OP_K(s, 0)}, {OP_K(s, 0)}, v{key}, s47"]
@@ -169,35 +160,18 @@ def gen():
         if wait:
             e(f"s_waitcnt lgkmcnt({WAIT[ks]})")
         e(f"s_add_u32 s44, s41, {ks}")
-        c = [vr(96), vr(96)] if ks == 0 else [vr(n[0]), vr(n[1])]
-        if PRODUCTS >= 3:
-            for s in range(2):
-                e(f"v_mfma_f32_32x32x16_bf16 {vr(n[s])}, {fr(ks, 0)}, {OP_BLO(s, ks)}, {c[s]}")
-            c = [vr(n[0]), vr(n[1])]
-        for x in extra[0]:
-            e(x)
-        if PRODUCTS == 1:          # one MFMA per set: each set's fold behind the other set's MFMA
-            e(f"v_mfma_f32_32x32x16_bf16 {vr(n[0])}, {fr(ks, 0)}, {OP_BHI(0, ks)}, {c[0]}")
-        for x in fold(0, ks, p):
-            e(x)
-        second, third = ((0, 1) if os.environ.get("ESFM_GEN_A_ORDER", "hl") == "hh" else (1, 0))   # which A half goes second
-        if PRODUCTS >= 2:
-            for s in range(2):
-                e(f"v_mfma_f32_32x32x16_bf16 {vr(n[s])}, {fr(ks, second)}, {OP_BHI(s, ks)}, {c[s]}")
-            c = [vr(n[0]), vr(n[1])]
-        else:
-            e(f"v_mfma_f32_32x32x16_bf16 {vr(n[1])}, {fr(ks, 0)}, {OP_BHI(1, ks)}, {c[1]}")
-        for x in extra[1]:
-            e(x)
-        for x in fold(1, ks, p):
-            e(x)
-        if PRODUCTS >= 2:
-            for s in range(2):
-                e(f"v_mfma_f32_32x32x16_bf16 {vr(n[s])}, {fr(ks, third)}, {OP_BHI(s, ks)}, {vr(n[s])}")
-        for x in extra[2]:
-            e(x)
-        for x in loads(ks, buf, base, nbuf, nbase):
-            e(x)
+        for s in range(2):
+            e(f"v_mfma_f32_32x32x16_bf16 {vr(n[s])}, {fr(ks, 0)}, {OP_BLO(s, ks)}, {vr(96) if ks == 0 else vr(n[s])}")
+        e.extend(extra[0])
+        e.extend(fold(0, ks, p))
+        for s in range(2):
+            e(f"v_mfma_f32_32x32x16_bf16 {vr(n[s])}, {fr(ks, 1)}, {OP_BHI(s, ks)}, {vr(n[s])}")
+        e.extend(extra[1])
+        e.extend(fold(1, ks, p))
+        for s in range(2):
+            e(f"v_mfma_f32_32x32x16_bf16 {vr(n[s])}, {fr(ks, 0)}, {OP_BHI(s, ks)}, {vr(n[s])}")
+        e.extend(extra[2])
+        e.extend(loads(ks, buf, base, nbuf, nbase))
 
     def end_step():
         e("s_lshl_b32 s41, s42, 2")
@@ -248,25 +222,17 @@ def gen():
         e("s_lshl_b32 s48, s44, 15")                           # (tile + 2) * 128 rows * 256 B
         e(f"s_lshl_b32 s49, {OP_WAVE}, 13")                    # wave * 32 rows * 256 B
         e(f"s_add_u32 s49, s49, {OP_LDS}")
-        if not DMA_SPREAD:
-            for i in range(8):
-                for x in dma_piece(i, buf):
-                    e(x)
         e(f"L_nodma_{tag}_%=:")
-        if DMA_SPREAD:
-            # the eight pieces ride behind the MFMA pairs of the step's last two K-steps (2 + 1 + 1 each) instead of going out
-            # back to back; a tile that does not exist reads zeros through the descriptor into a buffer nobody reads again, so
-            # they are issued unconditionally
-            e("s_add_u32 s44, s40, 2")
-            e("s_lshl_b32 s48, s44, 15")
-            e(f"s_lshl_b32 s49, {OP_WAVE}, 13")
-            e(f"s_add_u32 s49, s49, {OP_LDS}")
-            pcs = [dma_piece(i, buf) for i in range(8)]
-            kstep(2, "b", buf, 96, buf ^ 1, 0, wait=False, extra=(pcs[0] + pcs[1], pcs[2], pcs[3]))
-            kstep(3, "b", buf, 96, buf ^ 1, 0, wait=False, extra=(pcs[4] + pcs[5], pcs[6], pcs[7]))
-        else:
-            kstep(2, "b", buf, 96, buf ^ 1, 0, wait=False)
-            kstep(3, "b", buf, 96, buf ^ 1, 0, wait=False)
+        # the eight pieces ride behind the MFMA pairs of the step's last two K-steps (2 + 1 + 1 each) instead of going out back to
+        # back after the barrier (measured 2 % slower); a tile that does not exist reads zeros through the descriptor into a buffer
+        # nobody reads again, so they are issued unconditionally -- and their bases computed again for the waves that branched here
+        e("s_add_u32 s44, s40, 2")
+        e("s_lshl_b32 s48, s44, 15")
+        e(f"s_lshl_b32 s49, {OP_WAVE}, 13")
+        e(f"s_add_u32 s49, s49, {OP_LDS}")
+        pcs = [dma_piece(i, buf) for i in range(8)]
+        kstep(2, "b", buf, 96, buf ^ 1, 0, wait=False, extra=(pcs[0] + pcs[1], pcs[2], pcs[3]))
+        kstep(3, "b", buf, 96, buf ^ 1, 0, wait=False, extra=(pcs[4] + pcs[5], pcs[6], pcs[7]))
         end_step()
         e("s_add_u32 s40, s40, 1")
 
@@ -286,22 +252,20 @@ def gen():
     for ks in range(4):
         e(f"s_add_u32 s44, s41, {ks}")
         for s in range(2):
-            for x in fold(s, ks, ACC["b"]):
-                e(x)
+            e.extend(fold(s, ks, ACC["b"]))
     e("s_mov_b32 m0, s43")
-    return e.lines
+    return e
+
+
+def render():
+    """(text of the generated file, instruction lines)"""
+    lines = gen()
+    return render_inc("gen_l2_segment_asm.py", "ESFM_L2", [], lines, 136), lines
 
 
 def main():
-    lines = gen()
-    clob = [f"v{i}" for i in range(136 if KEEP == 3 else 144)] + [f"s{i}" for i in range(40, 54)] + ["scc", "vcc", "memory"]
-    out = ["// GENERATED by gen_l2_segment_asm.py -- do not edit; see that file for the schedule and the register map",
-           "#define ESFM_L2_SEGMENT_ASM \\"]
-    for l in lines:
-        out.append(f'    "{l}\\n" \\')
-    out.append('    ""')
-    out.append("#define ESFM_L2_SEGMENT_CLOBBERS " + ", ".join(f'"{c}"' for c in clob))
-    open(sys.argv[1] if len(sys.argv) > 1 else "l2_segment_gfx950.inc", "w").write("\n".join(out) + "\n")
+    text, lines = render()
+    open(sys.argv[1] if len(sys.argv) > 1 else "l2_segment_gfx950.inc", "w").write(text)
     n_mfma = sum("v_mfma" in l for l in lines)
     print(f"{len(lines)} instructions, {n_mfma} MFMAs")
 

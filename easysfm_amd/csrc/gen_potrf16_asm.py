@@ -24,11 +24,7 @@ Operands:  %0 (out, v) bad-pivot flag;  %1 (in, v) LDS byte address of row r of 
 column r of the inverse (written column-wise: lane r holds column r; row pitch PITCH bytes).
 The block's rows are only read: nothing uses a factored diagonal block again (panels and back-substitution go through the inverse).
 """
-import os
 import sys
-
-FMAC_DPP = os.environ.get("ESFM_GEN_POTRF_FMAC_DPP", "1") == "1"   # v_fmac_f64_dpp: the broadcast rides in the multiply-add (round 3)
-B64DPP = os.environ.get("ESFM_GEN_POTRF_B64DPP", "1") == "1"   # one v_mov_b64_dpp per broadcast (15.3 us per solve at n = 150) instead of two v_mov_b32_dpp (17.5 us)
 
 SB = 16
 PITCH = 18 * 8          # VLD doubles
@@ -36,9 +32,9 @@ PITCH = 18 * 8          # VLD doubles
 def X(c): return 2 * c
 def T(c): return 32 + 2 * c
 PIV, Y, H, W, RINV = 64, 66, 68, 70, 72
-BC0, NBC = 74, 6
 C15 = 86                # 1.5
-NV = 88                 # v0..v87
+NV = 88                 # the clobber list names v0..v87: v74..v85 held the broadcasts of the v_mov_b64_dpp + v_fma_f64 form and are unused now,
+#                         but the list is part of the committed file, and trimming it could move the solve kernel's register assignment
 S_MASK, S_CMP, S_BAD = 4, 6, 8
 
 def pair(v): return "v[%d:%d]" % (v, v + 1)
@@ -57,12 +53,8 @@ def emit(text, reads, writes, kind="dp"):
     prog.append(Ins(text, reads, writes, kind))
 
 def dpp_bcast(dst, src, lane):
-    if B64DPP:
-        emit("v_mov_b64_dpp %s, %s row_newbcast:%d row_mask:0xf bank_mask:0xf bound_ctrl:1" % (pair(dst), pair(src), lane), regs(src), regs(dst), "dpp")
-        return
-    # two 32-bit row broadcasts (bound_ctrl: no dependence on the old destination)
-    emit("v_mov_b32_dpp v%d, v%d row_newbcast:%d row_mask:0xf bank_mask:0xf bound_ctrl:1" % (dst, src, lane), [src], [dst], "dpp")
-    emit("v_mov_b32_dpp v%d, v%d row_newbcast:%d row_mask:0xf bank_mask:0xf bound_ctrl:1" % (dst + 1, src + 1, lane), [src + 1], [dst + 1], "dpp")
+    # (one v_mov_b64_dpp: 15.3 us per solve at n = 150; two v_mov_b32_dpp: 17.5 us; bound_ctrl: no dependence on the old destination)
+    emit("v_mov_b64_dpp %s, %s row_newbcast:%d row_mask:0xf bank_mask:0xf bound_ctrl:1" % (pair(dst), pair(src), lane), regs(src), regs(dst), "dpp")
 
 def fmac_dpp(dst, bsrc, lane, src1):
     """dst += -row_newbcast:lane(bsrc) * src1"""
@@ -72,9 +64,6 @@ def fmac_dpp(dst, bsrc, lane, src1):
 
 def build():
     del prog[:]
-    bc_next = [0]
-    def new_bc():
-        v = BC0 + 2 * (bc_next[0] % NBC); bc_next[0] += 1; return v
     dpp_bcast(PIV, X(0), 0)
     for c in range(SB):
         # pivot checks (off the chain): anything but a positive finite number is bad
@@ -88,20 +77,12 @@ def build():
         emit("v_mul_f64 %s, %s, %s" % (pair(X(c)), pair(X(c)), pair(RINV)), regs(X(c)) + regs(RINV), regs(X(c)))
         emit("v_mul_f64 %s, %s, %s" % (pair(T(c)), pair(T(c)), pair(RINV)), regs(T(c)) + regs(RINV), regs(T(c)))
         for i in range(c + 1, SB):
-            if FMAC_DPP:
-                # broadcast and multiply-add in one instruction: D += -bcast_i(x[c]) * src1  (v_fmac_f64 is VOP2 on gfx90a+, and its
-                # DPP form takes row_newbcast like v_mov_b64_dpp): 2 instead of 3 instructions per (pivot, column)
-                fmac_dpp(X(i), X(c), i, X(c))
-                if i == c + 1:
-                    dpp_bcast(PIV, X(i), i)
-                fmac_dpp(T(i), X(c), i, T(c))
-                continue
-            bc = new_bc()
-            dpp_bcast(bc, X(c), i)
-            emit("v_fma_f64 %s, -%s, %s, %s" % (pair(X(i)), pair(X(c)), pair(bc), pair(X(i))), regs(X(c)) + regs(bc) + regs(X(i)), regs(X(i)))
+            # broadcast and multiply-add in one instruction: D += -bcast_i(x[c]) * src1  (v_fmac_f64 is VOP2 on gfx90a+, and its
+            # DPP form takes row_newbcast like v_mov_b64_dpp): 2 instead of 3 instructions per (pivot, column)
+            fmac_dpp(X(i), X(c), i, X(c))
             if i == c + 1:
                 dpp_bcast(PIV, X(i), i)
-            emit("v_fma_f64 %s, -%s, %s, %s" % (pair(T(i)), pair(bc), pair(T(c)), pair(T(i))), regs(bc) + regs(T(c)) + regs(T(i)), regs(T(i)))
+            fmac_dpp(T(i), X(c), i, T(c))
 
 LAT = {"dp": 10, "trans": 20, "dpp": 6, "dppfma": 12, "cmp": 8, "salu": 2, "lds": 4}     # issue-to-use estimates (cycles); only the ORDER depends on them
 ISSUE = {"dp": 4, "trans": 8, "dpp": 8, "dppfma": 8, "cmp": 4, "salu": 1, "lds": 4}
