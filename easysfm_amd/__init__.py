@@ -10,7 +10,7 @@ from .types import DMatch, Frame, SparsePointCloud  # noqa: F401
 from .matching import (DescriptorBank, FeatureMatching, PairMatcher, knn_match_hamming, knn_match_l2,  # noqa: F401
                        match_cross_hamming, match_cross_l2, match_cross_pairs_host, match_guided_hamming, match_guided_l2,
                        match_guided_pairs_host, match_hamming, match_l2, match_pairs_host, shard_pair_list)
-from .ba import (BAProblem, BundleAdjustment, Comm, ba_solve, ba_solve_ex, ba_solve_groups, ba_sweep_bytes_per_obs, default_options, line_search_next_step, reduced_plan, shard_points,  # noqa: F401
+from .ba import (BAProblem, BundleAdjustment, Comm, ba_solve, ba_solve_ex, ba_solve_groups, ba_solve_radial, ba_sweep_bytes_per_obs, default_options, line_search_next_step, reduced_plan, shard_points,  # noqa: F401
                  torch_allreduce_callback)
 
 from .cloud import (CProceesing, read_ply_mesh, read_ply_normals, read_ply_textured_mesh, read_ply_vertices, sor_filter,  # noqa: F401

@@ -46,6 +46,8 @@ EXPORTED_SYMBOLS = [
     "esfm_ba_problem_fix_camera", "esfm_ba_solve_ex", "esfm_ba_line_search_next_step",
     "esfm_ba_problem_create_calib_groups", "esfm_ba_problem_set_calib_groups", "esfm_ba_problem_get_calib_groups", "esfm_ba_problem_calib_groups",
     "esfm_ba_solve_groups",
+    "esfm_ba_problem_create_radial_groups", "esfm_ba_problem_set_radial_groups", "esfm_ba_problem_get_radial_groups", "esfm_ba_problem_radial_groups",
+    "esfm_ba_solve_radial_groups",
     "esfm_sor_filter", "esfm_sor_mean_distances_dev", "esfm_triangulate_points", "esfm_triangulate_pairs",
     "esfm_find_essential_mat", "esfm_find_essential_pairs", "esfm_recover_pose", "esfm_recover_pose_pairs", "esfm_ransac_sample_stream", "esfm_five_point_models", "esfm_five_point_models_host",
     "esfm_find_homography", "esfm_find_homography_pairs", "esfm_homography_models", "esfm_homography_models_host", "esfm_homography_refit_host",
@@ -259,6 +261,12 @@ def lib() -> C.CDLL:
     L.esfm_ba_problem_calib_groups.argtypes = [vp]
     L.esfm_ba_solve_groups.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, C.c_int, C.c_double,
                                        C.POINTER(BAOptions), ALLREDUCE_FN, vp, C.POINTER(BASummary)]
+    L.esfm_ba_problem_create_radial_groups.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, C.POINTER(C.c_void_p)]
+    L.esfm_ba_problem_set_radial_groups.argtypes = [vp, vp, vp]
+    L.esfm_ba_problem_get_radial_groups.argtypes = [vp, vp]
+    L.esfm_ba_problem_radial_groups.argtypes = [vp]
+    L.esfm_ba_solve_radial_groups.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp, C.c_int, C.c_double,
+                                              C.POINTER(BAOptions), ALLREDUCE_FN, vp, C.POINTER(BASummary)]
     L.esfm_ba_line_search_next_step.restype = C.c_double
     L.esfm_ba_line_search_next_step.argtypes = [C.c_double] * 5 + [C.c_int] + [C.c_double] * 3 + [C.c_int]
     L.esfm_sor_filter.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_double, vp, vp, i32p, f64p]

@@ -119,10 +119,13 @@ class BAProblem:
     six parameters to ``+-ref_threshold`` (ba.cpp:155-162).
 
     ``calib_groups = (group_of_cam[n_cam], calib4[G, 4], tol[G])`` is the multiple-camera mode: one free block per camera
-    group, block g bounded to ``calib4[g] +- tol[g]`` (esfm_ba_problem_create_calib_groups); ``K4`` and ``calib`` are ignored."""
+    group, block g bounded to ``calib4[g] +- tol[g]`` (esfm_ba_problem_create_calib_groups); ``K4`` and ``calib`` are ignored.
+
+    With ``calib_groups``, ``radial = radial2[G, 2]`` and ``radial_tol`` (a scalar or [G], each > 0) also free k1, k2 of every
+    group, boxed to ``radial2[g] +- radial_tol[g]`` (esfm_ba_problem_create_radial_groups)."""
 
     def __init__(self, cam_idx, pt_idx, uv, K4, cams, pts, ctx: Optional[Context] = None, calib=None, calib_tol: float = 0.0,
-                 ref_cam: int = -1, ref_threshold: float = 1e-10, calib_groups=None):
+                 ref_cam: int = -1, ref_threshold: float = 1e-10, calib_groups=None, radial=None, radial_tol=None):
         self.ctx = ctx or default_context()
         self.cam_idx = np.ascontiguousarray(cam_idx, np.int32).reshape(-1)
         self.pt_idx = np.ascontiguousarray(pt_idx, np.int32).reshape(-1)
@@ -135,6 +138,8 @@ class BAProblem:
         if self.pt_idx.shape[0] != self.n_obs or self.uv.shape[0] != self.n_obs:
             raise ValueError("inconsistent BA array sizes")
         self._h = C.c_void_p()
+        if radial is not None and calib_groups is None:
+            raise ValueError("radial needs calib_groups")
         if calib_groups is not None:
             group_of_cam, cal4, tol = calib_groups
             grp = np.ascontiguousarray(group_of_cam, np.int32).reshape(-1)
@@ -143,9 +148,18 @@ class BAProblem:
             if grp.shape[0] != self.n_cam:
                 raise ValueError("inconsistent BA array sizes")
             self.n_groups = cal4.shape[0]
-            check(lib().esfm_ba_problem_create_calib_groups(self.ctx.handle, self.n_cam, self.n_pt, self.n_obs, _p(self.cam_idx),
-                                                            _p(self.pt_idx), _p(self.uv), self.n_groups, _p(grp), _p(cal4), _p(tol),
-                                                            _p(cams), _p(pts), C.byref(self._h)))
+            if radial is not None:
+                rad = np.ascontiguousarray(radial, np.float64).reshape(-1, 2)
+                rtol = np.ascontiguousarray(np.broadcast_to(np.asarray(radial_tol, np.float64), (cal4.shape[0],)))
+                if rad.shape[0] != cal4.shape[0]:
+                    raise ValueError("inconsistent BA array sizes")
+                check(lib().esfm_ba_problem_create_radial_groups(self.ctx.handle, self.n_cam, self.n_pt, self.n_obs, _p(self.cam_idx),
+                                                                 _p(self.pt_idx), _p(self.uv), self.n_groups, _p(grp), _p(cal4), _p(tol),
+                                                                 _p(rad), _p(rtol), _p(cams), _p(pts), C.byref(self._h)))
+            else:
+                check(lib().esfm_ba_problem_create_calib_groups(self.ctx.handle, self.n_cam, self.n_pt, self.n_obs, _p(self.cam_idx),
+                                                                _p(self.pt_idx), _p(self.uv), self.n_groups, _p(grp), _p(cal4), _p(tol),
+                                                                _p(cams), _p(pts), C.byref(self._h)))
         elif self.free_calib:
             cal = np.ascontiguousarray(calib, np.float64).reshape(4)
             check(lib().esfm_ba_problem_create_free_calib(self.ctx.handle, self.n_cam, self.n_pt, self.n_obs, _p(self.cam_idx),
@@ -182,6 +196,16 @@ class BAProblem:
         cal4 = np.empty((self.n_groups, 4), np.float64)
         check(lib().esfm_ba_problem_get_calib_groups(self._h, _p(cal4)))
         return cal4
+
+    def set_radial_groups(self, radial2, radial_tol) -> None:
+        rad = np.ascontiguousarray(radial2, np.float64).reshape(max(self.n_groups, 1), 2)
+        rtol = np.ascontiguousarray(np.broadcast_to(np.asarray(radial_tol, np.float64), (max(self.n_groups, 1),)))
+        check(lib().esfm_ba_problem_set_radial_groups(self._h, _p(rad), _p(rtol)))
+
+    def get_radial_groups(self) -> np.ndarray:
+        rad = np.empty((max(self.n_groups, 1), 2), np.float64)
+        check(lib().esfm_ba_problem_get_radial_groups(self._h, _p(rad)))
+        return rad
 
     def set_params(self, cams, pts) -> None:
         cams = np.ascontiguousarray(cams, np.float64).reshape(-1, 6); pts = np.ascontiguousarray(pts, np.float64).reshape(-1, 3)
@@ -273,6 +297,35 @@ def ba_solve_groups(cam_idx, pt_idx, uv, cams, pts, group_of_cam, calib4, calib_
     return c, p, k, summ
 
 
+def ba_solve_radial(cam_idx, pt_idx, uv, cams, pts, group_of_cam, calib4, calib_tol, radial2, radial_tol, ref_cam: int = -1,
+                    ref_threshold: float = 1e-10, options: Optional[BAOptions] = None, ctx: Optional[Context] = None, allreduce=None):
+    """solveBA with free radial distortion per camera group (esfm_ba_solve_radial_groups): block g is fx, cx, fy, cy, k1, k2 with
+    ``calib4[g] +- calib_tol[g]`` and ``radial2[g] +- radial_tol[g]``.  Returns (cams, pts, calib[G, 4], radial[G, 2], summary); the
+    inputs are not modified."""
+    ctx = ctx or default_context()
+    cam_idx = np.ascontiguousarray(cam_idx, np.int32).reshape(-1); pt_idx = np.ascontiguousarray(pt_idx, np.int32).reshape(-1)
+    uv = np.ascontiguousarray(uv, np.float32).reshape(-1, 2)
+    c = np.array(cams, np.float64).reshape(-1, 6); p = np.array(pts, np.float64).reshape(-1, 3)      # copies: in/out in the C call
+    grp = np.ascontiguousarray(group_of_cam, np.int32).reshape(-1)
+    k = np.array(calib4, np.float64).reshape(-1, 4)
+    rad = np.array(radial2, np.float64).reshape(-1, 2)
+    tol = np.ascontiguousarray(np.broadcast_to(np.asarray(calib_tol, np.float64), (k.shape[0],)))
+    rtol = np.ascontiguousarray(np.broadcast_to(np.asarray(radial_tol, np.float64), (k.shape[0],)))
+    if pt_idx.shape[0] != cam_idx.shape[0] or uv.shape[0] != cam_idx.shape[0] or grp.shape[0] != c.shape[0] or rad.shape[0] != k.shape[0]:
+        raise ValueError("inconsistent BA array sizes")
+    summ = BASummary()
+    opt = options if options is not None else default_options()
+    user = None
+    if isinstance(allreduce, Comm):
+        cb, user = C.cast(lib().esfm_comm_allreduce, ALLREDUCE_FN), allreduce.handle
+    else:
+        cb = allreduce if allreduce is not None else _NULL_ALLREDUCE
+    check(lib().esfm_ba_solve_radial_groups(ctx.handle, c.shape[0], p.shape[0], cam_idx.shape[0], _p(cam_idx), _p(pt_idx), _p(uv), _p(c), _p(p),
+                                            k.shape[0], _p(grp), _p(k), _p(tol), _p(rad), _p(rtol), int(ref_cam), float(ref_threshold),
+                                            C.byref(opt), cb, user, C.byref(summ)))
+    return c, p, k, rad, summ
+
+
 def line_search_next_step(f0: float, g0: float, prev, cur) -> float:
     """Host-only: next Armijo trial step (esfm_ba_line_search_next_step); prev / cur = (x, f, g) or None."""
     xp, fp, gp = prev if prev is not None else (0.0, 0.0, 0.0)
@@ -339,6 +392,8 @@ def angle_axis_to_rotation(aa: np.ndarray) -> np.ndarray:
 class BundleAdjustment:
     """Mirror of p3dv::BundleAdjustment (ba.h:28-106)."""
 
+    kHeldPinhole = 1e-3     # pixels: the box that holds fx, cx, fy, cy in a radial solve with fix_calib_tolerance_BA == 0
+
     def __init__(self, ctx: Optional[Context] = None, options: Optional[BAOptions] = None):
         self._ctx = ctx
         self.options = options
@@ -359,16 +414,24 @@ class BundleAdjustment:
         # camera_id of every group in order of first appearance; one distinct id leaves both empty and the shared block in charge
         self.camera_group_ = np.zeros(0, np.int32)
         self.group_camera_ids_: List[int] = []
+        # free radial distortion (radial_tolerance > 0): one block fx, cx, fy, cy, k1, k2 per distinct camera_id, ONE id included; k1, k2
+        # of the groups ride behind the 4 G pinhole values at the end of parameters_
+        self.radial_tolerance_ = 0.0
         self.parameters_ = np.zeros(0, np.float64)
         self.summary: Optional[BASummary] = None
         return True
 
     def setBAProblem(self, frames: Sequence[Frame], process_frame_id: Sequence[bool], sfm_sparse_points: SparsePointCloud,
-                     fix_calib_tolerance_BA: float = 0.0, reference_frame_id: int = -1) -> bool:
+                     fix_calib_tolerance_BA: float = 0.0, reference_frame_id: int = -1, radial_tolerance: float = 0.0) -> bool:
         """ba.cpp:12-130.  Same observation list, in the same order (camera-major, point index
         ascending), as the reference's O(Ncam*Npts*Nkp) triple loop (:22-56), derived with an
         O(N log N) join: for every registered frame, each point picks the FIRST keypoint j with
-        unique_pixel_has_match[j] and unique_pixel_ids[j] == unique_point_ids[k] (the `break` at :44)."""
+        unique_pixel_has_match[j] and unique_pixel_ids[j] == unique_point_ids[k] (the `break` at :44).
+        radial_tolerance > 0: every distinct camera_id opens a block fx, cx, fy, cy, k1, k2 that starts from its first processed
+        frame's K_cam and radial_cam; the observations are the frames' keypoints_raw (the pixels as detected) where a frame has
+        them.  0: the path and the bits are as before."""
+        radial = float(radial_tolerance) > 0.0
+        self.radial_tolerance_ = float(radial_tolerance) if radial else 0.0
         pid = np.asarray(sfm_sparse_points.unique_point_ids, np.int64)
         self.num_points_ = len(pid)
         cams_i, pts_i, uv = [], [], []
@@ -392,7 +455,8 @@ class BundleAdjustment:
                 j_idx = u_j[pos_c[hit]]
                 cams_i.append(np.full(len(k_idx), self.num_cameras_, np.int32))
                 pts_i.append(k_idx.astype(np.int32))
-                uv.append(np.asarray(fr.keypoints, np.float32).reshape(-1, 2)[j_idx])
+                obs = fr.keypoints_raw if radial and fr.keypoints_raw is not None else fr.keypoints
+                uv.append(np.asarray(obs, np.float32).reshape(-1, 2)[j_idx])
             if i == reference_frame_id:
                 self.ref_process_camera_id_ = self.num_cameras_
             self.num_cameras_ += 1
@@ -401,11 +465,13 @@ class BundleAdjustment:
         self.points_2d_ = np.concatenate(uv) if uv else np.zeros((0, 2), np.float32)
         self.num_observations_ = len(self.camera_index_)
         ids = [int(fr.camera_id) for i, fr in enumerate(frames) if not process_frame_id[i]]
-        if fix_calib_tolerance_BA != 0 and len(set(ids)) > 1:
+        if (fix_calib_tolerance_BA != 0 and len(set(ids)) > 1) or (radial and ids):
             self.group_camera_ids_ = list(dict.fromkeys(ids))                     # distinct ids, first appearance first
             self.camera_group_ = np.array([self.group_camera_ids_.index(c) for c in ids], np.int32)
         n_blocks = len(self.group_camera_ids_) if self.group_camera_ids_ else 1
-        self.num_parameters_ = 6 * self.num_cameras_ + 3 * self.num_points_ + (4 * n_blocks if fix_calib_tolerance_BA != 0 else 0)
+        n_radial = 2 * n_blocks if radial and self.group_camera_ids_ else 0
+        free_pinhole = fix_calib_tolerance_BA != 0 or n_radial > 0
+        self.num_parameters_ = 6 * self.num_cameras_ + 3 * self.num_points_ + (4 * n_blocks if free_pinhole else 0) + n_radial
         par = np.zeros(self.num_parameters_, np.float64)
         k = 0
         for i, fr in enumerate(frames):
@@ -418,25 +484,49 @@ class BundleAdjustment:
             k += 1
         xyz = np.asarray(sfm_sparse_points.xyz, np.float32).reshape(-1, 3)
         par[6 * self.num_cameras_:6 * self.num_cameras_ + 3 * self.num_points_] = xyz.astype(np.float64).reshape(-1)
-        if fix_calib_tolerance_BA != 0 and self.calibs_ and self.group_camera_ids_:
-            # the reference's calibs_[0] rule, per group: a group starts from the K_cam of its first processed frame
+        if free_pinhole and self.calibs_ and self.group_camera_ids_:
+            # the reference's calibs_[0] rule, per group: a group starts from the K_cam (and, in a radial problem, the radial_cam) of
+            # its first processed frame; the 2 G coefficients ride behind the 4 G pinhole values
+            processed = [fr for i, fr in enumerate(frames) if not process_frame_id[i]]
+            k4_at = len(par) - n_radial - 4 * n_blocks
             for g in range(n_blocks):
-                Kg = self.calibs_[int(np.nonzero(self.camera_group_ == g)[0][0])]
-                par[len(par) - 4 * (n_blocks - g):len(par) - 4 * (n_blocks - g) + 4] = [Kg[0, 0], Kg[0, 2], Kg[1, 1], Kg[1, 2]]
+                first = int(np.nonzero(self.camera_group_ == g)[0][0])
+                Kg = self.calibs_[first]
+                par[k4_at + 4 * g:k4_at + 4 * g + 4] = [Kg[0, 0], Kg[0, 2], Kg[1, 1], Kg[1, 2]]
+                if n_radial:
+                    par[len(par) - n_radial + 2 * g:len(par) - n_radial + 2 * g + 2] = [float(v) for v in processed[first].radial_cam]
         elif fix_calib_tolerance_BA != 0 and self.calibs_:
             K0 = self.calibs_[0]
             par[-4:] = [K0[0, 0], K0[0, 2], K0[1, 1], K0[1, 2]]
         self.parameters_ = par
         return 2 * self.num_observations_ > self.num_parameters_   # "Ready to solve" (:120-129)
 
-    def solveBA(self, fix_calib_tolerance_BA: float = 0.0) -> bool:
+    def solveBA(self, fix_calib_tolerance_BA: float = 0.0, radial_tolerance: float = 0.0) -> bool:
         """ba.cpp:132-212: fixed intrinsics (:142-164) or the shared free intrinsics bounded to +-tolerance (:167-196);
-        the reference frame, if one was named in setBAProblem, is bounded to +-1e-10 (:134, :155-162)."""
+        the reference frame, if one was named in setBAProblem, is bounded to +-1e-10 (:134, :155-162).
+        radial_tolerance > 0: the box half width of k1, k2 of every group; the problem must have been set up with radial blocks
+        (setBAProblem's radial_tolerance > 0), and one set up with them must be solved with a positive value."""
+        if (float(radial_tolerance) > 0.0) != (self.radial_tolerance_ > 0.0):
+            raise ValueError("solveBA: radial_tolerance must be positive exactly when setBAProblem's was")
         fixed_threshold = 1e-10   # ba.cpp:134
         nc, npt = self.num_cameras_, self.num_points_
         K4 = np.array([[K[0, 0], K[0, 2], K[1, 1], K[1, 2]] for K in self.calibs_], np.float32).reshape(-1, 4)
         cams = self.parameters_[:6 * nc].reshape(nc, 6)
         pts = self.parameters_[6 * nc:6 * nc + 3 * npt].reshape(npt, 3)
+        if radial_tolerance > 0 and self.group_camera_ids_:
+            # (fixed pinhole intrinsics in a radial solve: a box of kHeldPinhole pixels holds them -- every free block has a box)
+            G = len(self.group_camera_ids_)
+            tol = float(fix_calib_tolerance_BA) if fix_calib_tolerance_BA != 0 else self.kHeldPinhole
+            c, p, k, rad, summ = ba_solve_radial(self.camera_index_, self.point_index_, self.points_2d_, cams, pts, self.camera_group_,
+                                                 self.parameters_[-6 * G:-2 * G].reshape(G, 4), np.full(G, tol), self.parameters_[-2 * G:].reshape(G, 2),
+                                                 np.full(G, float(radial_tolerance)), ref_cam=self.ref_process_camera_id_, ref_threshold=fixed_threshold,
+                                                 options=self.options, ctx=self._ctx or default_context())
+            self.parameters_[:6 * nc] = c.reshape(-1)
+            self.parameters_[6 * nc:6 * nc + 3 * npt] = p.reshape(-1)
+            self.parameters_[-6 * G:-2 * G] = k.reshape(-1)
+            self.parameters_[-2 * G:] = rad.reshape(-1)
+            self.summary = summ
+            return True
         if fix_calib_tolerance_BA != 0 and self.group_camera_ids_:
             G = len(self.group_camera_ids_)
             c, p, k, summ = ba_solve_groups(self.camera_index_, self.point_index_, self.points_2d_, cams, pts, self.camera_group_,
@@ -460,11 +550,13 @@ class BundleAdjustment:
         return True
 
     def doSFMBA(self, frames: Sequence[Frame], process_frame_id: Sequence[bool], sfm_sparse_points: SparsePointCloud,
-                fix_calib_tolerance_BA: float = 0.0, reference_frame_id: int = -1) -> bool:
-        """ba.cpp:214-288: initBA, setBAProblem, solveBA, then the float write-back (:223-281)."""
+                fix_calib_tolerance_BA: float = 0.0, reference_frame_id: int = -1, radial_tolerance: float = 0.0) -> bool:
+        """ba.cpp:214-288: initBA, setBAProblem, solveBA, then the float write-back (:223-281).
+        radial_tolerance > 0: each group's K_cam and radial_cam go back to its processed frames."""
         self.initBA()
-        self.setBAProblem(frames, process_frame_id, sfm_sparse_points, fix_calib_tolerance_BA, reference_frame_id)
-        self.solveBA(fix_calib_tolerance_BA)
+        self.setBAProblem(frames, process_frame_id, sfm_sparse_points, fix_calib_tolerance_BA, reference_frame_id, radial_tolerance)
+        self.solveBA(fix_calib_tolerance_BA, radial_tolerance)
+        radial = self.radial_tolerance_ > 0 and bool(self.group_camera_ids_)
         k = 0
         for i, fr in enumerate(frames):
             if process_frame_id[i]:
@@ -475,7 +567,14 @@ class BundleAdjustment:
             pose[:3, 3] = self.parameters_[6 * k + 3:6 * k + 6].astype(np.float32)      # :244-246
             fr.pose_cam = pose
             k += 1
-            if fix_calib_tolerance_BA != 0:                                            # :250-256 (float K_cam)
+            if radial:
+                G = len(self.group_camera_ids_)
+                g = int(self.camera_group_[k - 1])
+                K = np.array(fr.K_cam, np.float32, copy=True)
+                K[0, 0], K[0, 2], K[1, 1], K[1, 2] = self.parameters_[len(self.parameters_) - 6 * G + 4 * g:][:4].astype(np.float32)
+                fr.K_cam = K
+                fr.radial_cam = tuple(float(v) for v in self.parameters_[len(self.parameters_) - 2 * G + 2 * g:][:2])
+            elif fix_calib_tolerance_BA != 0:                                          # :250-256 (float K_cam)
                 K = np.array(fr.K_cam, np.float32, copy=True)
                 if self.group_camera_ids_:          # each group's result goes to that group's frames only
                     G = len(self.group_camera_ids_)

@@ -73,6 +73,59 @@ def check_one_image_size(frames: Sequence[Frame]) -> None:
         raise ValueError(f"dense outputs need images of one size; this run has {sorted(sizes)}")
 
 
+# ---- free radial distortion: the pinhole-equivalent pixels of detected keypoints ------------------------------------------------------
+RADIAL_TOKEN = "+radial"
+RADIAL_TOKEN_TOLERANCE = 1.0        # the box half width of k1, k2 the +radial token stands for: a convention, not tuned
+
+
+def undistort_normalised(xd, yd, k1: float, k2: float):
+    """The inverse of (x, y) -> (x, y) L(x, y), L = 1 + k1 r2 + k2 r2^2, by 20 fixed-point iterations (x, y) <- (xd, yd) / L(x, y) in
+    float64 (a few thousand points per frame, on the host)."""
+    xd = np.asarray(xd, np.float64); yd = np.asarray(yd, np.float64)
+    x, y = xd.copy(), yd.copy()
+    for _ in range(20):
+        r2 = x * x + y * y
+        L = 1.0 + k1 * r2 + k2 * r2 * r2
+        x, y = xd / L, yd / L
+    return x, y
+
+
+def pinhole_keypoints(keypoints_raw, K, radial) -> np.ndarray:
+    """The pixels a pinhole camera K would have seen: raw pixel -> normalised distorted point -> undistort_normalised -> pixel.
+    float64 inside, float32 out.  k1 = k2 = 0: a copy of the input, bit for bit."""
+    kp = np.asarray(keypoints_raw, np.float32).reshape(-1, 2)
+    k1, k2 = float(radial[0]), float(radial[1])
+    if k1 == 0.0 and k2 == 0.0:
+        return kp.copy()
+    K = np.asarray(K, np.float32).astype(np.float64)
+    x, y = undistort_normalised((kp[:, 0].astype(np.float64) - K[0, 2]) / K[0, 0], (kp[:, 1].astype(np.float64) - K[1, 2]) / K[1, 1], k1, k2)
+    return np.stack([x * K[0, 0] + K[0, 2], y * K[1, 1] + K[1, 2]], 1).astype(np.float32)
+
+
+def refresh_pinhole_keypoints(frames: Sequence[Frame]) -> None:
+    """keypoints <- pinhole_keypoints(keypoints_raw, K_cam, radial_cam) for every frame (keypoints_raw is taken from keypoints the
+    first time)."""
+    for f in frames:
+        if f.keypoints_raw is None:
+            f.keypoints_raw = np.array(f.keypoints, np.float32, copy=True).reshape(-1, 2)
+        f.keypoints = pinhole_keypoints(f.keypoints_raw, f.K_cam, f.radial_cam)
+
+
+def distortion_line(frames: Sequence[Frame]) -> str:
+    by_id = {}
+    for f in frames:
+        by_id.setdefault(int(f.camera_id), f.radial_cam)
+    return "Distortion: " + ", ".join(f"camera {c}: k1 [{k[0]:.6g}] k2 [{k[1]:.6g}]" for c, k in sorted(by_id.items()))
+
+
+def split_radial_token(match_filter: str) -> Tuple[str, bool]:
+    """(the filter without a final "+radial", whether it was there).  Called after split_cameras_token: "+radial" stands at the end of
+    the filter, in front of "+cameras" if both are given."""
+    if match_filter.endswith(RADIAL_TOKEN) and len(match_filter) > len(RADIAL_TOKEN):
+        return match_filter[:-len(RADIAL_TOKEN)], True
+    return match_filter, False
+
+
 # ---- the drivers' arguments ---------------------------------------------------------------------------------------------------------
 def split_cameras_token(match_filter: str) -> Tuple[str, bool]:
     """(the filter without a final "+cameras", whether it was there).  Stripped first: the rest of the token grammar is unchanged."""

@@ -77,6 +77,8 @@ struct CalibGroups {
     const int32_t *group_of_cam = nullptr;
     const double *calib4 = nullptr;
     const double *tol = nullptr;
+    const double *radial2 = nullptr;      // radial problems: k1, k2 per block (2 n doubles) boxed to radial2 +- radial_tol[g]; else NULL
+    const double *radial_tol = nullptr;
     bool checked = false;      // the grouped entry points validate these arrays before anything else (checked_groups)
 };
 
@@ -115,7 +117,8 @@ int create_impl(esfm_ctx *ctx, int n_real, int n_pt, int n_obs, const int32_t *c
     if (int rc = esfm::set_device(ctx)) return rc;
     const bool calib = cg.n > 0;
     const int n_cam = n_real + cg.n;   // 6-wide blocks of the reduced system
-    const esfm::BaForms forms = esfm::ba_forms(n_real, calib, n_obs, calib ? cg.n : 1);
+    const bool radial = calib && cg.radial2;
+    const esfm::BaForms forms = esfm::ba_forms(n_real, calib, n_obs, calib ? cg.n : 1, radial);
     const esfm::BaLayout L = esfm::make_ba_layout(n_real, n_pt, n_obs, cam_idx, pt_idx, ctx->num_cu, forms.schur == esfm::BaForms::SCHUR_TABLES);
     std::vector<float> s_uv((size_t)2 * n_obs);
     for (size_t t = 0; t < (size_t)n_obs; ++t) {
@@ -130,15 +133,16 @@ int create_impl(esfm_ctx *ctx, int n_real, int n_pt, int n_obs, const int32_t *c
     for (int c = 0; c < n_real; ++c) P->cam_nobs_local[(size_t)c] = (double)L.cam_nobs[(size_t)c];
     if (calib) {
         // every observation involves the intrinsics block of its camera's group
-        if (cg.n == 1) P->cam_nobs_local[(size_t)n_real] = (double)n_obs;
+        if (cg.n == 1 && !radial) P->cam_nobs_local[(size_t)n_real] = (double)n_obs;
         else for (int c = 0; c < n_real; ++c) P->cam_nobs_local[(size_t)n_real + cg.group_of_cam[c]] += (double)L.cam_nobs[(size_t)c];
         P->calib_center.assign(cg.calib4, cg.calib4 + 4 * (size_t)cg.n);
         P->calib_tol.assign(cg.tol, cg.tol + cg.n);
+        if (radial) { P->radial_center.assign(cg.radial2, cg.radial2 + 2 * (size_t)cg.n); P->radial_tol.assign(cg.radial_tol, cg.radial_tol + cg.n); }
     }
     if (!calib && forms.solve == esfm::BaForms::SOLVE_TILED) { P->h_pt_start = L.pt_start; P->h_obs_cam = L.cam; }   // (for the reduced system's structure)
     BADev &d = P->d;
     d.n_cam = n_cam; d.n_pt = n_pt; d.n_obs = n_obs;
-    d.n_real_cam = n_real; d.has_calib = cg.n;
+    d.n_real_cam = n_real; d.has_calib = cg.n; d.radial = radial ? 1 : 0;
     d.parts = &P->parts;
     d.n_cchunks = (int)L.cchunk_cam.size();
     for (int tb = 0; tb < 2; ++tb) d.n_mchunks[tb] = (int)L.mchunk_cam0[tb].size();
@@ -166,14 +170,14 @@ int create_impl(esfm_ctx *ctx, int n_real, int n_pt, int n_obs, const int32_t *c
     index_table(&d.wide_obs, L.wide_obs);
     index_table(&d.pchunk_pt0, L.pchunk_pt0);
     table(&d.pchunk_info, L.pchunk_info.data(), L.pchunk_info.size());
-    if (cg.n > 1) table(&d.cam_group, cg.group_of_cam, (size_t)n_real);
+    if (cg.n > 1 || radial) table(&d.cam_group, cg.group_of_cam, (size_t)n_real);
 
     // the tables first, then the work arrays (an empty table takes one padded slot of the arena like any other array)
     const size_t no = (size_t)n_obs, nc6 = (size_t)6 * n_cam, np3 = (size_t)3 * n_pt;
     int rc = ESFM_OK;
     for (const Table &t : tables) if (rc == ESFM_OK) rc = esfm::ba_dev_alloc_bytes(P, t.dev, t.bytes);
     auto A = [&](auto **ptr, size_t count) { if (rc == ESFM_OK) rc = esfm::ba_dev_alloc(P, ptr, count); };
-    if (calib) A(&d.Jk, 4 * no);
+    if (calib) A(&d.Jk, (radial ? 8 : 4) * no);
     A(&d.lo_c, nc6); A(&d.up_c, nc6); A(&d.delta_c, nc6); A(&d.delta_p, np3);
     A(&d.cam_nobs, (size_t)n_cam);
     A(&d.x_c, nc6); A(&d.x_p, np3); A(&d.cand_c, nc6); A(&d.cand_p, np3); A(&d.x0_p, np3);
@@ -191,6 +195,7 @@ int create_impl(esfm_ctx *ctx, int n_real, int n_pt, int n_obs, const int32_t *c
         A(&d.lin_slabs, d.lin_slab_cap);
     }
     A(&d.cam_part, L.cchunk_cam.size() * (size_t)esfm::kCamPart);
+    if (radial) A(&d.cam_part_k, L.cchunk_cam.size() * (size_t)esfm::kRadialPart);
     // room for a few launches' partials per slot between two read-backs (a full slot is flushed by an extra reduce launch)
     d.scal_cap = std::max(1 << 12, 4 * (std::max((n_pt + 63) / 64, (n_obs + 255) / 256) + n_pt / 256 + 2));
     A(&d.scal_part, (size_t)esfm::SC_SUM_COUNT * (size_t)d.scal_cap);
@@ -207,6 +212,7 @@ int create_impl(esfm_ctx *ctx, int n_real, int n_pt, int n_obs, const int32_t *c
     for (const Table &t : tables) up(*t.dev, t.src, t.bytes);
     std::vector<double> calib_blocks(6 * (size_t)cg.n, 0.0);      // four unknowns and two padding unknowns per block
     for (int g = 0; g < cg.n; ++g) for (int i = 0; i < 4; ++i) calib_blocks[6 * (size_t)g + i] = cg.calib4[4 * (size_t)g + i];
+    for (int g = 0; g < cg.n && radial; ++g) for (int i = 0; i < 2; ++i) calib_blocks[6 * (size_t)g + 4 + i] = cg.radial2[2 * (size_t)g + i];
     if (calib) up(d.x_c + 6 * (size_t)n_real, calib_blocks.data(), sizeof(double) * calib_blocks.size());
     up(d.x_c, cams, sizeof(double) * 6 * (size_t)n_real); up(d.x_p, pts, sizeof(double) * np3);
     // red: the entries no kernel ever writes (blocks above the diagonal) must read as zero
@@ -239,6 +245,19 @@ int checked_groups(int n_real, int n_groups, const int32_t *group_of_cam, const 
     for (int i = 0; i < 4 * n_groups; ++i) if (!std::isfinite(calib4[i])) { esfm::set_error("non-finite intrinsics"); return ESFM_ERR_NUMERIC; }
     for (int c = 0; c < n_real; ++c) ESFM_REQUIRE(group_of_cam[c] >= 0 && group_of_cam[c] < n_groups, "camera group index out of range");
     cg.n = n_groups; cg.group_of_cam = group_of_cam; cg.calib4 = calib4; cg.tol = tol; cg.checked = true;
+    return ESFM_OK;
+}
+
+// the radial arguments of the radial entry points, checked like the group arguments and right behind them
+int checked_radial(int n_groups, const double *radial2, const double *radial_tol, CalibGroups &cg)
+{
+    ESFM_REQUIRE(radial2 && radial_tol, "radial2 / radial_tolerance is NULL");
+    for (int g = 0; g < n_groups; ++g) {
+        if (radial_tol[g] != radial_tol[g] || std::isinf(radial_tol[g])) { esfm::set_error("non-finite radial tolerance"); return ESFM_ERR_NUMERIC; }
+        ESFM_REQUIRE(radial_tol[g] > 0.0, "radial tolerance must be positive");
+    }
+    for (int i = 0; i < 2 * n_groups; ++i) if (!std::isfinite(radial2[i])) { esfm::set_error("non-finite radial coefficient"); return ESFM_ERR_NUMERIC; }
+    cg.radial2 = radial2; cg.radial_tol = radial_tol;
     return ESFM_OK;
 }
 
@@ -275,6 +294,52 @@ int esfm_ba_problem_create_calib_groups(esfm_ctx *ctx, int n_cam, int n_pt, int 
 
 int esfm_ba_problem_calib_groups(const esfm_ba_problem *P) { return P ? P->d.has_calib : 0; }
 
+int esfm_ba_problem_create_radial_groups(esfm_ctx *ctx, int n_cam, int n_pt, int n_obs, const int32_t *cam_idx, const int32_t *pt_idx,
+                                         const float *obs_uv, int n_groups, const int32_t *group_of_cam, const double *calib4,
+                                         const double *calib_tolerance, const double *radial2, const double *radial_tolerance,
+                                         const double *cams, const double *pts, esfm_ba_problem **out)
+{
+    CalibGroups cg;
+    if (int rc = checked_groups(n_cam, n_groups, group_of_cam, calib4, calib_tolerance, out, cg)) return rc;
+    if (int rc = checked_radial(n_groups, radial2, radial_tolerance, cg)) return rc;
+    return create_impl(ctx, n_cam, n_pt, n_obs, cam_idx, pt_idx, obs_uv, nullptr, cg, cams, pts, out);
+}
+
+int esfm_ba_problem_radial_groups(const esfm_ba_problem *P) { return P && P->d.radial ? P->d.has_calib : 0; }
+
+int esfm_ba_problem_set_radial_groups(esfm_ba_problem *P, const double *radial2, const double *radial_tolerance)
+{
+    if (!P || !radial2 || !radial_tolerance) { esfm::set_error("NULL argument"); return ESFM_ERR_INVALID_ARG; }
+    ESFM_REQUIRE(P->d.radial, "problem was created without free radial distortion");
+    const int G = P->d.has_calib;
+    CalibGroups cg;
+    if (int rc = checked_radial(G, radial2, radial_tolerance, cg)) return rc;
+    if (int rc = esfm::set_device(P->ctx)) return rc;
+    P->radial_center.assign(radial2, radial2 + 2 * (size_t)G);
+    P->radial_tol.assign(radial_tolerance, radial_tolerance + G);
+    // slots 4 and 5 of every block; the four pinhole values in front of them stay as they are
+    std::vector<double> blocks(6 * (size_t)G);
+    ESFM_HIP_TRY(esfm::copy_d2h(blocks.data(), P->d.x_c + 6 * (size_t)P->d.n_real_cam, sizeof(double) * blocks.size(), P->ctx->stream));
+    ESFM_HIP_TRY(hipStreamSynchronize(P->ctx->stream));
+    for (int g = 0; g < G; ++g) for (int i = 0; i < 2; ++i) blocks[6 * (size_t)g + 4 + i] = radial2[2 * (size_t)g + i];
+    ESFM_HIP_TRY(esfm::copy_h2d(P->d.x_c + 6 * (size_t)P->d.n_real_cam, blocks.data(), sizeof(double) * blocks.size(), P->ctx->stream));
+    ESFM_HIP_TRY(hipStreamSynchronize(P->ctx->stream));
+    return ESFM_OK;
+}
+
+int esfm_ba_problem_get_radial_groups(esfm_ba_problem *P, double *radial2)
+{
+    if (!P || !radial2) { esfm::set_error("NULL argument"); return ESFM_ERR_INVALID_ARG; }
+    ESFM_REQUIRE(P->d.radial, "problem was created without free radial distortion");
+    if (int rc = esfm::set_device(P->ctx)) return rc;
+    const int G = P->d.has_calib;
+    std::vector<double> blocks(6 * (size_t)G);
+    ESFM_HIP_TRY(esfm::copy_d2h(blocks.data(), P->d.x_c + 6 * (size_t)P->d.n_real_cam, sizeof(double) * blocks.size(), P->ctx->stream));
+    ESFM_HIP_TRY(hipStreamSynchronize(P->ctx->stream));
+    for (int g = 0; g < G; ++g) for (int i = 0; i < 2; ++i) radial2[2 * (size_t)g + i] = blocks[6 * (size_t)g + 4 + i];
+    return ESFM_OK;
+}
+
 int esfm_ba_problem_set_calib_groups(esfm_ba_problem *P, const double *calib4, const double *calib_tolerance)
 {
     if (!P || !calib4 || !calib_tolerance) { esfm::set_error("NULL argument"); return ESFM_ERR_INVALID_ARG; }
@@ -286,6 +351,11 @@ int esfm_ba_problem_set_calib_groups(esfm_ba_problem *P, const double *calib4, c
     P->calib_center.assign(calib4, calib4 + 4 * (size_t)G);
     P->calib_tol.assign(calib_tolerance, calib_tolerance + G);
     std::vector<double> blocks(6 * (size_t)G, 0.0);
+    // (a radial problem: k1, k2 in slots 4 and 5 stay as they are)
+    if (P->d.radial) {
+        ESFM_HIP_TRY(esfm::copy_d2h(blocks.data(), P->d.x_c + 6 * (size_t)P->d.n_real_cam, sizeof(double) * blocks.size(), P->ctx->stream));
+        ESFM_HIP_TRY(hipStreamSynchronize(P->ctx->stream));
+    }
     for (int g = 0; g < G; ++g) for (int i = 0; i < 4; ++i) blocks[6 * (size_t)g + i] = calib4[4 * (size_t)g + i];
     ESFM_HIP_TRY(esfm::copy_h2d(P->d.x_c + 6 * (size_t)P->d.n_real_cam, blocks.data(), sizeof(double) * blocks.size(), P->ctx->stream));
     ESFM_HIP_TRY(hipStreamSynchronize(P->ctx->stream));
@@ -309,7 +379,7 @@ int esfm_ba_problem_set_calib(esfm_ba_problem *P, const double *calib4, double c
 {
     if (!P || !calib4) { esfm::set_error("NULL argument"); return ESFM_ERR_INVALID_ARG; }
     ESFM_REQUIRE(P->d.has_calib, "problem was created with fixed intrinsics");
-    ESFM_REQUIRE(P->d.has_calib == 1, "problem has several intrinsics blocks: use esfm_ba_problem_set_calib_groups");
+    ESFM_REQUIRE(P->d.has_calib == 1 && !P->d.radial, "problem has several intrinsics blocks or a radial one: use esfm_ba_problem_set_calib_groups");
     ESFM_REQUIRE(calib_tolerance > 0.0, "intrinsics tolerance must be positive");
     for (int i = 0; i < 4; ++i) if (!std::isfinite(calib4[i])) { esfm::set_error("non-finite intrinsics"); return ESFM_ERR_NUMERIC; }
     if (int rc = esfm::set_device(P->ctx)) return rc;
@@ -324,7 +394,7 @@ int esfm_ba_problem_get_calib(esfm_ba_problem *P, double *calib4)
 {
     if (!P || !calib4) { esfm::set_error("NULL argument"); return ESFM_ERR_INVALID_ARG; }
     ESFM_REQUIRE(P->d.has_calib, "problem was created with fixed intrinsics");
-    ESFM_REQUIRE(P->d.has_calib == 1, "problem has several intrinsics blocks: use esfm_ba_problem_get_calib_groups");
+    ESFM_REQUIRE(P->d.has_calib == 1 && !P->d.radial, "problem has several intrinsics blocks or a radial one: use esfm_ba_problem_get_calib_groups");
     if (int rc = esfm::set_device(P->ctx)) return rc;
     ESFM_HIP_TRY(esfm::copy_d2h(calib4, P->d.x_c + 6 * (size_t)P->d.n_real_cam, sizeof(double) * 4, P->ctx->stream));
     ESFM_HIP_TRY(hipStreamSynchronize(P->ctx->stream));
@@ -456,6 +526,26 @@ int esfm_ba_solve_groups(esfm_ctx *ctx, int n_cam, int n_pt, int n_obs, const in
     if (rc == ESFM_OK || rc == ESFM_ERR_NUMERIC) {
         int rc2 = esfm_ba_problem_get_params(P, cams, pts);
         if (rc2 == ESFM_OK) rc2 = esfm_ba_problem_get_calib_groups(P, calib4);
+        if (rc == ESFM_OK) rc = rc2;
+    }
+    esfm_ba_problem_destroy(P);
+    return rc;
+}
+
+int esfm_ba_solve_radial_groups(esfm_ctx *ctx, int n_cam, int n_pt, int n_obs, const int32_t *cam_idx, const int32_t *pt_idx, const float *obs_uv,
+                                double *cams, double *pts, int n_groups, const int32_t *group_of_cam, double *calib4, const double *calib_tolerance,
+                                double *radial2, const double *radial_tolerance, int ref_cam, double ref_threshold, const esfm_ba_options *options,
+                                esfm_allreduce_fn allreduce, void *allreduce_user, esfm_ba_summary *summary)
+{
+    esfm_ba_problem *P = nullptr;
+    if (int rc = esfm_ba_problem_create_radial_groups(ctx, n_cam, n_pt, n_obs, cam_idx, pt_idx, obs_uv, n_groups, group_of_cam, calib4, calib_tolerance,
+                                                      radial2, radial_tolerance, cams, pts, &P)) return rc;
+    int rc = esfm_ba_problem_fix_camera(P, ref_cam, ref_threshold);
+    if (rc == ESFM_OK) rc = esfm_ba_problem_solve(P, options, allreduce, allreduce_user, summary);
+    if (rc == ESFM_OK || rc == ESFM_ERR_NUMERIC) {
+        int rc2 = esfm_ba_problem_get_params(P, cams, pts);
+        if (rc2 == ESFM_OK) rc2 = esfm_ba_problem_get_calib_groups(P, calib4);
+        if (rc2 == ESFM_OK) rc2 = esfm_ba_problem_get_radial_groups(P, radial2);
         if (rc == ESFM_OK) rc = rc2;
     }
     esfm_ba_problem_destroy(P);

@@ -287,6 +287,65 @@ __device__ __forceinline__ void reproject_jac(const double cam[6], const double 
     xn = x; yn = y;
 }
 
+// Radial problems (BADev::radial; always the grouped path): the block of the camera's group is fx, cx, fy, cy, k1, k2.
+__device__ __forceinline__ void load_intrinsics_radial(const BADev &d, const double *__restrict__ cams, int c, double in6[6])
+{
+    const double *kp = cams + 6 * (size_t)calib_block_of<true>(d, c);
+#pragma unroll
+    for (int i = 0; i < 6; ++i) in6[i] = kp[i];
+}
+
+// Residual of the radial model (OpenCV's with p1 = p2 = 0, the one esfm_undistort inverts) at the camera-frame point pt:
+// x = p0/p2, y = p1/p2, r2 = x^2 + y^2, L = 1 + k1 r2 + k2 r2^2,  r = uv - (fx x L + cx, fy y L + cy).
+__device__ __forceinline__ void reproject_radial(const double pt[3], const double in6[6], float2 uv, double &r0, double &r1)
+{
+    const double x = pt[0] / pt[2], y = pt[1] / pt[2];
+    const double r2 = x * x + y * y;
+    const double L = 1.0 + in6[4] * r2 + in6[5] * r2 * r2;
+    r0 = (double)uv.x - (x * L * in6[0] + in6[1]);
+    r1 = (double)uv.y - (y * L * in6[2] + in6[3]);
+}
+
+// reproject_jac for the radial model.  With D = 2 k1 + 4 k2 r2:  d(xL)/dx = L + x^2 D, d(xL)/dy = d(yL)/dx = x y D, d(yL)/dy = L + y^2 D,
+// chained in front of d(x, y)/dp.  Jk[8]: d r0 / d(fx, cx), d r1 / d(fy, cy) -- the four the pinhole block stores -- then
+// d r0 / d(k1, k2), d r1 / d(k1, k2).
+__device__ __forceinline__ void reproject_jac_radial(const double cam[6], const double X[3], const double in6[6], float2 uv,
+                                                     double &r0, double &r1, double Jc[12], double Jp[6], double Jk[8])
+{
+    double pt[3], R[9], Ja[9];
+    transform_point<true>(cam, X, pt, R, Ja);
+    const double iz = 1.0 / pt[2];
+    const double x = pt[0] * iz, y = pt[1] * iz;
+    const double fx = in6[0], cx = in6[1], fy = in6[2], cy = in6[3], k1 = in6[4], k2 = in6[5];
+    const double r2 = x * x + y * y, r4 = r2 * r2;
+    const double L = 1.0 + k1 * r2 + k2 * r4, D = 2.0 * k1 + 4.0 * k2 * r2;
+    const double xl = x * L, yl = y * L;
+    r0 = (double)uv.x - (xl * fx + cx);
+    r1 = (double)uv.y - (yl * fy + cy);
+    const double a00 = L + x * x * D, a01 = x * y * D, a11 = L + y * y * D;
+    // d r / d p  (rows)
+    const double g0[3] = {-fx * iz * a00, -fx * iz * a01, fx * (a00 * x + a01 * y) * iz};
+    const double g1[3] = {-fy * iz * a01, -fy * iz * a11, fy * (a01 * x + a11 * y) * iz};
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        Jc[j] = g0[0] * Ja[j] + g0[1] * Ja[3 + j] + g0[2] * Ja[6 + j];
+        Jc[6 + j] = g1[0] * Ja[j] + g1[1] * Ja[3 + j] + g1[2] * Ja[6 + j];
+        Jc[3 + j] = g0[j];
+        Jc[9 + j] = g1[j];
+        Jp[j] = g0[0] * R[j] + g0[1] * R[3 + j] + g0[2] * R[6 + j];
+        Jp[3 + j] = g1[0] * R[j] + g1[1] * R[3 + j] + g1[2] * R[6 + j];
+    }
+    Jk[0] = -xl; Jk[1] = -1.0; Jk[2] = -yl; Jk[3] = -1.0;
+    Jk[4] = -fx * x * r2; Jk[5] = -fx * x * r4; Jk[6] = -fy * y * r2; Jk[7] = -fy * y * r4;
+}
+
+// The radial block's columns in the two residual rows, from the 8 stored scalars: row 0 (K0, K1, 0, 0, K4, K5), row 1 (0, 0, K2, K3, K6, K7).
+__device__ __forceinline__ void radial_rows(const double K[8], double g0[6], double g1[6])
+{
+    g0[0] = K[0]; g0[1] = K[1]; g0[2] = 0.0; g0[3] = 0.0; g0[4] = K[4]; g0[5] = K[5];
+    g1[0] = 0.0; g1[1] = 0.0; g1[2] = K[2]; g1[3] = K[3]; g1[4] = K[6]; g1[5] = K[7];
+}
+
 // W_i = F_i'E_i (6 x 3, row-major) of observation i, re-formed from its 18 Jacobian entries.  (Round 2 had the sweep store W -- 144 B
 // per observation -- and the Schur kernels load it: as many loads here, 36 multiply-adds less.  Measured in round 3: without the
 // store the sweep of BA-512 takes 262 us instead of 369, the Schur kernels 927 against 928 us; BA-25 29.2 against 30.7 and 41.5

@@ -24,7 +24,8 @@ struct BaForms {
 // n_groups: the free intrinsics blocks (one per camera group; read only with has_calib).  The rule is the one of a single block with
 // n_cam = n_real_cam + n_groups, except that with several groups the sweep never keeps the per-camera sums in LDS: a group's ten
 // sums G'G / G'r are its cameras' chunk sums added in chunk order (ba_camacc_groups_kernel), so every size takes the camera chunks.
-BaForms ba_forms(int n_real_cam, bool has_calib, int n_obs, int n_groups = 1);
+// radial: the blocks also carry k1, k2; such a problem takes the grouped path even with one group.
+BaForms ba_forms(int n_real_cam, bool has_calib, int n_obs, int n_groups = 1, bool radial = false);
 
 // dynamic LDS of the three kernels that have an in-LDS form
 constexpr int kLinLdsPerCam = 27 * 8 + 7 * 8 + 4 + 7 * 4;   // ba_linearize_kernel: acc, maxima, count, exponents
@@ -50,11 +51,16 @@ constexpr bool ba_calib_row_in_lds(int n_real_cam) { return calib_row_lds_bytes(
 // ba_schur_groups_kernel (several free intrinsics blocks): the block rows of ALL groups, 4 n_groups rows of 6 (n_real_cam + n_groups)
 // fixed-point entries -- the camera columns and the group-by-group cross blocks -- under the same budget (two groups: up to 168
 // cameras); beyond, every addend goes to d.red directly
-constexpr size_t calib_groups_lds_bytes(int n_real_cam, int n_groups)
+// radial problems (k1, k2 free in slots 4 and 5 of every block, one group or several): 6 n_groups rows, 8 * 6 G * 6 (n_real_cam + G)
+// bytes (two groups: up to 111 cameras)
+constexpr size_t calib_groups_lds_bytes(int n_real_cam, int n_groups, bool radial = false)
 {
-    return sizeof(double) * ((size_t)4 * n_groups * 6 * ((size_t)n_real_cam + n_groups));
+    return sizeof(double) * ((size_t)(radial ? 6 : 4) * n_groups * 6 * ((size_t)n_real_cam + n_groups));
 }
-constexpr bool ba_calib_groups_in_lds(int n_real_cam, int n_groups) { return calib_groups_lds_bytes(n_real_cam, n_groups) <= kCalibRowLdsBudget; }
+constexpr bool ba_calib_groups_in_lds(int n_real_cam, int n_groups, bool radial = false)
+{
+    return calib_groups_lds_bytes(n_real_cam, n_groups, radial) <= kCalibRowLdsBudget;
+}
 // the one-workgroup MFMA solve (ba_chol_small_kernel) holds at most kSmallMaxNb block rows of kSmallTile (= SB, ba_chol_tile.hpp)
 // unknowns: n = 6 n_cam <= 176
 constexpr int kSmallTile = 16, kSmallMaxNb = 11;

@@ -65,7 +65,7 @@ struct BADev {
     double *Jc = nullptr;   // 12 arrays: row 0 cols 0..5, then row 1 cols 0..5
     double *Jp = nullptr;   // 6 arrays: row 0 cols 0..2, row 1 cols 0..2
     double *res = nullptr;  // 2 arrays
-    double *Jk = nullptr;   // has_calib, 4 arrays: d r0/d fx, d r0/d cx, d r1/d fy, d r1/d cy (the other four are 0)
+    double *Jk = nullptr;   // has_calib, 4 arrays: d r0/d fx, d r0/d cx, d r1/d fy, d r1/d cy (the other four are 0); radial: 8 arrays, below
     double *lo_c = nullptr, *up_c = nullptr;          // box bounds [6 n_cam]
     double *delta_c = nullptr, *delta_p = nullptr;    // the LM step in parameter units, [6 n_cam], [3 n_pt]
     double *scale_c = nullptr, *scale_p = nullptr;  // Jacobi scaling [6 n_cam], [3 n_pt]
@@ -133,7 +133,14 @@ struct BADev {
     int n_pchunks = 0;
     // several free intrinsics blocks (has_calib = G > 1): camera c uses block n_real_cam + cam_group[c].  One block: not read.
     int32_t *cam_group = nullptr;       // [n_real_cam]
+    // radial problems (free k1, k2 per camera group in slots 4 and 5 of the group's block; always the grouped path, whatever G, and
+    // always bounded): Jk then holds 8 arrays -- the four above, then d r0/d k1, d r0/d k2, d r1/d k1, d r1/d k2 -- and a camera chunk
+    // leaves the sums of its group's block here
+    int radial = 0;
+    double *cam_part_k = nullptr;       // [n_cchunks][kRadialPart]
 };
+// several free blocks, or a radial problem: the intrinsics are read per observation and the block rows come from ba_schur_groups_kernel
+inline bool ba_grouped(const BADev &d) { return d.has_calib > 1 || d.radial; }
 
 inline size_t ba_camacc_doubles(int n_cam) { return (size_t)42 * (size_t)n_cam; }
 inline size_t ba_red_doubles(int n_cam) { const size_t n = 6 * (size_t)n_cam; return n * n + n; }

@@ -11,6 +11,7 @@
 namespace esfm {
 
 constexpr int kCamChunk = 256, kCamPart = 37;  // observations per camera chunk; doubles of one chunk's partial sums (BADev::cam_part)
+constexpr int kRadialPart = 27;                // radial problems: a chunk's sums of its group's block, G'G (21, upper triangle) and G'r (6) (BADev::cam_part_k)
 constexpr int kPtChunkObs = 256;               // observations per point chunk (back-substitution, per-point normal blocks)
 constexpr int kSchurWinCams = 28;              // cameras in the windowed Schur kernel's LDS window
 constexpr int kSchurMfCams = 13;               // cameras in the matrix-core Schur kernel's window (80 rows = 5 MFMA block rows)

@@ -46,7 +46,9 @@ constexpr int kLinThreadsLarge = 512, kLinThreadsSmall = 256;
 
 // GROUPS (several free intrinsics blocks, has_calib = G > 1; always !PRIV): the intrinsics and their column scales are those of the
 // observation's camera's group, gathered with the camera's parameters; the per-group sums come from the camera chunks.
-template <bool PRIV, bool CALIB, int kLinThreads, bool GROUPS = false>
+// RADIAL (a GROUPS sweep): the group's block is fx, cx, fy, cy, k1, k2 (reproject_jac_radial) and the block's columns mix the two
+// residual rows, so 8 scalars per observation are stored, not 4.
+template <bool PRIV, bool CALIB, int kLinThreads, bool GROUPS = false, bool RADIAL = false>
 __global__ __launch_bounds__(kLinThreads, 1) void ba_linearize_kernel(BADev d, double cauchy_a, int use_scaling, ScalBase sbase, double *__restrict__ slabs,
                                                                    int prov_rexp)
 {
@@ -58,6 +60,8 @@ __global__ __launch_bounds__(kLinThreads, 1) void ba_linearize_kernel(BADev d, d
     // runs the two-pass form below.  Either way the integers are exact sums on the grid the slab is converted with.  (Round 3: the
     // re-read of pass 2 was 336 MB of BA-512's sweep.)
     static_assert(!GROUPS || (CALIB && !PRIV), "the grouped sweep is a free-intrinsics sweep without LDS sums");
+    static_assert(!RADIAL || GROUPS, "the radial sweep is a grouped sweep");
+    constexpr int NKD = RADIAL ? 6 : 4, NJK = RADIAL ? 8 : 4;      // unknowns of the intrinsics block; scalars stored per observation
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     double *red = reinterpret_cast<double *>(lds_raw);                                  // [8] reduction scratch, [10] intrinsics-block sums
     unsigned long long *acc = reinterpret_cast<unsigned long long *>(lds_raw) + 18;     // PRIV: [n_real_cam * 27]
@@ -114,16 +118,17 @@ __global__ __launch_bounds__(kLinThreads, 1) void ba_linearize_kernel(BADev d, d
     // register copy that has to wait for the load -- in front of the stores.  The camera's float calibration is converted where it
     // is used, for the same reason.)
     struct LinIdx { int c, p; float2 uv; };
-    struct LinPar { float4 K; double kd[4], cam[6], X[3], sc[6], sp[3], ksc[4]; };
+    struct LinPar { float4 K; double kd[NKD], cam[6], X[3], sc[6], sp[3], ksc[NKD]; };
     auto load_idx = [&](int k, LinIdx &o) { o.c = d.obs_cam[k]; o.p = d.obs_pt[k]; o.uv = d.obs_uv[k]; };
     auto load_par = [&](const LinIdx &ix, LinPar &o) {
         if (CALIB) {         // (== d.has_calib: the free block rides behind the real cameras, load_intrinsics)
             const size_t kb = 6 * (size_t)calib_block_of<GROUPS>(d, ix.c);
             const double *kp = d.x_c + kb;
             o.kd[0] = kp[0]; o.kd[1] = kp[1]; o.kd[2] = kp[2]; o.kd[3] = kp[3];
+            if (RADIAL) { o.kd[NKD - 2] = kp[4]; o.kd[NKD - 1] = kp[5]; }
             if (GROUPS) {
 #pragma unroll
-                for (int i = 0; i < 4; ++i) o.ksc[i] = use_scaling ? d.scale_c[kb + i] : 1.0;
+                for (int i = 0; i < NKD; ++i) o.ksc[i] = use_scaling ? d.scale_c[kb + i] : 1.0;
             }
         } else {
             o.K = d.K4[ix.c];
@@ -174,9 +179,17 @@ __global__ __launch_bounds__(kLinThreads, 1) void ba_linearize_kernel(BADev d, d
         if (CALIB) { in4[0] = par_cur.kd[0]; in4[1] = par_cur.kd[1]; in4[2] = par_cur.kd[2]; in4[3] = par_cur.kd[3]; }
         else { in4[0] = (double)par_cur.K.x; in4[1] = (double)par_cur.K.y; in4[2] = (double)par_cur.K.z; in4[3] = (double)par_cur.K.w; }
         double r0, r1, Jc[12], Jp[6], xn, yn;
-        reproject_jac(par_cur.cam, par_cur.X, in4, uv, r0, r1, Jc, Jp, xn, yn);
-        // intrinsics columns (ba.h:199-206): u = x fx + cx, v = y fy + cy
-        double Jk[4] = {-xn, -1.0, -yn, -1.0};
+        double Jk[NJK];
+        if constexpr (RADIAL) {
+            reproject_jac_radial(par_cur.cam, par_cur.X, par_cur.kd, uv, r0, r1, Jc, Jp, Jk);
+            xn = Jk[0]; yn = Jk[2];          // (for the finite check: the rest of Jk is products of these, the intrinsics and r2)
+#pragma unroll
+            for (int i = 4; i < NJK; ++i) { if (!isfinite(Jk[i])) xn = Jk[i]; }
+        } else {
+            reproject_jac(par_cur.cam, par_cur.X, in4, uv, r0, r1, Jc, Jp, xn, yn);
+            // intrinsics columns (ba.h:199-206): u = x fx + cx, v = y fy + cy
+            Jk[0] = -xn; Jk[1] = -1.0; Jk[2] = -yn; Jk[3] = -1.0;
+        }
         const double s = r0 * r0 + r1 * r1;
         bool fin = isfinite(s);
 #pragma unroll
@@ -191,7 +204,7 @@ __global__ __launch_bounds__(kLinThreads, 1) void ba_linearize_kernel(BADev d, d
 #pragma unroll
             for (int i = 0; i < 6; ++i) Jp[i] = 0.0;
 #pragma unroll
-            for (int i = 0; i < 4; ++i) Jk[i] = 0.0;
+            for (int i = 0; i < NJK; ++i) Jk[i] = 0.0;
         } else {
             double rho0, rho1;
             loss_eval(cauchy_a, s, rho0, rho1);
@@ -211,11 +224,15 @@ __global__ __launch_bounds__(kLinThreads, 1) void ba_linearize_kernel(BADev d, d
             if (CALIB) {
 #pragma unroll
                 for (int i = 0; i < 4; ++i) Jk[i] *= sq * (GROUPS ? par_cur.ksc[i] : kscale[i]);
+                if constexpr (RADIAL) {
+#pragma unroll
+                    for (int i = 4; i < NJK; ++i) Jk[i] *= sq * par_cur.ksc[4 + (i & 1)];      // columns k1, k2 of row 0, then of row 1
+                }
             }
         }
         if (CALIB) {
 #pragma unroll
-            for (int i = 0; i < 4; ++i) d.Jk[(size_t)i * n_obs + k] = Jk[i];
+            for (int i = 0; i < NJK; ++i) d.Jk[(size_t)i * n_obs + k] = Jk[i];
             if (PRIV) {
                 // G'G (upper triangle of the 4x4: rows fx, cx | fy, cy never mix) and G'r, kept in registers over the sweep
                 kacc[0] += Jk[0] * Jk[0]; kacc[1] += Jk[0] * Jk[1]; kacc[2] += Jk[1] * Jk[1];
@@ -388,7 +405,13 @@ __global__ __launch_bounds__(256) void ba_camacc_reduce_kernel(BADev d, const do
 // cam_obs[beg, end) of ONE camera.  Lane l takes observations l, l + 64, l + 128, l + 192 in that order (all four index loads,
 // then all Jacobian loads, are issued before the first use: the kernel is two memory round trips deep, not eight); the 37 sums
 // then go through the wave shuffle tree.  A fixed association: bit-reproducible.
-template <bool CALIB>
+// RADIAL: the block of the camera's group is 6 wide and its columns mix the two residual rows: G'G is the full upper triangle (21)
+// and G'r has 6 entries, from the 8 stored scalars; they go to cam_part_k (the ten sums of the pinhole block are not formed).
+// (This instance compiles to exactly 256 VGPRs, the most a wave may have without AGPR copies, and no scratch
+// (profiles/r14_ba_radial_kernel_resources.txt): four observations' 12 + 8 + 2 values and 27 + 27 sums in f64.  Check the scratch
+// count after a compiler change; if it ever spills, form the 27 radial sums in a second pass over K, r0, r1 -- the order of the adds,
+// hence the bits, stays.)
+template <bool CALIB, bool RADIAL = false>
 __global__ __launch_bounds__(64) void ba_camacc_chunk_kernel(BADev d)
 {
     const int lane = threadIdx.x;
@@ -398,7 +421,8 @@ __global__ __launch_bounds__(64) void ba_camacc_chunk_kernel(BADev d)
     int k[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) { const int idx = beg + lane + 64 * u; k[u] = idx < end ? d.cam_obs[idx] : -1; }
-    double J[U][12], r0[U], r1[U], K[U][4];
+    constexpr int NJK = RADIAL ? 8 : 4;
+    double J[U][12], r0[U], r1[U], K[U][NJK];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
         const int kk = k[u] < 0 ? 0 : k[u];
@@ -407,12 +431,17 @@ __global__ __launch_bounds__(64) void ba_camacc_chunk_kernel(BADev d)
         r0[u] = d.res[kk]; r1[u] = d.res[n + kk];
         if (CALIB) {
 #pragma unroll
-            for (int a = 0; a < 4; ++a) K[u][a] = d.Jk[a * n + kk];
+            for (int a = 0; a < NJK; ++a) K[u][a] = d.Jk[a * n + kk];
         }
     }
     double acc[kCamPart];
 #pragma unroll
     for (int q = 0; q < kCamPart; ++q) acc[q] = 0.0;
+    double acck[RADIAL ? kRadialPart : 1];
+    if constexpr (RADIAL) {
+#pragma unroll
+        for (int q = 0; q < kRadialPart; ++q) acck[q] = 0.0;
+    }
 #pragma unroll
     for (int u = 0; u < U; ++u) {
         if (k[u] < 0) continue;
@@ -423,13 +452,23 @@ __global__ __launch_bounds__(64) void ba_camacc_chunk_kernel(BADev d)
             for (int b = a; b < 6; ++b) acc[e++] += J[u][a] * J[u][b] + J[u][6 + a] * J[u][6 + b];
 #pragma unroll
         for (int a = 0; a < 6; ++a) acc[21 + a] += J[u][a] * r0[u] + J[u][6 + a] * r1[u];
-        if (CALIB) {
+        if constexpr (RADIAL) {
+            double g0[6], g1[6];
+            radial_rows(K[u], g0, g1);
+            int e2 = 0;
+#pragma unroll
+            for (int a = 0; a < 6; ++a)
+#pragma unroll
+                for (int b = a; b < 6; ++b) acck[e2++] += g0[a] * g0[b] + g1[a] * g1[b];
+#pragma unroll
+            for (int a = 0; a < 6; ++a) acck[21 + a] += g0[a] * r0[u] + g1[a] * r1[u];
+        } else if (CALIB) {
             const double k0 = K[u][0], k1 = K[u][1], k2 = K[u][2], k3 = K[u][3];
             acc[27] += k0 * k0; acc[28] += k0 * k1; acc[29] += k1 * k1; acc[30] += k2 * k2; acc[31] += k2 * k3; acc[32] += k3 * k3;
             acc[33] += k0 * r0[u]; acc[34] += k1 * r0[u]; acc[35] += k2 * r1[u]; acc[36] += k3 * r1[u];
         }
     }
-    constexpr int NQ = CALIB ? kCamPart : 27;
+    constexpr int NQ = RADIAL ? 27 : CALIB ? kCamPart : 27;
     double mine = 0.0;
 #pragma unroll
     for (int q = 0; q < NQ; ++q) {
@@ -439,6 +478,17 @@ __global__ __launch_bounds__(64) void ba_camacc_chunk_kernel(BADev d)
         if (lane == q) mine = v;
     }
     if (lane < NQ) d.cam_part[(size_t)blockIdx.x * kCamPart + lane] = mine;
+    if constexpr (RADIAL) {
+        double minek = 0.0;
+#pragma unroll
+        for (int q = 0; q < kRadialPart; ++q) {
+            double v = acck[q];
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+            if (lane == q) minek = v;
+        }
+        if (lane < kRadialPart) d.cam_part_k[(size_t)blockIdx.x * kRadialPart + lane] = minek;
+    }
 }
 
 // camacc = F'F (36 per camera, both triangles) | F'r (6 per camera): a camera's chunk sums added in chunk order; the
@@ -462,7 +512,7 @@ __global__ __launch_bounds__(256) void ba_camacc_final_kernel(BADev d)
         return;
     }
     const int q = e - nr * 27;
-    if (d.has_calib != 1 || q >= 42) return;     // (several blocks: ba_camacc_groups_kernel)
+    if (d.has_calib != 1 || d.radial || q >= 42) return;     // (several blocks, or a radial one: ba_camacc_groups_kernel)
     // the shared intrinsics block rides as camera-side block nr: 6 x 6 with the 4 x 4 part G'G (fx, cx | fy, cy never mix), then G'r
     const int kc = nr;
     if (q < 36) {
@@ -488,12 +538,22 @@ __global__ __launch_bounds__(256) void ba_camacc_final_kernel(BADev d)
 // right-hand side: lane l takes chunks l, l + 64, ... in that order -- a chunk of another group adds 0.0 -- then the wave shuffle
 // tree: a fixed association whatever the launch timing.  (One thread per entry walking all chunks was a chain of three dependent
 // loads per chunk: 2 ms per sweep at 938 chunks.)  A group without observations gets zeros.
+// RADIAL: every entry of the 6 x 6 and of the right-hand side has a sum, among the chunk's 27 of cam_part_k.
+template <bool RADIAL = false>
 __global__ __launch_bounds__(64) void ba_camacc_groups_kernel(BADev d)
 {
     const int g = blockIdx.x / 42, q = blockIdx.x % 42, lane = threadIdx.x;
     const int kc = d.n_real_cam + g;
+    const double *part = RADIAL ? d.cam_part_k : d.cam_part;
+    constexpr int kPart = RADIAL ? kRadialPart : kCamPart;
     int src = -1;
-    if (q < 36) {
+    if constexpr (RADIAL) {
+        if (q < 36) {
+            const int a = q / 6, b2 = q % 6;
+            const int lo = a < b2 ? a : b2, hi = a < b2 ? b2 : a;
+            src = lo * 6 - lo * (lo - 1) / 2 + hi - lo;      // packed index of (lo, hi) in the upper triangle
+        } else src = 21 + (q - 36);
+    } else if (q < 36) {
         const int a = q / 6, b2 = q % 6;
         const int lo = a < b2 ? a : b2, hi = a < b2 ? b2 : a;
         if (lo == 0 && hi == 0) src = 27; else if (lo == 0 && hi == 1) src = 28; else if (lo == 1 && hi == 1) src = 29;
@@ -508,7 +568,7 @@ __global__ __launch_bounds__(64) void ba_camacc_groups_kernel(BADev d)
             for (int u = 0; u < U; ++u) {
                 const int b = b0 + 64 * u;
                 const bool mine = b < d.n_cchunks && d.cam_group[d.cchunk_cam[b < d.n_cchunks ? b : 0]] == g;
-                t[u] = mine ? d.cam_part[(size_t)b * kCamPart + src] : 0.0;
+                t[u] = mine ? part[(size_t)b * kPart + src] : 0.0;
             }
 #pragma unroll
             for (int u = 0; u < U; ++u) v += t[u];
@@ -768,7 +828,7 @@ int ba_linearize(hipStream_t st, const BADev &d, int num_cu, double cauchy_a, bo
     // after the first, paying the 9-us prologue (LDS clear, exponents) and the 8-us epilogue (guard, slab) again: one per CU)
     const int grid = std::min(div_up(d.n_obs, kLinThreads), std::max(1, num_cu) * (small ? 2 : 1));
     const bool priv = forms.sweep_sums_in_lds;
-    if (priv && d.has_calib > 1) { set_error("BA sweep: several intrinsics blocks take the camera-chunk sums"); return ESFM_ERR_INVALID_ARG; }
+    if (priv && ba_grouped(d)) { set_error("BA sweep: several intrinsics blocks, or a radial one, take the camera-chunk sums"); return ESFM_ERR_INVALID_ARG; }
     if (priv && (size_t)grid * ba_lin_slab_doubles(d.n_cam) > d.lin_slab_cap) { set_error("BA sweep: %d slabs do not fit lin_slabs", grid); return ESFM_ERR_INVALID_ARG; }
     ScalBase sbase;
     { const int slots[2] = {SC_COST, SC_LIN_BAD}; if (int rc = scal_reserve<2>(st, d, slots, grid, sbase)) return rc; }
@@ -793,15 +853,20 @@ int ba_linearize(hipStream_t st, const BADev &d, int num_cu, double cauchy_a, bo
         auto kern = small ? (d.has_calib ? &ba_linearize_kernel<false, true, kLinThreadsSmall> : &ba_linearize_kernel<false, false, kLinThreadsSmall>)
                           : (d.has_calib ? &ba_linearize_kernel<false, true, kLinThreadsLarge> : &ba_linearize_kernel<false, false, kLinThreadsLarge>);
         if (d.has_calib > 1) kern = small ? &ba_linearize_kernel<false, true, kLinThreadsSmall, true> : &ba_linearize_kernel<false, true, kLinThreadsLarge, true>;
+        if (d.radial) kern = small ? &ba_linearize_kernel<false, true, kLinThreadsSmall, true, true> : &ba_linearize_kernel<false, true, kLinThreadsLarge, true, true>;
         hipLaunchKernelGGL(kern, dim3(grid), dim3(kLinThreads), 18 * sizeof(double), st, d, cauchy_a, use_scaling ? 1 : 0, sbase, (double *)nullptr, INT_MIN);
     }
     LAUNCH_CHECK();
-    if (d.has_calib) hipLaunchKernelGGL(ba_camacc_chunk_kernel<true>, dim3(d.n_cchunks), dim3(64), 0, st, d);
+    if (d.radial) hipLaunchKernelGGL((ba_camacc_chunk_kernel<true, true>), dim3(d.n_cchunks), dim3(64), 0, st, d);
+    else if (d.has_calib) hipLaunchKernelGGL(ba_camacc_chunk_kernel<true>, dim3(d.n_cchunks), dim3(64), 0, st, d);
     else hipLaunchKernelGGL(ba_camacc_chunk_kernel<false>, dim3(d.n_cchunks), dim3(64), 0, st, d);
     hipLaunchKernelGGL(ba_camacc_final_kernel, dim3(div_up(d.n_real_cam * 27 + 42, 256)), dim3(256), 0, st, d);
     LAUNCH_CHECK();
-    if (d.has_calib > 1) {
-        hipLaunchKernelGGL(ba_camacc_groups_kernel, dim3(d.has_calib * 42), dim3(64), 0, st, d);
+    if (d.radial) {
+        hipLaunchKernelGGL(ba_camacc_groups_kernel<true>, dim3(d.has_calib * 42), dim3(64), 0, st, d);
+        LAUNCH_CHECK();
+    } else if (d.has_calib > 1) {
+        hipLaunchKernelGGL(ba_camacc_groups_kernel<false>, dim3(d.has_calib * 42), dim3(64), 0, st, d);
         LAUNCH_CHECK();
     }
     return ESFM_OK;

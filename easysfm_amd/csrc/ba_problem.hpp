@@ -19,6 +19,7 @@ struct esfm_ba_problem {
     int ref_cam = -1;
     double ref_threshold = 0.0;
     std::vector<double> calib_center, calib_tol;   // per free intrinsics block: [4 G] box centres, [G] half widths
+    std::vector<double> radial_center, radial_tol; // radial problems (BADev::radial): [2 G] box centres of k1, k2, [G] half widths
     esfm::ScalParts parts{};    // the kernel forms of this problem and the per-workgroup scalar partials pending on the device (BADev::parts points here)
     double *h_scal = nullptr;   // pinned host copy of the scalar slots: the LM loop reads them back twice per iteration
     unsigned long long seq = 0; // sequence number of the last publication (the flag sits behind the scalars)

@@ -573,29 +573,46 @@ __global__ __launch_bounds__(256) void ba_schur_calib_kernel(BADev d, int use_ld
 // Every addend is rounded to its entry's fixed-point grid and added as an integer -- through an LDS copy of all 4 G block rows while
 // that fits (ba_calib_groups_in_lds), else into d.red directly -- so the sums do not depend on the order of arrival.  A track of T
 // observations over L groups walks its rows L (L + 1) T / 2 + 2 L T times: the tracks are short.  Runs after ba_schur.
+// RADIAL (also with one group): the blocks are fx, cx, fy, cy, k1, k2; Wk_g is 6 x 3 and formed from both residual rows, G_j'F_j uses
+// both rows, the cross blocks are 6 x 6 and the LDS copy holds 6 G rows (calib_groups_lds_bytes).
+template <bool RADIAL = false>
 __global__ __launch_bounds__(256) void ba_schur_groups_kernel(BADev d, int use_lds, int rhs_exp)
 {
-    extern __shared__ __attribute__((aligned(16))) unsigned long long rowq[];   // use_lds: [4 G][6 n_cam]
+    constexpr int NK = RADIAL ? 6 : 4;       // unknowns of a block that have columns
+    extern __shared__ __attribute__((aligned(16))) unsigned long long rowq[];   // use_lds: [NK G][6 n_cam]
     const int tid = threadIdx.x;
     const int nr = d.n_real_cam, G = d.has_calib, n = 6 * d.n_cam;
     unsigned long long *redq = reinterpret_cast<unsigned long long *>(d.red);
     if (use_lds) {
-        for (int e = tid; e < 4 * G * n; e += 256) rowq[e] = 0ull;
+        for (int e = tid; e < NK * G * n; e += 256) rowq[e] = 0ull;
         __syncthreads();
     }
     auto add = [&](int g, int a, int col, double v, int sh) {
         const unsigned long long q = fx64(v, sh);
         if (q == 0ull) return;
-        if (use_lds) atomicAdd(&rowq[(size_t)(4 * g + a) * n + col], q);
+        if (use_lds) atomicAdd(&rowq[(size_t)(NK * g + a) * n + col], q);
         else atomicAdd(&redq[(size_t)(6 * (nr + g) + a) * n + col], q);
     };
     const size_t no = d.n_obs;
     // Wk of group g over the track [b, e)
-    auto group_W = [&](int b, int e, int g, double (&Wk)[4][3]) {
+    auto group_W = [&](int b, int e, int g, double (&Wk)[NK][3]) {
 #pragma unroll
-        for (int a = 0; a < 4; ++a) Wk[a][0] = Wk[a][1] = Wk[a][2] = 0.0;
+        for (int a = 0; a < NK; ++a) Wk[a][0] = Wk[a][1] = Wk[a][2] = 0.0;
         for (int k = b; k < e; ++k) {
             if (d.cam_group[d.obs_cam[k]] != g) continue;
+            if constexpr (RADIAL) {
+                double K[8], g0[6], g1[6];
+#pragma unroll
+                for (int q = 0; q < 8; ++q) K[q] = d.Jk[q * no + k];
+                radial_rows(K, g0, g1);
+#pragma unroll
+                for (int m = 0; m < 3; ++m) {
+                    const double e0 = d.Jp[m * no + k], e1 = d.Jp[(3 + m) * no + k];
+#pragma unroll
+                    for (int a = 0; a < 6; ++a) Wk[a][m] += g0[a] * e0 + g1[a] * e1;
+                }
+                continue;
+            }
             const double k0 = d.Jk[k], k1 = d.Jk[no + k], k2 = d.Jk[2 * no + k], k3 = d.Jk[3 * no + k];
 #pragma unroll
             for (int m = 0; m < 3; ++m) {
@@ -618,11 +635,11 @@ __global__ __launch_bounds__(256) void ba_schur_groups_kernel(BADev d, int use_l
             const int g = d.cam_group[d.obs_cam[kl]];
             if (!first_of_group(b, kl, g)) continue;
             const int kap = 6 * (nr + g);
-            double Wk[4][3], Yk[4][3];
+            double Wk[NK][3], Yk[NK][3];
             group_W(kl, e, g, Wk);
-            int qe[4];
+            int qe[NK];
 #pragma unroll
-            for (int a = 0; a < 4; ++a) {
+            for (int a = 0; a < NK; ++a) {
                 qe[a] = d.qexp[kap + a];
 #pragma unroll
                 for (int m = 0; m < 3; ++m) Yk[a][m] = Wk[a][0] * M[m] + Wk[a][1] * M[3 + m] + Wk[a][2] * M[6 + m];
@@ -634,7 +651,17 @@ __global__ __launch_bounds__(256) void ba_schur_groups_kernel(BADev d, int use_l
                 const int c = d.obs_cam[k];
                 const bool same = d.cam_group[c] == g;
                 double kk[4] = {0.0, 0.0, 0.0, 0.0};
-                if (same) { kk[0] = d.Jk[k]; kk[1] = d.Jk[no + k]; kk[2] = d.Jk[2 * no + k]; kk[3] = d.Jk[3 * no + k]; }
+                double g0[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, g1[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};      // RADIAL: G_j in both residual rows
+                if constexpr (RADIAL) {
+                    if (same) {
+                        double K[8];
+#pragma unroll
+                        for (int q = 0; q < 8; ++q) K[q] = d.Jk[q * no + k];
+                        radial_rows(K, g0, g1);
+                    }
+                } else if (same) {
+                    kk[0] = d.Jk[k]; kk[1] = d.Jk[no + k]; kk[2] = d.Jk[2 * no + k]; kk[3] = d.Jk[3 * no + k];
+                }
                 double Ej[6];
 #pragma unroll
                 for (int m = 0; m < 6; ++m) Ej[m] = d.Jp[m * no + k];
@@ -644,8 +671,11 @@ __global__ __launch_bounds__(256) void ba_schur_groups_kernel(BADev d, int use_l
                     const double w0 = f0 * Ej[0] + f1 * Ej[3], w1 = f0 * Ej[1] + f1 * Ej[4], w2 = f0 * Ej[2] + f1 * Ej[5];
                     const int ej = d.qexp[6 * c + c2];
 #pragma unroll
-                    for (int a = 0; a < 4; ++a) {
-                        const double v = (a < 2 ? kk[a] * f0 : kk[a] * f1) - (Yk[a][0] * w0 + Yk[a][1] * w1 + Yk[a][2] * w2);
+                    for (int a = 0; a < NK; ++a) {
+                        double gf;
+                        if constexpr (RADIAL) gf = g0[a] * f0 + g1[a] * f1;
+                        else gf = a < 2 ? kk[a] * f0 : kk[a] * f1;
+                        const double v = gf - (Yk[a][0] * w0 + Yk[a][1] * w1 + Yk[a][2] * w2);
                         add(g, a, 6 * c + c2, v, kFxBits - qe[a] - ej);
                     }
                 }
@@ -654,18 +684,18 @@ __global__ __launch_bounds__(256) void ba_schur_groups_kernel(BADev d, int use_l
             for (int k2 = b; k2 < e; ++k2) {
                 const int g2 = d.cam_group[d.obs_cam[k2]];
                 if (g2 > g || !first_of_group(b, k2, g2)) continue;
-                double W2[4][3];
+                double W2[NK][3];
                 if (g2 == g) {
 #pragma unroll
-                    for (int a = 0; a < 4; ++a) { W2[a][0] = Wk[a][0]; W2[a][1] = Wk[a][1]; W2[a][2] = Wk[a][2]; }
+                    for (int a = 0; a < NK; ++a) { W2[a][0] = Wk[a][0]; W2[a][1] = Wk[a][1]; W2[a][2] = Wk[a][2]; }
                 } else {
                     group_W(k2, e, g2, W2);
                 }
                 const int kap2 = 6 * (nr + g2);
 #pragma unroll
-                for (int a = 0; a < 4; ++a)
+                for (int a = 0; a < NK; ++a)
 #pragma unroll
-                    for (int b2 = 0; b2 < 4; ++b2) {
+                    for (int b2 = 0; b2 < NK; ++b2) {
                         if (g2 == g && b2 > a) continue;
                         const double v = -(Yk[a][0] * W2[b2][0] + Yk[a][1] * W2[b2][1] + Yk[a][2] * W2[b2][2]);
                         add(g, a, kap2 + b2, v, kFxBits - qe[a] - d.qexp[kap2 + b2]);
@@ -675,10 +705,10 @@ __global__ __launch_bounds__(256) void ba_schur_groups_kernel(BADev d, int use_l
     }
     if (use_lds) {
         __syncthreads();
-        for (int e2 = tid; e2 < 4 * G * n; e2 += 256) {
+        for (int e2 = tid; e2 < NK * G * n; e2 += 256) {
             const unsigned long long v = rowq[e2];
             const int row = e2 / n, col = e2 % n;
-            if (v != 0ull) atomicAdd(&redq[(size_t)(6 * (nr + row / 4) + row % 4) * n + col], v);
+            if (v != 0ull) atomicAdd(&redq[(size_t)(6 * (nr + row / NK) + row % NK) * n + col], v);
         }
     }
 }
@@ -863,11 +893,12 @@ int ba_schur(hipStream_t st, const BADev &d, int num_cu, double rhs_bound)
 int ba_schur_calib(hipStream_t st, const BADev &d, double rhs_bound)
 {
     if (!d.has_calib || d.n_pt <= 0 || d.n_obs <= 0) return ESFM_OK;
-    if (d.has_calib > 1) {
-        const bool rows_in_lds = ba_calib_groups_in_lds(d.n_real_cam, d.has_calib);
-        const size_t bytes = rows_in_lds ? calib_groups_lds_bytes(d.n_real_cam, d.has_calib) : 0;
+    if (ba_grouped(d)) {
+        const bool rows_in_lds = ba_calib_groups_in_lds(d.n_real_cam, d.has_calib, d.radial != 0);
+        const size_t bytes = rows_in_lds ? calib_groups_lds_bytes(d.n_real_cam, d.has_calib, d.radial != 0) : 0;
         const int exp = bound_exponent(rhs_bound);
-        hipLaunchKernelGGL(ba_schur_groups_kernel, dim3(div_up(d.n_pt, 256)), dim3(256), bytes, st, d, rows_in_lds ? 1 : 0, exp);
+        if (d.radial) hipLaunchKernelGGL(ba_schur_groups_kernel<true>, dim3(div_up(d.n_pt, 256)), dim3(256), bytes, st, d, rows_in_lds ? 1 : 0, exp);
+        else hipLaunchKernelGGL(ba_schur_groups_kernel<false>, dim3(div_up(d.n_pt, 256)), dim3(256), bytes, st, d, rows_in_lds ? 1 : 0, exp);
         LAUNCH_CHECK();
         return schur_to_double(st, d, exp);
     }

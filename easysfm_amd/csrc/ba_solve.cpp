@@ -182,6 +182,10 @@ struct Solver {
                 lo[6 * blk + i] = P->calib_center[4 * (size_t)g + i] - P->calib_tol[(size_t)g];
                 up[6 * blk + i] = P->calib_center[4 * (size_t)g + i] + P->calib_tol[(size_t)g];
             }
+            for (int i = 0; i < 2 && d.radial; ++i) {
+                lo[6 * blk + 4 + i] = P->radial_center[2 * (size_t)g + i] - P->radial_tol[(size_t)g];
+                up[6 * blk + 4 + i] = P->radial_center[2 * (size_t)g + i] + P->radial_tol[(size_t)g];
+            }
             d.constrained = 1;
         }
         if (d.n_cam) {

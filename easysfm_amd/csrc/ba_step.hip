@@ -243,9 +243,12 @@ __device__ __forceinline__ void candidate_cost(const BADev &d, int k, const doub
 // workgroups per CU spills, 25.7 / 36 us against 22.5; the f64-MFMA Schur kernel at one / three: 462 / 640 us against 294.)
 // GROUPS (several free intrinsics blocks): the intrinsics part of the step is that of the observation's camera's group, read per
 // observation where the one block's is read once per workgroup.
-template <bool WITH_COST, bool GROUPS = false>
+// RADIAL (a GROUPS form; a radial problem is bounded, so its candidate cost is a pass of its own: never WITH_COST): six values of
+// the block's step against the 8 stored scalars.
+template <bool WITH_COST, bool GROUPS = false, bool RADIAL = false>
 __global__ __launch_bounds__(kPtChunkObs, 4) void ba_backsub_chunk_kernel(BADev d, ScalBase sbase, double cauchy_a)
 {
+    static_assert(!RADIAL || (GROUPS && !WITH_COST), "the radial back-substitution is grouped and leaves the candidate cost to ba_cost");
     __shared__ double red[8];
     __shared__ double tE[kPtChunkObs][3];
     __shared__ double sps[kPtChunkObs][3];
@@ -256,7 +259,7 @@ __global__ __launch_bounds__(kPtChunkObs, 4) void ba_backsub_chunk_kernel(BADev 
     const int nobs = k1 - k0;
     const size_t n = d.n_obs;
     double mc = 0.0, ssq = 0.0, csq = 0.0, gd = 0.0, dmax = 0.0, ccost = 0.0, cbad = 0.0;
-    double yk[4] = {0.0, 0.0, 0.0, 0.0};
+    double yk[RADIAL ? 6 : 4] = {0.0, 0.0, 0.0, 0.0};
     if (d.has_calib && !GROUPS) {
 #pragma unroll
         for (int a = 0; a < 4; ++a) yk[a] = d.y_c[6 * d.n_real_cam + a];
@@ -264,7 +267,16 @@ __global__ __launch_bounds__(kPtChunkObs, 4) void ba_backsub_chunk_kernel(BADev 
     auto group_step = [&](int c) {
         if (GROUPS) {
 #pragma unroll
-            for (int a = 0; a < 4; ++a) yk[a] = d.y_c[6 * calib_block_of<true>(d, c) + a];
+            for (int a = 0; a < (RADIAL ? 6 : 4); ++a) yk[a] = d.y_c[6 * calib_block_of<true>(d, c) + a];
+        }
+    };
+    // the block's part of F_k y_c: rows 0 and 1
+    auto block_f = [&](size_t k, double &f0, double &f1) {
+        f0 = d.Jk[k] * yk[0] + d.Jk[n + k] * yk[1];
+        f1 = d.Jk[2 * n + k] * yk[2] + d.Jk[3 * n + k] * yk[3];
+        if constexpr (RADIAL) {
+            f0 += d.Jk[4 * n + k] * yk[4] + d.Jk[5 * n + k] * yk[5];
+            f1 += d.Jk[6 * n + k] * yk[4] + d.Jk[7 * n + k] * yk[5];
         }
     };
     auto point_step_pre = [&](int p, const double g[3], const double (&Mi)[6], const double (&xq)[3], const double (&scq)[3]) {   // the same from operands already in registers
@@ -328,8 +340,14 @@ __global__ __launch_bounds__(kPtChunkObs, 4) void ba_backsub_chunk_kernel(BADev 
             for (int a = 0; a < 6; ++a) { f0 += Jc[a] * yc[a]; f1 += Jc[6 + a] * yc[a]; }
             if (d.has_calib) {
                 group_step(c);
-                f0 += d.Jk[k] * yk[0] + d.Jk[n + k] * yk[1];
-                f1 += d.Jk[2 * n + k] * yk[2] + d.Jk[3 * n + k] * yk[3];
+                if constexpr (RADIAL) {
+                    double b0, b1;
+                    block_f(k, b0, b1);
+                    f0 += b0; f1 += b1;
+                } else {
+                    f0 += d.Jk[k] * yk[0] + d.Jk[n + k] * yk[1];
+                    f1 += d.Jk[2 * n + k] * yk[2] + d.Jk[3 * n + k] * yk[3];
+                }
             }
 #pragma unroll
             for (int a = 0; a < 3; ++a) tE[tid][a] = Jp[a] * f0 + Jp[3 + a] * f1;
@@ -378,8 +396,14 @@ __global__ __launch_bounds__(kPtChunkObs, 4) void ba_backsub_chunk_kernel(BADev 
             for (int a = 0; a < 6; ++a) { const double yc = d.y_c[6 * c + a]; f0 += d.Jc[a * n + k] * yc; f1 += d.Jc[(6 + a) * n + k] * yc; }
             if (d.has_calib) {
                 group_step(c);
-                f0 += d.Jk[k] * yk[0] + d.Jk[n + k] * yk[1];
-                f1 += d.Jk[2 * n + k] * yk[2] + d.Jk[3 * n + k] * yk[3];
+                if constexpr (RADIAL) {
+                    double b0, b1;
+                    block_f(k, b0, b1);
+                    f0 += b0; f1 += b1;
+                } else {
+                    f0 += d.Jk[k] * yk[0] + d.Jk[n + k] * yk[1];
+                    f1 += d.Jk[2 * n + k] * yk[2] + d.Jk[3 * n + k] * yk[3];
+                }
             }
 #pragma unroll
             for (int a = 0; a < 3; ++a) t[a] += d.Jp[a * n + k] * f0 + d.Jp[(3 + a) * n + k] * f1;
@@ -401,8 +425,14 @@ __global__ __launch_bounds__(kPtChunkObs, 4) void ba_backsub_chunk_kernel(BADev 
             for (int a = 0; a < 6; ++a) { const double sc = -d.y_c[6 * c + a]; m0 += d.Jc[a * n + k] * sc; m1 += d.Jc[(6 + a) * n + k] * sc; }
             if (d.has_calib) {
                 group_step(c);
-                m0 -= d.Jk[k] * yk[0] + d.Jk[n + k] * yk[1];
-                m1 -= d.Jk[2 * n + k] * yk[2] + d.Jk[3 * n + k] * yk[3];
+                if constexpr (RADIAL) {
+                    double b0, b1;
+                    block_f(k, b0, b1);
+                    m0 -= b0; m1 -= b1;
+                } else {
+                    m0 -= d.Jk[k] * yk[0] + d.Jk[n + k] * yk[1];
+                    m1 -= d.Jk[2 * n + k] * yk[2] + d.Jk[3 * n + k] * yk[3];
+                }
             }
 #pragma unroll
             for (int a = 0; a < 3; ++a) { m0 += d.Jp[a * n + k] * sps[0][a]; m1 += d.Jp[(3 + a) * n + k] * sps[0][a]; }
@@ -434,7 +464,8 @@ __global__ __launch_bounds__(kPtChunkObs, 4) void ba_backsub_chunk_kernel(BADev 
 // Robustified cost 1/2 sum rho(|r|^2) of (cams, pts) over this rank's observations.
 // SLOPE: also d/dt cost(Plus(x, t delta)) at this point = gradient . delta = sum rho' r.(J delta), the derivative
 // the Armijo search's cubic interpolation uses [upstream line_search.cc LineSearchFunction::Evaluate].
-template <bool SLOPE, bool GROUPS = false>
+// RADIAL (a GROUPS form): the radial model and six values of the block and of its step.
+template <bool SLOPE, bool GROUPS = false, bool RADIAL = false>
 __global__ __launch_bounds__(256) void ba_cost_kernel(BADev d, const double *__restrict__ cams, const double *__restrict__ pts,
                                                       double cauchy_a, int slot, int bad_slot, ScalBase sbase)
 {
@@ -443,8 +474,9 @@ __global__ __launch_bounds__(256) void ba_cost_kernel(BADev d, const double *__r
     for (int k = blockIdx.x * 256 + threadIdx.x; k < d.n_obs; k += gridDim.x * 256) {
         const int c = d.obs_cam[k], p = d.obs_pt[k];
         const float2 uv = d.obs_uv[k];
-        double in4[4];
-        load_intrinsics<GROUPS>(d, cams, c, in4);
+        double in4[RADIAL ? 6 : 4];
+        if constexpr (RADIAL) load_intrinsics_radial(d, cams, c, in4);
+        else load_intrinsics<GROUPS>(d, cams, c, in4);
         double cam[6], X[3];
 #pragma unroll
         for (int i = 0; i < 6; ++i) cam[i] = cams[6 * (size_t)c + i];
@@ -453,12 +485,18 @@ __global__ __launch_bounds__(256) void ba_cost_kernel(BADev d, const double *__r
         double r0, r1, m0 = 0.0, m1 = 0.0;
         if (SLOPE) {
             double Jc[12], Jp[6], xn, yn;
-            reproject_jac(cam, X, in4, uv, r0, r1, Jc, Jp, xn, yn);
+            double Jk[8];
+            if constexpr (RADIAL) reproject_jac_radial(cam, X, in4, uv, r0, r1, Jc, Jp, Jk);
+            else reproject_jac(cam, X, in4, uv, r0, r1, Jc, Jp, xn, yn);
 #pragma unroll
             for (int a = 0; a < 6; ++a) { const double dl = d.delta_c[6 * (size_t)c + a]; m0 += Jc[a] * dl; m1 += Jc[6 + a] * dl; }
 #pragma unroll
             for (int a = 0; a < 3; ++a) { const double dl = d.delta_p[3 * (size_t)p + a]; m0 += Jp[a] * dl; m1 += Jp[3 + a] * dl; }
-            if (d.has_calib) {
+            if constexpr (RADIAL) {
+                const double *dk = d.delta_c + 6 * (size_t)calib_block_of<true>(d, c);
+                m0 += Jk[0] * dk[0] + Jk[1] * dk[1] + Jk[4] * dk[4] + Jk[5] * dk[5];
+                m1 += Jk[2] * dk[2] + Jk[3] * dk[3] + Jk[6] * dk[4] + Jk[7] * dk[5];
+            } else if (d.has_calib) {
                 const double *dk = d.delta_c + 6 * (size_t)calib_block_of<GROUPS>(d, c);
                 m0 -= xn * dk[0] + dk[1];
                 m1 -= yn * dk[2] + dk[3];
@@ -466,9 +504,13 @@ __global__ __launch_bounds__(256) void ba_cost_kernel(BADev d, const double *__r
         } else {
             double pt[3];
             transform_point<false>(cam, X, pt, nullptr, nullptr);
-            const double x = pt[0] / pt[2], y = pt[1] / pt[2];
-            r0 = (double)uv.x - (x * in4[0] + in4[1]);
-            r1 = (double)uv.y - (y * in4[2] + in4[3]);
+            if constexpr (RADIAL) {
+                reproject_radial(pt, in4, uv, r0, r1);
+            } else {
+                const double x = pt[0] / pt[2], y = pt[1] / pt[2];
+                r0 = (double)uv.x - (x * in4[0] + in4[1]);
+                r1 = (double)uv.y - (y * in4[2] + in4[3]);
+            }
         }
         const double s = r0 * r0 + r1 * r1;
         if (!isfinite(s)) { bad += 1.0; continue; }
@@ -650,13 +692,14 @@ int ba_backsub(hipStream_t st, const BADev &d, bool with_cost, double cauchy_a)
         // the candidate's cost comes out of the same launch (SC_CAND_COST / SC_CAND_BAD): no ba_cost pass over the observations
         const int slots[6] = {SC_MODEL_CHANGE, SC_STEP_SQ_PT, SC_CAND_SQ_PT, SC_GDOTD, SC_CAND_COST, SC_CAND_BAD};
         if (int rc = scal_reserve<6>(st, d, slots, d.n_pchunks, sbase)) return rc;
+        if (d.radial) { set_error("BA back-substitution: a radial problem is bounded and takes the candidate cost in its own pass"); return ESFM_ERR_INVALID_ARG; }
         auto kern = d.has_calib > 1 ? &ba_backsub_chunk_kernel<true, true> : &ba_backsub_chunk_kernel<true>;
         hipLaunchKernelGGL(kern, dim3(d.n_pchunks), dim3(kPtChunkObs), 0, st, d,
                            sbase, cauchy_a);
     } else {
         const int slots[4] = {SC_MODEL_CHANGE, SC_STEP_SQ_PT, SC_CAND_SQ_PT, SC_GDOTD};
         if (int rc = scal_reserve<4>(st, d, slots, d.n_pchunks, sbase)) return rc;
-        auto kern = d.has_calib > 1 ? &ba_backsub_chunk_kernel<false, true> : &ba_backsub_chunk_kernel<false>;
+        auto kern = d.radial ? &ba_backsub_chunk_kernel<false, true, true> : d.has_calib > 1 ? &ba_backsub_chunk_kernel<false, true> : &ba_backsub_chunk_kernel<false>;
         hipLaunchKernelGGL(kern, dim3(d.n_pchunks), dim3(kPtChunkObs), 0, st, d,
                            sbase, cauchy_a);
     }
@@ -673,13 +716,13 @@ int ba_cost(hipStream_t st, const BADev &d, int num_cu, const double *cams, cons
     if (with_slope) {
         const int slots[3] = {slot, bad_slot, SC_LS_GRAD};
         if (int rc = scal_reserve<3>(st, d, slots, grid, sbase)) return rc;
-        auto kern = d.has_calib > 1 ? &ba_cost_kernel<true, true> : &ba_cost_kernel<true>;
+        auto kern = d.radial ? &ba_cost_kernel<true, true, true> : d.has_calib > 1 ? &ba_cost_kernel<true, true> : &ba_cost_kernel<true>;
         hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, st, d, cams, pts, cauchy_a, slot, bad_slot,
                            sbase);
     } else {
         const int slots[2] = {slot, bad_slot};
         if (int rc = scal_reserve<2>(st, d, slots, grid, sbase)) return rc;
-        auto kern = d.has_calib > 1 ? &ba_cost_kernel<false, true> : &ba_cost_kernel<false>;
+        auto kern = d.radial ? &ba_cost_kernel<false, true, true> : d.has_calib > 1 ? &ba_cost_kernel<false, true> : &ba_cost_kernel<false>;
         hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, st, d, cams, pts, cauchy_a, slot, bad_slot,
                            sbase);
     }

@@ -87,6 +87,10 @@ struct frame_t {  // utility.h:21-55
     Matrix4f pose_cam = Matrix4f::Identity();
     Matrix3f K_cam = Matrix3f::Identity();
     int camera_id = 0;  // multiple-camera mode: which physical camera (intrinsics model) took the frame; not in the reference's frame_t
+    // free radial distortion (BundleAdjustment's radial_tolerance; not in the reference's frame_t): k1, k2 of the frame's camera, and
+    // the pixels as detected (empty: `keypoints` are what bundle adjustment observes)
+    double radial_cam[2] = {0.0, 0.0};
+    std::vector<Point2f> keypoints_raw;
     frame_t() = default;
     frame_t(unsigned int id, const std::string &path) : frame_id(id), image_file_path(path) {}
     bool init_pixel_ids()
@@ -1239,11 +1243,16 @@ public:
     double *mutable_cameras() { return parameters_.data(); }
     double *mutable_points() { return parameters_.data() + 6 * num_cameras_; }
     double *mutable_calib() { return parameters_.data() + 6 * num_cameras_ + 3 * num_points_; }   // ba.h:45; several blocks: 4 doubles each
+    // radial solves: k1, k2 of every group, behind the 4 G pinhole values
+    double *mutable_radial() { return mutable_calib() + 4 * group_camera_ids_.size(); }
+    // pixels: the box that holds fx, cx, fy, cy in a radial solve with fix_calib_tolerance_BA == 0 (every free block has a box)
+    static constexpr double kHeldPinhole = 1e-3;
 
     bool initBA()  // ba.h:59-75
     {
         point_index_.clear(); camera_index_.clear(); points_2d_.clear(); calibs_.clear(); parameters_.clear();
         camera_group_.clear(); group_camera_ids_.clear();
+        radial_tolerance_ = 0.0;
         num_cameras_ = num_points_ = num_parameters_ = num_observations_ = 0;
         ref_process_camera_id_ = -1;
         if (verbose) std::cout << "Bundle Ajustment parameters initialization done." << std::endl;
@@ -1253,9 +1262,13 @@ public:
     // ba.cpp:12-130.  Same observation list in the same order (camera-major, point index ascending; for a
     // point the FIRST keypoint with has_match and a matching id, the `break` at :44) as the reference's
     // O(Ncam*Npts*Nkp) triple loop, derived with one hash map per frame.
+    // radial_tolerance > 0: every distinct camera_id -- ONE id included -- opens a block fx, cx, fy, cy, k1, k2 that starts from its first
+    // processed frame's K_cam and radial_cam; the observations are a frame's keypoints_raw where it has them.  0: as before.
     bool setBAProblem(std::vector<frame_t> &frames, std::vector<bool> &process_frame_id, pointcloud_sparse_t &sfm_sparse_points,
-                      double fix_calib_tolerance_BA, int reference_frame_id)
+                      double fix_calib_tolerance_BA, int reference_frame_id, double radial_tolerance = 0.0)
     {
+        const bool radial = radial_tolerance > 0.0;
+        radial_tolerance_ = radial ? radial_tolerance : 0.0;
         num_observations_ = 0; num_cameras_ = 0;
         num_points_ = int(sfm_sparse_points.unique_point_ids.size());
         for (size_t i = 0; i < frames.size(); ++i) {
@@ -1268,7 +1281,7 @@ public:
             for (int k = 0; k < num_points_; ++k) {
                 auto it = first_kp.find(sfm_sparse_points.unique_point_ids[size_t(k)]);
                 if (it == first_kp.end()) continue;
-                points_2d_.push_back(fr.keypoints[size_t(it->second)].pt);
+                points_2d_.push_back(radial && !fr.keypoints_raw.empty() ? fr.keypoints_raw[size_t(it->second)] : fr.keypoints[size_t(it->second)].pt);
                 point_index_.push_back(k);
                 camera_index_.push_back(num_cameras_);
                 ++num_observations_;
@@ -1278,20 +1291,21 @@ public:
         }
         // multiple-camera mode: free intrinsics over processed frames of more than one camera_id open one block per distinct id, in
         // order of first appearance; one distinct id leaves the shared block of calibs_[0] in charge
-        if (fix_calib_tolerance_BA != 0) {
+        if (fix_calib_tolerance_BA != 0 || radial) {
             std::vector<int> ids, order;
             for (size_t i = 0; i < frames.size(); ++i) {
                 if (process_frame_id[i]) continue;
                 ids.push_back(frames[i].camera_id);
                 if (std::find(order.begin(), order.end(), frames[i].camera_id) == order.end()) order.push_back(frames[i].camera_id);
             }
-            if (order.size() > 1) {
+            if (order.size() > 1 || (radial && !order.empty())) {
                 group_camera_ids_ = order;
                 for (int id : ids) camera_group_.push_back(int(std::find(order.begin(), order.end(), id) - order.begin()));
             }
         }
         const int n_blocks = group_camera_ids_.empty() ? 1 : int(group_camera_ids_.size());
-        num_parameters_ = 6 * num_cameras_ + 3 * num_points_ + (fix_calib_tolerance_BA != 0 ? 4 * n_blocks : 0);
+        const bool radial_blocks = radial && !group_camera_ids_.empty();
+        num_parameters_ = 6 * num_cameras_ + 3 * num_points_ + (fix_calib_tolerance_BA != 0 || radial_blocks ? 4 * n_blocks : 0) + (radial_blocks ? 2 * n_blocks : 0);
         parameters_.assign(size_t(num_parameters_), 0.0);
         int k = 0;
         for (size_t i = 0; i < frames.size(); ++i) {
@@ -1311,12 +1325,15 @@ public:
             parameters_[size_t(6 * num_cameras_ + 3 * i + 1)] = p.y;
             parameters_[size_t(6 * num_cameras_ + 3 * i + 2)] = p.z;
         }
-        if (fix_calib_tolerance_BA != 0 && !group_camera_ids_.empty()) {
-            // the reference's calibs_[0] rule, per group: a group starts from the K_cam of its first processed frame
+        if ((fix_calib_tolerance_BA != 0 || radial_blocks) && !group_camera_ids_.empty()) {
+            // the reference's calibs_[0] rule, per group: a group starts from the K_cam (and radial_cam) of its first processed frame
+            std::vector<const frame_t *> processed;
+            for (size_t i = 0; i < frames.size(); ++i) if (!process_frame_id[i]) processed.push_back(&frames[i]);
             for (int g = 0; g < n_blocks; ++g) {
                 const size_t first = size_t(std::find(camera_group_.begin(), camera_group_.end(), g) - camera_group_.begin());
                 double *k4 = mutable_calib() + 4 * g;
                 k4[0] = calibs_[first](0, 0); k4[1] = calibs_[first](0, 2); k4[2] = calibs_[first](1, 1); k4[3] = calibs_[first](1, 2);
+                if (radial_blocks) { mutable_radial()[2 * g] = processed[first]->radial_cam[0]; mutable_radial()[2 * g + 1] = processed[first]->radial_cam[1]; }
             }
         } else if (fix_calib_tolerance_BA != 0 && !calibs_.empty()) {
             parameters_[size_t(num_parameters_ - 4)] = calibs_[0](0, 0); parameters_[size_t(num_parameters_ - 3)] = calibs_[0](0, 2);
@@ -1331,8 +1348,14 @@ public:
 
     // ba.cpp:132-212: ceres::Solve -> esfm_ba_solve_ex.  Fixed intrinsics (:142-164) or the shared free block bounded to
     // +- tolerance (:167-196); a reference frame named in setBAProblem is bounded to +-1e-10 (:134, :155-162).
-    bool solveBA(double fix_calib_tolerance_BA)
+    // radial_tolerance > 0: the box half width of k1, k2 of every group; positive exactly when setBAProblem's was (the layout of
+    // parameters_ is the one set up there)
+    bool solveBA(double fix_calib_tolerance_BA, double radial_tolerance = 0.0)
     {
+        if ((radial_tolerance > 0.0) != (radial_tolerance_ > 0.0)) {
+            std::cerr << "solveBA: radial_tolerance must be positive exactly when setBAProblem's was" << std::endl;
+            return false;
+        }
         const double fixed_threshold = 1e-10;  // :134
         std::vector<float> K4(size_t(4 * num_cameras_));
         for (int c = 0; c < num_cameras_; ++c) {
@@ -1340,6 +1363,16 @@ public:
             K4[size_t(4 * c + 2)] = calibs_[size_t(c)](1, 1); K4[size_t(4 * c + 3)] = calibs_[size_t(c)](1, 2);
         }
         options_.verbose = verbose ? 1 : 0;  // minimizer_progress_to_stdout (:204)
+        if (radial_tolerance > 0 && !group_camera_ids_.empty()) {   // one block fx, cx, fy, cy, k1, k2 per camera group
+            const std::vector<double> tol(group_camera_ids_.size(), fix_calib_tolerance_BA != 0 ? fix_calib_tolerance_BA : kHeldPinhole);
+            const std::vector<double> rtol(group_camera_ids_.size(), radial_tolerance);
+            int rcr = esfm_ba_solve_radial_groups(default_ctx(), num_cameras_, num_points_, num_observations_, camera_index_.data(), point_index_.data(),
+                                                  reinterpret_cast<const float *>(points_2d_.data()), mutable_cameras(), mutable_points(),
+                                                  int(group_camera_ids_.size()), camera_group_.data(), mutable_calib(), tol.data(), mutable_radial(),
+                                                  rtol.data(), ref_process_camera_id_, fixed_threshold, &options_, nullptr, nullptr, &summary_);
+            if (rcr != ESFM_OK) { std::cerr << esfm_last_error() << std::endl; return false; }
+            return true;
+        }
         if (fix_calib_tolerance_BA != 0 && !group_camera_ids_.empty()) {   // one free block per camera group, each within +- tolerance
             const std::vector<double> tol(group_camera_ids_.size(), fix_calib_tolerance_BA);
             int rcg = esfm_ba_solve_groups(default_ctx(), num_cameras_, num_points_, num_observations_, camera_index_.data(), point_index_.data(),
@@ -1359,12 +1392,13 @@ public:
 
     // ba.cpp:214-288
     bool doSFMBA(std::vector<frame_t> &frames, std::vector<bool> &process_frame_id, pointcloud_sparse_t &sfm_sparse_points,
-                 double fix_calib_tolerance_BA = 0.0, int reference_frame_id = -1)
+                 double fix_calib_tolerance_BA = 0.0, int reference_frame_id = -1, double radial_tolerance = 0.0)
     {
         auto tic = std::chrono::steady_clock::now();
         initBA();
-        setBAProblem(frames, process_frame_id, sfm_sparse_points, fix_calib_tolerance_BA, reference_frame_id);
-        const bool ok = solveBA(fix_calib_tolerance_BA);
+        setBAProblem(frames, process_frame_id, sfm_sparse_points, fix_calib_tolerance_BA, reference_frame_id, radial_tolerance);
+        const bool ok = solveBA(fix_calib_tolerance_BA, radial_tolerance);
+        const bool radial_blocks = radial_tolerance_ > 0 && !group_camera_ids_.empty();
         int k = 0;
         for (size_t i = 0; i < frames.size(); ++i) {
             if (process_frame_id[i]) continue;
@@ -1377,7 +1411,11 @@ public:
                 frames[i].pose_cam(r, 3) = float(parameters_[size_t(6 * k + 3 + r)]);
             }
             ++k;
-            if (fix_calib_tolerance_BA != 0 && !group_camera_ids_.empty()) {   // each group's result goes to that group's frames only
+            if (radial_blocks) {
+                frames[i].radial_cam[0] = mutable_radial()[2 * camera_group_[size_t(k - 1)]];
+                frames[i].radial_cam[1] = mutable_radial()[2 * camera_group_[size_t(k - 1)] + 1];
+            }
+            if ((fix_calib_tolerance_BA != 0 || radial_blocks) && !group_camera_ids_.empty()) {   // each group's result goes to that group's frames only
                 const double *k4 = mutable_calib() + 4 * camera_group_[size_t(k - 1)];
                 frames[i].K_cam(0, 0) = float(k4[0]); frames[i].K_cam(0, 2) = float(k4[1]);
                 frames[i].K_cam(1, 1) = float(k4[2]); frames[i].K_cam(1, 2) = float(k4[3]);
@@ -1425,6 +1463,7 @@ public:
     // multiple-camera mode: group of every processed camera and the camera_id of every group (first appearance first); both empty
     // unless the intrinsics are free and the processed frames carry more than one camera_id
     std::vector<int> camera_group_, group_camera_ids_;
+    double radial_tolerance_ = 0.0;   // > 0: the problem set up last frees k1, k2 per camera_id (one id included)
 };
 
 // ---- dense reconstruction (esfm.h "Dense reconstruction"; the reference README's TODO "add multi-view stereo dense

@@ -123,6 +123,15 @@ int main(int argc, char **argv)
             filter_arg.erase(filter_arg.size() - token.size());
         }
     }
+    // +radial (free radial distortion k1, k2 per camera in every bundle adjustment; at the end of the filter, in front of +cameras):
+    // bin/sfm's mode, not provided by this driver -- refused, not ignored
+    {
+        const std::string token = "+radial";
+        if (filter_arg.size() > token.size() && filter_arg.compare(filter_arg.size() - token.size(), token.size(), token) == 0) {
+            fprintf(stderr, "sfm_native: +radial (free radial distortion) is not provided by this driver; use bin/sfm\n");
+            return 2;
+        }
+    }
     // +retrieval or +retrievalK (K decimal, 1 .. 999) at the very end, behind everything else (ratio+retrieval, ratio+guided+tracks+retrieval4):
     // only the pairs that image retrieval selects are matched (esfm.h "Image retrieval", default options, K = top_k; one "Pair selection:" line)
     bool retrieval = false;

@@ -26,7 +26,8 @@ from .mvs import MergeOptions, default_mvs_options, dense_reconstruction, frame_
 from .retrieval import RetrievalOptions, select_pairs, working_dim
 from .tracks import TrackOptions, refine_tracks
 from .types import DMatch, Frame, SparsePointCloud
-from .cameras import check_one_image_size, pair_stage_view
+from .cameras import check_one_image_size, distortion_line, pair_stage_view, refresh_pinhole_keypoints
+from .features import undistort
 
 
 @dataclass
@@ -208,7 +209,7 @@ def run_sfm(frames: List[Frame], output_file: Optional[str] = None, use_feature:
             dense_mesh_clean: Optional[MeshCleanOptions] = None, dense_mesh_simplify: Optional[float] = None,
             dense_mesh_texture: Optional[int] = None, dense_mesh_texture_level: bool = False, dense_mesh_render_dir: Optional[str] = None,
             init_max_h_inlier_ratio: Optional[float] = None, track_refine: Optional[TrackOptions] = None,
-            pair_selection: Optional[RetrievalOptions] = None):
+            pair_selection: Optional[RetrievalOptions] = None, ba_radial_tolerance: Optional[float] = None):
     """sfm.cpp:128-339.  Returns (sparse cloud before the final filter, filtered cloud, img_match_graph).
     dense_output_file: after the final BA and the sparse .ply, run dense_reconstruct on the registered frames and the cloud
     before the filter (it carries the track ids) and write the dense cloud there (esfm.h "Dense reconstruction").
@@ -244,7 +245,16 @@ def run_sfm(frames: List[Frame], output_file: Optional[str] = None, use_feature:
     added again by a later doTriangulation and is then judged again.  None: every output as before, to the bit.
     pair_selection: when given, retrieval.select_pairs chooses the pairs to match (esfm.h "Image retrieval": the top_k most similar
     images of every image by int8 VLAD, plus the `window` preceding ones) on the descriptor rows the matcher has uploaded, and only
-    those pairs are matched and verified; prints one "Pair selection:" line.  None: every output as before, to the bit."""
+    those pairs are matched and verified; prints one "Pair selection:" line.  None: every output as before, to the bit.
+    ba_radial_tolerance: when given (> 0), every bundle adjustment also frees k1, k2 of every camera_id, boxed to their start +- this
+    value (esfm.h "Free radial distortion"; with fix_calib_tolerance_BA == 0 a narrow box holds fx, cx, fy, cy).  Frames keep the
+    pixels as detected in keypoints_raw, which is what bundle adjustment observes; keypoints is the pinhole-equivalent pixel of the
+    frame's current (K_cam, radial_cam) (cameras.pinhole_keypoints), refreshed for every frame after every bundle adjustment, and
+    it is what the pair stage, PnP, triangulation, guided matching and track refinement read.  With a dense output every registered
+    frame's image is undistorted with its camera's final k1, k2 first.  Prints one "Distortion:" line.  None: every output as
+    before, to the bit."""
+    if ba_radial_tolerance is not None and not ba_radial_tolerance > 0.0:
+        raise ValueError("ba_radial_tolerance must be positive")
     ctx = ctx or default_context()
     fm, ee = FeatureMatching(ctx), MotionEstimator(ctx)
     for f in frames:
@@ -254,12 +264,23 @@ def run_sfm(frames: List[Frame], output_file: Optional[str] = None, use_feature:
     # Multiple-camera mode (cameras.py): frames that do not all share one K_cam go through the pair stage with their keypoints remapped
     # into the canonical camera's pixels and its K -- ransac_reproj_distance is then in canonical pixels; everything behind the pair
     # stage sees the original pixels and each frame's own K_cam.  One K_cam: nothing is touched.
+    if ba_radial_tolerance is not None:
+        refresh_pinhole_keypoints(frames)               # keypoints_raw <- the detected pixels; keypoints: those of the start (K_cam, radial_cam)
     with pair_stage_view(frames):
         graph = _pair_stage(frames, use_feature, ransac_reproj_distance, ctx, match_filter, init_max_h_inlier_ratio, pair_selection)
     return _run_sfm_after_pairs(frames, graph, fm, ee, output_file, ransac_reproj_distance, use_track_frames_as_init, fix_calib_tolerance_BA,
                                 frequency_BA, ctx, verbose, dense_output_file, dense_merged_output_file, dense_mesh_output_file, dense_mesh_clean,
                                 dense_mesh_simplify, dense_mesh_texture, dense_mesh_texture_level, dense_mesh_render_dir, init_max_h_inlier_ratio,
-                                track_refine)
+                                track_refine, ba_radial_tolerance)
+
+
+def undistort_registered_images(frames, todo, ctx: Optional[Context] = None) -> None:
+    """The dense chain models a pinhole: every registered frame's image goes once more through the existing undistortion (esfm_undistort:
+    k1, k2, p1, p2) with its own K_cam and its camera's final k1, k2 (p1 = p2 = 0).  Frames without an image, or with k1 = k2 = 0, and
+    frames still to be registered are left alone."""
+    for f, t in zip(frames, todo):
+        if not t and f.rgb_image is not None and any(f.radial_cam):
+            f.rgb_image = undistort(f.rgb_image, f.K_cam, np.array([f.radial_cam[0], f.radial_cam[1], 0.0, 0.0], np.float64), ctx)
 
 
 def _pair_stage(frames, use_feature, ransac_reproj_distance, ctx, match_filter, init_max_h_inlier_ratio, pair_selection):
@@ -280,7 +301,23 @@ def _pair_stage(frames, use_feature, ransac_reproj_distance, ctx, match_filter, 
 
 def _run_sfm_after_pairs(frames, graph, fm, ee, output_file, ransac_reproj_distance, use_track_frames_as_init, fix_calib_tolerance_BA, frequency_BA,
                          ctx, verbose, dense_output_file, dense_merged_output_file, dense_mesh_output_file, dense_mesh_clean, dense_mesh_simplify,
-                         dense_mesh_texture, dense_mesh_texture_level, dense_mesh_render_dir, init_max_h_inlier_ratio, track_refine):
+                         dense_mesh_texture, dense_mesh_texture_level, dense_mesh_render_dir, init_max_h_inlier_ratio, track_refine,
+                         ba_radial_tolerance=None):
+    radial_tol = float(ba_radial_tolerance) if ba_radial_tolerance is not None else 0.0
+
+    def adjust(tolerance):
+        """doSFMBA; in a radial run every frame of a camera then takes that camera's k1, k2 and its keypoints are refreshed"""
+        ba.doSFMBA(frames, todo, cloud, tolerance, -1, radial_tol)
+        if radial_tol > 0:
+            # doSFMBA wrote each group's K_cam and radial_cam to its registered frames; the camera's frames still to be registered take
+            # BOTH too, so that their refreshed keypoints are the inverse of one model (and PnP sees the K those pixels belong to)
+            by_id = {int(f.camera_id): (f.K_cam, f.radial_cam) for f, t in zip(frames, todo) if not t}
+            for f, t in zip(frames, todo):
+                if t and int(f.camera_id) in by_id:
+                    K, k = by_id[int(f.camera_id)]
+                    f.K_cam, f.radial_cam = np.array(K, np.float32, copy=True), k
+            refresh_pinhole_keypoints(frames)
+
     track, n_unique = propagate_track_ids(frames, graph)
     if verbose:
         for i in range(len(frames)):
@@ -310,7 +347,7 @@ def _run_sfm_after_pairs(frames, graph, fm, ee, output_file, ransac_reproj_dista
     ba = BundleAdjustment(ctx)
     if track_refine is not None:
         refine_tracks(frames, todo, cloud, track_refine, ctx)
-    ba.doSFMBA(frames, todo, cloud, fix_calib_tolerance_BA)
+    adjust(fix_calib_tolerance_BA)
     remaining = len(frames) - 2
     reproj = ransac_reproj_distance
     while remaining > 0:
@@ -333,18 +370,22 @@ def _run_sfm_after_pairs(frames, graph, fm, ee, output_file, ransac_reproj_dista
             ba.initBA()
             if track_refine is not None:
                 refine_tracks(frames, todo, cloud, track_refine, ctx)
-            ba.doSFMBA(frames, todo, cloud, fix_calib_tolerance_BA)
+            adjust(fix_calib_tolerance_BA)
             reproj = ransac_reproj_distance
         if verbose:
             print(f"Progress: [ {len(frames) - remaining} / {len(frames)} ]")
     if track_refine is not None:
         refine_tracks(frames, todo, cloud, track_refine, ctx)
-    ba.doSFMBA(frames, todo, cloud)
+    adjust(0.0)
+    if radial_tol > 0:
+        print(distortion_line([f for f, t in zip(frames, todo) if not t]))
     if track_refine is not None:
         refine_tracks(frames, todo, cloud, track_refine, ctx, evaluate_only=True)
     out = CProceesing(ctx).SORFilter(cloud)
     if output_file:
         write_ply(output_file, out)
+    if (dense_output_file or dense_merged_output_file or dense_mesh_output_file) and radial_tol > 0:
+        undistort_registered_images(frames, todo, ctx)
     if dense_output_file or dense_merged_output_file or dense_mesh_output_file:
         dense, nb, rng, depth, _ = dense_reconstruction(frames, todo, cloud, ctx=ctx)
         if dense_output_file:

@@ -5,7 +5,7 @@ Only the fields the hot path touches are kept; OpenCV/PCL/Eigen value types beco
 from __future__ import annotations
 
 from dataclasses import dataclass, field
-from typing import List, NamedTuple, Optional
+from typing import List, NamedTuple, Optional, Tuple
 
 import numpy as np
 
@@ -31,6 +31,10 @@ class Frame:
     K_cam: np.ndarray = field(default_factory=lambda: np.eye(3, dtype=np.float32))        # Eigen::Matrix3f
     rgb_image: Optional[np.ndarray] = None          # cv::Mat CV_8UC3, BGR as cv::imread delivers it (utility.h:27)
     camera_id: int = 0      # multiple-camera mode: which physical camera (intrinsics model) took the frame; not in the reference's frame_t
+    # free radial distortion (run_sfm's ba_radial_tolerance; not in the reference's frame_t): k1, k2 of the frame's camera, and the
+    # pixels as detected -- `keypoints` is then the pinhole-equivalent pixel of the current (K_cam, radial_cam), cameras.pinhole_keypoints
+    radial_cam: Tuple[float, float] = (0.0, 0.0)
+    keypoints_raw: Optional[np.ndarray] = None
 
     def init_pixel_ids(self) -> None:
         """frame_t::init_pixel_ids (utility.h:47-54)."""

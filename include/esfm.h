@@ -534,7 +534,8 @@ int esfm_ba_solve_ex(esfm_ctx *ctx, int n_cam, int n_pt, int n_obs,
  * Multi-GPU: every rank passes the same group arrays; a rank need not hold observations of every group; the
  * exchanged sizes are the documented ones with n_cam + n_groups camera-side blocks.
  * Not provided: a mix of fixed and free cameras in one problem (give the cameras to hold a group with a narrow box),
- * and intrinsics models other than fx, cx, fy, cy.
+ * tangential distortion terms, k3, fisheye models, and the radial mode in bin/sfm_native's driver.  (Free radial distortion k1, k2
+ * per group: esfm_ba_problem_create_radial_groups, below.)
  * In front of the solver the two-view entry points (esfm_find_essential_*, esfm_recover_pose_*, esfm_find_homography_*,
  * esfm_match_guided_*) keep taking ONE K per pair: the host mirrors hand them the keypoints of both images remapped into the
  * pixels of one canonical camera (camera 0), so their pixel thresholds are in canonical pixels in a multi-camera run; the dense
@@ -558,6 +559,39 @@ int esfm_ba_solve_groups(esfm_ctx *ctx, int n_cam, int n_pt, int n_obs,
                          int ref_cam, double ref_threshold,
                          const esfm_ba_options *options, esfm_allreduce_fn allreduce, void *allreduce_user,
                          esfm_ba_summary *summary);
+
+/* Free radial distortion per camera group: block g is fx, cx, fy, cy, k1, k2.  The model is OpenCV's with p1 = p2 = 0, the one
+ * esfm_undistort inverts: with p = R(a) X + t, x = p0/p2, y = p1/p2, r2 = x^2 + y^2 and L = 1 + k1 r2 + k2 r2^2,
+ *   r0 = u - (fx x L + cx),   r1 = v - (fy y L + cy).
+ * radial2 holds k1, k2 of every group (2 n_groups doubles); they are boxed to their start +- radial_tolerance[g] (each > 0), the four
+ * pinhole values to calib4 +- calib_tolerance[g] as above, so a radial problem is always a bounded problem (the constrained loop
+ * with the Armijo search).  A radial problem takes the grouped kernels with any group count, one included; a group nobody observes
+ * keeps its six values bit for bit; two solves of the same problem agree in every bit.  Every non-radial problem gives the bits it
+ * gave before these entry points existed.
+ * Errors, before anything is written, as for esfm_ba_problem_create_calib_groups, and: a radial tolerance <= 0
+ * (ESFM_ERR_INVALID_ARG), a non-finite coefficient or radial tolerance (ESFM_ERR_NUMERIC).
+ * esfm_ba_problem_get / set_calib_groups serve a radial problem too (the four pinhole values; k1, k2 stay as they are); the radial
+ * accessors on a problem created without radial distortion return ESFM_ERR_INVALID_ARG. */
+int esfm_ba_problem_create_radial_groups(esfm_ctx *ctx, int n_cam, int n_pt, int n_obs,
+                                         const int32_t *cam_idx, const int32_t *pt_idx, const float *obs_uv,
+                                         int n_groups, const int32_t *group_of_cam /*n_cam*/, const double *calib4 /*4 n_groups*/,
+                                         const double *calib_tolerance /*n_groups, each > 0*/,
+                                         const double *radial2 /*2 n_groups*/, const double *radial_tolerance /*n_groups, each > 0*/,
+                                         const double *cams, const double *pts, esfm_ba_problem **out);
+/* new start values and box centres / half widths of k1, k2 of every block */
+int esfm_ba_problem_set_radial_groups(esfm_ba_problem *p, const double *radial2, const double *radial_tolerance);
+int esfm_ba_problem_get_radial_groups(esfm_ba_problem *p, double *radial2 /*2 n_groups*/);
+/* 0: no free radial distortion, else the number of blocks */
+int esfm_ba_problem_radial_groups(const esfm_ba_problem *p);
+/* One-shot, as esfm_ba_solve_groups, plus radial2 (in/out) and radial_tolerance */
+int esfm_ba_solve_radial_groups(esfm_ctx *ctx, int n_cam, int n_pt, int n_obs,
+                                const int32_t *cam_idx, const int32_t *pt_idx, const float *obs_uv,
+                                double *cams, double *pts,
+                                int n_groups, const int32_t *group_of_cam, double *calib4, const double *calib_tolerance,
+                                double *radial2, const double *radial_tolerance,
+                                int ref_cam, double ref_threshold,
+                                const esfm_ba_options *options, esfm_allreduce_fn allreduce, void *allreduce_user,
+                                esfm_ba_summary *summary);
 
 /* The step-length rule of that line search alone (host arithmetic, no GPU): next trial step after the trial
  * (x_cur, f_cur, g_cur) failed the sufficient-decrease test, given the start point (0, f0, g0) and optionally
