@@ -18,6 +18,8 @@ from .cloud import (CProceesing, read_ply_mesh, read_ply_normals, read_ply_textu
 from .motion import (MotionEstimator, find_essential_mat, find_essential_pairs, find_homography, find_homography_pairs, five_point_models,
                      homography_models, homography_refit_host, homography_sample_stream, pixel2cam, ransac_sample_stream, recover_pose,  # noqa: F401
                      recover_pose_pairs, solve_pnp_ransac, triangulate_pairs, triangulate_points)
+from .motion import (find_fundamental, find_fundamental_pairs, focal_candidates, focal_cost, focal_from_fundamentals,  # noqa: F401
+                     fundamental_models, fundamental_refit_host, fundamental_sample_stream)
 
 from .features import (detectFeaturesORB, detectFeaturesSIFT, detectFeaturesSURF, import_distort, orb_detect_and_compute,  # noqa: F401
                        sift_detect_and_compute, surf_detect_and_compute, undistort)
@@ -34,7 +36,7 @@ from .render import MeshRenderOptions, default_mesh_render_options, mesh_render,
 from .tracks import TrackOptions, TrackResult, refine_tracks, track_evaluate, track_observations, track_triangulate  # noqa: F401
 from .retrieval import (RetrievalOptions, retrieval_pair_list, retrieval_rank, retrieval_train, retrieval_vlad,  # noqa: F401
                         select_pairs)
-from .pipeline import MATCH_FILTERS, FramePair, match_and_verify_all_pairs, propagate_track_ids, run_sfm  # noqa: F401
+from .pipeline import MATCH_FILTERS, AutoFocalOptions, FramePair, match_and_verify_all_pairs, propagate_track_ids, run_sfm  # noqa: F401
 
 __version__ = "0.1.0"
 from .cameras import (canonical_camera, cameras_line, check_one_image_size, pair_stage_view, parse_camera_distort, parse_camera_file,  # noqa: F401

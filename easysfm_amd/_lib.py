@@ -52,6 +52,8 @@ EXPORTED_SYMBOLS = [
     "esfm_find_essential_mat", "esfm_find_essential_pairs", "esfm_recover_pose", "esfm_recover_pose_pairs", "esfm_ransac_sample_stream", "esfm_five_point_models", "esfm_five_point_models_host",
     "esfm_find_homography", "esfm_find_homography_pairs", "esfm_homography_models", "esfm_homography_models_host", "esfm_homography_refit_host",
     "esfm_homography_sample_stream",
+    "esfm_find_fundamental", "esfm_find_fundamental_pairs", "esfm_fundamental_models", "esfm_fundamental_models_host", "esfm_fundamental_refit_host",
+    "esfm_fundamental_sample_stream", "esfm_focal_cost", "esfm_focal_cost_host",
     "esfm_solve_pnp_ransac", "esfm_surf_detect_and_compute", "esfm_orb_detect_and_compute", "esfm_sift_detect_and_compute", "esfm_undistort",
     "esfm_mvs_options_default", "esfm_mvs_plan", "esfm_mvs_depth_maps", "esfm_mvs_fuse",
     "esfm_mvs_normal_options_default", "esfm_mvs_normals", "esfm_mvs_fuse_ex", "esfm_cloud_voxel_merge",
@@ -286,6 +288,14 @@ def lib() -> C.CDLL:
     L.esfm_homography_models_host.argtypes = [vp, vp, C.c_int, vp, vp]
     L.esfm_homography_refit_host.argtypes = [vp, vp, C.c_int, vp, vp]
     L.esfm_homography_sample_stream.argtypes = [vp, vp, C.c_int, C.c_int, vp, i64p]
+    L.esfm_find_fundamental.argtypes = [vp, vp, vp, C.c_int, C.c_double, C.c_double, vp, vp, i32p]
+    L.esfm_find_fundamental_pairs.argtypes = [vp, C.c_int, vp, vp, vp, C.c_double, C.c_double, vp, vp, vp, vp, vp]
+    L.esfm_fundamental_models.argtypes = [vp, vp, vp, C.c_int, vp, vp]
+    L.esfm_fundamental_models_host.argtypes = [vp, vp, C.c_int, vp, vp]
+    L.esfm_fundamental_refit_host.argtypes = [vp, vp, C.c_int, vp, vp]
+    L.esfm_fundamental_sample_stream.argtypes = [C.c_int, C.c_int, vp]
+    L.esfm_focal_cost.argtypes = [vp, C.c_int, vp, vp, C.c_double, C.c_double, C.c_int, vp, vp]
+    L.esfm_focal_cost_host.argtypes = [C.c_int, vp, vp, C.c_double, C.c_double, C.c_int, vp, vp]
     L.esfm_surf_detect_and_compute.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, vp, vp, i32p]
     L.esfm_orb_detect_and_compute.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, i32p]
     L.esfm_sift_detect_and_compute.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, i32p]

@@ -16,8 +16,10 @@ namespace ransac {
 
 constexpr int kFivePoints = 5;           // the 5-point essential kernel and solvePnPRansac's EPnP kernel draw 5
 constexpr int kFourPoints = 4;           // the homography model (esfm.h "Homography RANSAC") draws 4
+constexpr int kSevenPoints = 7;          // the fundamental matrix (esfm.h "Fundamental-matrix RANSAC") draws 7
 constexpr int kEssentialMaxIters = 1000; // RANSACPointSetRegistrator default (findEssentialMat does not override it)
 constexpr int kHomogMaxIters = 2000;     // cv::findHomography's maxIters default
+constexpr int kFundamentalMaxIters = 1000; // the registrator's default, as for the essential matrix
 constexpr int kSubsetAttempts = 1000;    // getSubset's maxAttempts
 
 struct CvRng {                        // cv::RNG((uint64)-1)

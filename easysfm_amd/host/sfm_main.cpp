@@ -132,6 +132,12 @@ int main(int argc, char **argv)
             return 2;
         }
     }
+    // calib_K_file auto (the focal length estimated from the pairs' fundamental matrices, esfm.h "Fundamental-matrix RANSAC"): bin/sfm's
+    // mode, not provided by this driver -- refused, not read as a file name
+    if (argc >= 4 && std::string(argv[3]) == "auto") {
+        fprintf(stderr, "sfm_native: calib_K_file auto (focal length from the image pairs) is not provided by this driver; use bin/sfm\n");
+        return 2;
+    }
     // +retrieval or +retrievalK (K decimal, 1 .. 999) at the very end, behind everything else (ratio+retrieval, ratio+guided+tracks+retrieval4):
     // only the pairs that image retrieval selects are matched (esfm.h "Image retrieval", default options, K = top_k; one "Pair selection:" line)
     bool retrieval = false;

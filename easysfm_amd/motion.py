@@ -243,6 +243,127 @@ def homography_sample_stream(pts1, pts2, n_samples: int):
     return idx[:n_samples], redraws.value
 
 
+def _point_pair(pts1, pts2):
+    a = np.ascontiguousarray(pts1, np.float32).reshape(-1, 2); b = np.ascontiguousarray(pts2, np.float32).reshape(-1, 2)
+    if a.shape != b.shape:
+        raise ValueError("point sets differ in size")
+    return a, b
+
+
+def find_fundamental(pts1, pts2, threshold: float = 3.0, confidence: float = 0.99, ctx: Optional[Context] = None):
+    """esfm_find_fundamental: 7-point RANSAC after cv::findFundamentalMat(pts1, pts2, FM_RANSAC, threshold, confidence) by the rule list of
+    esfm.h "Fundamental-matrix RANSAC" -> (F [3,3] float64 of unit Frobenius norm with x2' F x1 = 0, mask [n] bool, iterations).
+    Raises EsfmError for n < 7 (ESFM_ERR_UNSUPPORTED) and when there is no model (ESFM_ERR_NUMERIC)."""
+    ctx = ctx or default_context()
+    a, b = _point_pair(pts1, pts2)
+    n = a.shape[0]
+    F = np.zeros(9, np.float64); mask = np.zeros(max(n, 1), np.uint8); it = C.c_int32(0)
+    check(lib().esfm_find_fundamental(ctx.handle, C.c_void_p(a.ctypes.data), C.c_void_p(b.ctypes.data), n, float(threshold), float(confidence),
+                                      C.c_void_p(F.ctypes.data), C.c_void_p(mask.ctypes.data), C.byref(it)))
+    return F.reshape(3, 3), mask[:n].astype(bool), it.value
+
+
+def find_fundamental_pairs(point_offset, pts1, pts2, threshold: float = 3.0, confidence: float = 0.99, ctx: Optional[Context] = None):
+    """esfm_find_fundamental_pairs: every pair's fundamental-matrix RANSAC in shared launches -> (F [p,3,3], mask [n_total] bool,
+    status [p] bool, iterations [p], n_inliers [p] under the returned F)."""
+    ctx = ctx or default_context()
+    off = np.ascontiguousarray(point_offset, np.int32)
+    n_pairs = len(off) - 1
+    a, b = _point_pair(pts1, pts2)
+    n = a.shape[0]
+    if n_pairs > 0 and int(off[-1]) != n:
+        raise ValueError("point_offset does not end at the number of points")
+    a = a if n else np.zeros((1, 2), np.float32); b = b if n else np.zeros((1, 2), np.float32)
+    F = np.zeros((max(n_pairs, 1), 9), np.float64); mask = np.zeros(max(n, 1), np.uint8)
+    status = np.zeros(max(n_pairs, 1), np.int32); iters = np.zeros(max(n_pairs, 1), np.int32); ninl = np.zeros(max(n_pairs, 1), np.int32)
+    check(lib().esfm_find_fundamental_pairs(ctx.handle, n_pairs, C.c_void_p(off.ctypes.data), C.c_void_p(a.ctypes.data), C.c_void_p(b.ctypes.data),
+                                            float(threshold), float(confidence), C.c_void_p(F.ctypes.data), C.c_void_p(mask.ctypes.data),
+                                            C.c_void_p(status.ctypes.data), C.c_void_p(iters.ctypes.data), C.c_void_p(ninl.ctypes.data)))
+    return F[:n_pairs].reshape(n_pairs, 3, 3), mask[:n].astype(bool), status[:n_pairs].astype(bool), iters[:n_pairs], ninl[:n_pairs]
+
+
+def fundamental_models(q1, q2, ctx: Optional[Context] = None, host: bool = False):
+    """esfm_fundamental_models / esfm_fundamental_models_host: the 7-point solve alone on [n, 7, 2] pixel correspondences ->
+    (F [n, 3, 3, 3], the models in root order and zeros behind them, n_models [n]).  host=True runs the host build (no GPU)."""
+    a = np.ascontiguousarray(q1, np.float64).reshape(-1, 7, 2); b = np.ascontiguousarray(q2, np.float64).reshape(-1, 7, 2)
+    if a.shape != b.shape:
+        raise ValueError("sample sets differ in size")
+    n = len(a)
+    Fs = np.zeros((max(n, 1), 27)); nm = np.zeros(max(n, 1), np.int32)
+    if host:
+        check(lib().esfm_fundamental_models_host(C.c_void_p(a.ctypes.data), C.c_void_p(b.ctypes.data), n, C.c_void_p(Fs.ctypes.data), C.c_void_p(nm.ctypes.data)))
+    else:
+        ctx = ctx or default_context()
+        check(lib().esfm_fundamental_models(ctx.handle, C.c_void_p(a.ctypes.data), C.c_void_p(b.ctypes.data), n, C.c_void_p(Fs.ctypes.data),
+                                            C.c_void_p(nm.ctypes.data)))
+    return Fs[:n].reshape(n, 3, 3, 3), nm[:n]
+
+
+def fundamental_refit_host(pts1, pts2, mask=None) -> np.ndarray:
+    """Host-only: esfm_fundamental_refit_host, the 8-point re-fit on the masked points in the refit kernel's summation order -> F [3,3]."""
+    a, b = _point_pair(pts1, pts2)
+    m = None if mask is None else np.ascontiguousarray(np.asarray(mask).astype(np.uint8))
+    if m is not None and len(m) != len(a):
+        raise ValueError("mask size")
+    F = np.zeros(9)
+    check(lib().esfm_fundamental_refit_host(C.c_void_p(a.ctypes.data), C.c_void_p(b.ctypes.data), len(a), None if m is None else C.c_void_p(m.ctypes.data),
+                                            C.c_void_p(F.ctypes.data)))
+    return F.reshape(3, 3)
+
+
+def fundamental_sample_stream(count: int, n_samples: int) -> np.ndarray:
+    """Host-only: the 7-index samples the fundamental-matrix RANSAC draws for `count` points (esfm_fundamental_sample_stream)."""
+    idx = np.zeros((max(n_samples, 1), 7), np.int32)
+    check(lib().esfm_fundamental_sample_stream(int(count), int(n_samples), C.c_void_p(idx.ctypes.data)))
+    return idx[:n_samples]
+
+
+def focal_cost(F, weights, cx: float, cy: float, candidates, ctx: Optional[Context] = None, host: bool = False) -> np.ndarray:
+    """esfm_focal_cost / esfm_focal_cost_host: the weighted mean over the pairs of (s1 - s2) / (s1 + s2) of K' F K for every candidate
+    focal length -> cost [n_cand] float64."""
+    Fs = np.ascontiguousarray(F, np.float64).reshape(-1, 9); w = np.ascontiguousarray(weights, np.float64).reshape(-1)
+    cand = np.ascontiguousarray(candidates, np.float64).reshape(-1)
+    if len(w) != len(Fs) or len(Fs) == 0:
+        raise ValueError("one weight per fundamental matrix, at least one matrix")
+    cost = np.zeros(max(len(cand), 1))
+    args = (len(Fs), C.c_void_p(Fs.ctypes.data), C.c_void_p(w.ctypes.data), float(cx), float(cy), len(cand), C.c_void_p(cand.ctypes.data),
+            C.c_void_p(cost.ctypes.data))
+    if host:
+        check(lib().esfm_focal_cost_host(*args))
+    else:
+        ctx = ctx or default_context()
+        check(lib().esfm_focal_cost(ctx.handle, *args))
+    return cost[:len(cand)]
+
+
+FOCAL_SWEEP = 129            # candidates per sweep
+FOCAL_MIN_DEPTH = 0.01       # the estimate is trusted from this depth of the coarse cost curve's minimum on (DESIGN: a convention)
+
+
+def focal_candidates(lo: float, hi: float, n: int = FOCAL_SWEEP) -> np.ndarray:
+    """n log-spaced focal lengths from lo to hi: lo * (hi / lo) ** (k / (n - 1))"""
+    return np.array([float(lo) * (float(hi) / float(lo)) ** (k / (n - 1)) for k in range(n)], np.float64)
+
+
+def focal_from_fundamentals(F, weights, width: float, height: float, options=None, ctx: Optional[Context] = None, host: bool = False) -> dict:
+    """One focal length for the fundamental matrices of pairs taken with ONE camera (Mendonca and Cipolla's cost, esfm_focal_cost), the
+    principal point at (width / 2, height / 2).  A coarse sweep over FOCAL_SWEEP log-spaced candidates in 0.3 .. 3 x max(width, height),
+    then as many between the two grid neighbours of the coarse minimum; the first index wins on ties.  Returns a dict: f, coarse and
+    fine (each (candidates, cost)), depth = median(coarse cost) - min(coarse cost), confident = depth >= min_depth (options.min_depth,
+    default FOCAL_MIN_DEPTH)."""
+    size = float(max(width, height))
+    cx, cy = float(width) / 2.0, float(height) / 2.0
+    min_depth = float(getattr(options, "min_depth", FOCAL_MIN_DEPTH)) if options is not None else FOCAL_MIN_DEPTH
+    c0 = focal_candidates(0.3 * size, 3.0 * size)
+    k0 = focal_cost(F, weights, cx, cy, c0, ctx, host)
+    i0 = int(np.argmin(k0))                                   # (the first index on ties; a NaN cost would win: the curve is then useless)
+    c1 = focal_candidates(c0[max(i0 - 1, 0)], c0[min(i0 + 1, len(c0) - 1)])
+    k1 = focal_cost(F, weights, cx, cy, c1, ctx, host)
+    i1 = int(np.argmin(k1))
+    depth = float(np.median(k0) - k0[i0])
+    return {"f": float(c1[i1]), "coarse": (c0, k0), "fine": (c1, k1), "depth": depth, "confident": bool(depth >= min_depth), "coarse_index": i0}
+
+
 def pixel2cam(p: np.ndarray, K: np.ndarray) -> np.ndarray:
     """estimate_motion.h:41-46, float arithmetic on the float K: ((u - cx) / fx, (v - cy) / fy)."""
     p = np.asarray(p, np.float32).reshape(-1, 2); K = np.asarray(K, np.float32)
@@ -289,6 +410,20 @@ class MotionEstimator:
             return False, np.zeros((3, 3)), 0
         inlier_matches.extend(m for m, keep in zip(matches, mask) if keep)
         return True, H[0], int(n_inl[0])
+
+    def estimate2D2D_F7P_RANSAC(self, cur_frame_1: Frame, cur_frame_2: Frame, matches: Sequence[DMatch], inlier_matches: list,
+                                ransac_thre: float = 1.0, ransac_prob: float = 0.99):
+        """The uncalibrated counterpart of estimate2D2D_E5P_RANSAC (no such member in the reference): 7-point RANSAC on the matched
+        pixels (esfm.h "Fundamental-matrix RANSAC"), no K_cam is read; the matches of the RANSAC mask are appended to `inlier_matches`.
+        Returns (found, F [3,3] float64 with x2' F x1 = 0 for frame 1's pixel x1 and frame 2's x2, n_inliers under the returned F).
+        found is False, F zero and n_inliers 0 with fewer than 7 matches or without a model."""
+        k1 = np.asarray(cur_frame_1.keypoints, np.float32).reshape(-1, 2)[[m.queryIdx for m in matches]].reshape(-1, 2)
+        k2 = np.asarray(cur_frame_2.keypoints, np.float32).reshape(-1, 2)[[m.trainIdx for m in matches]].reshape(-1, 2)
+        F, mask, status, _, n_inl = find_fundamental_pairs([0, len(matches)], k1, k2, ransac_thre, ransac_prob, self._ctx)
+        if not status[0]:
+            return False, np.zeros((3, 3)), 0
+        inlier_matches.extend(m for m, keep in zip(matches, mask) if keep)
+        return True, F[0], int(n_inl[0])
 
     def doUnDistort(self, cur_frame: Frame, distort_coeff) -> bool:
         """estimate_motion.cpp:431-441: cur_frame.rgb_image = cv::undistort(rgb_image, K_cam, distort_coeff)."""

@@ -10,7 +10,7 @@ from __future__ import annotations
 
 from dataclasses import dataclass, field
 import os
-from typing import List, Optional, Sequence
+from typing import Callable, List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -18,7 +18,8 @@ from ._lib import Context, ESFM_HAMMING, ESFM_L2_F32, default_context
 from .ba import BundleAdjustment
 from .cloud import CProceesing, write_ply, write_ply_mesh, write_ply_normals, write_ply_textured_mesh, write_png_rgb
 from .matching import DescriptorBank, FeatureMatching, PairMatcher
-from .motion import MotionEstimator, _dehomogenise, find_essential_pairs, find_homography_pairs, pixel2cam, recover_pose_pairs, triangulate_pairs
+from .motion import (FOCAL_MIN_DEPTH, MotionEstimator, _dehomogenise, find_essential_pairs, find_fundamental_pairs, find_homography_pairs,
+                     focal_from_fundamentals, pixel2cam, recover_pose_pairs, triangulate_pairs)
 from .mesh import (MeshCleanOptions, MeshOptions, auto_texels, default_atlas_width, mesh_arrays, mesh_clean, mesh_components, mesh_simplify,
                    mesh_texture_bake, mesh_texture_level, mesh_texture_views)
 from .render import mesh_render, mesh_render_error
@@ -41,6 +42,60 @@ class FramePair:
     h_inliers: int = 0            # correspondences within the threshold of the returned, re-fitted homography (esfm_find_homography_pairs'
                                   # n_inliers: not the RANSAC mask's count); homography_check only
     h_inlier_ratio: float = 0.0   # ... divided by the essential matrix's RANSAC mask count: near 1 for a planar or rotation-only pair
+
+
+@dataclass
+class AutoFocalOptions:
+    """run_sfm(auto_focal=...): the uncalibrated start (esfm.h "Fundamental-matrix RANSAC").  Every camera_id's K_cam is set from the
+    fundamental matrices of its own pairs; what the frames carried in K_cam before is not read."""
+    image_size: Optional[Tuple[int, int]] = None   # (width, height) of frames that carry no rgb_image
+    min_depth: float = FOCAL_MIN_DEPTH             # the estimate counts from this depth of the coarse cost curve's minimum on
+    max_h_inlier_ratio: float = 0.8                # homography inliers / F inliers above which a pair is planar or panoramic: its F means nothing
+    fallback_factor: float = 1.2                   # f = this x max(width, height) without a usable estimate: the common convention
+
+
+def _frame_size(f: Frame, options: AutoFocalOptions) -> Tuple[float, float]:
+    if f.rgb_image is not None:
+        h, w = np.asarray(f.rgb_image).shape[:2]
+        return float(w), float(h)
+    if options.image_size is None:
+        raise ValueError("auto_focal needs the image size: a frame carries no rgb_image and AutoFocalOptions.image_size is not set")
+    return float(options.image_size[0]), float(options.image_size[1])
+
+
+def _centred_K(f: float, w: float, h: float) -> np.ndarray:
+    return np.array([[f, 0.0, w / 2.0], [0.0, f, h / 2.0], [0.0, 0.0, 1.0]], np.float32)
+
+
+def auto_focal_calibration(frames: Sequence[Frame], options: AutoFocalOptions, ransac_reproj_distance: float, num_min_pair: int,
+                           ctx: Optional[Context] = None) -> Callable:
+    """The `calibrate` callable run_sfm hands to match_and_verify_all_pairs.  Over the matched correspondences of all pairs: one
+    esfm_find_fundamental_pairs call (threshold ransac_reproj_distance, confidence 0.99) and one esfm_find_homography_pairs call; a pair
+    is kept when its F has more than num_min_pair inliers and its homography inliers / F inliers do not exceed
+    options.max_h_inlier_ratio, and weighs as much as its F inliers.  Every camera_id then gets K_cam = [f 0 w/2; 0 f h/2; 0 0 1] on all
+    its frames, f from motion.focal_from_fundamentals over the kept pairs BOTH of whose frames it took; without such a pair, or with an
+    estimate that is not confident, f = options.fallback_factor x max(w, h).  Prints one "Auto focal:" line per camera."""
+    sizes = {}
+    for f in frames:
+        sizes.setdefault(int(f.camera_id), _frame_size(f, options))
+
+    def calibrate(pairs, sel, off, p1, p2):
+        F, _, status, _, f_inl = find_fundamental_pairs(off, p1, p2, ransac_reproj_distance, 0.99, ctx)
+        _, _, _, _, h_inl = find_homography_pairs(off, p1, p2, ransac_reproj_distance, 0.995, ctx)
+        for cam, (w, h) in sorted(sizes.items()):
+            own = [s for s, k in enumerate(sel) if int(frames[pairs[k][0]].camera_id) == cam and int(frames[pairs[k][1]].camera_id) == cam]
+            used = [s for s in own if status[s] and f_inl[s] > num_min_pair and float(h_inl[s]) / float(f_inl[s]) <= options.max_h_inlier_ratio]
+            focal, depth, verdict = options.fallback_factor * max(w, h), 0.0, "fallback"
+            if used:
+                est = focal_from_fundamentals(F[used], f_inl[used].astype(np.float64), w, h, options, ctx)
+                depth = est["depth"]
+                if est["confident"]:
+                    focal, verdict = est["f"], "estimated"
+            for f in frames:
+                if int(f.camera_id) == cam:
+                    f.K_cam = _centred_K(focal, w, h)
+            print(f"Auto focal: camera [{cam}] f = [{focal:.2f}] from [{len(used)}] of [{len(own)}] pairs, depth [{depth:.4f}], {verdict}")
+    return calibrate
 
 
 MATCH_FILTERS = ("ratio", "cross", "ratio+cross", "ratio+guided", "cross+guided", "ratio+cross+guided")
@@ -70,7 +125,7 @@ def _checked_pairs(pairs, n_frames: int) -> np.ndarray:
 
 def match_and_verify_all_pairs(frames: Sequence[Frame], use_feature: str = "S", ransac_reproj_distance: float = 1.0,
                                num_min_pair: int = 20, ctx: Optional[Context] = None, match_filter: str = "ratio",
-                               homography_check: bool = False, pairs=None) -> List[List[FramePair]]:
+                               homography_check: bool = False, pairs=None, calibrate: Optional[Callable] = None) -> List[List[FramePair]]:
     """sfm.cpp:140-167 for every (i, j < i): matchFeatures{SURF,ORB,SIFT}(frames[i], frames[j]) (use_feature S, O or I); if more than num_min_pair
     matches survive, estimate2D2D_E5P_RANSAC (threshold = ransac_reproj_distance, prob 0.99) and getDepthFast on the inliers;
     otherwise no inliers, identity transform, depth 1 (:147-148).  Returns img_match_graph[i][j].
@@ -85,7 +140,10 @@ def match_and_verify_all_pairs(frames: Sequence[Frame], use_feature: str = "S", 
     and appro_depth are untouched.
     pairs: None for every (i, j < i); else an int32 [P, 2] list of (i, j < i) pairs (retrieval.select_pairs' output), or a callable
     that is given the DescriptorBank built here and returns such a list (so that a selection runs on the rows already uploaded).
-    Only the listed pairs are matched and verified; every other graph[i][j] stays the default FramePair."""
+    Only the listed pairs are matched and verified; every other graph[i][j] stays the default FramePair.
+    calibrate: when given, it is called once as calibrate(pairs, sel, off, p1, p2) after matching and before any frame's K_cam is read --
+    pairs the int32 [P, 2] pair list, sel the indices into it of the pairs with more than num_min_pair matches, off / p1 / p2 their
+    concatenated matched pixels -- and may set the frames' K_cam (auto_focal_calibration).  None: nothing changes."""
     if match_filter not in MATCH_FILTERS:
         raise ValueError(f"match_filter must be one of {MATCH_FILTERS}, not {match_filter!r}")
     ctx = ctx or default_context()
@@ -120,6 +178,8 @@ def match_and_verify_all_pairs(frames: Sequence[Frame], use_feature: str = "S", 
         off = np.concatenate([[0], np.cumsum([len(res[k][0]) for k in sel])]).astype(np.int32)
         p1 = np.concatenate([np.asarray(frames[pairs[k][0]].keypoints, np.float32).reshape(-1, 2)[res[k][0]] for k in sel])
         p2 = np.concatenate([np.asarray(frames[pairs[k][1]].keypoints, np.float32).reshape(-1, 2)[res[k][1]] for k in sel])
+        if calibrate is not None:
+            calibrate(pairs, sel, off, p1, p2)
         K4 = np.array([[frames[pairs[k][0]].K_cam[0, 0], frames[pairs[k][0]].K_cam[0, 2], frames[pairs[k][0]].K_cam[1, 1],
                         frames[pairs[k][0]].K_cam[1, 2]] for k in sel], np.float32)
         Es, mask, status, _ = find_essential_pairs(off, p1, p2, K4, 0.99, ransac_reproj_distance, ctx)
@@ -209,7 +269,8 @@ def run_sfm(frames: List[Frame], output_file: Optional[str] = None, use_feature:
             dense_mesh_clean: Optional[MeshCleanOptions] = None, dense_mesh_simplify: Optional[float] = None,
             dense_mesh_texture: Optional[int] = None, dense_mesh_texture_level: bool = False, dense_mesh_render_dir: Optional[str] = None,
             init_max_h_inlier_ratio: Optional[float] = None, track_refine: Optional[TrackOptions] = None,
-            pair_selection: Optional[RetrievalOptions] = None, ba_radial_tolerance: Optional[float] = None):
+            pair_selection: Optional[RetrievalOptions] = None, ba_radial_tolerance: Optional[float] = None,
+            auto_focal: Optional[AutoFocalOptions] = None):
     """sfm.cpp:128-339.  Returns (sparse cloud before the final filter, filtered cloud, img_match_graph).
     dense_output_file: after the final BA and the sparse .ply, run dense_reconstruct on the registered frames and the cloud
     before the filter (it carries the track ids) and write the dense cloud there (esfm.h "Dense reconstruction").
@@ -252,9 +313,23 @@ def run_sfm(frames: List[Frame], output_file: Optional[str] = None, use_feature:
     frame's current (K_cam, radial_cam) (cameras.pinhole_keypoints), refreshed for every frame after every bundle adjustment, and
     it is what the pair stage, PnP, triangulation, guided matching and track refinement read.  With a dense output every registered
     frame's image is undistorted with its camera's final k1, k2 first.  Prints one "Distortion:" line.  None: every output as
-    before, to the bit."""
+    before, to the bit.
+    auto_focal: when given, no K_cam is read: after matching, every camera_id's K_cam is set from the fundamental matrices of its own
+    pairs (auto_focal_calibration; esfm.h "Fundamental-matrix RANSAC"), the principal point at the image centre, and everything behind
+    runs as with that K given; one "Auto focal:" line per camera.  It is a start value: give fix_calib_tolerance_BA > 0 so that
+    bundle adjustment polishes it.  A pair across two cameras is verified with its first frame's K, as in a one-camera run (two focal
+    lengths per pair are left out); not combined with ba_radial_tolerance.  None: every output as before, to the bit."""
     if ba_radial_tolerance is not None and not ba_radial_tolerance > 0.0:
         raise ValueError("ba_radial_tolerance must be positive")
+    calibrate = None
+    if auto_focal is not None:
+        if ba_radial_tolerance is not None:
+            raise ValueError("auto_focal cannot be combined with ba_radial_tolerance")
+        ctx = ctx or default_context()
+        calibrate = auto_focal_calibration(frames, auto_focal, ransac_reproj_distance, 20, ctx)     # (reads every frame's size: fails before any work)
+        w, h = _frame_size(frames[0], auto_focal)
+        for f in frames:                                # one placeholder K until `calibrate` runs: the pair stage then sees the pixels as detected
+            f.K_cam = _centred_K(auto_focal.fallback_factor * max(w, h), w, h)
     ctx = ctx or default_context()
     fm, ee = FeatureMatching(ctx), MotionEstimator(ctx)
     for f in frames:
@@ -267,7 +342,7 @@ def run_sfm(frames: List[Frame], output_file: Optional[str] = None, use_feature:
     if ba_radial_tolerance is not None:
         refresh_pinhole_keypoints(frames)               # keypoints_raw <- the detected pixels; keypoints: those of the start (K_cam, radial_cam)
     with pair_stage_view(frames):
-        graph = _pair_stage(frames, use_feature, ransac_reproj_distance, ctx, match_filter, init_max_h_inlier_ratio, pair_selection)
+        graph = _pair_stage(frames, use_feature, ransac_reproj_distance, ctx, match_filter, init_max_h_inlier_ratio, pair_selection, calibrate)
     return _run_sfm_after_pairs(frames, graph, fm, ee, output_file, ransac_reproj_distance, use_track_frames_as_init, fix_calib_tolerance_BA,
                                 frequency_BA, ctx, verbose, dense_output_file, dense_merged_output_file, dense_mesh_output_file, dense_mesh_clean,
                                 dense_mesh_simplify, dense_mesh_texture, dense_mesh_texture_level, dense_mesh_render_dir, init_max_h_inlier_ratio,
@@ -283,10 +358,10 @@ def undistort_registered_images(frames, todo, ctx: Optional[Context] = None) -> 
             f.rgb_image = undistort(f.rgb_image, f.K_cam, np.array([f.radial_cam[0], f.radial_cam[1], 0.0, 0.0], np.float64), ctx)
 
 
-def _pair_stage(frames, use_feature, ransac_reproj_distance, ctx, match_filter, init_max_h_inlier_ratio, pair_selection):
+def _pair_stage(frames, use_feature, ransac_reproj_distance, ctx, match_filter, init_max_h_inlier_ratio, pair_selection, calibrate=None):
     if pair_selection is None:
         graph = match_and_verify_all_pairs(frames, use_feature, ransac_reproj_distance, 20, ctx, match_filter,
-                                           homography_check=init_max_h_inlier_ratio is not None)
+                                           homography_check=init_max_h_inlier_ratio is not None, calibrate=calibrate)
     else:
         def choose(bank):
             chosen = select_pairs(bank, bank.metric, pair_selection, ctx)
@@ -295,7 +370,7 @@ def _pair_stage(frames, use_feature, ransac_reproj_distance, ctx, match_filter, 
                   f"window [{pair_selection.window}], codebook [{pair_selection.n_centres}] x [{working_dim(bank.metric, bank.width)}]")
             return chosen
         graph = match_and_verify_all_pairs(frames, use_feature, ransac_reproj_distance, 20, ctx, match_filter,
-                                           homography_check=init_max_h_inlier_ratio is not None, pairs=choose)
+                                           homography_check=init_max_h_inlier_ratio is not None, pairs=choose, calibrate=calibrate)
     return graph
 
 

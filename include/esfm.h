@@ -771,6 +771,69 @@ int esfm_homography_refit_host(const float *pts1, const float *pts2, int n, cons
 int esfm_homography_sample_stream(const float *pts1, const float *pts2, int count, int n_samples, int32_t *idx /*4 per sample*/,
                                   int64_t *redraws /*or NULL*/);
 
+/* ---- Fundamental-matrix RANSAC: the uncalibrated start ------------------------------------------------
+ * Two views without a calibration matrix are still related by a fundamental matrix F (x2' F x1 = 0 in pixels), and the F of many pairs
+ * taken with one camera pin its focal length down (esfm_focal_cost below; pipeline.run_sfm(auto_focal=...), `bin/sfm ... auto`).
+ *
+ * esfm_find_fundamental follows cv::findFundamentalMat(pts1, pts2, cv::FM_RANSAC, threshold, confidence); where the two differ, the
+ * rule list written here is the authority (parity with OpenCV is not pinned).  Every order of operations:
+ * easysfm_amd/csrc/fundamental_core.hpp; the restatement tests/fundamental_ref.py agrees with the host build and the kernels to the bit.
+ *   Sampling and iteration
+ *   - 7 model points, at most 1000 iterations, on the sample stream of cv::RNG((uint64)-1): seven distinct indices (a repeat is
+ *     redrawn).  No subset check.
+ *   - n = 7: the models of the seven points as given, *iterations = 0, the mask all ones.  The winner is the model with the most
+ *     inliers under the score below, the first in model order on ties.
+ *   - n < 7 is ESFM_ERR_UNSUPPORTED; no model with at least 7 inliers (n = 7: no model at all) is ESFM_ERR_NUMERIC.
+ *   Minimal solve (f64)
+ *   - Hartley normalisation of the seven points per image (centroid to the origin, mean distance sqrt 2); the 7 x 9 system of the rows
+ *     (p u, p v, p, q u, q v, q, u, v, 1) of (u, v) -> (p, q); its two-dimensional null space f1, f2 by a Householder QR of the transpose
+ *     (the last two columns of the orthogonal factor).
+ *   - The cubic det(x f1 + (1 - x) f2) by one written-out expansion; its real roots by a bracketed Newton iteration with a fixed sweep
+ *     cap (80) between the Cauchy bound and the cubic's stationary points, using only + - * / sqrt and comparisons (not the 5-point
+ *     solver's iteration).
+ *   - Vanishing leading coefficient (|c3| <= 1e-12 max|c_i|): the cubic is read as the quadratic of the remaining coefficients (by the
+ *     same test as the linear equation, or as nothing); the root at infinity, the model f1 - f2, is dropped.
+ *   - Every model is de-normalised, scaled to unit Frobenius norm and given the canonical sign: the entry of largest magnitude (the
+ *     first on ties) is positive.  Models are ordered by ascending root.  A model with a non-finite entry is no model.
+ *   Score, in float on (float)F
+ *   - image 2: a = F0 x + F1 y + F2, b = F3 x + F4 y + F5, c = F6 x + F7 y + F8, d2 = x' a + y' b + c, e2 = d2 d2 / (a a + b b); image 1
+ *     the same with F' and the points exchanged; err = max(e1, e2); inlier iff err <= (float)(threshold * threshold).  A NaN (in
+ *     either error) is no inlier.
+ *   Best model and re-fit
+ *   - A model replaces the best iff it has more inliers and at least 7; RANSACUpdateNumIters runs with 7 model points.  mask[n] = the
+ *     inliers of the winning RANSAC model, *iterations = iterations the sequential loop runs.
+ *   - The re-fit is the normalised 8-point algorithm on the winner's inliers, at least 8 of them: the 9 x 9 normal matrix in the
+ *     homography re-fit's summation order (256 lanes, lane l the points l, l + 256, .. ascending, then the halving tree), its smallest
+ *     eigenvector by the cyclic Jacobi, rank 2 by zeroing the smallest singular value found by a one-sided Jacobi, de-normalisation,
+ *     then the same norm and sign.  The mask stays the RANSAC mask.  A re-fit without a model (or with 7 inliers) leaves the winner.
+ * esfm_find_fundamental_pairs batches many pairs like esfm_find_homography_pairs (point_offset, status, iterations as there; a pair
+ * with fewer than 7 points: status 0, zeros, no error).  n_inliers[p] (or NULL) is counted under the RETURNED F.
+ * Left out: pairs across two cameras (two focal lengths per pair), a free principal point, EXIF. */
+int esfm_find_fundamental(esfm_ctx *ctx, const float *pts1, const float *pts2, int n, double threshold, double confidence,
+                          double *F /*9*/, uint8_t *mask /*n*/, int32_t *iterations /*or NULL*/);
+int esfm_find_fundamental_pairs(esfm_ctx *ctx, int n_pairs, const int32_t *point_offset /*n_pairs+1*/, const float *pts1,
+                                const float *pts2, double threshold, double confidence, double *F /*9 per pair*/,
+                                uint8_t *mask /*per point*/, int32_t *status /*per pair*/, int32_t *iterations /*per pair or NULL*/,
+                                int32_t *n_inliers /*per pair or NULL*/);
+/* The minimal solve alone: q1, q2 [n_samples][7][2] doubles in pixels -> F_out [n_samples][3][9] (the models in root order, zeros
+ * behind them), n_models[n_samples] 0 .. 3.  On the GPU, and the host build of the same header (no GPU). */
+int esfm_fundamental_models(esfm_ctx *ctx, const double *q1, const double *q2, int n_samples, double *F_out, int32_t *n_models);
+int esfm_fundamental_models_host(const double *q1, const double *q2, int n_samples, double *F_out, int32_t *n_models);
+/* Host-only (no GPU): the 8-point re-fit on the points whose mask is set (mask NULL: all), in the refit kernel's summation order.
+ * Fewer than 8 such points or no model: ESFM_ERR_NUMERIC, F zeros. */
+int esfm_fundamental_refit_host(const float *pts1, const float *pts2, int n, const uint8_t *mask /*or NULL*/, double *F /*9*/);
+/* Host-only (no GPU): the first n_samples 7-index samples the RANSAC above draws for `count` points. */
+int esfm_fundamental_sample_stream(int count, int n_samples, int32_t *idx /*7 per sample*/);
+/* Focal length from fundamental matrices (Mendonca and Cipolla): with the right K = [f 0 cx; 0 f cy; 0 0 1], K' F K is an essential
+ * matrix and its two non-zero singular values are equal.  cost[k] = sum_p w_p (s1 - s2) / (s1 + s2) / sum_p w_p for candidates[k],
+ * s1 >= s2 the two largest singular values of K_k' F_p K_k by a one-sided Jacobi in f64; one thread per (candidate, pair), the sums over
+ * the pairs in pair order by a fixed tree (256 lanes, lane l the pairs l, l + 256, .., then halving), so the curve is bit-exact
+ * against the host twin and the restatement.  The candidates come from the caller (a log grid needs pow).  n_pairs >= 1. */
+int esfm_focal_cost(esfm_ctx *ctx, int n_pairs, const double *F /*9 per pair*/, const double *weight /*per pair*/, double cx, double cy,
+                    int n_cand, const double *candidates, double *cost_out /*n_cand*/);
+int esfm_focal_cost_host(int n_pairs, const double *F /*9 per pair*/, const double *weight /*per pair*/, double cx, double cy, int n_cand,
+                         const double *candidates, double *cost_out /*n_cand*/);
+
 /* ---- SURF detection + description (SURF half) ----------------------------
  * FeatureMatching::detectFeaturesSURF (cpp_code/src/feature_matching.cpp:43-58): cv::xfeatures2d::SURF::create(minHessian)
  * ->detect(image, keypoints) then SURF::create()->compute(image, keypoints, descriptors), OpenCV defaults (4 octaves, 3 layers
