@@ -34,6 +34,7 @@ from .mesh import (MeshCleanOptions, MeshOptions, MeshSimplifyOptions, MeshTextu
                    mesh_texture_bake, mesh_texture_level, mesh_texture_views, mvs_mesh, tsdf_extract, tsdf_grid, tsdf_integrate)
 from .render import MeshRenderOptions, default_mesh_render_options, mesh_render, mesh_render_error, orbit_poses  # noqa: F401
 from .tracks import TrackOptions, TrackResult, refine_tracks, track_evaluate, track_observations, track_triangulate  # noqa: F401
+from .tracks import TrackCompleteOptions, TrackCompleteResult, complete_inputs, complete_tracks, free_keypoints, track_complete  # noqa: F401
 from .retrieval import (RetrievalOptions, retrieval_pair_list, retrieval_rank, retrieval_train, retrieval_vlad,  # noqa: F401
                         select_pairs)
 from .pipeline import MATCH_FILTERS, AutoFocalOptions, FramePair, match_and_verify_all_pairs, propagate_track_ids, run_sfm  # noqa: F401

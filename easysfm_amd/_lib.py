@@ -23,6 +23,7 @@ ESFM_HAMMING = 1
 ESFM_REDUCE_SUM = 0
 ESFM_REDUCE_MAX = 1
 K_L2_KNN, K_HAMMING_KNN, K_BA_LINEARIZE, K_BA_SCHUR, K_BA_SOLVE, K_L2_RESCAN, K_SOR_KNN, K_TRIANGULATE, K_RANSAC, K_SURF_DET, K_SURF_DESC, K_UNDISTORT, K_ORB_FAST, K_L2_SECOND, K_CROSS_CHECK, K_SIFT_PYR, K_SIFT_DESC, K_MVS_SWEEP, K_MVS_FUSE = range(19)
+K_COMPLETE_GRID, K_COMPLETE_JOBS, K_COMPLETE_SEARCH = 19, 20, 21
 BA_MAX_LOG = 256
 
 STATUS_NAMES = {
@@ -64,6 +65,7 @@ EXPORTED_SYMBOLS = [
     "esfm_mesh_texture_level_options_default", "esfm_mesh_texture_level", "esfm_mesh_texture_bake_ex",
     "esfm_mesh_render_options_default", "esfm_mesh_render",
     "esfm_track_options_default", "esfm_track_triangulate", "esfm_track_evaluate", "esfm_track_triangulate_host", "esfm_track_evaluate_host",
+    "esfm_track_complete_options_default", "esfm_track_complete", "esfm_track_complete_dev", "esfm_track_complete_host",
     "esfm_retrieval_options_default", "esfm_retrieval_train", "esfm_retrieval_vlad", "esfm_retrieval_rank", "esfm_retrieval_pair_list",
     "esfm_retrieval_pairs", "esfm_retrieval_pairs_dev", "esfm_retrieval_last_stage_ms",
 ]
@@ -160,6 +162,12 @@ class MeshTextureLevelStats(C.Structure):
 class MeshRenderOptions(C.Structure):
     """esfm_mesh_render_options (include/esfm.h, "Mesh rendering")."""
     _fields_ = [("background", C.c_uint8 * 3), ("reserved", C.c_uint8)]
+
+
+class TrackCompleteOptionsStruct(C.Structure):
+    """esfm_track_complete_options (include/esfm.h, "Track completion")."""
+    _fields_ = [("search_radius_px", C.c_double), ("max_distance", C.c_double), ("ratio", C.c_double), ("max_refs", C.c_int32),
+                ("reserved", C.c_int32)]
 
 
 class TrackOptionsStruct(C.Structure):
@@ -346,6 +354,14 @@ def lib() -> C.CDLL:
     L.esfm_track_evaluate.argtypes = [vp] + track_in + track_out
     L.esfm_track_triangulate_host.argtypes = track_in + [vp] + track_out
     L.esfm_track_evaluate_host.argtypes = track_in + track_out
+    L.esfm_track_complete_options_default.argtypes = [C.POINTER(TrackCompleteOptionsStruct)]
+    L.esfm_track_complete_options_default.restype = None
+    # metric, desc, kp, kp_free, set_row_offset, n_cam, width, K4, Rt, n_pt, xyz, n_obs, cam_idx, pt_idx, obs_kp, options, kp_point, kp_dist, stats
+    complete_args = [C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, C.c_int, vp, C.c_int, vp, vp, vp,
+                     C.POINTER(TrackCompleteOptionsStruct), vp, vp, vp]
+    L.esfm_track_complete.argtypes = [vp] + complete_args
+    L.esfm_track_complete_dev.argtypes = [vp] + complete_args
+    L.esfm_track_complete_host.argtypes = complete_args
     L.esfm_retrieval_options_default.argtypes = [C.POINTER(RetrievalOptionsStruct)]
     L.esfm_retrieval_options_default.restype = None
     rows_in = [vp, C.c_int, vp, vp, C.c_int, C.c_int]                                               # ctx, metric, rows, set_row_offset, n_sets, width

@@ -126,6 +126,9 @@ struct esfm_ctx {
     // the host-pointer forms' uploaded descriptor rows
     esfm::DevBuf retrieval, retrieval_bank;
     double retrieval_stage_ms[4] = {0, 0, 0, 0};   // under esfm_ctx_set_kernel_timing: the last esfm_retrieval_pairs[_dev] call's train, assign + accumulate, finalise, rank
+    // track completion's own scratch (complete_api.cpp alone touches it): every intermediate in one carved buffer, and the
+    // host-pointer form's uploaded descriptor rows and keypoints
+    esfm::DevBuf complete, complete_bank, complete_kp;
     // pinned host staging for small tables / counters
     void *pinned = nullptr;
     size_t pinned_cap = 0;

@@ -96,7 +96,7 @@ int esfm_ctx_set_kernel_timing(esfm_ctx *ctx, int enable)
 
 int esfm_ctx_kernel_time(esfm_ctx *ctx, int kernel_id, double *total_ms, int64_t *launches)
 {
-    if (!ctx || !total_ms || !launches || kernel_id < 0 || kernel_id >= ESFM_K_COUNT) { esfm::set_error("bad argument"); return ESFM_ERR_INVALID_ARG; }
+    if (!ctx || !total_ms || !launches || kernel_id < 0 || kernel_id >= ESFM_K_END) { esfm::set_error("bad argument"); return ESFM_ERR_INVALID_ARG; }
     if (int rc = esfm::set_device(ctx)) return rc;
     ESFM_HIP_TRY(hipStreamSynchronize(ctx->stream));
     std::vector<esfm_ctx::TimedLaunch> keep;
@@ -171,7 +171,8 @@ int esfm_ctx_destroy(esfm_ctx *ctx)
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
     for (esfm::DevBuf *b : {&ctx->knn_dist, &ctx->stage_a, &ctx->stage_b, &ctx->stage_c, &ctx->stage_d, &ctx->stage_e, &ctx->guided_tab, &ctx->guided_idx,
-                            &ctx->guided_dist, &ctx->guided_bank, &ctx->guided_kp, &ctx->retrieval, &ctx->retrieval_bank}) b->release();
+                            &ctx->guided_dist, &ctx->guided_bank, &ctx->guided_kp, &ctx->retrieval, &ctx->retrieval_bank, &ctx->complete,
+                            &ctx->complete_bank, &ctx->complete_kp}) b->release();
     ctx->match.release();
     if (ctx->pinned) (void)hipHostFree(ctx->pinned);
     if (ctx->pinned_rounds) (void)hipHostFree(ctx->pinned_rounds);

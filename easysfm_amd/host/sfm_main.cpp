@@ -155,6 +155,15 @@ int main(int argc, char **argv)
     const std::string tracks_suffix = "+tracks";
     const bool refine_tracks = filter_arg.size() > tracks_suffix.size() && filter_arg.compare(filter_arg.size() - tracks_suffix.size(), tracks_suffix.size(), tracks_suffix) == 0;
     if (refine_tracks) filter_arg.erase(filter_arg.size() - tracks_suffix.size());
+    // +complete (track completion, esfm.h "Track completion"; directly in front of +tracks' position): bin/sfm's mode, not provided by
+    // this driver -- refused, not ignored
+    {
+        const std::string token = "+complete";
+        if (filter_arg.size() > token.size() && filter_arg.compare(filter_arg.size() - token.size(), token.size(), token) == 0) {
+            fprintf(stderr, "sfm_native: +complete (track completion) is not provided by this driver; use bin/sfm\n");
+            return 2;
+        }
+    }
     const std::string guided_suffix = "+guided";
     const bool guided = filter_arg.size() > guided_suffix.size() && filter_arg.compare(filter_arg.size() - guided_suffix.size(), guided_suffix.size(), guided_suffix) == 0;
     const std::string match_filter = guided ? filter_arg.substr(0, filter_arg.size() - guided_suffix.size()) : filter_arg;      // the first pass's filter

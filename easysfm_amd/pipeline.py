@@ -25,7 +25,7 @@ from .mesh import (MeshCleanOptions, MeshOptions, auto_texels, default_atlas_wid
 from .render import mesh_render, mesh_render_error
 from .mvs import MergeOptions, default_mvs_options, dense_reconstruction, frame_arrays, merge_arrays
 from .retrieval import RetrievalOptions, select_pairs, working_dim
-from .tracks import TrackOptions, refine_tracks
+from .tracks import TrackCompleteOptions, TrackOptions, complete_tracks, refine_tracks
 from .types import DMatch, Frame, SparsePointCloud
 from .cameras import check_one_image_size, distortion_line, pair_stage_view, refresh_pinhole_keypoints
 from .features import undistort
@@ -270,7 +270,7 @@ def run_sfm(frames: List[Frame], output_file: Optional[str] = None, use_feature:
             dense_mesh_texture: Optional[int] = None, dense_mesh_texture_level: bool = False, dense_mesh_render_dir: Optional[str] = None,
             init_max_h_inlier_ratio: Optional[float] = None, track_refine: Optional[TrackOptions] = None,
             pair_selection: Optional[RetrievalOptions] = None, ba_radial_tolerance: Optional[float] = None,
-            auto_focal: Optional[AutoFocalOptions] = None):
+            auto_focal: Optional[AutoFocalOptions] = None, track_complete: Optional[TrackCompleteOptions] = None):
     """sfm.cpp:128-339.  Returns (sparse cloud before the final filter, filtered cloud, img_match_graph).
     dense_output_file: after the final BA and the sparse .ply, run dense_reconstruct on the registered frames and the cloud
     before the filter (it carries the track ids) and write the dense cloud there (esfm.h "Dense reconstruction").
@@ -304,6 +304,15 @@ def run_sfm(frames: List[Frame], output_file: Optional[str] = None, use_feature:
     observations of the others leave bundle adjustment) and once more after the final doSFMBA, before SORFilter, as a filter alone
     (evaluate_only); each call prints one "Track refine:" line (esfm.h "Track triangulation").  A point dropped by one call may be
     added again by a later doTriangulation and is then judged again.  None: every output as before, to the bit.
+    track_complete: when given, tracks.complete_tracks runs immediately before every refine_tracks call but the final evaluate-only
+    one (without track_refine: immediately before every doSFMBA call), so that re-triangulation and bundle adjustment see the new
+    observations: every cloud point is projected into the registered frames that do not observe it, and a keypoint no verified match
+    has touched, near the projection and with a descriptor that agrees with the track's, takes the point's id (esfm.h "Track
+    completion"); max_distance left at +inf becomes the 0.9 quantile of the verified matches' distances between registered frames;
+    each call prints one "Track complete:" line.  It reads keypoints (the pinhole-equivalent pixels) and every frame's own K_cam.
+    A new observation also gets unique_pixel_has_match = True and so enters bundle adjustment -- except in a frame none of whose
+    keypoints is in bundle adjustment yet (the first frame, always): there it takes the id alone, for re-triangulation, and the
+    frame stays out of the adjustment as it was (DESIGN 6.5a "One deviation").  None: every output as before, to the bit.
     pair_selection: when given, retrieval.select_pairs chooses the pairs to match (esfm.h "Image retrieval": the top_k most similar
     images of every image by int8 VLAD, plus the `window` preceding ones) on the descriptor rows the matcher has uploaded, and only
     those pairs are matched and verified; prints one "Pair selection:" line.  None: every output as before, to the bit.
@@ -346,7 +355,7 @@ def run_sfm(frames: List[Frame], output_file: Optional[str] = None, use_feature:
     return _run_sfm_after_pairs(frames, graph, fm, ee, output_file, ransac_reproj_distance, use_track_frames_as_init, fix_calib_tolerance_BA,
                                 frequency_BA, ctx, verbose, dense_output_file, dense_merged_output_file, dense_mesh_output_file, dense_mesh_clean,
                                 dense_mesh_simplify, dense_mesh_texture, dense_mesh_texture_level, dense_mesh_render_dir, init_max_h_inlier_ratio,
-                                track_refine, ba_radial_tolerance)
+                                track_refine, ba_radial_tolerance, track_complete)
 
 
 def undistort_registered_images(frames, todo, ctx: Optional[Context] = None) -> None:
@@ -377,8 +386,15 @@ def _pair_stage(frames, use_feature, ransac_reproj_distance, ctx, match_filter, 
 def _run_sfm_after_pairs(frames, graph, fm, ee, output_file, ransac_reproj_distance, use_track_frames_as_init, fix_calib_tolerance_BA, frequency_BA,
                          ctx, verbose, dense_output_file, dense_merged_output_file, dense_mesh_output_file, dense_mesh_clean, dense_mesh_simplify,
                          dense_mesh_texture, dense_mesh_texture_level, dense_mesh_render_dir, init_max_h_inlier_ratio, track_refine,
-                         ba_radial_tolerance=None):
+                         ba_radial_tolerance=None, track_complete=None):
     radial_tol = float(ba_radial_tolerance) if ba_radial_tolerance is not None else 0.0
+
+    def before_adjust():
+        """what runs in front of a bundle adjustment: track completion, then track refinement, each when asked for"""
+        if track_complete is not None:
+            complete_tracks(frames, todo, cloud, track_complete, ctx, graph=graph, track_matrix=track)
+        if track_refine is not None:
+            refine_tracks(frames, todo, cloud, track_refine, ctx)
 
     def adjust(tolerance):
         """doSFMBA; in a radial run every frame of a camera then takes that camera's k1, k2 and its keypoints are refreshed"""
@@ -420,8 +436,7 @@ def _run_sfm_after_pairs(frames, graph, fm, ee, output_file, ransac_reproj_dista
     todo = [True] * len(frames)
     todo[init_1] = todo[init_2] = False
     ba = BundleAdjustment(ctx)
-    if track_refine is not None:
-        refine_tracks(frames, todo, cloud, track_refine, ctx)
+    before_adjust()
     adjust(fix_calib_tolerance_BA)
     remaining = len(frames) - 2
     reproj = ransac_reproj_distance
@@ -443,14 +458,12 @@ def _run_sfm_after_pairs(frames, graph, fm, ee, output_file, ransac_reproj_dista
         remaining -= 1
         if remaining % frequency_BA == 0:
             ba.initBA()
-            if track_refine is not None:
-                refine_tracks(frames, todo, cloud, track_refine, ctx)
+            before_adjust()
             adjust(fix_calib_tolerance_BA)
             reproj = ransac_reproj_distance
         if verbose:
             print(f"Progress: [ {len(frames) - remaining} / {len(frames)} ]")
-    if track_refine is not None:
-        refine_tracks(frames, todo, cloud, track_refine, ctx)
+    before_adjust()
     adjust(0.0)
     if radial_tol > 0:
         print(distortion_line([f for f, t in zip(frames, todo) if not t]))

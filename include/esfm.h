@@ -102,7 +102,11 @@ typedef enum esfm_kernel_id {
     ESFM_K_SIFT_DESC = 16,    /* esfm_sift_detect_and_compute: sift_orient_kernel and sift_describe_kernel                   */
     ESFM_K_MVS_SWEEP = 17,    /* esfm_mvs_depth_maps: mvs_sweep_kernel (plane sweep, all views x tiles in one launch)       */
     ESFM_K_MVS_FUSE = 18,     /* esfm_mvs_fuse: mvs_fuse_kernel, the block-offset scan and the ordered write                */
-    ESFM_K_COUNT = 19
+    ESFM_K_COUNT = 19,        /* the ids above; its value is pinned (tests/test_mvs_cpu.py), so later ids follow it and ESFM_K_END bounds them */
+    ESFM_K_COMPLETE_GRID = 19,   /* esfm_track_complete: complete_box_kernel, complete_keys_kernel and the radix sort of the grid keys  */
+    ESFM_K_COMPLETE_JOBS = 20,   /* esfm_track_complete: the job count over n_pt x n_cam, its block scan and complete_jobs_kernel      */
+    ESFM_K_COMPLETE_SEARCH = 21, /* esfm_track_complete: complete_search_kernel (with the claims), complete_decode_kernel, the stats   */
+    ESFM_K_END = 22           /* one past the last id esfm_ctx_kernel_time accepts */
 } esfm_kernel_id;
 int esfm_ctx_set_kernel_timing(esfm_ctx *ctx, int enable);
 int esfm_ctx_kernel_time(esfm_ctx *ctx, int kernel_id, double *total_ms, int64_t *launches);
@@ -1518,6 +1522,77 @@ int esfm_track_evaluate_host(int n_cam, int n_pt, int n_obs, const int32_t *cam_
                              const float *K4_per_cam, const double *Rt12_per_cam, const double *xyz_in,
                              const esfm_track_options *opt, uint8_t *obs_inlier, float *obs_err2 /*or NULL*/, int32_t *pt_status,
                              int32_t *pt_n_inliers, double *pt_min_cos /*or NULL*/, double *pt_mse /*or NULL*/);
+
+/* ---- Track completion: projection search for missing observations -----------------------------------------------
+ * Adds observations to tracks: every cloud point is projected into every registered camera that does not observe it yet, and the
+ * free keypoint near the projection whose descriptor is nearest to the track's takes the point.  Opt-in: nothing else in the
+ * library calls it.  One arithmetic (csrc/complete_core.hpp) serves the kernels, the host build (esfm_track_complete_host, no GPU)
+ * and the restatement in tests/complete_ref.py; the three agree to the bit.
+ *
+ * Inputs: n_cam registered cameras with K4 (fx, cx, fy, cy floats) and Rt (12 doubles) as in "Track triangulation"; their keypoints
+ * (2 floats) and descriptor rows back to back with set_row_offset[n_cam + 1], as the guided matcher takes them (L2 of any
+ * dim >= 1, or Hamming of 16, 32 or 64 bytes; a device buffer starts on a multiple of 4 bytes); one byte kp_free per keypoint
+ * row; n_pt points xyz (double); the existing observations cam_idx, pt_idx, obs_kp (the keypoint index LOCAL to its camera), in
+ * any order.
+ * Jobs: one job (p, c) for every point p and camera c without an observation of p in the input.
+ * Reference rows: the descriptor rows of p's first max_refs observations in input order.  A point without observations has no job.
+ * Admissible: keypoint row k of camera c is admissible for (p, c) iff kp_free[k] != 0, the projection has p_2 > 0, and
+ *   err2 <= search_radius_px^2 -- p_r, xn, yn, ru, rv, err2 exactly as in "Track triangulation" (f64, no FMA, the same association;
+ *   the radius is squared in f64).  A NaN anywhere makes the row inadmissible.  No image size enters; the predicate alone decides
+ *   (the kernels' grid only finds the rows to ask it about).
+ * Score: d(p, k) = the minimum over the reference rows of the matcher's distance -- sqrtf of the canonical sum for L2, the bit
+ *   count as a float for Hamming; a NaN distance is never the minimum.  As in the matcher, a row takes part as a candidate only
+ *   with d < FLT_MAX (so neither +inf nor an all-NaN score does).
+ * Choice: the two best candidates under ascending (d, k).  The job proposes k0 iff (double)d0 <= max_distance and it has only
+ *   one candidate or (double)d0 < ratio * (double)d1.  A lone candidate is accepted on purpose: the window is small and
+ *   max_distance is the gate.
+ * Conflicts: of the points that propose one keypoint, the lowest (d0, point index) gets it; the others get nothing in that
+ *   camera (no second choice).  Implemented as a 64-bit integer minimum over (float bits of d0) << 32 | p: order-free.
+ * Output per keypoint row: kp_point (the winning point index, or -1) and kp_dist (d0, or FLT_MAX).  stats (may be NULL), int64[4]:
+ *   jobs with at least one admissible row, proposals, proposals lost to a conflict, keypoints assigned.
+ * It follows that an assigned observation is an inlier of esfm_track_evaluate at max_reproj_error_px = search_radius_px, that a
+ * second call returns nothing once the assignments are applied (kp_free cleared, the observations added), that no keypoint gets
+ * two points and no point two keypoints in one camera, and that the results do not depend on the order of execution.
+ *
+ * Options (esfm_track_complete_options_default): search_radius_px 4.0, max_distance +inf, ratio 0.8, max_refs 8 (1 .. 8,
+ * ESFM_TRACK_COMPLETE_MAX_REFS).  These are conventions of incremental SfM (the reprojection threshold of the track options, Lowe's
+ * ratio); they have NOT been measured on this project's data.  Rejected with ESFM_ERR_INVALID_ARG, nothing written: options NULL,
+ * a NULL required array, a radius that is not finite and > 0, a NaN ratio or max_distance, max_refs outside 1 .. 8, an index out
+ * of range, a width < 1 or a Hamming width other than 16, 32, 64, an unknown metric, offsets that do not start at 0 or
+ * decrease, a set of more than 2^21 - 1 rows.  2^22 cameras or more, or more than 2^31 - 1 (point, camera) combinations, are
+ * ESFM_ERR_UNSUPPORTED.
+ *
+ * esfm_track_complete takes host pointers, uploads and calls esfm_track_complete_dev.  That form takes the descriptors and the
+ * keypoints on the device (everything else on the host) and writes kp_point, kp_dist and stats to device memory, on the
+ * context's stream; it waits for the stream once, to size the job list by the number of jobs.  On the device: per camera the box
+ * of the free keypoints and a grid of square cells at least 2 search_radius_px wide (at most 1024 per axis), keys
+ * camera | cell | row through the radix sort; the jobs by an ordered compaction over n_pt x n_cam (camera not in the track, point
+ * in front, window meets the box); sixteen lanes per job walk the at most 3 x 3 cells of the window.  esfm_track_complete_host
+ * asks the predicate about every row of every camera on the CPU. */
+#define ESFM_TRACK_COMPLETE_MAX_REFS 8
+typedef struct esfm_track_complete_options {
+    double search_radius_px;
+    double max_distance;
+    double ratio;
+    int32_t max_refs;
+    int32_t reserved;
+} esfm_track_complete_options;
+void esfm_track_complete_options_default(esfm_track_complete_options *opt);
+int esfm_track_complete(esfm_ctx *ctx, esfm_metric metric, const void *desc, const float *kp /*2 each*/, const uint8_t *kp_free,
+                        const int32_t *set_row_offset /*n_cam + 1*/, int n_cam, int width, const float *K4_per_cam,
+                        const double *Rt12_per_cam, int n_pt, const double *xyz /*3 each*/, int n_obs, const int32_t *cam_idx,
+                        const int32_t *pt_idx, const int32_t *obs_kp, const esfm_track_complete_options *opt,
+                        int32_t *kp_point /*per row*/, float *kp_dist /*per row*/, int64_t *stats /*4, may be NULL*/);
+int esfm_track_complete_dev(esfm_ctx *ctx, esfm_metric metric, const void *desc_dev, const float *kp_dev, const uint8_t *kp_free,
+                            const int32_t *set_row_offset, int n_cam, int width, const float *K4_per_cam,
+                            const double *Rt12_per_cam, int n_pt, const double *xyz, int n_obs, const int32_t *cam_idx,
+                            const int32_t *pt_idx, const int32_t *obs_kp, const esfm_track_complete_options *opt,
+                            int32_t *kp_point_dev, float *kp_dist_dev, int64_t *stats_dev /*may be NULL*/);
+int esfm_track_complete_host(esfm_metric metric, const void *desc, const float *kp, const uint8_t *kp_free,
+                             const int32_t *set_row_offset, int n_cam, int width, const float *K4_per_cam,
+                             const double *Rt12_per_cam, int n_pt, const double *xyz, int n_obs, const int32_t *cam_idx,
+                             const int32_t *pt_idx, const int32_t *obs_kp, const esfm_track_complete_options *opt,
+                             int32_t *kp_point, float *kp_dist, int64_t *stats /*may be NULL*/);
 
 /* ---- Image retrieval: VLAD global descriptors and a k-nearest pair list ------------------------------------------
  * Which images look alike, as an opt-in stage in front of the matcher: one global descriptor per image (VLAD over a k-means
